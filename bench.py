@@ -11,9 +11,12 @@ one step = one gallery batch through the hot path exactly as the reference's eva
 (evaluator_baseline.py:100-121): `batch` images [B,3,224,224] + B query texts + B target texts -> three sets of
 L2-normalised embeddings, resident in HBM.  Synthetic inputs and seeded random-init weights of the ViT-L/14
 architecture (no network).  `value` = (images + texts) encoded per second over all ranks (weak scaling: every rank
-encodes its own `batch` gallery items per step).  After the timed region the same process measures
+encodes its own `batch` gallery items per step).  A plain run sets up, warms up, times the steps and prints the line.
+`--dump-outputs DIR` writes what the last timed step computed (its image embeddings and the embeddings of the text calls it
+made, float32) as DIR/<name>.npy.  With `--full` the same process then measures
   * the fused similarity + top-10 kernel on the 43k gallery (sharded over the ranks) for Q = 1024 and Q = 43000,
   * per-kernel-class time with hipEvents on the launch stream (roofline of the dominant kernel, the bf16 GEMM),
+  * the host input pipeline, the reference's arithmetic, other text lengths and other precisions (sub-results),
   * on rank 0 at N = 1: the CPU oracle on a bounded sample of the same workload (cpu_baseline).
 Prints ONE JSON line on rank 0.
 """
@@ -156,6 +159,23 @@ def tower_gemm_flops(width, layers, rows, items, pooled):
     return unit * layers * 12.0 * rows
 
 
+DUMP_LIMIT = 64 << 20            # bytes of --dump-outputs in all
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT):
+    """Write {name: tensor} as directory/<name>.npy in float32.  If they would exceed `limit` bytes together, every array keeps
+    the same fixed, seeded sample of its rows (sorted), sized so that the files fit."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if total > limit - 4096 * len(arrays):                      # room for the .npy headers
+            keep = max(1, int(t.shape[0] * (limit - 4096 * len(arrays)) / total))
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(t.cpu().numpy()))
+
+
 def main():
     if os.environ.get("KEMR_DEBUG_SET"):               # A/B runs only (tools/ab_env.sh): "key=value,key=value" for kemr_debug_set
         from knowledge_enhanced_multimodal_retrieval_amd import debug
@@ -175,6 +195,9 @@ def main():
     ap.add_argument("--text-group", type=int, default=0, help="texts per encoder call (0 = engine.tile_friendly_batch: 851 for ViT-L/14; 255 = one call per text column and step, round 1 / early round 2)")
     ap.add_argument("--full-context", action="store_true", help="compute all 77 positions of every text (the reference's arithmetic; default: only the positions up to the end-of-text token, which are the ones that can reach the embedding)")
     ap.add_argument("--resadd", type=int, default=-1, help="A/B: 1 / 0 = residual add inside the out-proj / fc2 epilogues on / off (default: the library's setting)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure the sub-results, rooflines and the CPU baseline "
+                                                         "(the --no-* switches below leave parts of them out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's embeddings as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sim", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="skip the host-pipeline sub-result (N = 1: uint8 sources through encode_dataset)")
@@ -267,13 +290,14 @@ def main():
 
         def step(self):
             a = self.e.encode_image(pixels, normalize=True)
+            self.last_image, self.last_texts = a, []      # what this step hands back (--dump-outputs): its images, its text calls
             self.calls.append(("image", B, self.resadd, B * arch.v_tokens, self.pooled))
             self.images += B
             self.pending += 2 * B
             p = self.pool
             self.e.pack_text = p.packed
             while self.pending >= p.group:
-                self.e.encode_text(p.ids, normalize=True, lens=p.lens)
+                self.last_texts.append(self.e.encode_text(p.ids, normalize=True, lens=p.lens))
                 self.calls.append(("text", p.group, self.resadd, p.rows(p.group), self.pooled))
                 self.pending -= p.group
                 self.texts += p.group
@@ -284,7 +308,7 @@ def main():
             if self.pending:
                 p = self.pool
                 self.e.pack_text = p.packed
-                self.e.encode_text(p.ids[:self.pending], normalize=True, lens=p.lens[:self.pending])
+                self.last_texts.append(self.e.encode_text(p.ids[:self.pending], normalize=True, lens=p.lens[:self.pending]))
                 self.calls.append(("text", self.pending, self.resadd, p.rows(self.pending), self.pooled))
                 self.texts += self.pending
                 self.text_rows += p.rows(self.pending)
@@ -317,7 +341,9 @@ def main():
     drain()
     barrier()
     elapsed = time.perf_counter() - t0
-    out = main_steps.check_outputs()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image_embeddings": main_steps.last_image, "text_embeddings": torch.cat(main_steps.last_texts)})
+
     def max_over_ranks(x: float) -> float:
         if dist is None:
             return x
@@ -326,7 +352,6 @@ def main():
         return float(t.item())
 
     elapsed = max_over_ranks(elapsed)
-    assert all(torch.isfinite(o).all().item() for o in out)
 
     rccl_ranks = dist.get_world_size() if dist is not None else 1
     per_shard = (GALLERY + world - 1) // world
@@ -354,6 +379,18 @@ def main():
         "encode_tflops_per_gpu": flops_item_step * args.steps / elapsed / 1e12,
         "encode_frac_of_bf16_peak": flops_item_step * args.steps / elapsed / 1e12 / PEAK_BF16_TFLOPS,
     }
+
+    def emit():
+        if rank == 0:
+            print(json.dumps(result))
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:
+        emit()
+        return
+    out = main_steps.check_outputs()
+    assert all(torch.isfinite(o).all().item() for o in out)
 
     def pipeline_leg():
         # ------------------------------------------------------------------ the same encode through the host input pipeline
@@ -716,10 +753,7 @@ def main():
     # what the PMC passes of tools/profile_round.sh average over: every persistent-GEMM launch of this process
     c_launches, c_bytes = gemm256u_census(arch, all_calls)
     result["roofline"]["census"] = {"gemm256u_launches": c_launches, "algorithmic_bytes_per_launch": c_bytes / max(c_launches, 1)}
-    if rank == 0:
-        print(json.dumps(result))
-    if dist is not None:
-        dist.destroy_process_group()
+    emit()
 
 
 if __name__ == "__main__":

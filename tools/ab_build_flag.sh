@@ -11,7 +11,7 @@ from knowledge_enhanced_multimodal_retrieval_amd import build
 build.build(force=True, extra_flags=[f for f in "$1".split() if f])
 PY
 }
-line() { python3 $R/bench.py --steps 40 --no-extras --no-pipeline --no-sim --no-cpu-baseline 2>/dev/null | tail -n 1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', round(d['value']), {k: round(v, 3) for k, v in d['kernel_ms_per_step'].items()}, 'gemm frac', round(d['roofline']['frac'], 4))"; }
+line() { python3 $R/bench.py --full --steps 40 --no-extras --no-pipeline --no-sim --no-cpu-baseline 2>/dev/null | tail -n 1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', round(d['value']), {k: round(v, 3) for k, v in d['kernel_ms_per_step'].items()}, 'gemm frac', round(d['roofline']['frac'], 4))"; }
 for i in $(seq $ROUNDS); do
   build ""; line "plain       "
   build "$FLAG"; line "$FLAG"

@@ -3,7 +3,7 @@
 VAR=$1; VALS=$2; ROUNDS=${3:-2}; shift 3 || true
 for i in $(seq $ROUNDS); do
   for v in $VALS; do
-    env $VAR=$v timeout -k 10 400 python bench.py --steps 60 --no-pipeline --no-extras "$@" 2>/dev/null > /tmp/ab_env.json || exit 1
+    env $VAR=$v timeout -k 10 400 python bench.py --full --steps 60 --no-pipeline --no-extras "$@" 2>/dev/null > /tmp/ab_env.json || exit 1
     python3 - "$VAR" "$v" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_env.json").read().strip().splitlines()[-1])
