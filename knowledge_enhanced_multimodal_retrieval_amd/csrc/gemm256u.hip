@@ -680,6 +680,18 @@ __global__ __launch_bounds__(512, 2) void gemm256u_bf16_nt_kernel(const GemmPara
     // skips them, and its two waits let the 16 stores stay in flight: W(1) is followed by 4 A pieces + 16 stores + W0(2) = 22
     // operations, A(1) by 16 stores + W(2) = 20.  The next wait that covers the stores is K-tile 1's, fourteen intervals behind them.
     constexpr bool PRE_OK = KEMR_GEMM_PRESTAGE && !LONGK && SIM == 0 && (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16);
+    // The counts behind those two waits.  An epilogue, staging plan or store pass that issues a different number of operations must
+    // change them: the static_asserts here and in KEMR_STORE_PASS_ fail to compile until it does.
+    constexpr int PIECES_PER_STAGE = 2;                                  // KEMR_GLDS per stage_a / stage_w call
+    constexpr int PRE_A_PIECES = 2 * PIECES_PER_STAGE;                   // the epilogue's stage_a(0) + stage_a(1) of the next tile
+    constexpr int STORES_PER_PASS = 2;                                   // global_store_dwordx4 per KEMR_STORE_PASS_
+    constexpr int STORE_PASSES = 8;                                      // one KEMR_STORE_PASS_ per 16-row pass of acc
+    constexpr int TILE_STORES = STORE_PASSES * STORES_PER_PASS;          // per wave and tile
+    constexpr int PRE_VM_W1 = PRE_A_PIECES + TILE_STORES + PIECES_PER_STAGE;       // behind W(1): A(1), the stores, W0(2)
+    constexpr int PRE_VM_A1 = TILE_STORES + 2 * PIECES_PER_STAGE;                  // behind A(1): the stores, W0(2), W1(2)
+    static_assert(STORE_PASSES == std::extent<decltype(acc)>::value, "the store epilogue stores one pass per 16-row block of acc");
+    static_assert(PRE_VM_W1 == 22 && PRE_VM_A1 == 20, "the pre-staged first K-tile's waits (vmcnt 22 / 20) no longer match the counts");
+    static_assert(PRE_VM_W1 < 64, "vmcnt holds 6 bits");
     bool pre = false;                              // this tile's first K-tile finds its A(1) pieces staged
     // MID: a K-tile in which no stream wraps (no bias piece either: that rides with a tile's first W piece).
     auto ktile = [&](auto first_c, auto mid_c) {
@@ -715,12 +727,12 @@ __global__ __launch_bounds__(512, 2) void gemm256u_bf16_nt_kernel(const GemmPara
             __builtin_amdgcn_s_barrier();
             stamp(4);
             quad8<1, 1, FIRST>(acc, af8, w18, one, nohook);
-            if (FIRST && PRE_OK && pre) asm volatile("s_waitcnt vmcnt(22)" ::: "memory");
+            if (FIRST && PRE_OK && pre) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PRE_VM_W1) : "memory");
             else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // W(g+1) landed (and everything older: a tile's stores); all waves agree on it at this barrier
             __builtin_amdgcn_s_barrier();
             stamp(5);
             stage_w(ow1, buf_this + 3 * PHALF);
-            if (FIRST && PRE_OK && pre) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
+            if (FIRST && PRE_OK && pre) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PRE_VM_A1) : "memory");
             else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // the half's own A(g+1) pieces landed; W(g+2) stays in flight
             if constexpr (!MID) stage_bias();
             __builtin_amdgcn_s_barrier();
@@ -771,13 +783,13 @@ __global__ __launch_bounds__(512, 2) void gemm256u_bf16_nt_kernel(const GemmPara
             __builtin_amdgcn_s_barrier();
             stamp(4);
             cluster<1, FIRST>(acc, ak0, wk0, b4, hook_m3);
-            if (FIRST && PRE_OK && pre) asm volatile("s_waitcnt vmcnt(22)" ::: "memory");
+            if (FIRST && PRE_OK && pre) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PRE_VM_W1) : "memory");
             else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // W(g+1) landed (and everything older: a tile's stores); all waves agree on it at this barrier
             __builtin_amdgcn_s_barrier();
             stamp(5);
             stage_w(ow1, buf_this + 3 * PHALF);
             stamp_pre(12);
-            if (FIRST && PRE_OK && pre) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
+            if (FIRST && PRE_OK && pre) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PRE_VM_A1) : "memory");
             else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // the half's own A(g+1) pieces landed; W(g+2) stays in flight
             stamp_pre(13);
             if constexpr (!MID) stage_bias();
@@ -1093,6 +1105,7 @@ __global__ __launch_bounds__(512, 2) void gemm256u_bf16_nt_kernel(const GemmPara
     #define KEMR_STORE_PASS(D0, D1, WAIT) KEMR_STORE_PASS_(D0, D1, WAIT, 0)
     #define KEMR_STORE_PASS_(D0, D1, WAIT, ODD)                                                                                     \
             do {                                                                                                                    \
+                static_assert(STORES_PER_PASS == 2, "a store pass issues two global_store_dwordx4 (PRE's vmcnt counts them)");      \
                 asm volatile("s_waitcnt lgkmcnt(" #WAIT ")" : "+v"(D0), "+v"(D1) :: "memory");                                      \
                 const unsigned voff8 = voff + step8;                                                                                \
                 if (!DBG || !(p.dbg & 1)) {                                                                                         \
