@@ -76,8 +76,16 @@ typedef enum kemr_precision { KEMR_PREC_BF16 = 1, KEMR_PREC_BF16_RES16 = 2, KEMR
 
 typedef enum kemr_tower { KEMR_TOWER_VISION = 0, KEMR_TOWER_TEXT = 1 } kemr_tower;
 
+/* Longest sequences the encoders take: vision (image_size / patch)^2 + 1 tokens up to KEMR_MAX_VISION_TOKENS (a 32 x 32 patch
+ * grid: ViT-L/14 at 448 px; ViT-L/14@336px has 577), the text context up to KEMR_MAX_TEXT_CTX (causal attention, 77 in CLIP).
+ * Non-causal sequences of more than 288 tokens run on the streaming (flash-form) attention kernel, shorter ones on the
+ * whole-sequence-in-LDS kernel. */
+#define KEMR_MAX_VISION_TOKENS 1025
+#define KEMR_MAX_TEXT_CTX 288
+
 /* Architecture numbers of an OpenAI-CLIP style model (heads are width/64, MLP is 4*width).
- * ViT-L/14: {768,224,14,1024,24,768,12,49408,77}; ViT-B/32: {512,224,32,768,12,512,12,49408,77}. */
+ * ViT-L/14: {768,224,14,1024,24,768,12,49408,77}; ViT-L/14@336px: {768,336,14,1024,24,768,12,49408,77};
+ * ViT-B/32: {512,224,32,768,12,512,12,49408,77}. */
 typedef struct kemr_cfg {
     int32_t embed_dim;    /* joint embedding size D */
     int32_t image_size;   /* input resolution (square) */
@@ -314,7 +322,8 @@ int kemr_op_layernorm_resid(float* x_dev, const void* delta_dev, const float* ga
 int kemr_op_layernorm_rows(void* x_dev, int x_dtype, const void* delta_dev, const void* delta2_dev, int writeback,
                            const float* gamma_dev, const float* beta_dev, void* y_dev, int rows, int width, int out_dtype,
                            void* stream);
-/* qkv bf16 [batch*t, 3*width] (q pre-scaled by 1/8) -> out bf16 [batch*t, width] */
+/* qkv bf16 [batch*t, 3*width] (q pre-scaled by 1/8) -> out bf16 [batch*t, width]; t <= 288, or non-causal
+ * t <= KEMR_MAX_VISION_TOKENS (streaming kernel); longer causal sequences are KEMR_ERR_INVALID */
 int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, int t, int width, int causal, void* stream);
 
 #ifdef __cplusplus

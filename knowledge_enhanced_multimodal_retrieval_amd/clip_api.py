@@ -6,8 +6,10 @@ re-exports these functions so those imports resolve to the HIP engine.
 
 Weights: upstream ``clip.load(name)`` downloads a checkpoint, which is impossible offline.  Here
 * ``name`` may be a path to a state-dict file (``.pt`` with ``model_state_dict`` / ``state_dict`` / bare dict,
-  loaded with ``weights_only=True``; or ``.safetensors``), optionally ``"ViT-L/14@/path/file"``;
-* or a known model name: ``$KEMR_CLIP_WEIGHTS/<name with / -> ->.pt|.safetensors`` is used when present;
+  loaded with ``weights_only=True``; or ``.safetensors``), optionally ``"ViT-L/14@/path/file"``; a registered model name is
+  matched first, so ``"ViT-L/14@336px"`` is that model and ``"ViT-L/14@336px@/path/file"`` its checkpoint;
+* or a known model name: ``$KEMR_CLIP_WEIGHTS/<name with / and @ -> ->.pt|.safetensors`` is used when present (upstream's
+  file names: ``ViT-L-14.pt``, ``ViT-L-14-336px.pt``);
 * otherwise ``load`` raises: a run on random weights looks like any other run in its metrics file.  Synthetic-data runs
   opt in explicitly with ``allow_random_weights()`` (what ``--synthetic`` does) or ``KEMR_ALLOW_RANDOM_WEIGHTS=1``; the
   model then records ``weights_source = "random(seed 0)"``, which the evaluators write into their results JSON.
@@ -25,7 +27,7 @@ from .config import ARCHS, get_arch
 from .preprocess import ClipPreprocess, gpu_preprocessing_enabled
 from .tokenizer import tokenize  # noqa: F401  (re-exported)
 
-_PUBLIC = ("ViT-B/32", "ViT-B/16", "ViT-L/14")
+_PUBLIC = ("ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px")
 _allow_random = False
 
 
@@ -54,11 +56,15 @@ def read_state_dict(path: str) -> dict:
     return ckpt
 
 
+def _weights_stem(name: str) -> str:
+    return name.replace("/", "-").replace("@", "-")
+
+
 def _weights_for(name: str):
     root = os.environ.get("KEMR_CLIP_WEIGHTS")
     if not root:
         return None
-    stem = name.replace("/", "-")
+    stem = _weights_stem(name)
     for ext in (".safetensors", ".pt"):
         p = os.path.join(root, stem + ext)
         if os.path.exists(p):
@@ -76,10 +82,15 @@ def load(name: str, device: Union[str, torch.device, None] = None,
     if jit:
         raise RuntimeError("clip.load(jit=True) is not supported by the HIP engine")
     path = None
-    if "@" in name:
-        name, path = name.split("@", 1)
-    elif os.path.isfile(name):
-        raise RuntimeError("pass a checkpoint as '<model name>@<path>' so that the architecture is known")
+    if name not in ARCHS:
+        # "<registered name>@<path>" -- the longest registered name first: "ViT-L/14@336px@/x.pt" is not "ViT-L/14" + "336px@/x.pt"
+        arch_name = next((a for a in sorted(ARCHS, key=len, reverse=True) if name.startswith(a + "@")), None)
+        if arch_name is not None:
+            name, path = arch_name, name[len(arch_name) + 1:]
+        elif "@" in name:
+            name, path = name.split("@", 1)
+        elif os.path.isfile(name):
+            raise RuntimeError("pass a checkpoint as '<model name>@<path>' so that the architecture is known")
     if name not in ARCHS:
         raise RuntimeError(f"Model {name} not found; available models = {available_models()}")
     if path and not os.path.isfile(path):
@@ -87,7 +98,7 @@ def load(name: str, device: Union[str, torch.device, None] = None,
     path = path or _weights_for(name)
     if not path and not random_weights_allowed():
         raise FileNotFoundError(
-            f"clip.load({name!r}): no checkpoint available offline.  Set KEMR_CLIP_WEIGHTS=<dir with {name.replace('/', '-')}.pt|.safetensors>, "
+            f"clip.load({name!r}): no checkpoint available offline.  Set KEMR_CLIP_WEIGHTS=<dir with {_weights_stem(name)}.pt|.safetensors>, "
             f"pass '{name}@/path/to/state_dict.pt', or opt in to seeded RANDOM weights (synthetic-data runs: --synthetic, "
             "clip_api.allow_random_weights(), KEMR_ALLOW_RANDOM_WEIGHTS=1)")
     seed_state = torch.random.get_rng_state()

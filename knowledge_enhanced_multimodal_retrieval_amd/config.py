@@ -1,6 +1,6 @@
 """Architecture presets of the CLIP models the reference evaluates
 (`--model_name` choices at /root/reference/src/clip/eval/evaluator.py:264-266: ViT-B/32, ViT-B/16, ViT-L/14;
-embed_dim rule at src/clip/eval/evaluator_fusion.py:192)."""
+embed_dim rule at src/clip/eval/evaluator_fusion.py:192), plus ViT-L/14@336px, the higher-resolution OpenAI CLIP model."""
 from __future__ import annotations
 
 from dataclasses import dataclass, asdict
@@ -52,6 +52,7 @@ class ClipArch:
 
 ARCHS: Dict[str, ClipArch] = {
     "ViT-L/14": ClipArch(768, 224, 14, 1024, 24, 768, 12),
+    "ViT-L/14@336px": ClipArch(768, 336, 14, 1024, 24, 768, 12),      # 24 x 24 + 1 = 577 vision tokens
     "ViT-B/16": ClipArch(512, 224, 16, 768, 12, 512, 12),
     "ViT-B/32": ClipArch(512, 224, 32, 768, 12, 512, 12),
     # small shapes for tests (same structure, head dim 64)

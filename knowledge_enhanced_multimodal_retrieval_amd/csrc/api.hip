@@ -115,7 +115,9 @@ int check_cfg(const kemr_cfg& c) {
         KEMR_FAIL(KEMR_ERR_INVALID, "cfg: widths must be multiples of 256 in 256..1280 (got %d, %d)", c.v_width, c.t_width);
     if (c.v_layers <= 0 || c.t_layers <= 0 || c.vocab <= 0 || c.ctx <= 0) KEMR_FAIL(KEMR_ERR_INVALID, "cfg: non-positive field");
     const int g = c.image_size / c.patch;
-    if (g * g + 1 > 288 || c.ctx > 288) KEMR_FAIL(KEMR_ERR_INVALID, "cfg: sequence length > 288 not supported");
+    if (c.ctx > KEMR_MAX_TEXT_CTX) KEMR_FAIL(KEMR_ERR_INVALID, "cfg: sequence length > 288 not supported");
+    if ((int64_t)g * g + 1 > KEMR_MAX_VISION_TOKENS)
+        KEMR_FAIL(KEMR_ERR_INVALID, "cfg: vision sequence length %lld > %d not supported", (long long)g * g + 1, KEMR_MAX_VISION_TOKENS);
     const int kpad = (int)round_up(3 * c.patch * c.patch, 64);
     if (kpad > 4 * c.v_width) KEMR_FAIL(KEMR_ERR_INVALID, "cfg: patch too large for the workspace layout");
     return KEMR_OK;
@@ -450,7 +452,7 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int f
         resadd = gemm256u_fits(a, 2, cs) && gemm256u_fits(b, 2, cs);
     }
     *pending = !resadd && t.layers > 0;
-    const bool pooled = last_pooled && compact && !resadd && !f1 && t.layers > 0 && t.tokens <= 320;
+    const bool pooled = last_pooled && compact && !resadd && !f1 && t.layers > 0 && t.tokens <= KEMR_MAX_VISION_TOKENS;
     if (compact) *compact = pooled;
     if (pooled) KEMR_TRY(launch_pool_index(causal ? ids : nullptr, row_start, batch, t.tokens, w.pool_idx, s));
     for (int l = 0; l < t.layers; ++l) {

@@ -1,5 +1,7 @@
 // Multi-head self-attention for the CLIP towers (head dim 64; T = 257 / 197 / 50 non-causal, T = 77 causal).
 //
+// Sequences of more than 288 tokens (non-causal) go to the streaming kernel of attention_long.hip.
+//
 // One workgroup of NW waves per (image or text, head): NW = 4, or 5 for the 77-token text tower (5 query tiles: one per wave
 // instead of 2 / 1 / 1 / 1; with the key tiles behind the causal diagonal skipped: 27.7 -> 22.7 us per launch at B = 255).
 // Tried and dropped for T = 257 (17 query tiles = 5 / 4 / 4 / 4 per wave; round 2, same device): 6 waves per workgroup
@@ -361,7 +363,10 @@ int launch_attention(const bf16_t* qkv, bf16_t* out, int batch, int t, int width
         case 8: return launch_nt<8>(qkv, out, batch, t, width, causal, stream);
         case 9: return launch_nt<9>(qkv, out, batch, t, width, causal, stream);
     }
-    KEMR_FAIL(KEMR_ERR_INVALID, "attention: sequence length %d > 288 not supported", t);
+    // longer sequences: non-causal only (the vision towers of larger images), K / V streamed (attention_long.hip)
+    if (!causal && t <= KEMR_MAX_VISION_TOKENS) return launch_attention_long(qkv, out, batch, t, width, stream);
+    if (!causal) KEMR_FAIL(KEMR_ERR_INVALID, "attention: sequence length %d > %d not supported", t, KEMR_MAX_VISION_TOKENS);
+    KEMR_FAIL(KEMR_ERR_INVALID, "attention: sequence length %d > 288 not supported (causal)", t);
 }
 
 // ---- the attention of the pooled row alone (last block of a tower) ----------------------------------------------------------------
@@ -378,12 +383,15 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// MAXK: keys per item the LDS row holds -- 320 (every tower of at most 320 tokens: this instantiation is the one of the 224 px models,
+// unchanged) or KEMR_MAX_VISION_TOKENS rounded up to 64 (the long vision towers; the extra passes add exp2(-inf) = +0 to the sum and
+// leave max and P as they are, so both instantiations give the same bits where both apply).
+template <int MAXK>
 __global__ __launch_bounds__(256) void attention_pooled_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ qkv,
                                                                bf16_t* __restrict__ out, const int* __restrict__ pool_idx,
                                                                const int* __restrict__ row_start, int items, int tokens, int width,
                                                                int causal) {
     constexpr float LOG2E = 1.4426950408889634f;
-    constexpr int MAXK = 320;
     __shared__ float sp[4][MAXK];
     const int heads = width >> 6, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int item = blockIdx.x * 4 + wv;
@@ -469,12 +477,16 @@ __global__ __launch_bounds__(256) void attention_pooled_kernel(const bf16_t* __r
 int launch_attention_pooled(const bf16_t* q, const bf16_t* qkv, bf16_t* out, const int* pool_idx, const int* row_start, int items,
                             int tokens, int width, int causal, hipStream_t stream) {
     if (items <= 0) return KEMR_OK;
-    if (width % 64 != 0 || tokens <= 0 || tokens > 320) KEMR_FAIL(KEMR_ERR_INVALID, "attention (pooled row): bad shape t=%d width=%d", tokens, width);
+    if (width % 64 != 0 || tokens <= 0 || tokens > KEMR_MAX_VISION_TOKENS)
+        KEMR_FAIL(KEMR_ERR_INVALID, "attention (pooled row): bad shape t=%d width=%d", tokens, width);
     if (causal && !pool_idx) KEMR_FAIL(KEMR_ERR_INVALID, "attention (pooled row): the causal form needs the pooled positions");
     ProfScope prof(PROF_ATTENTION, stream);
     const long waves = (long)items * (width / 64);
-    hipLaunchKernelGGL(attention_pooled_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, q, qkv, out, pool_idx, row_start,
-                       items, tokens, width, causal);
+    constexpr int MAXK_LONG = (KEMR_MAX_VISION_TOKENS + 63) / 64 * 64;
+    void (*kern)(const bf16_t*, const bf16_t*, bf16_t*, const int*, const int*, int, int, int, int) =
+        tokens <= 320 ? attention_pooled_kernel<320> : attention_pooled_kernel<MAXK_LONG>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, q, qkv, out, pool_idx, row_start, items, tokens,
+                       width, causal);
     KEMR_CHECK_LAUNCH("attention_pooled_kernel");
     return KEMR_OK;
 }

@@ -46,6 +46,17 @@ def tile_friendly_batch(tokens: int, width: int, lo: int, hi: int, num_cu: int =
     return max(i for i, e in effs.items() if e >= top - 2e-3)
 
 
+def image_call_items(arch: ClipArch) -> int:
+    """Images per vision-encoder call.  Towers of at most 288 tokens: MAX_IMAGE_BATCH (255 images of ViT-L/14 = 256 row tiles).
+    Longer towers (ViT-L/14@336px: 577 tokens) keep about the same token rows per call, 255 * 257 = 65 535, and take the item
+    count in [half, all] of that which fills the persistent GEMM's rounds best (tile_friendly_batch: 85 images at 577 x 1024)."""
+    t = arch.v_tokens
+    if t <= 288:
+        return MAX_IMAGE_BATCH
+    hi = max(1, MAX_IMAGE_BATCH * 257 // t)
+    return tile_friendly_batch(t, arch.v_width, max(1, hi // 2), hi)
+
+
 def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -67,6 +78,7 @@ class ClipEngine:
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {precision!r}")
         self.precision = precision
         self.arch = arch
+        self.image_batch = image_call_items(arch)        # images per kemr_encode_image call
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("ClipEngine needs a GPU device; the HIP path has no CPU fallback")
@@ -169,7 +181,7 @@ class ClipEngine:
         if pixels.dim() != 4 or tuple(pixels.shape[1:]) != (3, a.image_size, a.image_size):
             raise RuntimeError(f"encode_image expects [B,3,{a.image_size},{a.image_size}], got {tuple(pixels.shape)}")
         pixels = pixels.to(dtype=torch.float32).contiguous()
-        return self._encode(self._L.kemr_encode_image, _lib.TOWER_VISION, pixels, MAX_IMAGE_BATCH, normalize)
+        return self._encode(self._L.kemr_encode_image, _lib.TOWER_VISION, pixels, self.image_batch, normalize)
 
     def encode_text(self, ids: torch.Tensor, normalize: bool = False, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``model.encode_text(tokens)`` (+ the optional L2 normalisation).  The rows behind a text's end-of-text token cannot reach

@@ -161,7 +161,10 @@ def encode_dataset(model, dataset, batch_size: int = 64, seed: int = 42, num_wor
     # GEMM; 255 texts leave 10 % of the out-proj round empty).  Rows are independent, so the embeddings do
     # not depend on the grouping.
     arch = getattr(model, "arch", None)
-    n_img = ENCODE_ITEMS if arch is None else engine.tile_friendly_batch(arch.v_tokens, arch.v_width, ENCODE_ITEMS // 2, ENCODE_ITEMS)
+    # (towers of more than 288 tokens -- ViT-L/14@336px -- take the engine's own call size, about ENCODE_ITEMS * 257 token rows)
+    n_img = ENCODE_ITEMS if arch is None else (
+        engine.tile_friendly_batch(arch.v_tokens, arch.v_width, ENCODE_ITEMS // 2, ENCODE_ITEMS) if arch.v_tokens <= 288
+        else engine.image_call_items(arch))
     n_txt = ENCODE_ITEMS if arch is None else max(1, engine.tile_friendly_batch(arch.ctx, arch.t_width, ENCODE_ITEMS, engine.MAX_TEXT_BATCH) // 2)
     pend_i, pend_q, pend_t, pend_ql, pend_tl = [], [], [], [], []
     count = {"i": 0, "t": 0, "rows": 0}
@@ -301,7 +304,7 @@ def evaluate_clip_model_baseline(model, dataset, batch_size: int = 64, device: s
 
 # ------------------------------------------------------------------------------------------------ CLIs
 def _common_args(parser, baseline: bool):
-    parser.add_argument("--model_name", type=str, default="ViT-L/14", choices=["ViT-B/32", "ViT-B/16", "ViT-L/14"])
+    parser.add_argument("--model_name", type=str, default="ViT-L/14", choices=["ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px"])
     parser.add_argument("--checkpoint", type=str, help="Path to checkpoint, if None uses pretrained model")
     parser.add_argument("--images_dir", type=str, default=None)
     parser.add_argument("--texts_dir", type=str, default=None, help="Directory containing query-target JSON files")
