@@ -59,6 +59,26 @@ int kemr_debug_sim_lists(const void* workspace_dev, int nq, int ng, int64_t kdim
  * intervals of the K loop, K-loop tail, epilogue, tiles, K-tiles per tile.  Synchronises the device. */
 int kemr_debug_gemm_stamps(unsigned* host_out, int n_words);
 
+/* Kernels the product reaches only inside a tower, each a pass-through to its launcher (tests/test_numerics_paths_gpu.py).  Device
+ * pointers; row_start_dev: batch + 1 ints, item b = the rows row_start[b] .. row_start[b + 1] - 1 (may be NULL where marked).
+ * causal attention over packed items: qkv bf16 [rows, 3 width] (q pre-scaled by 1/8) -> out bf16 [rows, width], every length in
+ * 1 .. max_t <= 128 */
+int kemr_debug_op_attention_packed(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width,
+                                   void* stream);
+/* the attention of one query row per item (the last block of a tower): q bf16 [items, width], k / v from qkv bf16 [rows, 3 width],
+ * out bf16 [items, width]; keys of item b: vision (causal 0) the `tokens` rows from row_start[b] (NULL: b * tokens), text (causal 1)
+ * the rows from row_start[b] (NULL: b * tokens) up to pool_idx[b], at least 1 and at most the instantiation's.  force_long = 1: the
+ * 1088-key instantiation even for tokens <= 320 */
+int kemr_debug_op_attention_pooled(const void* q_dev, const void* qkv_dev, void* out_dev, const int* pool_idx_dev,
+                                   const int* row_start_dev, int items, int tokens, int width, int causal, int force_long, void* stream);
+/* the pooling tail: x rows of x_dtype (KEMR_F32, KEMR_BF16 or 24 = the 24-bit rows of the residual stream, W bf16 upper halves
+ * then W third bytes per row) [+ delta [+ delta2]] (bf16, may be NULL) at the pooled row -- b * tokens (ids NULL) or the first
+ * arg-max of ids [batch, tokens], inside row_start's rows when given (clamped to the item's last row) -- LayerNorm(gamma, beta)
+ * @ proj fp32 [width, d] -> out fp32 [batch, d]; normalize != 0: each row divided by its L2 norm.  d % 4 == 0, batch <= 65535 */
+int kemr_debug_op_tail(const void* x_dev, int x_dtype, const void* delta_dev, const void* delta2_dev, const int32_t* ids_dev,
+                       const int* row_start_dev, int batch, int tokens, int width, const float* gamma_dev, const float* beta_dev,
+                       const float* proj_dev, int d, int normalize, float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libkemr.so")
 
 KEMR_F32, KEMR_BF16, KEMR_I32, KEMR_FP8 = 0, 1, 2, 3
+KEMR_F24 = 24               # internal: the 24-bit rows of the residual stream (csrc/common.h f24_t; debug entry points and tests only)
 PREC_BF16 = 1
 PREC_BF16_RES16 = 2
 PREC_FP8 = 3
@@ -94,6 +95,9 @@ DEBUG_SIGNATURES = {
     "kemr_debug_get": (_i, [C.c_char_p, C.POINTER(_i)]),
     "kemr_debug_sim_lists": (_i, [_vp, _i, _i, _i64, _i, _vp]),
     "kemr_debug_gemm_stamps": (_i, [_vp, _i]),
+    "kemr_debug_op_attention_packed": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "kemr_debug_op_attention_pooled": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "kemr_debug_op_tail": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
 }
 ABI_VERSION = 4
 

@@ -696,6 +696,30 @@ extern "C" int kemr_debug_gemm_stamps(unsigned* host_out, int n_words) {
     return gemm_read_stamps(host_out, n_words);
 }
 
+// pass-throughs to the launchers of the kernels a tower reaches only inside itself (tests hold them to their rounding budgets)
+extern "C" int kemr_debug_op_attention_packed(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width,
+                                              void* stream) {
+    if (!qkv_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_attention_packed: null argument");
+    return launch_attention_packed((const bf16_t*)qkv_dev, (bf16_t*)out_dev, row_start_dev, batch, max_t, width, (hipStream_t)stream);
+}
+
+extern "C" int kemr_debug_op_attention_pooled(const void* q_dev, const void* qkv_dev, void* out_dev, const int* pool_idx_dev,
+                                              const int* row_start_dev, int items, int tokens, int width, int causal, int force_long,
+                                              void* stream) {
+    if (!q_dev || !qkv_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_attention_pooled: null argument");
+    return launch_attention_pooled((const bf16_t*)q_dev, (const bf16_t*)qkv_dev, (bf16_t*)out_dev, pool_idx_dev, row_start_dev, items,
+                                   tokens, width, causal, (hipStream_t)stream, force_long);
+}
+
+extern "C" int kemr_debug_op_tail(const void* x_dev, int x_dtype, const void* delta_dev, const void* delta2_dev, const int32_t* ids_dev,
+                                  const int* row_start_dev, int batch, int tokens, int width, const float* gamma_dev, const float* beta_dev,
+                                  const float* proj_dev, int d, int normalize, float* out_dev, void* stream) {
+    if (!x_dev || !gamma_dev || !beta_dev || !proj_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_tail: null argument");
+    if (x_dtype != KEMR_F32 && x_dtype != KEMR_BF16 && x_dtype != KEMR_F24) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_tail: bad row dtype %d", x_dtype);
+    return launch_tail(x_dev, x_dtype, (const bf16_t*)delta_dev, (const bf16_t*)delta2_dev, ids_dev, batch, tokens, width, gamma_dev, beta_dev,
+                       proj_dev, d, normalize, out_dev, (hipStream_t)stream, row_start_dev);
+}
+
 // ------------------------------------------------------------------------------------------------ event profiler
 extern "C" int kemr_profile_begin(int max_launches) {
     if (max_launches <= 0 || max_launches > (1 << 20)) KEMR_FAIL(KEMR_ERR_INVALID, "profile_begin: bad max_launches");

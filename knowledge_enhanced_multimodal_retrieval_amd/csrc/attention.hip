@@ -475,7 +475,7 @@ __global__ __launch_bounds__(256) void attention_pooled_kernel(const bf16_t* __r
 }
 
 int launch_attention_pooled(const bf16_t* q, const bf16_t* qkv, bf16_t* out, const int* pool_idx, const int* row_start, int items,
-                            int tokens, int width, int causal, hipStream_t stream) {
+                            int tokens, int width, int causal, hipStream_t stream, int force_long) {
     if (items <= 0) return KEMR_OK;
     if (width % 64 != 0 || tokens <= 0 || tokens > KEMR_MAX_VISION_TOKENS)
         KEMR_FAIL(KEMR_ERR_INVALID, "attention (pooled row): bad shape t=%d width=%d", tokens, width);
@@ -484,7 +484,7 @@ int launch_attention_pooled(const bf16_t* q, const bf16_t* qkv, bf16_t* out, con
     const long waves = (long)items * (width / 64);
     constexpr int MAXK_LONG = (KEMR_MAX_VISION_TOKENS + 63) / 64 * 64;
     void (*kern)(const bf16_t*, const bf16_t*, bf16_t*, const int*, const int*, int, int, int, int) =
-        tokens <= 320 ? attention_pooled_kernel<320> : attention_pooled_kernel<MAXK_LONG>;
+        tokens <= 320 && !force_long ? attention_pooled_kernel<320> : attention_pooled_kernel<MAXK_LONG>;
     hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, q, qkv, out, pool_idx, row_start, items, tokens,
                        width, causal);
     KEMR_CHECK_LAUNCH("attention_pooled_kernel");

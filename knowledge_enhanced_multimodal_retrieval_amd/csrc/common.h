@@ -200,9 +200,10 @@ int launch_pool_index(const int32_t* ids, const int* row_start, int batch, int t
 // x[pool_idx[b]] -> xc[b], h[pool_idx[b]] -> hc[b]: compact copies of the pooled rows
 int launch_gather_pooled(const void* x, int x_dtype, const void* h, int h_dtype /* KEMR_BF16 | KEMR_FP8 */, const int* pool_idx, int batch,
                          int width, void* xc, void* hc, hipStream_t stream);
-// attention of the pooled row alone: q [items, width] compact, k / v from the call's qkv buffer, out [items, width] compact
+// attention of the pooled row alone: q [items, width] compact, k / v from the call's qkv buffer, out [items, width] compact;
+// force_long (tests): the 1088-key instantiation even where the 320-key one applies
 int launch_attention_pooled(const bf16_t* q, const bf16_t* qkv, bf16_t* out, const int* pool_idx, const int* row_start, int items,
-                            int tokens, int width, int causal, hipStream_t stream);
+                            int tokens, int width, int causal, hipStream_t stream, int force_long = 0);
 // exclusive prefix sums of the (clamped) text lengths: the packed-row layout of the text tower
 int launch_row_starts(const int32_t* lens, int batch, int max_len, int rows, int* row_start, hipStream_t stream);
 // row_start (optional, device, batch + 1 ints): packed rows -- text i contributes only its first row_start[i + 1] - row_start[i]

@@ -69,3 +69,51 @@ def gemm_stamps(n_words: int):
     buf = (C.c_uint * n_words)()
     _lib.check(_lib.lib().kemr_debug_gemm_stamps(buf, n_words), "debug_gemm_stamps")
     return buf
+
+
+# ---- kernels a tower reaches only inside itself (tests/test_numerics_paths_gpu.py); device tensors in, outputs allocated here
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream(device):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def op_attention_packed(qkv, row_start, max_t: int, width: int):
+    """Causal attention over packed items: qkv bf16 [rows, 3 width], row_start int32 [batch + 1] (device) -> bf16 [rows, width]
+    (rows no item owns stay 0)."""
+    import torch
+    out = torch.zeros((qkv.shape[0], width), dtype=torch.bfloat16, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.lib().kemr_debug_op_attention_packed(_ptr(qkv), _ptr(out), _ptr(row_start), row_start.numel() - 1, max_t,
+                                                             width, _stream(qkv.device)), "debug_op_attention_packed")
+    return out
+
+
+def op_attention_pooled(q, qkv, pool_idx, row_start, tokens: int, causal: bool, force_long: bool = False):
+    """One query row per item: q bf16 [items, width], k / v from qkv bf16 [rows, 3 width], pool_idx / row_start int32 (device, or
+    None) -> bf16 [items, width]."""
+    import torch
+    items, width = q.shape
+    out = torch.zeros((items, width), dtype=torch.bfloat16, device=q.device)
+    with torch.cuda.device(q.device):
+        _lib.check(_lib.lib().kemr_debug_op_attention_pooled(_ptr(q), _ptr(qkv), _ptr(out), _ptr(pool_idx), _ptr(row_start), items,
+                                                             tokens, width, 1 if causal else 0, 1 if force_long else 0,
+                                                             _stream(q.device)), "debug_op_attention_pooled")
+    return out
+
+
+def op_tail(x, x_dtype: int, delta, delta2, ids, row_start, batch: int, tokens: int, width: int, gamma, beta, proj,
+            normalize: bool):
+    """The pooling tail: rows x of x_dtype (_lib.KEMR_F32 / KEMR_BF16 / KEMR_F24) [+ delta [+ delta2]] at the pooled row ->
+    LayerNorm -> @ proj fp32 [width, d] (-> / L2 norm) = fp32 [batch, d]."""
+    import torch
+    d = proj.shape[1]
+    out = torch.zeros((batch, d), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().kemr_debug_op_tail(_ptr(x), x_dtype, _ptr(delta), _ptr(delta2), _ptr(ids), _ptr(row_start), batch,
+                                                 tokens, width, _ptr(gamma), _ptr(beta), _ptr(proj), d, 1 if normalize else 0,
+                                                 _ptr(out), _stream(x.device)), "debug_op_tail")
+    return out

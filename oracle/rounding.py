@@ -12,7 +12,12 @@ device the tensors live on:
 * ``budget_ratio(got, ref64, extra)``: ``|got - ref64| / (0.5 ulp(got) + extra)`` elementwise: <= 1 for a correctly rounded
   output of a value that the fp32 arithmetic moved by at most ``extra``.
 * ``signed_bias_ulps(got, ref64)``: the mean of ``(got - ref64) sign(ref64) / ulp(ref64)``: ~0 for round-to-nearest-even,
-  -0.5 for truncation, positive for an output that is systematically too large in magnitude.
+  -0.5 for truncation, positive for an output that is systematically too large in magnitude.  ``relative_bias`` is the form for
+  fp32 outputs that carry accumulated error.
+* fp64 statements of the kernels: ``attention_emulation`` (csrc/attention.hip tile kernels), ``attention_long_emulation`` (the
+  streaming kernel, P rounded against the running max of 64-key chunks), ``attention_pooled_emulation`` (one pooled query row),
+  ``tail_emulation`` / ``l2norm_emulation`` (the pooling tail: LayerNorm @ proj, then the L2 step).  Each returns the exact value
+  and ``extra``, derived in its docstring.
 """
 from __future__ import annotations
 
@@ -72,9 +77,17 @@ def budget_ratio(got: torch.Tensor, ref64: torch.Tensor, extra=0.0, fmt: str = "
     return (got - ref64.double().cpu()).abs() / (0.5 * ulp(got, fmt) + extra)
 
 
-def signed_bias_ulps(got: torch.Tensor, ref64: torch.Tensor, fmt: str = "bf16") -> float:
+def signed_bias_ulps(got: torch.Tensor, ref64: torch.Tensor, fmt: str = "bf16", extra=None) -> float:
+    """With `extra`: the mean over the elements whose extra is at most a quarter ulp, i.e. whose error the final rounding dominates.
+    Where the fp32 arithmetic before the rounding is larger than an ulp -- outputs near 0, whose absolute error is their row's --
+    the error in ulps is large and of either sign: one such element of a correct streaming-attention stand-in reads 8236 ulp and
+    alone moves the mean over 300k outputs by 0.028 (tests/test_rounding_budget.py)."""
     ref64 = ref64.double().cpu()
-    return float(((got.double().cpu() - ref64) * torch.sign(ref64) / ulp(ref64, fmt)).mean())
+    e = (got.double().cpu() - ref64) * torch.sign(ref64) / ulp(ref64, fmt)
+    if extra is not None:
+        extra = extra.double().cpu() if isinstance(extra, torch.Tensor) else torch.full_like(ref64, float(extra))
+        e = e[(extra <= 0.25 * ulp(ref64, fmt)).expand_as(e)]
+    return float(e.mean())
 
 
 def worst(ratio: torch.Tensor, got: torch.Tensor, ref64: torch.Tensor) -> str:
@@ -87,12 +100,13 @@ def worst(ratio: torch.Tensor, got: torch.Tensor, ref64: torch.Tensor) -> str:
 
 
 def check_budget(got: torch.Tensor, ref64: torch.Tensor, extra=0.0, fmt: str = "bf16", limit: float = 1.0,
-                 max_bias: float | None = None, what: str = "") -> tuple[float, float]:
-    """Asserts budget_ratio <= limit everywhere (and |signed bias| <= max_bias when given); returns (max ratio, bias)."""
+                 max_bias: float | None = None, what: str = "", bias_rounding_only: bool = False) -> tuple[float, float]:
+    """Asserts budget_ratio <= limit everywhere (and |signed bias| <= max_bias when given; bias_rounding_only: over the elements
+    the final rounding dominates, signed_bias_ulps with extra); returns (max ratio, bias)."""
     ratio = budget_ratio(got, ref64, extra, fmt)
     top = float(torch.nan_to_num(ratio, nan=float("inf")).max())
     assert top <= limit, f"{what}: budget ratio {top:.4g} > {limit} -- {worst(ratio, got, ref64)}"
-    bias = signed_bias_ulps(got, ref64, fmt)
+    bias = signed_bias_ulps(got, ref64, fmt, extra if bias_rounding_only else None)
     if max_bias is not None:
         assert abs(bias) <= max_bias, f"{what}: signed bias {bias:+.4f} ulp beyond +-{max_bias}"
     return top, bias
@@ -107,10 +121,18 @@ def attention_emulation(qkv_bf16, batch, t, width, causal):
     heads = width // 64
     x = qkv_bf16.double().view(batch, t, 3, heads, 64).permute(2, 0, 3, 1, 4)
     q, k, v = x[0], x[1], x[2]                                                   # [B, H, T, 64]
+    mask = torch.ones(t, t, dtype=torch.bool, device=q.device).triu_(1) if causal else None
+    o, extra = _attention_rows(q, k, v, mask)
+    back = lambda y: y.permute(0, 2, 1, 3).reshape(batch * t, width)            # noqa: E731
+    return back(o), back(extra)
+
+
+def _attention_rows(q, k, v, mask):
+    """attention_emulation's statement for query rows q [..., Tq, 64] against keys k, v [..., Tk, 64] (fp64 holding bf16 values);
+    mask (broadcast to [..., Tq, Tk], True = not a key of that row) or None.  Returns (O, extra), both [..., Tq, 64]."""
     s = q @ k.transpose(-1, -2)
     sabs = q.abs() @ k.abs().transpose(-1, -2)
-    if causal:
-        mask = torch.ones(t, t, dtype=torch.bool, device=s.device).triu_(1)
+    if mask is not None:
         s = s.masked_fill(mask, float("-inf"))
     mx = s.amax(-1, keepdim=True)
     p = torch.exp(s - mx)
@@ -122,6 +144,155 @@ def attention_emulation(qkv_bf16, batch, t, width, causal):
     eps = 2.0 ** -24 * (16 * sabs + 2 * (s.abs() + mx.abs()).nan_to_num(0.0, 0.0, 0.0) * 1.4427 + 4)
     prop = ((eps * p) @ vabs + (eps * p).sum(-1, keepdim=True) * o.abs()) / l
     acc = 2.0 ** -24 * (16 * (pb @ vabs) / l + 4 * o.abs())
-    extra = flip.expand_as(o) + prop + acc
+    return o, flip.expand_as(o) + prop + acc
+
+
+def attention_long_emulation(qkv_bf16, batch, t, width, kc=64):
+    """fp64 statement of what csrc/attention_long.hip computes (non-causal, K / V streamed in chunks of kc keys; KEMR_ATTN_LONG_KC,
+    default 64).  The kernel rounds P to bf16 against the RUNNING maximum of the keys seen so far, not the final one, so
+    attention_emulation (one pass, final maximum) does not state it.  Per query row, for chunk c (keys c kc .. min(T, (c + 1) kc) - 1;
+    the pad keys of the ragged last chunk are -inf, i.e. absent):
+        m_c = max of the scores of chunks 0 .. c,   P_c = exp(s - m_c),   f_c = exp(m_c - m_final)
+        l   = sum_c f_c sum(P_c)               (the row sum from the UNROUNDED P, as in the tile kernel)
+        O   = sum_c f_c (bf16(P_c) . V_c) / l  (the kernel's alpha = exp2(m_{c-1} - m_c) per chunk multiplies out to f_c)
+    Returns (O, extra) as attention_emulation, [B T, width].  With u = 2^-24 (fp32 unit roundoff) and n = ceil(T / kc), extra is:
+    * flip -- the bf16 rounding of a key's P is the one place where an fp32 error of relative size eps can move an output by a whole
+      bf16 step.  The kernel's P differs from P_c by at most eps P_c (below), so a key can round to another value only if bf16(P_c (1 - eps))
+      or bf16(P_c (1 + eps)) differs from bf16(P_c); its possible move is the larger of those two differences, and the term is
+      sum_c f_c (move . |V_c|) / l -- every such key counted, per output column (a key no perturbation can flip contributes nothing).
+      eps = u (16 sabs + 2 (|s| + |m_c|) log2 e + 4): the fp32 score (two bf16 MFMAs over 64 products, sabs = sum |q||k|, the bound
+      attention_emulation uses), the fma s log2e - m' whose operands (|s|, the rounded running maximum |m_c| log2e) are rounded once
+      each (< 2 u (|s| + |m_c|) log2 e in the exponent; its exp2 turns an error d of the exponent into ln 2 d of P) and exp2's own
+      error (< 2 ulp = 4 u).
+    * prop -- the same eps moves l (P enters l unrounded): sum_c f_c sum(eps P_c) |O| / l.
+    * chain -- what multiplies chunk c's part of O and of l is a product of up to n fp32 factors instead of f_c: per chunk an exp2
+      (< 4 u) and the roundings of O alpha and l alpha (u each), so < 6 n u; the exponent ml - m' of each alpha is an fp32
+      difference (rounding < u |m' - ml| log2 e, i.e. < u |m' - ml| in the factor; summed over the chunks < u (m_final - m_0)); and
+      the running maximum is kept as the rounded fp32 product m log2e (< 2 u |m| log2 e, ln 2 of it in the factor, at the chunk's and
+      at the final maximum: < 2 u max(|m_0|, |m_final|)).  rho = u (6 n + (m_final - m_0) + 2 max(|m_0|, |m_final|)) relative on every
+      term: rho (sum_c f_c bf16(P_c) . |V_c| + l |O|) / l.
+    * acc -- the fp32 sums: O, per chunk two MFMAs of 32 products (16 u, attention_emulation's bound) added to the running O (one
+      rounding per chunk), and the fp32 division: (16 + n) u sum_c f_c bf16(P_c) . |V_c| / l + 4 u |O|; l: positive terms, summed
+      per lane in two accumulators of kc / 8 (8 roundings), added (1), rescaled and added to l (2 per chunk), then 2 shuffles:
+      < (12 + 2 n) u relative, (12 + 2 n) u |O|."""
+    heads = width // 64
+    x = qkv_bf16.double().cpu().view(batch, t, 3, heads, 64).permute(2, 0, 3, 1, 4)
+    o, extra = _attention_chunked(x[0], x[1], x[2], None, kc)                   # q, k, v [B, H, T, 64]
     back = lambda y: y.permute(0, 2, 1, 3).reshape(batch * t, width)            # noqa: E731
     return back(o), back(extra)
+
+
+def _attention_chunked(q, k, v, key_ok, kc):
+    """attention_long_emulation's statement for query rows q [..., Tq, 64] against keys k, v [..., Tk, 64] in chunks of kc keys;
+    key_ok (broadcast to [..., 1, Tk], False = not a key of that item) or None.  Returns (O, extra), both [..., Tq, 64]."""
+    u = 2.0 ** -24
+    t = k.shape[-2]
+    n = (t + kc - 1) // kc
+    chunks = [(c * kc, min(t, (c + 1) * kc)) for c in range(n)]
+
+    def scores(a, b):
+        s = q @ k[..., a:b, :].transpose(-1, -2)
+        return s if key_ok is None else s.masked_fill(~key_ok[..., a:b], float("-inf"))
+
+    m_run, m = [], torch.full(q.shape[:-1] + (1,), float("-inf"), dtype=torch.float64)
+    for a, b in chunks:
+        m = torch.maximum(m, scores(a, b).amax(-1, keepdim=True))
+        m_run.append(m)
+    m_fin, m_0 = m_run[-1], m_run[0]
+    zero = torch.zeros_like(q)
+    o_sum, w_abs, flip = zero.clone(), zero.clone(), zero.clone()
+    l, l_eps = torch.zeros_like(m_fin), torch.zeros_like(m_fin)
+    for (a, b), m_c in zip(chunks, m_run):
+        kk, vv = k[..., a:b, :], v[..., a:b, :]
+        s = scores(a, b)
+        sabs = q.abs() @ kk.abs().transpose(-1, -2)
+        f = torch.exp(m_c - m_fin)
+        p = torch.exp(s - m_c)                                                   # 0 where s = -inf
+        pb = rne_bf16(p)
+        eps = u * (16 * sabs + 2 * (s.nan_to_num(0.0, 0.0, 0.0).abs() + m_c.abs()) * 1.4427 + 4)
+        move = torch.maximum((rne_bf16(p * (1 - eps)) - pb).abs(), (rne_bf16(p * (1 + eps)) - pb).abs())
+        l = l + f * p.sum(-1, keepdim=True)
+        l_eps = l_eps + f * (eps * p).sum(-1, keepdim=True)
+        o_sum = o_sum + f * (pb @ vv)
+        w_abs = w_abs + f * (pb @ vv.abs())
+        flip = flip + f * (move @ vv.abs())
+    o = o_sum / l
+    rho = u * (6 * n + (m_fin - m_0) + 2 * torch.maximum(m_0.abs(), m_fin.abs()))
+    extra = (flip + l_eps * o.abs() + rho * (w_abs + l * o.abs()) + (16 + n) * u * w_abs) / l + (16 + 2 * n) * u * o.abs()
+    return o, extra
+
+
+def pooled_keys(pool_idx, row_start, items, tokens, causal, maxk):
+    """The key rows of each item as csrc/attention.hip attention_pooled_kernel takes them: r0 = row_start[b] (or b tokens), nk = tokens
+    (vision) or pool_idx[b] - r0 + 1 (text), clamped into 1 .. maxk (the instantiation: 320 or 1088 keys).  Returns (r0, nk) as int64."""
+    r0 = row_start[:items].long().cpu() if row_start is not None else torch.arange(items, dtype=torch.int64) * tokens
+    nk = pool_idx[:items].long().cpu() - r0 + 1 if causal else torch.full((items,), tokens, dtype=torch.int64)
+    return r0, nk.clamp(1, maxk)
+
+
+def attention_pooled_emulation(q_bf16, qkv_bf16, pool_idx, row_start, items, tokens, width, causal, maxk):
+    """fp64 statement of the pooled-row attention (csrc/attention.hip attention_pooled_kernel): one query row per item and head
+    against the keys r0 .. r0 + nk - 1 of pooled_keys.  Its arithmetic is the tile kernel's for one row -- the global maximum
+    of the row first, P = exp(s - max), the row sum from the unrounded P, bf16(P) into PV, one division at the end -- so
+    attention_emulation restricted to that row states its O.  Its extra does not serve here: the flip term (two keys at the row's
+    largest bf16(P) step) exceeds a quarter ulp of every output of a row of <= 77 keys, which leaves the signed-bias bar no element
+    to measure.  The statement used is attention_long_emulation's with ONE chunk holding every key (m_c = the final max, f = 1: the
+    single-pass O), whose flip term counts only the keys an fp32 error can flip.  Its fp32 sums are no longer than the bounds
+    assume where it matters: the score of a key is 8 fma per lane + 3 shuffle adds (< 16 u sabs), and the PV sum runs sequentially
+    over nk / 2 keys per lane, whose rounding errors are independent in sign, far below 17 u sum bf16(P)|V| in size at nk <= 1088
+    (tests/test_numerics_paths_gpu.py prints the worst ratio).  Returns (O, extra) [items, width]."""
+    heads = width // 64
+    qkv = qkv_bf16.double().cpu()
+    r0, nk = pooled_keys(pool_idx, row_start, items, tokens, causal, maxk)
+    j = torch.arange(int(nk.max()))
+    valid = j[None, :] < nk[:, None]
+    rows = torch.where(valid, r0[:, None] + j[None, :], r0[:, None])                # [items, K]: masked keys read row r0 (P = 0)
+    kv = qkv[rows]
+    k = kv[..., width:2 * width].reshape(items, -1, heads, 64).transpose(1, 2)        # [items, H, K, 64]
+    v = kv[..., 2 * width:].reshape(items, -1, heads, 64).transpose(1, 2)
+    qh = q_bf16.double().cpu().view(items, heads, 1, 64)
+    o, extra = _attention_chunked(qh, k, v, valid[:, None, None, :], max(1, int(nk.max())))
+    return o.reshape(items, width), extra.reshape(items, width)
+
+
+LN_EPS = 1e-5
+
+
+def tail_emulation(xs, gamma, beta, proj, kappa, ln_factor):
+    """fp64 statement of the pooling tail's first kernel (csrc/embed.hip tail_proj_kernel).  xs [batch, width]: the rows it normalises,
+    EXACTLY -- the stored pooled row decoded from fp32 / 24-bit / bf16 and the pending updates added in fp32 in the kernel's order,
+    (x + d1) + d2 (the caller builds them with torch fp32 adds, which round like the device's).  y = LayerNorm(xs) (eps LN_EPS,
+    biased variance) * gamma + beta, out = y @ proj, in fp64.  Returns (out, extra):
+        extra = kappa u sum_i |y_i| |P_ij|  +  ln_factor max_i |y_i| sum_i |P_ij|
+    the first term the fp32 accumulation of the projection (width / 16 fma per lane, then 4 shuffle adds; kappa measured), the second
+    the fp32 LayerNorm's error of y (< ln_factor max|y| per element: the bar tests/test_numerics_gpu.py holds the two-pass LayerNorm
+    kernels to, the same arithmetic) carried through |P|."""
+    x = xs.double().cpu()
+    mean = x.mean(-1, keepdim=True)
+    d = x - mean
+    rstd = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + LN_EPS)
+    y = d * rstd * gamma.double().cpu() + beta.double().cpu()
+    p = proj.double().cpu()
+    out = y @ p
+    extra = kappa * 2.0 ** -24 * (y.abs() @ p.abs()) + ln_factor * y.abs().amax(-1, keepdim=True) * p.abs().sum(0)
+    return out, extra
+
+
+def l2norm_emulation(r):
+    """fp64 statement of the pooling tail's L2 step (csrc/embed.hip l2norm_rows_kernel) applied to r, the kernel's own unnormalised
+    fp32 output (a normalize = 0 run): r / ||r||.  Returns (ref, extra).  The kernel sums r_i^2 per lane over ceil(d / 64) columns
+    (one rounding per product and per add: < (n + 1) u relative on positive terms), then over the wave in 6 butterfly adds (6 u):
+    the sum S carries < (n + 7) u; sqrtf halves that and rounds once (u), 1.0f / x rounds once (u), and the product r_i * inv
+    rounds once -- that last rounding is the half ulp of the budget ratio.  So extra = ((n + 7) / 2 + 2) u |ref|."""
+    r64 = r.double().cpu()
+    ref = r64 / r64.norm(dim=-1, keepdim=True)
+    n = (r.shape[-1] + 63) // 64
+    return ref, ((n + 7) / 2 + 2) * 2.0 ** -24 * ref.abs()
+
+
+def relative_bias(got: torch.Tensor, ref64: torch.Tensor) -> float:
+    """sum((got - ref64) sign(ref64)) / sum|ref64| in units of 2^-24: the signed bias of fp32 outputs that carry accumulated error
+    (signed_bias_ulps divides by each element's own ulp, so outputs near 0 -- whose absolute error is that of their row -- would
+    swamp it).  ~0 for unbiased arithmetic; 16 for outputs 2^-20 too large."""
+    ref64 = ref64.double().cpu()
+    return float(((got.double().cpu() - ref64) * torch.sign(ref64)).sum() / ref64.abs().sum()) * 2.0 ** 24

@@ -1,12 +1,14 @@
 """GPU: non-causal attention beyond 288 tokens (csrc/attention_long.hip: K / V streamed through LDS with an online softmax) against
-the fp32 softmax of the same bf16 inputs, with the bars of tests/test_ops_gpu.py::test_attention; and the pooled-row attention of
-the last block at 577 tokens."""
+the fp32 softmax of the same bf16 inputs, with the bars of tests/test_ops_gpu.py::test_attention, and against the fp64 statement of
+its chunked rounding (oracle/rounding.py attention_long_emulation: budget ratio <= 1, |signed bias| <= 0.02 ulp); and the pooled-row
+attention of the last block at 577 tokens."""
 import pytest
 import torch
 
 from knowledge_enhanced_multimodal_retrieval_amd import engine
 from knowledge_enhanced_multimodal_retrieval_amd.config import ClipArch
 from oracle import clip_ref
+from oracle import rounding as R
 
 pytestmark = pytest.mark.gpu
 T_MAX = 1025                       # include/kemr.h KEMR_MAX_VISION_TOKENS
@@ -18,12 +20,15 @@ def _ref(qkv, batch, t, width):
     return (torch.softmax(q @ k.transpose(-1, -2), -1) @ v).transpose(1, 2).reshape(batch * t, width)
 
 
-def _check(device, qkv_bf, batch, t, width):
+def _check(device, qkv_bf, batch, t, width, max_bias=0.02):
     ref = _ref(qkv_bf, batch, t, width)
     got = engine.op_attention(qkv_bf.to(device), batch, t, width, False).float().cpu()
     assert torch.isfinite(got).all()
     err = (got - ref).abs()
     assert float(err.max()) < 3e-2 and float(err.mean()) < 3e-3, (t, width, float(err.max()), float(err.mean()))
+    ref64, extra = R.attention_long_emulation(qkv_bf, batch, t, width)
+    top, bias = R.check_budget(got, ref64, extra, max_bias=max_bias, what=f"attn_long_t{t}_w{width}", bias_rounding_only=True)
+    print(f"NUMERICS attn_long_fp32bands_t{t}_w{width}_ratio_bias {(round(top, 4), round(bias, 5))}")
     return got
 
 
@@ -54,7 +59,9 @@ def test_online_rescale(device, case):
             spike = 5 if case == "spike_first_chunk" else t - 1
             for b in range(batch):
                 qkv[b * t + spike, width + hd * 64] = 5.0         # logit 20 over ~0
-    _check(device, qkv.to(torch.bfloat16), batch, t, width)
+    # spikes: most outputs sit just below a bf16 value (one key takes nearly all the weight), so the exact values do not spread over
+    # their ulp intervals and the signed bias is not centred at 0 even for correct rounding -- the ratio bar only
+    _check(device, qkv.to(torch.bfloat16), batch, t, width, max_bias=None if case.startswith("spike") else 0.02)
 
 
 def test_deterministic_and_limits(device):

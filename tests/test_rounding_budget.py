@@ -2,7 +2,15 @@
 bf16 like the HIP epilogues) passes them; the same kernel with one planted defect -- truncation instead of round-to-nearest-even,
 a scale a fraction of an ulp off, a dropped K-tile, the bias added twice, a wrong QuickGELU constant, a dropped key, a masked
 causal diagonal -- fails the elementwise bar, the bias bar or both.  The bars and their `extra` terms are the ones
-tests/test_numerics_gpu.py applies to the kernels."""
+tests/test_numerics_gpu.py applies to the kernels.
+
+The same for the kernels tests/test_numerics_paths_gpu.py holds to their budgets:
+* streaming attention (T > 288, 64-key chunks): pad keys scored 0 instead of -inf, no rescale when the max moves, the one-key
+  last chunk dropped, outputs x1.005, one chunk's P rounded against the stale max; and the chunked statement against the
+  single-pass one (they differ by more than the budget in most outputs at T = 577);
+* pooled-row attention: the pooled row's own key dropped, the first key row off by one;
+* pooling tail: LayerNorm eps 1e-6, variance over width - 1, one projection row dropped, delta2 ignored, outputs x(1 + 2^-20);
+  its L2 step: outputs x(1 + 2^-20), the norm of d - 1 columns."""
 import pytest
 import torch
 
@@ -16,10 +24,11 @@ def _trunc_bf16(x32):
     return (x32.contiguous().view(torch.int32) & ~0xffff).view(torch.float32)
 
 
-def _passes(got, ref64, extra):
+def _passes(got, ref64, extra, rounding_only=False):
     ratio = R.budget_ratio(got, ref64, extra)
     top = float(torch.nan_to_num(ratio, nan=float("inf")).max())
-    return top <= 1.0 and abs(R.signed_bias_ulps(got, ref64)) <= MAX_BIAS, top, R.signed_bias_ulps(got, ref64)
+    bias = R.signed_bias_ulps(got, ref64, extra=extra if rounding_only else None)
+    return top <= 1.0 and abs(bias) <= MAX_BIAS, top, bias
 
 
 # ------------------------------------------------------------------------------------------------ helpers themselves
@@ -153,3 +162,200 @@ def test_attention_bars(defect, causal):
     got = _attention_kernel_cpu(qkv_bf, batch, t, width, causal, defect)
     ok, top, bias_u = _passes(got, ref, extra)
     assert ok == (defect is None), (defect, causal, top, bias_u)
+
+
+# ------------------------------------------------------------------------------------------------ streaming attention (T > 288)
+def _long_case(t, batch=3, width=256, seed=17):
+    g = torch.Generator().manual_seed(seed + t)
+    qkv = torch.randn(batch * t, 3 * width, generator=g)
+    qkv[:, :width] *= 0.25                        # pre-scaled queries: logits of a few units
+    return qkv.to(torch.bfloat16)
+
+
+def _long_kernel_cpu(qkv_bf16, batch, t, width, kc=64, defect=None):
+    """csrc/attention_long.hip in fp32 on the CPU: K / V in chunks of kc keys, running max m and sum l, O and l rescaled by
+    exp(m - m') when the max moves, P rounded to bf16 against the running max, the sum from the unrounded P."""
+    heads = width // 64
+    x = qkv_bf16.float().view(batch, t, 3, heads, 64).permute(2, 0, 3, 1, 4)
+    q, k, v = x[0], x[1], x[2]
+    n = (t + kc - 1) // kc
+    if defect == "pad_keys_scored_0":             # the ragged chunk's zero-filled pad keys left unmasked: score 0, V 0
+        pad = torch.zeros(k.shape[:-2] + (n * kc - t, 64))
+        k, v = torch.cat([k, pad], -2), torch.cat([v, pad], -2)
+    m = torch.full(q.shape[:-1] + (1,), float("-inf"))
+    l = torch.zeros_like(m)
+    o = torch.zeros_like(q)
+    for c in range(n):
+        if defect == "drop_last_ragged_chunk" and c == n - 1:
+            continue
+        kk, vv = k[..., c * kc:(c + 1) * kc, :], v[..., c * kc:(c + 1) * kc, :]
+        s = q @ kk.transpose(-1, -2)
+        mnew = torch.maximum(m, s.amax(-1, keepdim=True))
+        alpha = torch.ones_like(m) if defect == "no_rescale" else torch.exp(m - mnew)
+        p = torch.exp(s - mnew)
+        if defect == "stale_max_chunk1" and c == 1:        # chunk 1's P rounded against the max before it, then rescaled
+            pb = torch.exp(s - m).to(torch.bfloat16).float() * torch.exp(m - mnew)
+        else:
+            pb = p.to(torch.bfloat16).float()
+        l = l * alpha + p.sum(-1, keepdim=True)
+        o = o * alpha + pb @ vv
+        m = mnew
+    o = o / l
+    if defect == "scale_1.005":
+        o = o * 1.005
+    return o.permute(0, 2, 1, 3).reshape(batch * t, width).to(torch.bfloat16)
+
+
+@pytest.mark.parametrize("t", [289, 385, 577, 1025])
+def test_long_attention_bars_pass_the_streaming_kernel(t):
+    batch, width = 3, 256
+    qkv = _long_case(t, batch, width)
+    ref, extra = R.attention_long_emulation(qkv, batch, t, width)
+    ok, top, bias_u = _passes(_long_kernel_cpu(qkv, batch, t, width), ref, extra, rounding_only=True)
+    assert ok, (t, top, bias_u)
+
+
+@pytest.mark.parametrize("defect", ["pad_keys_scored_0", "no_rescale", "drop_last_ragged_chunk", "scale_1.005", "stale_max_chunk1"])
+def test_long_attention_bars_catch_planted_defects(defect):
+    batch, t, width = 3, 577, 256                 # 577 = 9 x 64 + 1: the last chunk holds one key and 63 pad keys
+    qkv = _long_case(t, batch, width)
+    ref, extra = R.attention_long_emulation(qkv, batch, t, width)
+    ok, top, bias_u = _passes(_long_kernel_cpu(qkv, batch, t, width, defect=defect), ref, extra, rounding_only=True)
+    assert not ok, (defect, top, bias_u)
+
+
+def test_chunked_and_single_pass_statements_differ_at_577():
+    """The streaming kernel rounds P against the running max, the tile kernel against the final one: at T = 577 the two fp64
+    statements differ by more than the chunked statement's extra in most outputs (76 % here), so the correct streaming stand-in,
+    held to the single-pass O with that extra, fails by two orders of magnitude -- the chunked statement is what makes the bar tight."""
+    batch, t, width = 3, 577, 256
+    qkv = _long_case(t, batch, width)
+    got = _long_kernel_cpu(qkv, batch, t, width)
+    ref1, _ = R.attention_emulation(qkv, batch, t, width, False)
+    refc, extra = R.attention_long_emulation(qkv, batch, t, width)
+    frac = float(((refc - ref1).abs() > extra).double().mean())
+    assert frac > 0.5, frac
+    top = float(R.budget_ratio(got, ref1, extra).max())
+    assert top > 10.0, top
+
+
+def test_long_emulation_kc_is_the_chunk_size():
+    """One chunk holding every key is the single-pass statement: the same O as attention_emulation."""
+    batch, t, width = 2, 289, 128
+    qkv = _long_case(t, batch, width)
+    o1, _ = R.attention_emulation(qkv, batch, t, width, False)
+    oc, _ = R.attention_long_emulation(qkv, batch, t, width, kc=320)
+    assert torch.allclose(o1, oc, rtol=1e-13, atol=0)
+
+
+# ------------------------------------------------------------------------------------------------ pooled-row attention
+def _pooled_kernel_cpu(q_bf16, qkv_bf16, r0, nk, width, defect=None):
+    heads = width // 64
+    out = torch.empty(len(r0), width)
+    for b in range(len(r0)):
+        a, n = int(r0[b]), int(nk[b])
+        if defect == "r0_off_by_one" and a > 0:             # keys r0 - 1 .. r0 + nk - 2: the previous item's last row in, the pooled row out
+            a -= 1
+        if defect == "drop_pooled_key":
+            n = max(n - 1, 1)
+        kv = qkv_bf16[a:a + n].float()
+        k = kv[:, width:2 * width].view(n, heads, 64).transpose(0, 1)
+        v = kv[:, 2 * width:].view(n, heads, 64).transpose(0, 1)
+        qh = q_bf16[b].float().view(heads, 1, 64)
+        s = qh @ k.transpose(-1, -2)
+        p = torch.exp(s - s.amax(-1, keepdim=True))
+        out[b] = ((p.to(torch.bfloat16).float() @ v) / p.sum(-1, keepdim=True)).reshape(width)
+    return out.to(torch.bfloat16)
+
+
+def _pooled_case(width=256, lens=(9, 64, 65, 77, 40, 77, 33, 77)):
+    """Text form: packed items, each pooled at its last row (the end-of-text token), q of the pooled rows."""
+    g = torch.Generator().manual_seed(23)
+    lens = torch.tensor(lens)
+    row_start = torch.cat([torch.zeros(1, dtype=torch.int64), lens.cumsum(0)]).int()
+    qkv = torch.randn(int(lens.sum()), 3 * width, generator=g).to(torch.bfloat16)
+    q = (torch.randn(len(lens), width, generator=g) * 0.25).to(torch.bfloat16)
+    pool_idx = (row_start[1:] - 1).int()
+    return q, qkv, pool_idx, row_start
+
+
+@pytest.mark.parametrize("defect", [None, "drop_pooled_key", "r0_off_by_one"])
+def test_pooled_row_bars(defect):
+    width = 256
+    q, qkv, pool_idx, row_start = _pooled_case(width)
+    items = len(pool_idx)
+    ref, extra = R.attention_pooled_emulation(q, qkv, pool_idx, row_start, items, 77, width, True, 320)
+    r0, nk = R.pooled_keys(pool_idx, row_start, items, 77, True, 320)
+    got = _pooled_kernel_cpu(q, qkv, r0, nk, width, defect)
+    ok, top, bias_u = _passes(got, ref, extra, rounding_only=True)
+    assert ok == (defect is None), (defect, top, bias_u)
+
+
+def test_pooled_keys_clamp():
+    row_start = torch.tensor([0, 5, 300, 700], dtype=torch.int32)
+    pool_idx = torch.tensor([-3, 5, 650], dtype=torch.int32)           # before its first row / its first row / 351 keys
+    r0, nk = R.pooled_keys(pool_idx, row_start, 3, 77, True, 320)
+    assert r0.tolist() == [0, 5, 300] and nk.tolist() == [1, 1, 320]
+    r0, nk = R.pooled_keys(None, None, 3, 577, False, 1088)
+    assert r0.tolist() == [0, 577, 1154] and nk.tolist() == [577] * 3
+
+
+# ------------------------------------------------------------------------------------------------ pooling tail
+TAIL_KAPPA = 1             # as tests/test_numerics_paths_gpu.py
+LN_F32_FACTOR = 2.0 ** -21
+TAIL_MAX_REL_BIAS = 4      # units of 2^-24 (rounding.relative_bias), as tests/test_numerics_paths_gpu.py
+
+
+@pytest.fixture(scope="module")
+def tail_case():
+    g = torch.Generator().manual_seed(31)
+    batch, width, d = 32, 768, 512
+    x = torch.randn(batch, width, generator=g) + 0.5
+    d1 = (torch.randn(batch, width, generator=g) * 0.5).to(torch.bfloat16).float()
+    d2 = (torch.randn(batch, width, generator=g) * 0.5).to(torch.bfloat16).float()
+    gamma = 1 + 0.1 * torch.randn(width, generator=g)
+    beta = 0.1 * torch.randn(width, generator=g)
+    proj = torch.randn(width, d, generator=g) * width ** -0.5
+    return x, d1, d2, gamma, beta, proj
+
+
+def _tail_kernel_cpu(xs, gamma, beta, proj, defect=None):
+    width = xs.shape[1]
+    mean = xs.sum(-1, keepdim=True) / width
+    c = xs - mean
+    var = (c * c).sum(-1, keepdim=True) / (width - 1 if defect == "var_over_w-1" else width)
+    rstd = 1.0 / torch.sqrt(var + (1e-6 if defect == "eps_1e-6" else 1e-5))
+    y = c * rstd * gamma + beta
+    if defect == "drop_proj_row":
+        y[:, 100] = 0.0
+    out = y @ proj
+    return out * (1 + 2.0 ** -20) if defect == "scale_2^-20" else out
+
+
+def _tail_passes(got, ref, extra):
+    top = float(torch.nan_to_num(R.budget_ratio(got, ref, extra, "fp32"), nan=float("inf")).max())
+    bias = R.relative_bias(got, ref)
+    return top <= 1.0 and abs(bias) <= TAIL_MAX_REL_BIAS, top, bias
+
+
+@pytest.mark.parametrize("defect", [None, "eps_1e-6", "var_over_w-1", "drop_proj_row", "delta2_ignored", "scale_2^-20"])
+def test_tail_bars(tail_case, defect):
+    x, d1, d2, gamma, beta, proj = tail_case
+    xs = (x + d1) + d2
+    ref, extra = R.tail_emulation(xs, gamma, beta, proj, TAIL_KAPPA, LN_F32_FACTOR)
+    got = _tail_kernel_cpu(x + d1 if defect == "delta2_ignored" else xs, gamma, beta, proj, defect)
+    ok, top, bias = _tail_passes(got, ref, extra)
+    assert ok == (defect is None), (defect, top, bias)
+
+
+@pytest.mark.parametrize("defect", [None, "scale_2^-20", "norm_of_d-1_columns"])
+def test_l2norm_bars(tail_case, defect):
+    x, d1, d2, gamma, beta, proj = tail_case
+    r = _tail_kernel_cpu((x + d1) + d2, gamma, beta, proj)
+    ref, extra = R.l2norm_emulation(r)
+    s = (r[:, :-1] * r[:, :-1]).sum(-1, keepdim=True) if defect == "norm_of_d-1_columns" else (r * r).sum(-1, keepdim=True)
+    got = r * (1.0 / torch.sqrt(s))
+    if defect == "scale_2^-20":
+        got = got * (1 + 2.0 ** -20)
+    ok, top, bias = _tail_passes(got, ref, extra)
+    assert ok == (defect is None), (defect, top, bias)
