@@ -8,6 +8,7 @@
 #ifndef KEMR_DEBUG_H_
 #define KEMR_DEBUG_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -78,6 +79,18 @@ int kemr_debug_op_attention_pooled(const void* q_dev, const void* qkv_dev, void*
 int kemr_debug_op_tail(const void* x_dev, int x_dtype, const void* delta_dev, const void* delta2_dev, const int32_t* ids_dev,
                        const int* row_start_dev, int batch, int tokens, int width, const float* gamma_dev, const float* beta_dev,
                        const float* proj_dev, int d, int normalize, float* out_dev, void* stream);
+
+/* The token fronts of the encoders (tests/test_numerics_front_gpu.py): the same argument checks, workspace (kemr_workspace_bytes /
+ * kemr_text_packed_workspace_bytes) and launches as kemr_encode_image / kemr_encode_text / kemr_encode_text_packed up to the rows
+ * the first LayerNorm reads, then a copy of those rows to out_dev.
+ * image: im2col, the patch-embedding GEMM and the class rows -> fp32 [batch * tokens, v_width].
+ * text: lens_dev NULL = kemr_encode_text's batch * ctx rows, else kemr_encode_text_packed's `rows` rows and row_start_out_dev gets the
+ * batch + 1 row starts; the rows in the residual stream's storage type: fp32, bf16 or 24-bit (3 t_width bytes per row: the bf16
+ * upper halves, then the third bytes). */
+int kemr_debug_image_tokens(struct kemr_model* m, const float* pixels_dev, int batch, float* out_dev, void* workspace_dev,
+                            size_t workspace_bytes, void* stream);
+int kemr_debug_text_tokens(struct kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, void* out_dev,
+                           int* row_start_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -98,6 +98,8 @@ DEBUG_SIGNATURES = {
     "kemr_debug_op_attention_packed": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "kemr_debug_op_attention_pooled": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "kemr_debug_op_tail": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "kemr_debug_image_tokens": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "kemr_debug_text_tokens": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 ABI_VERSION = 4
 

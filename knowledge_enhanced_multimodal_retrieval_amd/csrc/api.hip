@@ -512,6 +512,52 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int f
     return KEMR_OK;
 }
 
+// The token fronts of the two towers, shared by the encoders and the kemr_debug_*_tokens pass-throughs (include/kemr_debug.h):
+// the argument checks, the workspace carve and the kernels up to the rows the first LayerNorm reads.  `what` prefixes the
+// messages; out_dev is only checked for null.  batch == 0 returns KEMR_OK with nothing launched (the caller stops there).
+// Vision: im2col, the patch-embedding GEMM (EPI_PATCH_F32: token rows + positional embedding) and the class rows -> w.x32, the
+// fp32 rows [batch * tokens, v_width] ln_pre reads.
+int image_front(kemr_model* m, const float* pixels_dev, int batch, const void* out_dev, void* workspace_dev, size_t workspace_bytes,
+                hipStream_t s, const char* what, Workspace& w) {
+    if (!m || !pixels_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
+    if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
+    if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
+    if ((int64_t)batch * (m->patches + 1) > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
+    const int W = m->cfg.v_width, T = m->patches + 1;
+    KEMR_TRY(carve(w, workspace_dev, workspace_bytes, W, (int64_t)batch * T, batch, m->res_dtype));
+    KEMR_TRY(launch_im2col(pixels_dev, w.big, batch, m->cfg.image_size, m->cfg.patch, m->kpad, s));
+    GemmParams g{};
+    g.A = w.big; g.lda = m->kpad; g.W = m->conv_w; g.ldw = m->kpad; g.bias = nullptr; g.C = w.x32; g.ldc = W;
+    g.pos = m->vpos; g.patches = m->patches; g.M = batch * m->patches; g.N = W; g.K = m->kpad;
+    KEMR_TRY(launch_gemm(g, EPI_PATCH_F32, s));
+    return launch_cls_rows(w.x32, m->cls, m->vpos, batch, T, W, s);
+}
+
+// Text: the token + positional embedding rows of the residual stream (w.x, the model's storage type).  packed: lens_dev gives the
+// lengths, `rows` the token rows (kemr_encode_text_packed) and *row_start the prefix sums row_starts_kernel leaves in the workspace;
+// otherwise batch * ctx rows.
+int text_front(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, bool packed, const void* out_dev,
+               void* workspace_dev, size_t workspace_bytes, hipStream_t s, const char* what, Workspace& w, int** row_start) {
+    if (!m || !ids_dev || !out_dev || (packed && !lens_dev)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
+    if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
+    if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
+    if ((int64_t)batch * m->cfg.ctx > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
+    const int W = m->cfg.t_width, T = m->cfg.ctx;
+    *row_start = nullptr;
+    if (!packed) {
+        KEMR_TRY(carve(w, workspace_dev, workspace_bytes, W, (int64_t)batch * T, batch, m->res_dtype));
+        return launch_text_embed(ids_dev, m->tok, m->tpos, w.x, w.x_dtype, batch, T, W, m->cfg.vocab, s);
+    }
+    if (m->cfg.ctx > 128) KEMR_FAIL(KEMR_ERR_INVALID, "%s: context length %d > 128", what, m->cfg.ctx);
+    if (rows < batch || (int64_t)rows > (int64_t)batch * T) KEMR_FAIL(KEMR_ERR_INVALID, "%s: %d rows for %d texts of 1 .. %d positions", what, rows, batch, T);
+    const size_t base_bytes = ws_bytes_rows(W, rows, m->res_dtype) + compact_bytes(W, batch), need = base_bytes + (size_t)round_up(((int64_t)batch + 1) * 4, 256);
+    if (workspace_bytes < need) KEMR_FAIL(KEMR_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    KEMR_TRY(carve(w, workspace_dev, workspace_bytes, W, rows, batch, m->res_dtype));
+    *row_start = (int*)((char*)workspace_dev + base_bytes);
+    KEMR_TRY(launch_row_starts(lens_dev, batch, T, rows, *row_start, s));
+    return launch_text_embed(ids_dev, m->tok, m->tpos, w.x, w.x_dtype, batch, T, W, m->cfg.vocab, s, *row_start, rows);
+}
+
 }  // namespace
 
 extern "C" size_t kemr_workspace_bytes(const kemr_model* m, int tower, int batch) {
@@ -529,20 +575,11 @@ extern "C" size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows
 
 extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize,
                                  void* workspace_dev, size_t workspace_bytes, void* stream) {
-    if (!m || !pixels_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: null argument");
-    if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "encode_image: model not finalized");
-    if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("encode_image: negative batch"), KEMR_ERR_INVALID);
-    if ((int64_t)batch * (m->patches + 1) > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: batch %d too large", batch);
     hipStream_t s = (hipStream_t)stream;
-    const int W = m->cfg.v_width, T = m->patches + 1;
     Workspace w;
-    KEMR_TRY(carve(w, workspace_dev, workspace_bytes, W, (int64_t)batch * T, batch, m->res_dtype));
-    KEMR_TRY(launch_im2col(pixels_dev, w.big, batch, m->cfg.image_size, m->cfg.patch, m->kpad, s));
-    GemmParams g{};
-    g.A = w.big; g.lda = m->kpad; g.W = m->conv_w; g.ldw = m->kpad; g.bias = nullptr; g.C = w.x32; g.ldc = W;
-    g.pos = m->vpos; g.patches = m->patches; g.M = batch * m->patches; g.N = W; g.K = m->kpad;
-    KEMR_TRY(launch_gemm(g, EPI_PATCH_F32, s));
-    KEMR_TRY(launch_cls_rows(w.x32, m->cls, m->vpos, batch, T, W, s));
+    KEMR_TRY(image_front(m, pixels_dev, batch, out_dev, workspace_dev, workspace_bytes, s, "encode_image", w));
+    if (batch == 0) return KEMR_OK;
+    const int W = m->cfg.v_width, T = m->patches + 1;
     KEMR_TRY(launch_layernorm(w.x32, KEMR_F32, nullptr, nullptr, 0, m->lnpre_g, m->lnpre_b, w.x, batch * T, W, w.x_dtype, s));
     bool vb = false, vc = false;
     KEMR_TRY(run_blocks(m->vis, w, batch, 0, m->fp8, m->resadd, s, &vb, nullptr, 0, m->last_pooled, nullptr, &vc));
@@ -553,15 +590,12 @@ extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int bat
 
 extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch, float* out_dev, int normalize,
                                 void* workspace_dev, size_t workspace_bytes, void* stream) {
-    if (!m || !ids_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "encode_text: null argument");
-    if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "encode_text: model not finalized");
-    if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("encode_text: negative batch"), KEMR_ERR_INVALID);
-    if ((int64_t)batch * m->cfg.ctx > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "encode_text: batch %d too large", batch);
     hipStream_t s = (hipStream_t)stream;
-    const int W = m->cfg.t_width, T = m->cfg.ctx;
     Workspace w;
-    KEMR_TRY(carve(w, workspace_dev, workspace_bytes, W, (int64_t)batch * T, batch, m->res_dtype));
-    KEMR_TRY(launch_text_embed(ids_dev, m->tok, m->tpos, w.x, w.x_dtype, batch, T, W, m->cfg.vocab, s));
+    int* no_rows = nullptr;
+    KEMR_TRY(text_front(m, ids_dev, nullptr, 0, batch, false, out_dev, workspace_dev, workspace_bytes, s, "encode_text", w, &no_rows));
+    if (batch == 0) return KEMR_OK;
+    const int W = m->cfg.t_width, T = m->cfg.ctx;
     bool tb = false, tc = false;
     KEMR_TRY(run_blocks(m->txt, w, batch, 1, 0, m->resadd, s, &tb, nullptr, 0, m->last_pooled, ids_dev, &tc));
     if (tc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
@@ -580,21 +614,12 @@ extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch
 // device (row_starts_kernel) so that no argument can index outside the workspace.
 extern "C" int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
                                        int normalize, void* workspace_dev, size_t workspace_bytes, void* stream) {
-    if (!m || !ids_dev || !out_dev || !lens_dev) KEMR_FAIL(KEMR_ERR_INVALID, "encode_text_packed: null argument");
-    if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "encode_text_packed: model not finalized");
-    if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("encode_text_packed: negative batch"), KEMR_ERR_INVALID);
-    if ((int64_t)batch * m->cfg.ctx > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "encode_text_packed: batch %d too large", batch);
-    if (m->cfg.ctx > 128) KEMR_FAIL(KEMR_ERR_INVALID, "encode_text_packed: context length %d > 128", m->cfg.ctx);
     hipStream_t s = (hipStream_t)stream;
-    const int W = m->cfg.t_width, T = m->cfg.ctx;
-    if (rows < batch || (int64_t)rows > (int64_t)batch * T) KEMR_FAIL(KEMR_ERR_INVALID, "encode_text_packed: %d rows for %d texts of 1 .. %d positions", rows, batch, T);
-    const size_t base_bytes = ws_bytes_rows(W, rows, m->res_dtype) + compact_bytes(W, batch), need = base_bytes + (size_t)round_up(((int64_t)batch + 1) * 4, 256);
-    if (workspace_bytes < need) KEMR_FAIL(KEMR_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
     Workspace w;
-    KEMR_TRY(carve(w, workspace_dev, workspace_bytes, W, rows, batch, m->res_dtype));
-    int* row_start = (int*)((char*)workspace_dev + base_bytes);
-    KEMR_TRY(launch_row_starts(lens_dev, batch, T, rows, row_start, s));
-    KEMR_TRY(launch_text_embed(ids_dev, m->tok, m->tpos, w.x, w.x_dtype, batch, T, W, m->cfg.vocab, s, row_start, rows));
+    int* row_start = nullptr;
+    KEMR_TRY(text_front(m, ids_dev, lens_dev, rows, batch, true, out_dev, workspace_dev, workspace_bytes, s, "encode_text_packed", w, &row_start));
+    if (batch == 0) return KEMR_OK;
+    const int W = m->cfg.t_width, T = m->cfg.ctx;
     bool tb = false, tc = false;
     KEMR_TRY(run_blocks(m->txt, w, batch, 1, 0, m->resadd, s, &tb, row_start, rows, m->last_pooled, ids_dev, &tc));
     if (tc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
@@ -718,6 +743,34 @@ extern "C" int kemr_debug_op_tail(const void* x_dev, int x_dtype, const void* de
     if (x_dtype != KEMR_F32 && x_dtype != KEMR_BF16 && x_dtype != KEMR_F24) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_tail: bad row dtype %d", x_dtype);
     return launch_tail(x_dev, x_dtype, (const bf16_t*)delta_dev, (const bf16_t*)delta2_dev, ids_dev, batch, tokens, width, gamma_dev, beta_dev,
                        proj_dev, d, normalize, out_dev, (hipStream_t)stream, row_start_dev);
+}
+
+// the token fronts of the encoders (image_front / text_front, the same checks and workspace), then a copy of what they leave behind
+extern "C" int kemr_debug_image_tokens(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, void* workspace_dev,
+                                       size_t workspace_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    Workspace w;
+    KEMR_TRY(image_front(m, pixels_dev, batch, out_dev, workspace_dev, workspace_bytes, s, "debug_image_tokens", w));
+    if (batch == 0) return KEMR_OK;
+    const size_t bytes = (size_t)batch * (m->patches + 1) * m->cfg.v_width * 4;
+    KEMR_CHECK_HIP(hipMemcpyAsync(out_dev, w.x32, bytes, hipMemcpyDeviceToDevice, s));
+    return KEMR_OK;
+}
+
+extern "C" int kemr_debug_text_tokens(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, void* out_dev,
+                                      int* row_start_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    const bool packed = lens_dev != nullptr;
+    if (packed && !row_start_out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_text_tokens: null row_start output");
+    hipStream_t s = (hipStream_t)stream;
+    Workspace w;
+    int* row_start = nullptr;
+    KEMR_TRY(text_front(m, ids_dev, lens_dev, rows, batch, packed, out_dev, workspace_dev, workspace_bytes, s, "debug_text_tokens", w, &row_start));
+    if (batch == 0) return KEMR_OK;
+    const int xb = w.x_dtype == KEMR_BF16 ? 2 : (w.x_dtype == KEMR_F24 ? 3 : 4);
+    const int64_t n = packed ? rows : (int64_t)batch * m->cfg.ctx;
+    KEMR_CHECK_HIP(hipMemcpyAsync(out_dev, w.x, (size_t)n * m->cfg.t_width * xb, hipMemcpyDeviceToDevice, s));
+    if (packed) KEMR_CHECK_HIP(hipMemcpyAsync(row_start_out_dev, row_start, ((size_t)batch + 1) * 4, hipMemcpyDeviceToDevice, s));
+    return KEMR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ event profiler

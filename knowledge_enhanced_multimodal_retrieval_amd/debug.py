@@ -117,3 +117,64 @@ def op_tail(x, x_dtype: int, delta, delta2, ids, row_start, batch: int, tokens: 
                                                  tokens, width, _ptr(gamma), _ptr(beta), _ptr(proj), d, 1 if normalize else 0,
                                                  _ptr(out), _stream(x.device)), "debug_op_tail")
     return out
+
+
+# ---- the token fronts of a ClipEngine's encoders (tests/test_numerics_front_gpu.py)
+def _front_workspace(eng, need: int, fill: int):
+    """The encoders' workspace, every byte `fill` (0xff: NaN in every fp32 / bf16 slot, so a row or pad column a kernel leaves
+    unwritten shows up)."""
+    import torch
+    return torch.full((max(need, 256),), fill, dtype=torch.uint8, device=eng.device)
+
+
+def image_tokens(eng, pixels, fill: int = 0xff):
+    """The fp32 rows [batch * tokens, v_width] the vision tower's ln_pre reads -- im2col, the patch-embedding GEMM with its
+    positional-embedding epilogue, the class rows -- for pixels fp32 [batch, 3, S, S] on the engine's device."""
+    import torch
+    a = eng.arch
+    batch = pixels.shape[0]
+    pixels = pixels.to(device=eng.device, dtype=torch.float32).contiguous()
+    out = torch.empty((batch * a.v_tokens, a.v_width), dtype=torch.float32, device=eng.device)
+    ws = _front_workspace(eng, int(_lib.lib().kemr_workspace_bytes(eng._h, _lib.TOWER_VISION, batch)), fill)
+    with torch.cuda.device(eng.device):
+        _lib.check(_lib.lib().kemr_debug_image_tokens(eng._h, _ptr(pixels), batch, _ptr(out), _ptr(ws), ws.numel(),
+                                                      _stream(eng.device)), "debug_image_tokens")
+    return out
+
+
+def residual_dtype(eng) -> int:
+    """Storage type of the engine's residual stream: _lib.KEMR_F32, KEMR_BF16 or KEMR_F24."""
+    v = C.c_int(0)
+    _lib.check(_lib.lib().kemr_model_get_option(eng._h, b"precision_residual_bf16", C.byref(v)), "model_get_option")
+    if v.value:
+        return _lib.KEMR_BF16
+    _lib.check(_lib.lib().kemr_model_get_option(eng._h, b"residual_stream_24bit", C.byref(v)), "model_get_option")
+    return _lib.KEMR_F24 if v.value else _lib.KEMR_F32
+
+
+def text_tokens(eng, ids, lens=None, rows: int = 0, fill: int = 0xff):
+    """The residual-stream rows the text tower's first LayerNorm reads.  ids int32 [batch, ctx]; lens None: kemr_encode_text's
+    batch * ctx rows; lens int32 [batch] (any values) with `rows` (host int): kemr_encode_text_packed's rows.  Returns (rows, row_start):
+    fp32 or bf16 [n, t_width], or the 24-bit rows as uint8 [n, 3 t_width] (engine.pack_f24_rows' layout); row_start int32 [batch + 1]
+    (packed) or None."""
+    import torch
+    a = eng.arch
+    batch = ids.shape[0]
+    ids = ids.to(device=eng.device, dtype=torch.int32).contiguous()
+    L = _lib.lib()
+    if lens is None:
+        n, need, lens_d, rs = batch * a.ctx, int(L.kemr_workspace_bytes(eng._h, _lib.TOWER_TEXT, batch)), None, None
+    else:
+        lens_d = torch.as_tensor(lens).to(device=eng.device, dtype=torch.int32).contiguous()
+        n, need = rows, int(L.kemr_text_packed_workspace_bytes(eng._h, rows, batch))
+        rs = torch.full((batch + 1,), -1, dtype=torch.int32, device=eng.device)
+    dt = residual_dtype(eng)
+    if dt == _lib.KEMR_F24:
+        out = torch.empty((n, 3 * a.t_width), dtype=torch.uint8, device=eng.device)
+    else:
+        out = torch.empty((n, a.t_width), dtype=torch.bfloat16 if dt == _lib.KEMR_BF16 else torch.float32, device=eng.device)
+    ws = _front_workspace(eng, need, fill)
+    with torch.cuda.device(eng.device):
+        _lib.check(L.kemr_debug_text_tokens(eng._h, _ptr(ids), _ptr(lens_d), rows, batch, _ptr(out), _ptr(rs), _ptr(ws), ws.numel(),
+                                            _stream(eng.device)), "debug_text_tokens")
+    return out, rs

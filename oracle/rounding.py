@@ -16,12 +16,17 @@ device the tensors live on:
   fp32 outputs that carry accumulated error.
 * fp64 statements of the kernels: ``attention_emulation`` (csrc/attention.hip tile kernels), ``attention_long_emulation`` (the
   streaming kernel, P rounded against the running max of 64-key chunks), ``attention_pooled_emulation`` (one pooled query row),
-  ``tail_emulation`` / ``l2norm_emulation`` (the pooling tail: LayerNorm @ proj, then the L2 step).  Each returns the exact value
+  ``tail_emulation`` / ``l2norm_emulation`` (the pooling tail: LayerNorm @ proj, then the L2 step), ``patch_tokens_emulation``
+  (the vision tower's token rows) and ``panel_scores_emulation`` (the similarity kernels' scores).  Each returns the exact value
   and ``extra``, derived in its docstring.
+* exact statements, compared bit for bit: ``text_tokens_statement`` (the text tower's token rows and packed row starts) and
+  ``panel_statement`` (the bf16 similarity panels); ``panel_representation_bound`` bounds what the panels' bf16 split costs
+  against fp64 of the fp32 embeddings.
 """
 from __future__ import annotations
 
 import torch
+import torch.nn.functional as F
 
 # significant bits (implicit one included) and the exponent of the smallest normal, as frexp reports it (x = m 2^e, m in [.5, 1))
 _FORMATS = {"bf16": (8, -125), "e4m3": (4, -5), "fp32": (24, -125)}
@@ -296,3 +301,150 @@ def relative_bias(got: torch.Tensor, ref64: torch.Tensor) -> float:
     swamp it).  ~0 for unbiased arithmetic; 16 for outputs 2^-20 too large."""
     ref64 = ref64.double().cpu()
     return float(((got.double().cpu() - ref64) * torch.sign(ref64)).sum() / ref64.abs().sum()) * 2.0 ** 24
+
+
+# ------------------------------------------------------------------------------------------------ token fronts
+def patch_conv(px, conv_w, patch, with_abs=False):
+    """The reference's patch embedding (OpenAI CLIP VisionTransformer: conv1, then reshape / permute to token rows) on the operands
+    the kernels see: conv2d(rne_bf16(px), rne_bf16(conv_w), stride=patch) in fp64 on px's device, as [batch, patches, width] (patch
+    py * grid + px).  with_abs: also the same of |px|, |w|.  Returns conv (or (conv, |conv|))."""
+    x, w = rne_bf16(px.double()), rne_bf16(conv_w.double().to(px.device))
+    tok = lambda y: y.flatten(2).transpose(1, 2)                                # noqa: E731
+    conv = tok(F.conv2d(x, w, stride=patch))
+    return (conv, tok(F.conv2d(x.abs(), w.abs(), stride=patch))) if with_abs else conv
+
+
+def patch_tokens_emulation(px, conv_w, cls, pos, patch, kappa):
+    """fp64 statement of the vision tower's token front: the fp32 rows [batch * tokens, width] ln_pre reads (csrc/embed.hip
+    im2col_kernel and cls_rows_kernel, the EPI_PATCH_F32 epilogue of csrc/gemm.hip / gemm256.hip).  im2col rounds every pixel to bf16
+    (RNE) and the host packs conv1.weight as bf16 (RNE), zero beyond its 3 p^2 columns; the GEMM sums the products in fp32 and its
+    epilogue adds pos[1 + patch] to the sum in fp32 and stores the token row (image b, patch i: row b tokens + 1 + i).  So
+        patch rows: ref = patch_conv + pos[1:],  extra = kappa u patch_conv(|px|, |w|)
+        class rows: ref = fp32(cls + pos[0])     (cls_rows_kernel: one fp32 add; extra 0)
+    A product of two bf16 values has at most 16 significant bits, exact in fp32, so the accumulation is the only error before the
+    epilogue: at most kappa u sum|a||w| (u = 2^-24; the GEMM accumulator bar of tests/test_numerics_gpu.py).  The add of pos rounds
+    once -- the half ulp of budget_ratio(fmt="fp32").  The K-pad columns add nothing (0 x 0).  Returns (ref, extra) on px's device."""
+    conv, cabs = patch_conv(px, conv_w, patch, with_abs=True)
+    b, _, width = conv.shape
+    row0 = (cls.float().cpu() + pos.float().cpu()[0]).double().to(conv.device)
+    ref = torch.cat([row0.expand(b, 1, width), conv + pos.double().to(conv.device)[1:]], 1)
+    extra = torch.cat([torch.zeros_like(conv[:, :1]), kappa * 2.0 ** -24 * cabs], 1)
+    return ref.reshape(-1, width), extra.reshape(-1, width)
+
+
+def text_row_starts(lens, rows, ctx):
+    """csrc/embed.hip row_starts_kernel: every length clamped into 1 .. ctx, the prefix sums capped so that every text keeps a row:
+    row_start[0] = 0, row_start[i + 1] = min(l_0 + .. + l_i, rows - (batch - i - 1)).  int32 [batch + 1] on the CPU."""
+    l = lens.long().cpu().reshape(-1).clamp(1, ctx)
+    batch = l.numel()
+    cap = rows - (batch - 1 - torch.arange(batch))
+    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.minimum(l.cumsum(0), cap)]).int()
+
+
+def text_tokens_statement(ids, lens, rows, tok, pos, vocab, ctx):
+    """Exact statement of the text tower's token front (csrc/embed.hip text_embed_kernel; row_starts_kernel for packed texts): the fp32
+    rows tok[clamp(id, 0, vocab - 1)] + pos[t], ONE fp32 add each (torch's fp32 add on the CPU rounds like the device's).
+    lens None: kemr_encode_text's batch * ctx rows, row b ctx + t = text b, position t.  Otherwise kemr_encode_text_packed's `rows`
+    rows: text i owns the rows row_start[i] .. row_start[i + 1] - 1 (text_row_starts); row r belongs to the last text i with
+    row_start[i] <= r, at position t = min(r - row_start[i], ctx - 1) -- so rows behind the last text (rows > the sum of the
+    lengths) repeat its last position.  Returns (rows fp32 [n, width], row_start int32 [batch + 1] or None) on the CPU; the caller
+    turns the rows into the storage type with .to(torch.bfloat16) (RNE) or engine.pack_f24_rows."""
+    ids = ids.long().cpu()
+    batch = ids.shape[0]
+    if lens is None:
+        r = torch.arange(batch * ctx)
+        text, t, rs = r // ctx, r % ctx, None
+    else:
+        rs = text_row_starts(lens, rows, ctx)
+        r = torch.arange(rows)
+        text = torch.searchsorted(rs[:batch].long(), r, right=True) - 1
+        t = (r - rs.long()[text]).clamp_max(ctx - 1)
+    idx = ids[text, t].clamp(0, vocab - 1)
+    return tok.float().cpu()[idx] + pos.float().cpu()[t], rs
+
+
+# ------------------------------------------------------------------------------------------------ similarity panels and scores
+def _f32_scale(s) -> float:
+    return float(torch.tensor(float(s), dtype=torch.float32))             # the ABI passes part scales as fp32
+
+
+def _bf16_bits(x64):
+    """bf16 tensor of values that bf16 represents exactly (subnormals included): the upper halves of their fp32 bits."""
+    return (x64.float().view(torch.int32) >> 16).to(torch.int16).view(torch.bfloat16)
+
+
+def panel_statement(parts, part_scale, row_scale, terms, side):
+    """Exact statement of csrc/sim.hip panel_build_kernel: the panel [round_up(rows, 256), nparts terms dpad] as bf16 bits (dpad =
+    round_up(d, 64), kemr_panel_kdim).  Per part p and row: sc = fp32(part_scale[p] row_scale[p][row]) (the part scale alone without
+    a row scale), v = fp32(src sc), hi = rne_bf16(v), lo = rne_bf16(v - hi).  v - hi is exact in fp32: hi is v rounded to 8
+    significant bits, so v - hi is a multiple of v's fp32 ulp (>= 2^-149) below 2^-8 |v|, at most 16 significant bits.  Subnormal
+    values are kept, not flushed, on the device as here (tests/test_numerics_sim_gpu.py pins a lo that is an fp32 subnormal).  Part
+    p's columns start at p terms dpad: terms 1 [hi]; terms 3 [hi | lo | hi] on the query side (side 0, KEMR_SIDE_QUERY), [hi | hi | lo]
+    on the gallery side, so that the contraction is hi.hi + lo.hi + hi.lo.  Columns d .. dpad of every segment and the rows rows ..
+    round_up(rows, 256) are +0 (simk_select_kernel relies on zero pad rows).  fp64 on the CPU with this module's explicit roundings."""
+    parts = [p.double().cpu() for p in parts]
+    rows, d = parts[0].shape
+    dpad = (d + 63) // 64 * 64
+    out = torch.zeros((rows + 255) // 256 * 256, len(parts) * terms * dpad, dtype=torch.float64)
+    for p, src in enumerate(parts):
+        sc = torch.full((rows, 1), _f32_scale(part_scale[p]) if part_scale is not None else 1.0, dtype=torch.float64)
+        if row_scale is not None and row_scale[p] is not None:
+            sc = rne_f32(sc * row_scale[p].double().cpu().reshape(rows, 1))
+        v = rne_f32(src * sc)
+        hi = _rne(v, "bf16")
+        lo = _rne(v - hi, "bf16")
+        segs = [hi] if terms == 1 else ([hi, lo, hi] if side == 0 else [hi, hi, lo])
+        for s, x in enumerate(segs):
+            c0 = (p * terms + s) * dpad
+            out[:rows, c0:c0 + d] = x
+    return _bf16_bits(out)
+
+
+def panel_scores_emulation(qpanel, gpanel, kappa, nq=None, ng=None):
+    """fp64 statement of the scores csrc/sim.hip computes from two panels (sim_kernel, whose dense form kemr_scores_dense hands back
+    the fp32 accumulators; pair_scores_kernel has the same operand roles and k order): S = Q[:nq] G[:ng]^T over the panels' own bf16
+    values.  Every product of two bf16 values is exact in fp32 (16 significant bits), so only the fp32 accumulation of the MFMA K loop
+    moves the result: extra = kappa u sum |Q||G| (u = 2^-24, the GEMM accumulator bar; kappa measured on the device).  The fp64 sum
+    of <= 4608 exact products is exact to ~2^-40 relative, far below that.  Returns (ref, extra) [nq, ng], fp64 on the CPU."""
+    q, g = qpanel[:nq].double().cpu(), gpanel[:ng].double().cpu()
+    return q @ g.T, kappa * 2.0 ** -24 * (q.abs() @ g.abs().T)
+
+
+def panel_representation_bound(q_parts, g_parts, terms, q_part_scale=None, q_row_scale=None, g_part_scale=None, g_row_scale=None):
+    """What the panels cost against fp64 of the fp32 inputs: ref = sum_p X_p Y_p^T with X = src part_scale row_scale of the query
+    parts and Y the same of the gallery parts (fp64: the product of three fp32 values carries < 2^-50, negligible here), and a bound
+    on |S_panel - ref|, S_panel = the panels' exact dot products (panel_scores_emulation's ref; the kernel's accumulation comes on
+    top).  u = 2^-24; per element v = the fp32 value the panel splits, v = X (1 + eta):
+    * eta: sc = fp32(part_scale row_scale) and v = fp32(src sc) round once each -- |eta| <= u when one of them can round (a part
+      scale != 1 alone, or a row scale alone: sc = row_scale exactly), 2 u + u^2 with both, 0 with neither;
+    * terms 1: hi = v (1 + d), |d| <= 2^-8 (bf16's unit roundoff), so |hi_q hi_g - v_q v_g| <= (2 2^-8 + 2^-16) |v_q v_g|;
+    * terms 3: v = hi + lo + e, |v - hi| <= 2^-8 |v|, |lo| <= (1 + 2^-8) 2^-8 |v|, |e| <= 2^-8 |v - hi| <= 2^-16 |v|.  Expanding
+      (hi + lo + e)(hi + lo + e) with hi + lo = v - e:
+          v_q v_g - (hi_q hi_g + lo_q hi_g + hi_q lo_g) = lo_q lo_g + e_q v_g + e_g v_q - e_q e_g,
+      the dropped lo.lo term and both second-split residuals: <= (3 2^-16 + 2^-23 + 2^-31) |v_q v_g|.
+    With c that factor: |S_panel - ref| <= sum_p sum_i (c (1 + eta_q)(1 + eta_g) + eta_q + eta_g + eta_q eta_g) |X_i| |Y_i|.  For
+    values in bf16's normal range (|v| >= 2^-126; below it a rounding's error is absolute, <= 2^-134).  On unit vectors (sum |X||Y|
+    <= 1) the worst case is 7.8e-3 (terms 1) / 4.6e-5 (terms 3); tests/test_sim_gpu.py::_fp64_slice_check's 2e-3 / 2e-6 are the
+    measured, not the worst-case, errors of d = 768 (the roundings of the d terms are independent in sign).  Returns (ref, bound)
+    [nq, ng], fp64 on the CPU."""
+    u = 2.0 ** -24
+    c = 2 * 2.0 ** -8 + 2.0 ** -16 if terms == 1 else 3 * 2.0 ** -16 + 2.0 ** -23 + 2.0 ** -31
+
+    def side(parts, ps, rs):
+        xs, etas = [], []
+        for p, src in enumerate(parts):
+            s = _f32_scale(ps[p]) if ps is not None else 1.0
+            r = rs[p] if rs is not None else None
+            x = src.double().cpu() * s
+            if r is not None:
+                x = x * r.double().cpu().reshape(-1, 1)
+            n = int(s != 1.0) + int(r is not None)
+            xs.append(x)
+            etas.append((0.0, u, 2 * u + u * u)[n])
+        return xs, etas
+
+    xq, eq = side(q_parts, q_part_scale, q_row_scale)
+    xg, eg = side(g_parts, g_part_scale, g_row_scale)
+    ref = sum(x @ y.T for x, y in zip(xq, xg))
+    bound = sum((c * (1 + a) * (1 + b) + a + b + a * b) * (x.abs() @ y.abs().T) for x, y, a, b in zip(xq, xg, eq, eg))
+    return ref, bound

@@ -359,3 +359,299 @@ def test_l2norm_bars(tail_case, defect):
         got = got * (1 + 2.0 ** -20)
     ok, top, bias = _tail_passes(got, ref, extra)
     assert ok == (defect is None), (defect, top, bias)
+
+
+# ------------------------------------------------------------------------------------------------ vision token front
+FRONT_KAPPA = 8                # as tests/test_numerics_front_gpu.py: the GEMM accumulator bar
+FRONT_MAX_REL_BIAS = 4         # units of 2^-24 (rounding.relative_bias), the tail's bar
+
+
+@pytest.fixture(scope="module")
+def patch_case():
+    g = torch.Generator().manual_seed(41)
+    b, s, p, width = 3, 56, 14, 256            # kv = 588: 52 K-pad columns, as ViT-L/14
+    px = torch.randn(b, 3, s, s, generator=g)
+    w = torch.randn(width, 3, p, p, generator=g) * (3 * p * p) ** -0.5
+    cls = torch.randn(width, generator=g) * 0.1
+    pos = torch.randn((s // p) ** 2 + 1, width, generator=g) * 0.1
+    return px, w, cls, pos, p
+
+
+def _patch_kernel_cpu(px, w, cls, pos, patch, defect=None):
+    """The token front in fp32 on the CPU: im2col (pixels rounded to bf16, k = c p^2 + dy p + dx, zero up to kpad) times the bf16
+    weights, + pos[1 + patch] in fp32 (the EPI_PATCH_F32 epilogue); class rows cls + pos[0]."""
+    b, _, s, _ = px.shape
+    width, gr = w.shape[0], s // patch
+    kv = 3 * patch * patch
+    kpad = (kv + 63) // 64 * 64
+    x = _trunc_bf16(px) if defect == "truncate_pixels" else px.to(torch.bfloat16).float()
+    x = x.view(b, 3, gr, patch, gr, patch)                                   # b c py dy px dx
+    x = x.permute(0, 2, 4, 1, 5, 3) if defect == "dy_dx_swapped" else x.permute(0, 2, 4, 1, 3, 5)
+    pad = float("nan") if defect == "kpad_not_zero" else 0.0                 # what an unwritten pad of a NaN-filled workspace holds
+    a = torch.nn.functional.pad(x.reshape(b * gr * gr, kv), (0, kpad - kv), value=pad)
+    wk = torch.nn.functional.pad(w.to(torch.bfloat16).float().reshape(width, kv), (0, kpad - kv))
+    pi = torch.arange(gr * gr).repeat(b)
+    tokens = (a @ wk.T + pos[pi if defect == "pos_pi" else pi + 1]).view(b, gr * gr, width)
+    row0 = cls if defect == "cls_without_pos0" else cls + pos[0]
+    return torch.cat([row0.expand(b, 1, width), tokens], 1).reshape(-1, width)
+
+
+def _front_failures(got, ref, extra, tokens):
+    """The checks tests/test_numerics_front_gpu.py applies to the vision rows, by name: class_rows (bit for bit), ratio (budget ratio
+    <= 1 in fp32 ulps), bias (|relative bias| <= FRONT_MAX_REL_BIAS)."""
+    failed = []
+    cls_rows = torch.arange(0, got.shape[0], tokens)
+    if not torch.equal(got[cls_rows].double(), ref[cls_rows].double()):
+        failed.append("class_rows")
+    if float(torch.nan_to_num(R.budget_ratio(got, ref, extra, "fp32"), nan=float("inf")).max()) > 1.0:
+        failed.append("ratio")
+    if not abs(R.relative_bias(got, ref)) <= FRONT_MAX_REL_BIAS:
+        failed.append("bias")
+    return failed
+
+
+def test_patch_front_bars_pass_the_stand_in(patch_case):
+    px, w, cls, pos, p = patch_case
+    ref, extra = R.patch_tokens_emulation(px, w, cls, pos, p, FRONT_KAPPA)
+    got = _patch_kernel_cpu(px, w, cls, pos, p)
+    assert _front_failures(got, ref, extra, pos.shape[0]) == []
+    kappa = float(((got - ref).abs() / (extra / FRONT_KAPPA)).nan_to_num(0.0, 0.0, 0.0).max())     # the accumulator bar itself
+    assert kappa <= FRONT_KAPPA, kappa
+
+
+@pytest.mark.parametrize("defect,check", [("truncate_pixels", "ratio"), ("dy_dx_swapped", "ratio"), ("pos_pi", "ratio"),
+                                          ("cls_without_pos0", "class_rows"), ("kpad_not_zero", "ratio")])
+def test_patch_front_bars_catch_planted_defects(patch_case, defect, check):
+    px, w, cls, pos, p = patch_case
+    ref, extra = R.patch_tokens_emulation(px, w, cls, pos, p, FRONT_KAPPA)
+    failed = _front_failures(_patch_kernel_cpu(px, w, cls, pos, p, defect), ref, extra, pos.shape[0])
+    assert check in failed, (defect, failed)
+
+
+# ------------------------------------------------------------------------------------------------ text token front
+@pytest.fixture(scope="module")
+def text_case():
+    """Ids outside 0 .. vocab - 1, lengths 0, negative, > ctx and exact; the first 8 columns of tok / pos hold bf16 ties of both
+    parities (tok = (m + 1/2) 2^-7 in [1, 2), pos = 0): the RNE bar."""
+    g = torch.Generator().manual_seed(43)
+    vocab, ctx, width, batch = 64, 16, 32, 40
+    tok = torch.randn(vocab, width, generator=g)
+    pos = torch.randn(ctx, width, generator=g) * 0.1
+    tok[:, :8] = (torch.randint(128, 256, (vocab, 8), generator=g).float() + 0.5) * 2.0 ** -7
+    pos[:, :8] = 0.0
+    ids = torch.randint(-5, vocab + 5, (batch, ctx), generator=g, dtype=torch.int32)
+    lens = torch.randint(-3, ctx + 4, (batch,), generator=g, dtype=torch.int32)
+    lens[:4] = torch.tensor([0, -2, ctx + 3, ctx])
+    return ids, lens, tok, pos, vocab, ctx
+
+
+def _text_kernel_cpu(ids, lens, rows, tok, pos, vocab, ctx, defect=None):
+    """row_starts_kernel and text_embed_kernel sequentially on the CPU (fp32 rows)."""
+    batch = ids.shape[0]
+    if lens is None:
+        r = torch.arange(batch * ctx)
+        text, t, rs = r // ctx, r % ctx, None
+    else:
+        lo = 0 if defect == "len_clamp_0" else 1
+        run, starts = 0, [0]
+        for i in range(batch):
+            run += min(max(int(lens[i]), lo), ctx)
+            cap = rows - (batch - (i + 1)) - (1 if defect == "cap_off_by_one" else 0)
+            starts.append(min(run, cap))
+        rs = torch.tensor(starts, dtype=torch.int32)
+        r = torch.arange(rows)
+        text = torch.searchsorted(rs[:batch].long(), r, right=True) - 1
+        t = (r - rs.long()[text]).clamp_max(ctx - 1)
+    idx = ids.long()[text, t]
+    idx = idx % vocab if defect == "unclamped_ids" else idx.clamp(0, vocab - 1)      # an unclamped id reads some other row
+    tp = (t + 1).clamp_max(ctx - 1) if defect == "pos_t+1" else t
+    return tok[idx] + pos[tp], rs
+
+
+def _half_up_bf16(x32):
+    return ((x32.contiguous().view(torch.int32) + 0x8000) & ~0xffff).view(torch.float32)
+
+
+def _text_failures(got_rows, got_rs, want_rows, want_rs):
+    """The checks of tests/test_numerics_front_gpu.py, by name: row_start and rows, both bit for bit."""
+    failed = []
+    if want_rs is not None and not torch.equal(got_rs, want_rs):
+        failed.append("row_start")
+    if got_rows.shape != want_rows.shape or not torch.equal(got_rows.view(torch.int16), want_rows.view(torch.int16)):
+        failed.append("rows")
+    return failed
+
+
+@pytest.mark.parametrize("layout", ["unpacked", "packed_exact", "packed_more_rows", "packed_capped"])
+def test_text_front_statement_passes_the_stand_in(text_case, layout):
+    ids, lens, tok, pos, vocab, ctx = text_case
+    total = int(lens.clamp(1, ctx).sum())
+    rows = {"unpacked": 0, "packed_exact": total, "packed_more_rows": total + 37, "packed_capped": total - 29}[layout]
+    ln = None if layout == "unpacked" else lens
+    want, want_rs = R.text_tokens_statement(ids, ln, rows, tok, pos, vocab, ctx)
+    got, got_rs = _text_kernel_cpu(ids, ln, rows, tok, pos, vocab, ctx)
+    assert _text_failures(got, got_rs, want, want_rs) == []
+    assert _text_failures(got.to(torch.bfloat16), got_rs, want.to(torch.bfloat16), want_rs) == []
+    if ln is not None:
+        assert int(want_rs[-1]) == min(rows, total) and bool((want_rs[1:] > want_rs[:-1]).all())     # every text keeps a row
+
+
+@pytest.mark.parametrize("defect,check", [("pos_t+1", "rows"), ("unclamped_ids", "rows"), ("bf16_half_up", "rows"),
+                                          ("len_clamp_0", "row_start"), ("cap_off_by_one", "row_start")])
+def test_text_front_statement_catches_planted_defects(text_case, defect, check):
+    ids, lens, tok, pos, vocab, ctx = text_case
+    rows = int(lens.clamp(1, ctx).sum()) - 29                  # the caps bind for the last texts
+    want, want_rs = R.text_tokens_statement(ids, lens, rows, tok, pos, vocab, ctx)
+    got, got_rs = _text_kernel_cpu(ids, lens, rows, tok, pos, vocab, ctx, defect)
+    want = want.to(torch.bfloat16)
+    got = _half_up_bf16(got).to(torch.bfloat16) if defect == "bf16_half_up" else got.to(torch.bfloat16)
+    failed = _text_failures(got, got_rs, want, want_rs)
+    assert check in failed, (defect, failed)
+
+
+# ------------------------------------------------------------------------------------------------ similarity panels
+def _panel_kernel_cpu(parts, part_scale, row_scale, terms, side, defect=None):
+    """panel_build_kernel in fp32 on the CPU (torch's fp32 -> bf16 cast is RNE)."""
+    rows, d = parts[0].shape
+    dpad = (d + 63) // 64 * 64
+    out = torch.zeros((rows + 255) // 256 * 256, len(parts) * terms * dpad, dtype=torch.bfloat16)
+    if defect == "nonzero_pad_rows":
+        out[rows:] = 1.0
+    for p, src in enumerate(parts):
+        ps = torch.tensor(part_scale[p], dtype=torch.float32)
+        sc = torch.full((rows, 1), 1.0 if defect == "part_scale_after_rounding" else float(ps))
+        if row_scale[p] is not None and defect != "row_scale_ignored":
+            sc = sc * row_scale[p].reshape(rows, 1)
+        v = src * sc
+        hi = _trunc_bf16(v).to(torch.bfloat16) if defect == "truncate_hi" else v.to(torch.bfloat16)
+        lo = (v - hi.float()).to(torch.bfloat16)
+        if defect == "part_scale_after_rounding":
+            hi, lo = (hi.float() * ps).to(torch.bfloat16), (lo.float() * ps).to(torch.bfloat16)
+        if defect == "lo_dropped" and side == 0:
+            lo = torch.zeros_like(lo)
+        query = (side == 0) != (defect == "layouts_swapped")
+        segs = [hi] if terms == 1 else ([hi, lo, hi] if query else [hi, hi, lo])
+        for s, x in enumerate(segs):
+            c0 = (p * terms + s) * dpad
+            out[:rows, c0:c0 + d] = x
+    return out
+
+
+def _panel_diff(got, want, rows, d, terms, nparts):
+    """Names of the regions whose bits differ: 'p{part}s{segment}' (valid rows and columns), 'pad_cols', 'pad_rows'."""
+    gb, wb = got.view(torch.int16), want.view(torch.int16)
+    dpad = (d + 63) // 64 * 64
+    names = [] if torch.equal(gb[rows:], wb[rows:]) else ["pad_rows"]
+    for p in range(nparts):
+        for s in range(terms):
+            c0 = (p * terms + s) * dpad
+            if not torch.equal(gb[:rows, c0:c0 + d], wb[:rows, c0:c0 + d]):
+                names.append(f"p{p}s{s}")
+            if not torch.equal(gb[:rows, c0 + d:c0 + dpad], wb[:rows, c0 + d:c0 + dpad]) and "pad_cols" not in names:
+                names.append("pad_cols")
+    return names
+
+
+@pytest.fixture(scope="module")
+def panel_case():
+    """Two parts of [100, 65]: part 0 scaled by 0.7 (not a power of two), part 1 by a row scale."""
+    g = torch.Generator().manual_seed(47)
+    rows, d = 100, 65
+    parts = [torch.randn(rows, d, generator=g), torch.randn(rows, d, generator=g) * 3]
+    return parts, [0.7, 1.0], [None, torch.rand(rows, generator=g) + 0.5], rows, d
+
+
+@pytest.mark.parametrize("terms,side", [(1, 0), (3, 0), (3, 1)])
+def test_panel_statement_is_the_stand_in(panel_case, terms, side):
+    parts, ps, rs, rows, d = panel_case
+    want = R.panel_statement(parts, ps, rs, terms, side)
+    assert want.shape == (256, 2 * terms * 128) and want.dtype == torch.bfloat16
+    assert _panel_diff(_panel_kernel_cpu(parts, ps, rs, terms, side), want, rows, d, terms, 2) == []
+
+
+@pytest.mark.parametrize("defect,side,check", [("truncate_hi", 1, "p0s0"), ("lo_dropped", 0, "p0s1"), ("layouts_swapped", 0, "p0s1"),
+                                               ("layouts_swapped", 1, "p1s2"), ("part_scale_after_rounding", 0, "p0s0"),
+                                               ("row_scale_ignored", 1, "p1s0"), ("nonzero_pad_rows", 0, "pad_rows")])
+def test_panel_statement_catches_planted_defects(panel_case, defect, side, check):
+    parts, ps, rs, rows, d = panel_case
+    want = R.panel_statement(parts, ps, rs, 3, side)
+    names = _panel_diff(_panel_kernel_cpu(parts, ps, rs, 3, side, defect), want, rows, d, 3, 2)
+    assert check in names, (defect, names)
+
+
+def test_panel_statement_keeps_subnormals():
+    """v = 1 + 2^-9 + 2^-17 scaled by 2^-120: hi = 2^-120, lo = 2^-129 + 2^-137 -- an fp32 subnormal, rounded to bf16's subnormal
+    grid (2^-133) = 2^-129 exactly; and v = 3 2^-132 (itself an fp32 subnormal, on bf16's grid): hi = v, lo = 0."""
+    src = torch.tensor([[1 + 2.0 ** -9 + 2.0 ** -17, 3 * 2.0 ** -12]], dtype=torch.float32)
+    panel = R.panel_statement([src], [2.0 ** -120], None, 3, 1).double()
+    assert panel[0, [0, 64, 128]].tolist() == [2.0 ** -120, 2.0 ** -120, 2.0 ** -129]
+    assert panel[0, [1, 65, 129]].tolist() == [3 * 2.0 ** -132, 3 * 2.0 ** -132, 0.0]
+
+
+# ------------------------------------------------------------------------------------------------ similarity scores
+SIM_KAPPA = 10                 # as tests/test_numerics_sim_gpu.py
+SIM_MAX_REL_BIAS = 4
+
+
+@pytest.fixture(scope="module")
+def scores_case():
+    """Two parts x 3 terms (kdim 4608, the fused T2I + T2T width) of unit rows, the second part weighted 0.4."""
+    g = torch.Generator().manual_seed(53)
+    nq, ng, d = 200, 300, 768
+    unit = lambda n: torch.nn.functional.normalize(torch.randn(n, d, generator=g), dim=-1)     # noqa: E731
+    q, gi, gt = unit(nq), unit(ng), unit(ng)
+    qp = R.panel_statement([q, q], [0.6, 0.4], None, 3, 0)
+    gp = R.panel_statement([gi, gt], None, None, 3, 1)
+    return q, gi, gt, qp, gp, nq, ng
+
+
+def _score_failures(got, ref, extra):
+    failed = []
+    if float(torch.nan_to_num(R.budget_ratio(got, ref, extra, "fp32"), nan=float("inf")).max()) > 1.0:
+        failed.append("ratio")
+    if not abs(R.relative_bias(got, ref)) <= SIM_MAX_REL_BIAS:
+        failed.append("bias")
+    return failed
+
+
+def _scores_cpu(qp, gp, nq, ng, defect=None):
+    q, g = qp[:nq].float(), gp[:ng].float()
+    if defect == "drop_last_ktile":
+        q, g = q[:, :-64], g[:, :-64]
+    if defect == "lo_hi_missing":                  # the query panel's lo segments zeroed: hi.hi + hi.lo only
+        q = q.clone()
+        q[:, 768:1536] = 0.0
+        q[:, 3 * 768 + 768:3 * 768 + 1536] = 0.0
+    s = q @ g.T
+    return s * (1 + 2.0 ** -20) if defect == "scale_2^-20" else s
+
+
+def test_scores_bars_pass_the_stand_in(scores_case):
+    q, gi, gt, qp, gp, nq, ng = scores_case
+    ref, extra = R.panel_scores_emulation(qp, gp, SIM_KAPPA, nq, ng)
+    got = _scores_cpu(qp, gp, nq, ng)
+    assert _score_failures(got, ref, extra) == []
+    rep, bound = R.panel_representation_bound([q, q], [gi, gt], 3, q_part_scale=[0.6, 0.4])
+    assert float(((got.double() - rep).abs() / (bound + extra)).max()) <= 1.0
+
+
+@pytest.mark.parametrize("defect,check", [("scale_2^-20", "bias"), ("drop_last_ktile", "ratio"), ("lo_hi_missing", "ratio")])
+def test_scores_bars_catch_planted_defects(scores_case, defect, check):
+    q, gi, gt, qp, gp, nq, ng = scores_case
+    ref, extra = R.panel_scores_emulation(qp, gp, SIM_KAPPA, nq, ng)
+    failed = _score_failures(_scores_cpu(qp, gp, nq, ng, defect), ref, extra)
+    assert check in failed, (defect, failed)
+
+
+def test_representation_bound_is_tight_enough_to_matter(scores_case):
+    """The bf16 panels (terms 1) of the same rows sit within their bound and break the terms-3 bound (worst 9.7 x it here): the
+    terms-3 bound catches a panel whose lo terms are lost on both sides."""
+    q, gi, gt, qp, gp, nq, ng = scores_case
+    qp1 = R.panel_statement([q, q], [0.6, 0.4], None, 1, 0)
+    gp1 = R.panel_statement([gi, gt], None, None, 1, 1)
+    s1, extra1 = R.panel_scores_emulation(qp1, gp1, SIM_KAPPA, nq, ng)
+    rep, b1 = R.panel_representation_bound([q, q], [gi, gt], 1, q_part_scale=[0.6, 0.4])
+    _, b3 = R.panel_representation_bound([q, q], [gi, gt], 3, q_part_scale=[0.6, 0.4])
+    err = (s1 - rep).abs()
+    assert float((err / (b1 + extra1)).max()) <= 1.0
+    assert float((err / (b3 + extra1)).max()) > 4.0
