@@ -36,7 +36,8 @@ extern "C" {
  *    last block's pooled-row area (callers that size their workspace with it need no change).
  * 4: the same entry points with changed defaults and semantics: option "residual_stream_24bit" defaults to 1; the fp8 precisions apply
  *    to the vision tower only and scale the e4m3 A operand per channel; kemr_preprocess_u8_batch accepts 0 x 0 items (an undecodable
- *    image: zeros after normalisation); kemr_debug_set refuses the experiment kernels the library was built without. */
+ *    image: zeros after normalisation); kemr_debug_set refuses the experiment kernels the library was built without.
+ *    Still 4: kemr_select_topk, kemr_sim_topk_deep and kemr_sim_topk_deep_workspace_bytes are additions, no existing entry point changed. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -243,6 +244,29 @@ int kemr_scores_dense(const void* q_panel_dev, int nq, const void* g_panel_dev, 
  * evaluate_retrieval (eval/fusion.py:6-20), evaluator_fusion.py:126.  Either output pair may be NULL. */
 int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t ld, const int32_t* gt_idx_dev,
                     int32_t* ahead_dev, int k, float* top_scores_dev, int32_t* top_idx_dev, void* stream);
+
+/* Deep ranked lists: up to KEMR_MAX_DEEP_K candidates per query, exact, by selection and a sort of the survivors instead of the
+ * register-resident lists behind kemr_sim_topk / kemr_rank_dense (k <= 32).  What the online engine needs to let a SPARQL hit
+ * that CLIP ranks 57th receive its bonus (reference src/retrieval.py:79-95 fuses over CLIP's own list), a shortlist for the
+ * cross_attention head, Recall@100, deduplication.  Same order rule as everywhere: score descending, then lower id; lists are
+ * padded with -inf / -1.  The result is a pure function of the input (same bits on every run).  No ground truth, `ahead` or
+ * bonus arguments: ranks have their own pass and the SPARQL bonus stays with kemr_sim_topk. */
+#define KEMR_MAX_DEEP_K 1024
+/* top-k of materialised rows: scores fp32 [nq, ld] (n <= ld valid columns; nothing at or beyond column n is read), idx int32
+ * [nq, ld] or NULL (id = id_offset + column).  Entries with id < 0 are padding and skipped; the ids of a row must be distinct.
+ * 1 <= k <= KEMR_MAX_DEEP_K; top_scores / top_idx [nq, k].  Ordering: -0.0 ties with +0.0, NaN ranks behind -inf (what
+ * np.argsort(-S, kind="stable") does); the scores written are the input's own bits.  Also the merge of sharded deep lists:
+ * concatenate the shards' lists along the row and pass their ids. */
+int kemr_select_topk(const float* scores_dev, const int32_t* idx_dev, int nq, int n, int64_t ld, int64_t id_offset,
+                     int k, float* top_scores_dev, int32_t* top_idx_dev, void* stream);
+/* Scores + deep top-k without the Q x N matrix leaving the device: the queries are walked in blocks; a block's fp32 scores
+ * against the whole gallery go to the workspace through the dense tile kernel (bit-identical to kemr_scores_dense,
+ * kemr_pair_scores and kemr_sim_topk), the selection runs on the block.  The block is what the workspace holds, rounded down to
+ * a multiple of 128 query rows of ceil4(ng) floats: kemr_sim_topk_deep_workspace_bytes returns the size for min(ceil128(nq),
+ * 1024) rows, any 256-byte aligned workspace of at least 128 rows is accepted, anything smaller is KEMR_ERR_WORKSPACE. */
+size_t kemr_sim_topk_deep_workspace_bytes(int nq, int ng, int64_t kdim, int k);
+int kemr_sim_topk_deep(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim, int64_t gallery_offset,
+                       int k, float* top_scores_dev, int32_t* top_idx_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Gate of the learned gated fusion heads in eval mode (reference src/clip/model/fusion_model.py: SimpleGatedFusion /
  * SimpleGatedFusionWithBias `sigmoid((q * w).sum(1) + b)`, GatedFusionHead `Linear(d,128) -> ReLU -> Linear(128,1) -> Sigmoid`):

@@ -18,7 +18,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 ROOT = os.path.dirname(PKG_DIR)
 LIB_PATH = os.path.join(PKG_DIR, "libkemr.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm256.hip", "gemm256u.hip", "gemm_skinny.hip", "layernorm.hip", "attention.hip", "attention_long.hip", "embed.hip", "sim.hip", "rank.hip", "preprocess.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm256.hip", "gemm256u.hip", "gemm_skinny.hip", "layernorm.hip", "attention.hip", "attention_long.hip", "embed.hip", "sim.hip", "select.hip", "rank.hip", "preprocess.hip"]
 # Experiment kernels kept for A/B timing from tools/ only -- earlier persistent-GEMM generations (gemm_variant 4, 5, 6, 9), the
 # attention variants of round 3 (attn_v 1..4), and, inside the product sources behind -DKEMR_AB_VARIANTS, the staggered 256x256
 # GEMM, the long-interval K loop, the stamped instantiations: built only with `python -m ...build --ab-variants` (or
@@ -65,6 +65,8 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), ab_variant
         (open(stamp, "w").close() if ab_variants else os.remove(stamp))
     if ab_variants:
         extra_flags = list(extra_flags) + ["-DKEMR_AB_VARIANTS"]
+    if not force and not extra_flags and not _stale(LIB_PATH, [os.path.join(CSRC, s) for s in sources] + HEADERS):
+        return LIB_PATH                              # a library newer than every source and header: nothing to do, objects or not
     with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
         objs = list(ex.map(lambda s: _compile(s, force, extra_flags), sources))
     if force or _stale(LIB_PATH, objs):

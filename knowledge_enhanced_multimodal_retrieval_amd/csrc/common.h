@@ -183,6 +183,9 @@ int launch_gemm256w(const GemmParams& p, int epi, hipStream_t stream);  // gemm2
 extern int g_gemm_variant;   // 0 auto, 1 = 128x128 (gemm.hip), 2 / 3 = 256x256 lockstep / staggered, 4 = persistent 256x256 (bf16 epilogues)
 
 // ---- other launchers --------------------------------------------------------------------------
+// select.hip: per row the k <= KEMR_MAX_DEEP_K best of n scores (ids: idx[row][col], or id_offset + col), sorted; arguments checked by the caller
+int launch_select_topk(const float* scores, const int32_t* idx, int nq, int n, long long ld, long long id_offset, int k,
+                       float* top_scores, int32_t* top_idx, hipStream_t stream);
 // delta != nullptr: x += delta (bf16 [rows, width], the previous GEMM's output) is applied first and written back
 // x_dtype (KEMR_F32 / KEMR_BF16) is the storage type of the residual rows
 // delta2 (needs delta and writeback) is added as well; writeback == 0 leaves x as it is and normalises x + delta

@@ -825,6 +825,44 @@ extern "C" int kemr_scores_dense(const void* q_panel_dev, int nq, const void* g_
     return launch_sim<10, true>(p, (hipStream_t)stream);
 }
 
+// Deep lists: the dense tile path writes a block of query rows against the whole gallery into the workspace, the selection
+// kernel (select.hip) takes each row's k best; the next block follows on the same stream.  The scores are kemr_scores_dense's.
+static int64_t deep_ld(int ng) { return round_up(ng, 4); }            // 16-byte aligned workspace rows
+
+extern "C" size_t kemr_sim_topk_deep_workspace_bytes(int nq, int ng, int64_t kdim, int k) {
+    (void)kdim;
+    if (nq <= 0 || ng <= 0 || k <= 0) return 0;
+    const int64_t rows = round_up(nq, ST) < 1024 ? round_up(nq, ST) : 1024;
+    return (size_t)round_up(rows * deep_ld(ng) * 4, 256);
+}
+
+extern "C" int kemr_sim_topk_deep(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim, int64_t gallery_offset,
+                                  int k, float* top_scores_dev, int32_t* top_idx_dev, void* workspace_dev, size_t workspace_bytes,
+                                  void* stream) {
+    KEMR_TRY(check_panels(q_panel_dev, nq, g_panel_dev, ng, kdim));
+    if (k < 1 || k > KEMR_MAX_DEEP_K) KEMR_FAIL(KEMR_ERR_INVALID, "sim_topk_deep: k=%d not in 1..%d", k, KEMR_MAX_DEEP_K);
+    if (!top_scores_dev || !top_idx_dev) KEMR_FAIL(KEMR_ERR_INVALID, "sim_topk_deep: null output");
+    if (gallery_offset < 0 || gallery_offset + ng > 0x7fffffffLL) KEMR_FAIL(KEMR_ERR_INVALID, "sim_topk_deep: candidate ids exceed int32");
+    const int64_t ld = deep_ld(ng);
+    const int64_t fit = (int64_t)(workspace_bytes / ((size_t)ld * 4)) / ST * ST;        // query rows per block: whole 128-row tiles
+    if (!workspace_dev || fit < ST)
+        KEMR_FAIL(KEMR_ERR_WORKSPACE, "sim_topk_deep: workspace %zu < %zu bytes (%d rows of scores)", workspace_bytes, (size_t)ST * ld * 4, ST);
+    if ((uintptr_t)workspace_dev % 256) KEMR_FAIL(KEMR_ERR_WORKSPACE, "sim_topk_deep: workspace must be 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    for (int64_t q0 = 0; q0 < nq; q0 += fit) {
+        const int nb = (int)(nq - q0 < fit ? nq - q0 : fit);
+        SimParams p{};
+        p.Q = (const bf16_t*)q_panel_dev + (size_t)q0 * kdim; p.G = (const bf16_t*)g_panel_dev; p.nq = nb; p.ng = ng; p.kdim = (int)kdim;
+        p.k = 1; p.dense = (float*)workspace_dev; p.ld_dense = ld;
+        p.nchunks = sim_chunks(nb, ng, &p.tiles_per_chunk);
+        p.g_tiles = (ng + ST - 1) / ST;
+        KEMR_TRY((launch_sim<10, true>(p, s)));
+        KEMR_TRY(launch_select_topk((const float*)workspace_dev, nullptr, nb, ng, ld, gallery_offset, k, top_scores_dev + (size_t)q0 * k,
+                                    top_idx_dev + (size_t)q0 * k, s));
+    }
+    return KEMR_OK;
+}
+
 extern "C" int kemr_pair_scores(const void* q_panel_dev, const void* g_panel_dev, int64_t kdim, const int32_t* q_rows_dev,
                                 const int32_t* g_rows_dev, int npairs, float* out_dev, void* stream) {
     if (npairs == 0) return KEMR_OK;

@@ -195,6 +195,24 @@ class ShardedGallery:
         top-k of the WHOLE batch against the WHOLE gallery: (scores [Q, k], global ids [Q, k])."""
         return self.search_async(local_query_parts, weights, k, row_gate).result()
 
+    def search_deep(self, local_query_parts: Sequence[torch.Tensor], weights: Optional[Sequence[float]] = None, k: int = 100,
+                    row_gate=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``search`` for lists of up to 1024 candidates (``kemr_sim_topk_deep``): every shard's k best of the whole query batch are
+        all-gathered as in ``search`` and the [Q, world * k] concatenation is merged by ``select_topk`` with explicit ids."""
+        qp, nq = self._query_panel(local_query_parts, weights, row_gate)
+        dev = local_query_parts[0].device
+        if self.panel is not None:
+            s, i = self.ops.sim_topk_deep(qp, self.panel, k, self.lo)
+        else:
+            s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev)
+            i = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
+        if _skip(self.world):
+            return s, i
+        ss, w1 = all_gather_rows_async(s.unsqueeze(0), self.group)          # [world, Q, k]
+        ii, w2 = all_gather_rows_async(i.unsqueeze(0), self.group)
+        merge = lambda a, b: self.ops.select_topk(a.permute(1, 0, 2).reshape(nq, -1), k, idx=b.permute(1, 0, 2).reshape(nq, -1))
+        return PendingSearch(merge, [w1, w2], (ss, ii)).result()
+
     def search_many(self, batches: Iterable[Sequence[torch.Tensor]], weights: Optional[Sequence[float]] = None, k: int = 10
                     ) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         """A stream of query batches with one batch of lookahead.  ``batches`` is consumed lazily: if producing an element

@@ -391,6 +391,72 @@ def topk_merge(scores: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.T
     return out_s, out_i
 
 
+def select_topk(scores: torch.Tensor, k: int, idx: Optional[torch.Tensor] = None, id_offset: int = 0
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Deep top-k (1 <= k <= 1024) of a materialised fp32 matrix [nq, n] on the GPU: (scores [nq, k], ids [nq, k]), score
+    descending then lower id, padded with -inf / -1.  ids: ``idx`` (int32, same shape and row stride as ``scores``; entries < 0
+    are skipped, the ids of a row are distinct) or ``id_offset + column``.  Row-strided views are read in place."""
+    L = _lib.lib()
+    _require_cuda(scores, "score matrix")
+    if scores.dim() != 2:
+        raise RuntimeError("select_topk: expected a [nq, n] score matrix")
+    scores = scores.to(torch.float32)
+    if scores.stride(-1) != 1 or (scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]):
+        scores = scores.contiguous()
+    nq, n = scores.shape
+    dev = scores.device
+    ld = scores.stride(0) if nq > 1 else max(n, 1)
+    if idx is not None:
+        if tuple(idx.shape) != (nq, n):
+            raise RuntimeError("select_topk: idx must have the shape of scores")
+        idx = idx.to(device=dev, dtype=torch.int32)
+        if idx.stride(-1) != 1 or (nq > 1 and idx.stride(0) != ld):
+            scores, idx, ld = scores.contiguous(), idx.contiguous(), max(n, 1)
+    if not 1 <= k <= _lib.MAX_DEEP_K:
+        raise RuntimeError(f"select_topk: k={k} not in 1..{_lib.MAX_DEEP_K}")
+    top_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    top_i = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    if nq == 0:
+        return top_s, top_i
+    if n == 0:
+        return top_s.fill_(float("-inf")), top_i.fill_(-1)
+    with torch.cuda.device(dev):
+        _lib.check(L.kemr_select_topk(C.c_void_p(scores.data_ptr()), _opt_ptr(idx), nq, n, ld, id_offset, k,
+                                      C.c_void_p(top_s.data_ptr()), C.c_void_p(top_i.data_ptr()), C.c_void_p(_stream_ptr(dev))),
+                   "select_topk")
+    return top_s, top_i
+
+
+def sim_topk_deep(qp: Panel, gp: Panel, k: int, gallery_offset: int = 0, query_block: Optional[int] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Scores + exact top-k for 1 <= k <= 1024: (scores [nq, k], global ids [nq, k]), the scores bit-identical to ``scores_dense`` /
+    ``pair_scores`` / ``sim_topk``.  The queries are walked in blocks of what the workspace holds (default: up to 1024 rows of fp32
+    scores against the whole gallery); ``query_block`` sizes the workspace for that many rows instead (tests: several blocks)."""
+    L = _lib.lib()
+    if qp.kdim != gp.kdim:
+        raise RuntimeError(f"sim_topk_deep: panel kdim mismatch ({qp.kdim} vs {gp.kdim})")
+    if not 1 <= k <= _lib.MAX_DEEP_K:
+        raise RuntimeError(f"sim_topk_deep: k={k} not in 1..{_lib.MAX_DEEP_K}")
+    dev = qp.device
+    nq, ng = qp.rows, gp.rows
+    top_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    top_i = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    if nq == 0:
+        return top_s, top_i
+    if ng == 0:
+        return top_s.fill_(float("-inf")), top_i.fill_(-1)
+    if query_block is None:
+        nbytes = int(L.kemr_sim_topk_deep_workspace_bytes(nq, ng, qp.kdim, k))
+    else:
+        nbytes = int(L.kemr_sim_topk_deep_workspace_bytes(128, ng, qp.kdim, k)) // 128 * int(query_block)
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.kemr_sim_topk_deep(C.c_void_p(qp.data.data_ptr()), nq, C.c_void_p(gp.data.data_ptr()), ng, qp.kdim,
+                                        gallery_offset, k, C.c_void_p(top_s.data_ptr()), C.c_void_p(top_i.data_ptr()),
+                                        C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(_stream_ptr(dev))), "sim_topk_deep")
+    return top_s, top_i
+
+
 def scores_dense(qp: Panel, gp: Panel) -> torch.Tensor:
     """Dense fp32 score matrix [nq, ng] (fusion heads that need every pair; debugging)."""
     L = _lib.lib()

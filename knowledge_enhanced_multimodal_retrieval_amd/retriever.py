@@ -27,6 +27,7 @@ import torch
 from . import _lib, engine, ranking
 
 MAX_TOP_K = 32
+MAX_DEEP_TOP_K = 1024        # search_deep / retrieve_text_deep: kemr_sim_topk_deep (selection + sort instead of register lists)
 
 
 class EmbeddingStore:
@@ -105,6 +106,22 @@ class CLIPRetriever:
         scores, idx = scores[0].cpu().tolist(), idx[0].cpu().tolist()
         return [{"uuid": self.store.uuids[i], "score": float(s)} for s, i in zip(scores, idx) if i >= 0]
 
+    @torch.no_grad()
+    def search_batch_deep(self, queries: Sequence[str], alpha: float = 0.5, top_k: int = 200):
+        """``search_batch`` for lists of up to MAX_DEEP_TOP_K candidates: the same scores and order, by ``engine.sim_topk_deep``."""
+        if not 1 <= top_k <= MAX_DEEP_TOP_K:
+            raise ValueError(f"top_k must be in 1..{MAX_DEEP_TOP_K}")
+        ids = self.tokenize_fn(list(queries))
+        q = self.model.encode_text(ids, normalize=True)
+        qp = engine.build_panel([q, q], _lib.SIDE_QUERY, ranking.PRECISION_TERMS[self.store.precision],
+                                part_scale=[alpha, 1.0 - alpha])
+        return engine.sim_topk_deep(qp, self.store.panel, min(top_k, len(self.store)))
+
+    def search_deep(self, query: str, alpha: float = 0.5, top_k: int = 200) -> List[Dict]:
+        scores, idx = self.search_batch_deep([query], alpha, top_k)
+        scores, idx = scores[0].cpu().tolist(), idx[0].cpu().tolist()
+        return [{"uuid": self.store.uuids[i], "score": float(s)} for s, i in zip(scores, idx) if i >= 0]
+
 
 class CLIPRetrieval:
     """``CLIPRetrieval(model_name=None).retrieval(query, alpha=0.5)`` (reference src/clip/clip_retrieval.py:10-40),
@@ -116,6 +133,10 @@ class CLIPRetrieval:
 
     def retrieval(self, query: str, alpha: float = 0.5):
         return self.retriever.search(query, alpha=alpha)
+
+    def retrieval_deep(self, query: str, alpha: float = 0.5, depth: int = 200):
+        """The ``depth`` best instead of the ten of ``retrieval`` (this build's addition: candidates for the SPARQL fusion)."""
+        return self.retriever.search_deep(query, alpha=alpha, top_k=depth)
 
 
 class NoText2SPARQL:
@@ -147,6 +168,16 @@ class RetrievalEngine:
 
     def retrieve_text(self, query: str, alpha: float = 0.8, beta: float = 0.2, alpha_clip: float = 0.5, threshold: float = 0):
         clip_results = self.clip_retriever.retrieval(query, alpha=alpha_clip)
+        t2s_results = self.t2s_retriever.retrieval(query)
+        fused = self._fuse_clip_sparql_linear(clip_results=clip_results, sparql_results=t2s_results, alpha=alpha, beta=beta)
+        return [{"uuid": it["uuid"], "score": it["score"]} for it in fused if it.get("score", 0) >= threshold]
+
+    def retrieve_text_deep(self, query: str, alpha: float = 0.8, beta: float = 0.2, alpha_clip: float = 0.5, threshold: float = 0,
+                           depth: int = 200):
+        """``retrieve_text`` over the ``depth`` best CLIP candidates instead of CLIP's own ten: the same linear fusion, so a SPARQL
+        hit that CLIP ranks anywhere among them receives ``beta`` and can be lifted, and ``threshold`` selects from a list long
+        enough to mean "everything that scores at least t".  (This build's addition; the reference has no counterpart.)"""
+        clip_results = self.clip_retriever.retrieval_deep(query, alpha=alpha_clip, depth=depth)
         t2s_results = self.t2s_retriever.retrieval(query)
         fused = self._fuse_clip_sparql_linear(clip_results=clip_results, sparql_results=t2s_results, alpha=alpha, beta=beta)
         return [{"uuid": it["uuid"], "score": it["score"]} for it in fused if it.get("score", 0) >= threshold]
