@@ -37,7 +37,8 @@ extern "C" {
  * 4: the same entry points with changed defaults and semantics: option "residual_stream_24bit" defaults to 1; the fp8 precisions apply
  *    to the vision tower only and scale the e4m3 A operand per channel; kemr_preprocess_u8_batch accepts 0 x 0 items (an undecodable
  *    image: zeros after normalisation); kemr_debug_set refuses the experiment kernels the library was built without.
- *    Still 4: kemr_select_topk, kemr_sim_topk_deep and kemr_sim_topk_deep_workspace_bytes are additions, no existing entry point changed. */
+ *    Still 4: kemr_select_topk, kemr_sim_topk_deep, kemr_sim_topk_deep_workspace_bytes and kemr_sim_topk_deep_fused are additions, no
+ *    existing entry point changed. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -249,8 +250,8 @@ int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t ld, const i
  * register-resident lists behind kemr_sim_topk / kemr_rank_dense (k <= 32).  What the online engine needs to let a SPARQL hit
  * that CLIP ranks 57th receive its bonus (reference src/retrieval.py:79-95 fuses over CLIP's own list), a shortlist for the
  * cross_attention head, Recall@100, deduplication.  Same order rule as everywhere: score descending, then lower id; lists are
- * padded with -inf / -1.  The result is a pure function of the input (same bits on every run).  No ground truth, `ahead` or
- * bonus arguments: ranks have their own pass and the SPARQL bonus stays with kemr_sim_topk. */
+ * padded with -inf / -1.  The result is a pure function of the input (same bits on every run).  kemr_select_topk and
+ * kemr_sim_topk_deep take no ground truth, `ahead` or bonus arguments; kemr_sim_topk_deep_fused is the deep route with them. */
 #define KEMR_MAX_DEEP_K 1024
 /* top-k of materialised rows: scores fp32 [nq, ld] (n <= ld valid columns; nothing at or beyond column n is read), idx int32
  * [nq, ld] or NULL (id = id_offset + column).  Entries with id < 0 are padding and skipped; the ids of a row must be distinct.
@@ -267,6 +268,22 @@ int kemr_select_topk(const float* scores_dev, const int32_t* idx_dev, int nq, in
 size_t kemr_sim_topk_deep_workspace_bytes(int nq, int ng, int64_t kdim, int k);
 int kemr_sim_topk_deep(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim, int64_t gallery_offset,
                        int k, float* top_scores_dev, int32_t* top_idx_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* kemr_sim_topk_deep with the knowledge side: the arguments of kemr_sim_topk in its order, 1 <= k <= KEMR_MAX_DEEP_K (rank only,
+ * k == 0, stays with kemr_sim_topk), the workspace of kemr_sim_topk_deep (the bonus is applied in place on the block of scores).
+ * Per block of query rows, between the score pass and the selection:
+ *   bonus (rowptr int32 [nq + 1], col int32 GLOBAL ids ascending within a row, val fp32; all three or none): every entry whose
+ *     column lies in [gallery_offset, gallery_offset + ng) is added to its score, entries of one column one after the other in
+ *     list order in fp32 -- the fused score has the bits kemr_sim_topk computes from the same list; the lists hold fused scores;
+ *   ground truth (gt_idx int32 [nq] GLOBAL ids that may lie outside this gallery, gt_score fp32 [nq] = the pair's fused score as
+ *     the caller computed it, ahead int32 [nq]; all three or none): ahead[q] += the candidates of this gallery other than gt_idx[q]
+ *     whose fused score ranks before (gt_score[q], gt_idx[q]) -- accumulated, so that shards sum; an integer count that does not
+ *     depend on the order anything arrives in.
+ * A partial triple is KEMR_ERR_INVALID; with all six NULL the call is kemr_sim_topk_deep, bit for bit. */
+int kemr_sim_topk_deep_fused(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim, int64_t gallery_offset,
+                             int k, float* top_scores_dev, int32_t* top_idx_dev,
+                             const int32_t* gt_idx_dev, const float* gt_score_dev, int32_t* ahead_dev,
+                             const int32_t* bonus_rowptr_dev, const int32_t* bonus_col_dev, const float* bonus_val_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Gate of the learned gated fusion heads in eval mode (reference src/clip/model/fusion_model.py: SimpleGatedFusion /
  * SimpleGatedFusionWithBias `sigmoid((q * w).sum(1) + b)`, GatedFusionHead `Linear(d,128) -> ReLU -> Linear(128,1) -> Sigmoid`):

@@ -37,7 +37,7 @@ TOWER_VISION, TOWER_TEXT = 0, 1
 SIDE_QUERY, SIDE_GALLERY = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RESID_F32 = 0, 1, 2
 EPI_BIAS_RESADD_BF16 = 4
-MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep
+MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused
 
 
 class KemrCfg(C.Structure):
@@ -75,6 +75,7 @@ SIGNATURES = {
     "kemr_select_topk": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp, _vp]),
     "kemr_sim_topk_deep_workspace_bytes": (_sz, [_i, _i, _i64, _i]),
     "kemr_sim_topk_deep": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "kemr_sim_topk_deep_fused": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "kemr_linear_head": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "kemr_gate_rows": (_i, [_vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "kemr_cross_attention_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -184,8 +184,11 @@ extern int g_gemm_variant;   // 0 auto, 1 = 128x128 (gemm.hip), 2 / 3 = 256x256 
 
 // ---- other launchers --------------------------------------------------------------------------
 // select.hip: per row the k <= KEMR_MAX_DEEP_K best of n scores (ids: idx[row][col], or id_offset + col), sorted; arguments checked by the caller
+// gt_idx != nullptr (with gt_score and ahead, [nq] each; idx must be nullptr): ahead[row] += the row's entries that rank before
+// (gt_score[row], gt_idx[row]) under the order rule, the entry whose id is gt_idx[row] itself left out -- counted in the first sweep
 int launch_select_topk(const float* scores, const int32_t* idx, int nq, int n, long long ld, long long id_offset, int k,
-                       float* top_scores, int32_t* top_idx, hipStream_t stream);
+                       float* top_scores, int32_t* top_idx, hipStream_t stream, const int32_t* gt_idx = nullptr,
+                       const float* gt_score = nullptr, int32_t* ahead = nullptr);
 // delta != nullptr: x += delta (bf16 [rows, width], the previous GEMM's output) is applied first and written back
 // x_dtype (KEMR_F32 / KEMR_BF16) is the storage type of the residual rows
 // delta2 (needs delta and writeback) is added as well; writeback == 0 leaves x as it is and normalises x + delta

@@ -74,14 +74,22 @@ __device__ __forceinline__ void select_for_each(const float* __restrict__ row, c
     if (tid < n - tail) one(tail + tid, row[tail + tid]);
 }
 
+// COUNT (kemr_sim_topk_deep_fused with a ground truth; ids are id_offset + column): the first sweep -- the one pass that sees every
+// entry of the row -- also counts the entries that rank before (gt_score[row], gt_idx[row]) and adds the sum to ahead[row].  On the
+// keys that is `key > key(gt_score, gt_idx)`: the key order IS sim.hip's ranks_before (score descending, -0.0 == +0.0, then lower
+// id; a NaN entry ranks before nothing finite), except for a NaN gt_score, before which ranks_before puts nothing: no count then.
+// The entry with the ground truth's own id is left out whatever its score.  Integer sums: wave shuffles, one LDS atomic per wave.
+template <bool COUNT>
 __global__ __launch_bounds__(SEL_THREADS) void select_topk_kernel(const float* __restrict__ S, const int32_t* __restrict__ I, int n,
                                                                   long long ld, long long id_offset, int k,
-                                                                  float* __restrict__ top_s, int32_t* __restrict__ top_i) {
+                                                                  float* __restrict__ top_s, int32_t* __restrict__ top_i,
+                                                                  const int32_t* __restrict__ gt_idx, const float* __restrict__ gt_score,
+                                                                  int32_t* __restrict__ ahead) {
     __shared__ u64 s_key[SEL_CAP];                    // 32 KiB
     __shared__ int s_hist[SEL_BINS];                  // 16 KiB; the gathered columns once the last histogram is read
     __shared__ int s_wave[SEL_THREADS / 64];
     __shared__ int s_pick[3];                         // boundary bin, entries in the bins above it, entries in it
-    __shared__ int s_total, s_fill;
+    __shared__ int s_total, s_fill, s_ahead;
     int* s_col = s_hist;
     static_assert(SEL_CAP <= SEL_BINS, "the gathered columns alias the histogram");
 
@@ -96,14 +104,31 @@ __global__ __launch_bounds__(SEL_THREADS) void select_topk_kernel(const float* _
     int need = k;             // keys still to take out of the entries that share the prefix
     int above = 0;            // entries known to rank before all of those
     int gathered = 0;
+    u64 gt_key = ~0ull;       // COUNT: the ground truth's key; all ones (above every key) = count nothing
+    if constexpr (COUNT) {
+        const float sg = gt_score[blockIdx.x];
+        if (sg == sg) gt_key = select_key(sg, gt_idx[blockIdx.x]);
+        if (tid == 0) s_ahead = 0;
+    }
     for (;;) {
         const int dbits = 64 - bits < SEL_DIGIT ? 64 - bits : SEL_DIGIT;
         const int shift = 64 - bits - dbits;
         for (int b = tid; b < SEL_BINS; b += SEL_THREADS) s_hist[b] = 0;
         __syncthreads();
-        select_for_each(row, ids, n, id_offset, tid, [&](u64 key, int) {
-            if (bits == 0 || (key >> (64 - bits)) == prefix) atomicAdd(&s_hist[(int)((key >> shift) & (u64)((1 << dbits) - 1))], 1);
-        });
+        if (COUNT && bits == 0) {
+            int cnt = 0;
+            select_for_each(row, ids, n, id_offset, tid, [&](u64 key, int) {
+                atomicAdd(&s_hist[(int)(key >> shift)], 1);
+                cnt += (key > gt_key && (uint32_t)key != (uint32_t)gt_key) ? 1 : 0;
+            });
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+            if (lane == 0 && cnt) atomicAdd(&s_ahead, cnt);
+        } else {
+            select_for_each(row, ids, n, id_offset, tid, [&](u64 key, int) {
+                if (bits == 0 || (key >> (64 - bits)) == prefix) atomicAdd(&s_hist[(int)((key >> shift) & (u64)((1 << dbits) - 1))], 1);
+            });
+        }
         __syncthreads();
         // inclusive suffix sums over the threads' groups of four bins
         const int h0 = s_hist[4 * tid], h1 = s_hist[4 * tid + 1], h2 = s_hist[4 * tid + 2], h3 = s_hist[4 * tid + 3];
@@ -180,11 +205,22 @@ __global__ __launch_bounds__(SEL_THREADS) void select_topk_kernel(const float* _
         out_s[j] = c >= 0 ? row[c] : -INFINITY;
         out_i[j] = c >= 0 ? (ids ? ids[c] : (int)(id_offset + c)) : -1;
     }
+    if constexpr (COUNT) {
+        if (tid == 0 && s_ahead) ahead[blockIdx.x] += s_ahead;       // one workgroup per row: a plain add, shards follow on the stream
+    }
 }
 
 int launch_select_topk(const float* scores, const int32_t* idx, int nq, int n, long long ld, long long id_offset, int k,
-                       float* top_scores, int32_t* top_idx, hipStream_t stream) {
-    hipLaunchKernelGGL(select_topk_kernel, dim3(nq), dim3(SEL_THREADS), 0, stream, scores, idx, n, ld, id_offset, k, top_scores, top_idx);
+                       float* top_scores, int32_t* top_idx, hipStream_t stream, const int32_t* gt_idx, const float* gt_score,
+                       int32_t* ahead) {
+    if (gt_idx) {
+        if (idx || !gt_score || !ahead) KEMR_FAIL(KEMR_ERR_INVALID, "select_topk: the rank count takes id_offset ids and gt_idx, gt_score, ahead together");
+        hipLaunchKernelGGL(select_topk_kernel<true>, dim3(nq), dim3(SEL_THREADS), 0, stream, scores, idx, n, ld, id_offset, k, top_scores,
+                           top_idx, gt_idx, gt_score, ahead);
+    } else {
+        hipLaunchKernelGGL(select_topk_kernel<false>, dim3(nq), dim3(SEL_THREADS), 0, stream, scores, idx, n, ld, id_offset, k, top_scores,
+                           top_idx, nullptr, nullptr, nullptr);
+    }
     KEMR_CHECK_LAUNCH("select_topk_kernel");
     return KEMR_OK;
 }

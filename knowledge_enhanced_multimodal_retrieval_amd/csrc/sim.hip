@@ -836,18 +836,46 @@ extern "C" size_t kemr_sim_topk_deep_workspace_bytes(int nq, int ng, int64_t kdi
     return (size_t)round_up(rows * deep_ld(ng) * 4, 256);
 }
 
-extern "C" int kemr_sim_topk_deep(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim, int64_t gallery_offset,
-                                  int k, float* top_scores_dev, int32_t* top_idx_dev, void* workspace_dev, size_t workspace_bytes,
-                                  void* stream) {
+// The SPARQL bonus of the deep route, in place on a block of score rows (block row r = query row q0 + r): one wave per row, a lane
+// per CSR entry.  Columns ascend within a row, so the entries of one candidate are adjacent: the lane that holds the first of such
+// a run adds the whole run in list order (fp32, one add per entry: the bits of sim_kernel's `sc += bval[...]`), the lanes behind it
+// in the run do nothing -- no two lanes touch one score.  Entries outside [goff, goff + ng) are skipped.
+__global__ __launch_bounds__(256) void deep_bonus_kernel(float* __restrict__ block, long long ld, int nb, int ng, long long q0,
+                                                         long long goff, const int32_t* __restrict__ brow,
+                                                         const int32_t* __restrict__ bcol, const float* __restrict__ bval) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= nb) return;
+    const int e0 = brow[q0 + r], e1 = brow[q0 + r + 1];          // the GLOBAL query row's list
+    float* row = block + (size_t)r * ld;
+    for (int e = e0 + lane; e < e1; e += 64) {
+        const int c = bcol[e];
+        if (e > e0 && bcol[e - 1] == c) continue;                // inside a run: its first entry's lane adds it
+        const long long loc = (long long)c - goff;
+        if (loc < 0 || loc >= ng) continue;
+        float sc = row[loc];
+        for (int t = e; t < e1 && bcol[t] == c; ++t) sc += bval[t];
+        row[loc] = sc;
+    }
+}
+
+static int sim_topk_deep_run(const char* what, const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim,
+                             int64_t gallery_offset, int k, float* top_scores_dev, int32_t* top_idx_dev, const int32_t* gt_idx_dev,
+                             const float* gt_score_dev, int32_t* ahead_dev, const int32_t* bonus_rowptr_dev, const int32_t* bonus_col_dev,
+                             const float* bonus_val_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
     KEMR_TRY(check_panels(q_panel_dev, nq, g_panel_dev, ng, kdim));
-    if (k < 1 || k > KEMR_MAX_DEEP_K) KEMR_FAIL(KEMR_ERR_INVALID, "sim_topk_deep: k=%d not in 1..%d", k, KEMR_MAX_DEEP_K);
-    if (!top_scores_dev || !top_idx_dev) KEMR_FAIL(KEMR_ERR_INVALID, "sim_topk_deep: null output");
-    if (gallery_offset < 0 || gallery_offset + ng > 0x7fffffffLL) KEMR_FAIL(KEMR_ERR_INVALID, "sim_topk_deep: candidate ids exceed int32");
+    if (k < 1 || k > KEMR_MAX_DEEP_K) KEMR_FAIL(KEMR_ERR_INVALID, "%s: k=%d not in 1..%d", what, k, KEMR_MAX_DEEP_K);
+    if (!top_scores_dev || !top_idx_dev) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null output", what);
+    if ((gt_idx_dev != nullptr) != (gt_score_dev != nullptr) || (gt_idx_dev != nullptr) != (ahead_dev != nullptr))
+        KEMR_FAIL(KEMR_ERR_INVALID, "%s: gt_idx, gt_score and ahead must be given together", what);
+    if ((bonus_rowptr_dev != nullptr) != (bonus_col_dev != nullptr) || (bonus_rowptr_dev != nullptr) != (bonus_val_dev != nullptr))
+        KEMR_FAIL(KEMR_ERR_INVALID, "%s: bonus CSR arrays must be given together", what);
+    if (gallery_offset < 0 || gallery_offset + ng > 0x7fffffffLL) KEMR_FAIL(KEMR_ERR_INVALID, "%s: candidate ids exceed int32", what);
     const int64_t ld = deep_ld(ng);
     const int64_t fit = (int64_t)(workspace_bytes / ((size_t)ld * 4)) / ST * ST;        // query rows per block: whole 128-row tiles
     if (!workspace_dev || fit < ST)
-        KEMR_FAIL(KEMR_ERR_WORKSPACE, "sim_topk_deep: workspace %zu < %zu bytes (%d rows of scores)", workspace_bytes, (size_t)ST * ld * 4, ST);
-    if ((uintptr_t)workspace_dev % 256) KEMR_FAIL(KEMR_ERR_WORKSPACE, "sim_topk_deep: workspace must be 256-byte aligned");
+        KEMR_FAIL(KEMR_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (%d rows of scores)", what, workspace_bytes, (size_t)ST * ld * 4, ST);
+    if ((uintptr_t)workspace_dev % 256) KEMR_FAIL(KEMR_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", what);
     hipStream_t s = (hipStream_t)stream;
     for (int64_t q0 = 0; q0 < nq; q0 += fit) {
         const int nb = (int)(nq - q0 < fit ? nq - q0 : fit);
@@ -857,10 +885,35 @@ extern "C" int kemr_sim_topk_deep(const void* q_panel_dev, int nq, const void* g
         p.nchunks = sim_chunks(nb, ng, &p.tiles_per_chunk);
         p.g_tiles = (ng + ST - 1) / ST;
         KEMR_TRY((launch_sim<10, true>(p, s)));
+        if (bonus_rowptr_dev) {
+            hipLaunchKernelGGL(deep_bonus_kernel, dim3((nb + 3) / 4), dim3(256), 0, s, (float*)workspace_dev, (long long)ld, nb, ng,
+                               (long long)q0, (long long)gallery_offset, bonus_rowptr_dev, bonus_col_dev, bonus_val_dev);
+            KEMR_CHECK_LAUNCH("deep_bonus_kernel");
+        }
         KEMR_TRY(launch_select_topk((const float*)workspace_dev, nullptr, nb, ng, ld, gallery_offset, k, top_scores_dev + (size_t)q0 * k,
-                                    top_idx_dev + (size_t)q0 * k, s));
+                                    top_idx_dev + (size_t)q0 * k, s, gt_idx_dev ? gt_idx_dev + q0 : nullptr,
+                                    gt_idx_dev ? gt_score_dev + q0 : nullptr, gt_idx_dev ? ahead_dev + q0 : nullptr));
     }
     return KEMR_OK;
+}
+
+extern "C" int kemr_sim_topk_deep(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim, int64_t gallery_offset,
+                                  int k, float* top_scores_dev, int32_t* top_idx_dev, void* workspace_dev, size_t workspace_bytes,
+                                  void* stream) {
+    return sim_topk_deep_run("sim_topk_deep", q_panel_dev, nq, g_panel_dev, ng, kdim, gallery_offset, k, top_scores_dev, top_idx_dev, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, nullptr, workspace_dev, workspace_bytes, stream);
+}
+
+// + the SPARQL bonus applied to each block of scores before the selection, and the ground-truth rank count taken in the selection
+// kernel's first sweep of the fused rows (select.hip).  All six optional pointers null: kemr_sim_topk_deep, the same launches.
+extern "C" int kemr_sim_topk_deep_fused(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim,
+                                        int64_t gallery_offset, int k, float* top_scores_dev, int32_t* top_idx_dev,
+                                        const int32_t* gt_idx_dev, const float* gt_score_dev, int32_t* ahead_dev,
+                                        const int32_t* bonus_rowptr_dev, const int32_t* bonus_col_dev, const float* bonus_val_dev,
+                                        void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return sim_topk_deep_run("sim_topk_deep_fused", q_panel_dev, nq, g_panel_dev, ng, kdim, gallery_offset, k, top_scores_dev, top_idx_dev,
+                             gt_idx_dev, gt_score_dev, ahead_dev, bonus_rowptr_dev, bonus_col_dev, bonus_val_dev, workspace_dev,
+                             workspace_bytes, stream);
 }
 
 extern "C" int kemr_pair_scores(const void* q_panel_dev, const void* g_panel_dev, int64_t kdim, const int32_t* q_rows_dev,

@@ -196,13 +196,18 @@ class ShardedGallery:
         return self.search_async(local_query_parts, weights, k, row_gate).result()
 
     def search_deep(self, local_query_parts: Sequence[torch.Tensor], weights: Optional[Sequence[float]] = None, k: int = 100,
-                    row_gate=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                    row_gate=None, bonus=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``search`` for lists of up to 1024 candidates (``kemr_sim_topk_deep``): every shard's k best of the whole query batch are
-        all-gathered as in ``search`` and the [Q, world * k] concatenation is merged by ``select_topk`` with explicit ids."""
+        all-gathered as in ``search`` and the [Q, world * k] concatenation is merged by ``select_topk`` with explicit ids.
+        ``bonus``: a CSR ``(rowptr, col, val)`` over the WHOLE gathered query batch with GLOBAL column ids, the same on every rank;
+        each shard adds the entries that fall into its own id range (``kemr_sim_topk_deep_fused``) and the lists hold fused scores."""
         qp, nq = self._query_panel(local_query_parts, weights, row_gate)
         dev = local_query_parts[0].device
         if self.panel is not None:
-            s, i = self.ops.sim_topk_deep(qp, self.panel, k, self.lo)
+            if bonus is None:
+                s, i = self.ops.sim_topk_deep(qp, self.panel, k, self.lo)
+            else:
+                s, i = self.ops.sim_topk_deep(qp, self.panel, k, self.lo, bonus=bonus)
         else:
             s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev)
             i = torch.full((nq, k), -1, dtype=torch.int32, device=dev)

@@ -427,11 +427,19 @@ def select_topk(scores: torch.Tensor, k: int, idx: Optional[torch.Tensor] = None
     return top_s, top_i
 
 
-def sim_topk_deep(qp: Panel, gp: Panel, k: int, gallery_offset: int = 0, query_block: Optional[int] = None
+def sim_topk_deep(qp: Panel, gp: Panel, k: int, gallery_offset: int = 0, query_block: Optional[int] = None,
+                  gt_idx: Optional[torch.Tensor] = None, gt_score: Optional[torch.Tensor] = None,
+                  ahead: Optional[torch.Tensor] = None,
+                  bonus: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None
                   ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Scores + exact top-k for 1 <= k <= 1024: (scores [nq, k], global ids [nq, k]), the scores bit-identical to ``scores_dense`` /
     ``pair_scores`` / ``sim_topk``.  The queries are walked in blocks of what the workspace holds (default: up to 1024 rows of fp32
-    scores against the whole gallery); ``query_block`` sizes the workspace for that many rows instead (tests: several blocks)."""
+    scores against the whole gallery); ``query_block`` sizes the workspace for that many rows instead (tests: several blocks).
+
+    ``bonus`` (CSR ``(rowptr [nq + 1], col, val)``, GLOBAL column ids ascending within a row) is added to the scores before the
+    selection, and with ``gt_idx`` (GLOBAL ids) / ``gt_score`` / ``ahead`` (int32, accumulated) the candidates ranked before the
+    ground truth are counted on the fused scores in the same call (``kemr_sim_topk_deep_fused``): the arguments, conversions and
+    checks of ``sim_topk``.  Without them the call is ``kemr_sim_topk_deep``."""
     L = _lib.lib()
     if qp.kdim != gp.kdim:
         raise RuntimeError(f"sim_topk_deep: panel kdim mismatch ({qp.kdim} vs {gp.kdim})")
@@ -445,15 +453,43 @@ def sim_topk_deep(qp: Panel, gp: Panel, k: int, gallery_offset: int = 0, query_b
         return top_s, top_i
     if ng == 0:
         return top_s.fill_(float("-inf")), top_i.fill_(-1)
+    if gt_idx is not None:
+        if gt_score is None or ahead is None:
+            raise RuntimeError("sim_topk_deep: gt_idx needs gt_score and ahead")
+        gt_idx = gt_idx.to(device=dev, dtype=torch.int32).contiguous()
+        gt_score = gt_score.to(device=dev, dtype=torch.float32).contiguous()
+        if ahead.dtype != torch.int32 or not ahead.is_contiguous() or ahead.device != dev:
+            raise RuntimeError("sim_topk_deep: ahead must be a contiguous int32 tensor on the panel's device")
+        if gt_idx.numel() != nq or gt_score.numel() != nq or ahead.numel() != nq:
+            raise RuntimeError("sim_topk_deep: gt_idx, gt_score and ahead must have one entry per query")
+    b_ptr = b_col = b_val = None
+    if bonus is not None and len(bonus[1]) == 0:      # no hit at all: same as no bonus (empty tensors have no address)
+        bonus = None
+    if bonus is not None:
+        b_ptr, b_col, b_val = (torch.as_tensor(bonus[0]).to(device=dev, dtype=torch.int32).contiguous(),
+                               torch.as_tensor(bonus[1]).to(device=dev, dtype=torch.int32).contiguous(),
+                               torch.as_tensor(bonus[2]).to(device=dev, dtype=torch.float32).contiguous())
+        if b_ptr.numel() != nq + 1:
+            raise RuntimeError("sim_topk_deep: bonus row pointer must have nq + 1 entries")
+        if b_val.numel() != b_col.numel():
+            raise RuntimeError("sim_topk_deep: bonus col and val must have one entry per hit")
     if query_block is None:
         nbytes = int(L.kemr_sim_topk_deep_workspace_bytes(nq, ng, qp.kdim, k))
     else:
         nbytes = int(L.kemr_sim_topk_deep_workspace_bytes(128, ng, qp.kdim, k)) // 128 * int(query_block)
     ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(L.kemr_sim_topk_deep(C.c_void_p(qp.data.data_ptr()), nq, C.c_void_p(gp.data.data_ptr()), ng, qp.kdim,
-                                        gallery_offset, k, C.c_void_p(top_s.data_ptr()), C.c_void_p(top_i.data_ptr()),
-                                        C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(_stream_ptr(dev))), "sim_topk_deep")
+        if gt_idx is None and ahead is None and gt_score is None and bonus is None:
+            _lib.check(L.kemr_sim_topk_deep(C.c_void_p(qp.data.data_ptr()), nq, C.c_void_p(gp.data.data_ptr()), ng, qp.kdim,
+                                            gallery_offset, k, C.c_void_p(top_s.data_ptr()), C.c_void_p(top_i.data_ptr()),
+                                            C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(_stream_ptr(dev))), "sim_topk_deep")
+        else:
+            _lib.check(L.kemr_sim_topk_deep_fused(C.c_void_p(qp.data.data_ptr()), nq, C.c_void_p(gp.data.data_ptr()), ng, qp.kdim,
+                                                  gallery_offset, k, C.c_void_p(top_s.data_ptr()), C.c_void_p(top_i.data_ptr()),
+                                                  _opt_ptr(gt_idx), _opt_ptr(gt_score), _opt_ptr(ahead),
+                                                  _opt_ptr(b_ptr), _opt_ptr(b_col), _opt_ptr(b_val),
+                                                  C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(_stream_ptr(dev))),
+                       "sim_topk_deep_fused")
     return top_s, top_i
 
 

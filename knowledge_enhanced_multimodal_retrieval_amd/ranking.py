@@ -50,8 +50,32 @@ def ranks_and_topk(query_parts: Sequence[ArrayLike], gallery_parts: Sequence[Arr
     Returns (ranks int64 [nq] (1-based, None when gt_idx is None), top scores [nq,k], top ids [nq,k]).
     gt_idx: "diag" (query i <-> candidate i, metrics.py:37), an index array of GLOBAL candidate ids, or None.
     """
+    qp, gp, gt, sgt, ahead = _panels_and_ground_truth(query_parts, gallery_parts, weights, row_gate, precision, gt_idx, bonus,
+                                                      gallery_offset)
+    top_s, top_i = engine.sim_topk(qp, gp, k, gallery_offset, gt, sgt, ahead, bonus)
+    ranks = None if ahead is None else ahead.long() + 1
+    return ranks, top_s, top_i
+
+
+def ranks_and_topk_deep(query_parts: Sequence[ArrayLike], gallery_parts: Sequence[ArrayLike],
+                        weights: Optional[Sequence[float]] = None, row_gate: Optional[Sequence[Optional[ArrayLike]]] = None,
+                        k: int = 100, precision: str = "fp32x3", gt_idx: Optional[ArrayLike] = "diag",
+                        bonus: Optional[Tuple[ArrayLike, ArrayLike, ArrayLike]] = None, gallery_offset: int = 0,
+                        query_block: Optional[int] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """``ranks_and_topk`` for lists of 1 <= k <= 1024 candidates (``engine.sim_topk_deep``: the bonus and the rank count inside the
+    deep route, one scoring pass): the same score, arguments and return value; ``query_block`` as in ``engine.sim_topk_deep``."""
+    if not 1 <= k <= _lib.MAX_DEEP_K:
+        raise ValueError(f"ranks_and_topk_deep: k={k} not in 1..{_lib.MAX_DEEP_K} (rank only, k = 0: ranks_and_topk)")
+    qp, gp, gt, sgt, ahead = _panels_and_ground_truth(query_parts, gallery_parts, weights, row_gate, precision, gt_idx, bonus,
+                                                      gallery_offset)
+    top_s, top_i = engine.sim_topk_deep(qp, gp, k, gallery_offset, query_block, gt, sgt, ahead, bonus)
+    ranks = None if ahead is None else ahead.long() + 1
+    return ranks, top_s, top_i
+
+
+def _panels_and_ground_truth(query_parts, gallery_parts, weights, row_gate, precision, gt_idx, bonus, gallery_offset):
+    """The operands both routes share: (query panel, gallery panel, gt ids, the ground-truth pairs' fused scores, zeroed ahead)."""
     terms = PRECISION_TERMS[precision]
-    dev = None
     qs = [to_device_f32(p) for p in query_parts]
     dev = qs[0].device
     gs = [to_device_f32(p, dev) for p in gallery_parts]
@@ -80,9 +104,7 @@ def ranks_and_topk(query_parts: Sequence[ArrayLike], gallery_parts: Sequence[Arr
             raise ValueError("ground-truth ids must lie inside this gallery (sharded use: see dist.py)")
         _require_finite(sgt, "ground-truth scores")
         ahead = torch.zeros(nq, dtype=torch.int32, device=dev)
-    top_s, top_i = engine.sim_topk(qp, gp, k, gallery_offset, gt, sgt, ahead, bonus)
-    ranks = None if ahead is None else ahead.long() + 1
-    return ranks, top_s, top_i
+    return qp, gp, gt, sgt, ahead
 
 
 def _bonus_of_pairs(bonus, gt: torch.Tensor, dev) -> torch.Tensor:

@@ -25,9 +25,23 @@ import numpy as np
 import torch
 
 from . import _lib, engine, ranking
+from .sparql_fusion import _uri_tail
 
 MAX_TOP_K = 32
 MAX_DEEP_TOP_K = 1024        # search_deep / retrieve_text_deep: kemr_sim_topk_deep (selection + sort instead of register lists)
+
+
+def hits_to_csr(hits_per_query: Sequence[Sequence[str]], row_of: Dict[str, int], value: float):
+    """SPARQL hit lists (uuids or URIs, one list per query) -> the one-value bonus CSR ``(rowptr int32 [Q + 1], col int32, val fp32)``
+    of ``engine.sim_topk_deep``: a URI counts by its tail after the last ``/`` (``sparql_fusion._uri_tail``), ids that ``row_of``
+    (uuid -> gallery row) does not hold are ignored, an id listed twice counts once (the reference tests
+    ``uuid in set(sparql_results)``), columns ascend within a row."""
+    rowptr = np.zeros(len(hits_per_query) + 1, np.int32)
+    cols: List[int] = []
+    for r, hits in enumerate(hits_per_query):
+        cols.extend(sorted({row_of[t] for t in map(_uri_tail, hits) if t in row_of}))
+        rowptr[r + 1] = len(cols)
+    return rowptr, np.asarray(cols, np.int32), np.full(len(cols), value, np.float32)
 
 
 class EmbeddingStore:
@@ -40,10 +54,25 @@ class EmbeddingStore:
         if self.image.shape != self.text.shape or self.image.shape[0] != len(self.uuids):
             raise ValueError("image / text embeddings and uuids must describe the same N items")
         self.precision = precision
+        self._row_of: Optional[Dict[str, int]] = None
         self.panel = engine.build_panel([self.image, self.text], _lib.SIDE_GALLERY, ranking.PRECISION_TERMS[precision])
 
     def __len__(self):
         return len(self.uuids)
+
+    @property
+    def row_of(self) -> Dict[str, int]:
+        """uuid -> gallery row, built on first use (a uuid stored twice: its first row, as ``list.index`` would say)."""
+        if self._row_of is None:
+            rows: Dict[str, int] = {}
+            for i, u in enumerate(self.uuids):
+                rows.setdefault(u, i)
+            self._row_of = rows
+        return self._row_of
+
+    def hits_csr(self, hits_per_query: Sequence[Sequence[str]], value: float):
+        """``hits_to_csr`` against this store's rows."""
+        return hits_to_csr(hits_per_query, self.row_of, value)
 
     @property
     def dim(self) -> int:
@@ -123,6 +152,31 @@ class CLIPRetriever:
         return [{"uuid": self.store.uuids[i], "score": float(s)} for s, i in zip(scores, idx) if i >= 0]
 
 
+    @torch.no_grad()
+    def search_batch_fused(self, queries: Sequence[str], hits_per_query: Sequence[Sequence[str]], alpha: float = 0.5,
+                           clip_weight: float = 1.0, hit_bonus: float = 0.2, top_k: int = 200):
+        """The ``top_k`` best of the WHOLE gallery by
+        ``clip_weight * (alpha * <q, image_i> + (1 - alpha) * <q, text_i>) + hit_bonus * [uuid_i in hits]``: one pass of
+        ``engine.sim_topk_deep`` with ``clip_weight`` folded into the query panel and the hits as a bonus list (``hits_csr``), so a
+        hit receives its bonus wherever CLIP alone would rank it."""
+        if not 1 <= top_k <= MAX_DEEP_TOP_K:
+            raise ValueError(f"top_k must be in 1..{MAX_DEEP_TOP_K}")
+        if len(hits_per_query) != len(queries):
+            raise ValueError("search_batch_fused: one hit list per query")
+        ids = self.tokenize_fn(list(queries))
+        q = self.model.encode_text(ids, normalize=True)
+        qp = engine.build_panel([q, q], _lib.SIDE_QUERY, ranking.PRECISION_TERMS[self.store.precision],
+                                part_scale=[clip_weight * alpha, clip_weight * (1.0 - alpha)])
+        return engine.sim_topk_deep(qp, self.store.panel, min(top_k, len(self.store)),
+                                    bonus=self.store.hits_csr(hits_per_query, hit_bonus))
+
+    def search_fused(self, query: str, hits: Sequence[str], alpha: float = 0.5, clip_weight: float = 1.0, hit_bonus: float = 0.2,
+                     top_k: int = 200) -> List[Dict]:
+        scores, idx = self.search_batch_fused([query], [hits], alpha, clip_weight, hit_bonus, top_k)
+        scores, idx = scores[0].cpu().tolist(), idx[0].cpu().tolist()
+        return [{"uuid": self.store.uuids[i], "score": float(s)} for s, i in zip(scores, idx) if i >= 0]
+
+
 class CLIPRetrieval:
     """``CLIPRetrieval(model_name=None).retrieval(query, alpha=0.5)`` (reference src/clip/clip_retrieval.py:10-40),
     without the hub download / ``exec`` / ``login``."""
@@ -137,6 +191,11 @@ class CLIPRetrieval:
     def retrieval_deep(self, query: str, alpha: float = 0.5, depth: int = 200):
         """The ``depth`` best instead of the ten of ``retrieval`` (this build's addition: candidates for the SPARQL fusion)."""
         return self.retriever.search_deep(query, alpha=alpha, top_k=depth)
+
+    def retrieval_fused(self, query: str, hits: Sequence[str], alpha: float = 0.5, clip_weight: float = 1.0, hit_bonus: float = 0.2,
+                        depth: int = 200):
+        """The ``depth`` best by the fused score ``clip_weight * clip + hit_bonus * [uuid in hits]`` over the whole gallery."""
+        return self.retriever.search_fused(query, hits, alpha=alpha, clip_weight=clip_weight, hit_bonus=hit_bonus, top_k=depth)
 
 
 class NoText2SPARQL:
@@ -181,6 +240,17 @@ class RetrievalEngine:
         t2s_results = self.t2s_retriever.retrieval(query)
         fused = self._fuse_clip_sparql_linear(clip_results=clip_results, sparql_results=t2s_results, alpha=alpha, beta=beta)
         return [{"uuid": it["uuid"], "score": it["score"]} for it in fused if it.get("score", 0) >= threshold]
+
+    def retrieve_text_fused(self, query: str, alpha: float = 0.8, beta: float = 0.2, alpha_clip: float = 0.5, threshold: float = 0,
+                            depth: int = 200):
+        """The reference's fusion formula (``src/retrieval.py:63-64``: ``alpha * clip + beta * [uuid in sparql]``) applied to EVERY
+        gallery item instead of to CLIP's own list: the SPARQL retriever is asked first, then one fused search scores the whole
+        gallery and returns its ``depth`` best, so a hit lands where its fused score puts it however low CLIP alone ranks it, and the
+        head of the list does not change with ``depth``.  ``{"uuid", "score": round(score, 4)}`` in the kernel's order (score
+        descending, then gallery row), cut at ``threshold``.  (This build's addition; the reference has no counterpart.)"""
+        t2s_results = self.t2s_retriever.retrieval(query)
+        fused = self.clip_retriever.retrieval_fused(query, t2s_results, alpha=alpha_clip, clip_weight=alpha, hit_bonus=beta, depth=depth)
+        return [{"uuid": it["uuid"], "score": round(it["score"], 4)} for it in fused if round(it["score"], 4) >= threshold]
 
     def retrieve_text_noknowledge(self, query: str, alpha: float = 0.8, beta: float = 0.2, alpha_clip: float = 0.5,
                                   threshold: float = 0):

@@ -92,9 +92,12 @@ def sparql_bonus(text2sparql_results, query_uuids, artefact_uuids, strategy: str
 
 def fused_ranks(query_parts, gallery_parts, weights, text2sparql_results, query_uuids, artefact_uuids,
                 strategy: str = "weighted", params: Optional[dict] = None, k: int = 10, precision: str = "fp32x3"):
-    """Ranks / top-k of  clip_scale * sum_p w_p <q_p, g_p>  + SPARQL bonus, fused in one kernel pass."""
+    """Ranks / top-k of  clip_scale * sum_p w_p <q_p, g_p>  + SPARQL bonus, fused in one kernel pass.  k <= 32 (0 = ranks only):
+    the register-list route; 33 <= k <= 1024: the deep route (``ranking.ranks_and_topk_deep``), same score, same order rule."""
     scale, bonus = sparql_bonus(text2sparql_results, query_uuids, artefact_uuids, strategy, params)
     weights = [scale * w for w in (weights if weights is not None else [1.0] * len(query_parts))]
+    if k > 32:
+        return ranking.ranks_and_topk_deep(query_parts, gallery_parts, weights=weights, k=k, precision=precision, bonus=bonus)
     return ranking.ranks_and_topk(query_parts, gallery_parts, weights=weights, k=k, precision=precision, bonus=bonus)
 
 
