@@ -248,8 +248,8 @@ int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t ld, const i
 
 /* Deep ranked lists: up to KEMR_MAX_DEEP_K candidates per query, exact, by selection and a sort of the survivors instead of the
  * register-resident lists behind kemr_sim_topk / kemr_rank_dense (k <= 32).  What the online engine needs to let a SPARQL hit
- * that CLIP ranks 57th receive its bonus (reference src/retrieval.py:79-95 fuses over CLIP's own list), a shortlist for the
- * cross_attention head, Recall@100, deduplication.  Same order rule as everywhere: score descending, then lower id; lists are
+ * that CLIP ranks 57th receive its bonus (reference src/retrieval.py:79-95 fuses over CLIP's own list), the shortlist that
+ * kemr_cross_attention_rerank scores with the cross_attention head, Recall@100, deduplication.  Same order rule as everywhere: score descending, then lower id; lists are
  * padded with -inf / -1.  The result is a pure function of the input (same bits on every run).  kemr_select_topk and
  * kemr_sim_topk_deep take no ground truth, `ahead` or bonus arguments; kemr_sim_topk_deep_fused is the deep route with them. */
 #define KEMR_MAX_DEEP_K 1024
@@ -305,6 +305,22 @@ int kemr_linear_head(const float* t2i_dev, const float* t2t_dev, int64_t n, cons
 int kemr_cross_attention_pairs(const float* st_i_dev, const float* st_t_dev, const float* p_i_dev, const float* p_t_dev,
                                const float* c0_dev, const float* w2t_dev, const float* b2_dev, const float* w3_dev, float b3,
                                int heads, int n_q, int n_c, int hid1, int hid2, float* out_t_dev, void* stream);
+
+/* The "cross_attention" head on LISTED pairs (retrieve-then-rerank: the consumer of the deep lists above): for every slot (q, j),
+ * j < depth, of cand_idx int32 [nq, ld] the score of query q against candidate c = cand_idx[q, j].  c < 0 is the deep lists' padding
+ * and scores -inf; an id >= ng is the caller's error (it is never dereferenced and scores -inf as well).
+ *   q fp32 [nq, dim]: the attention queries, already scaled by (dim / heads)^-0.5; k_x fp32 [ng, dim]: per-candidate keys
+ *   (x = image / target); p_x, c0, w2t, b2, w3, b3: as kemr_cross_attention_pairs takes them (hid1 a multiple of 4, hid2 <= 64).
+ * Per slot: the heads + heads dot products Q[q, head] . K_x[c, head] as fp32 FMA chains over the gathered rows, then the arithmetic
+ * of kemr_cross_attention_pairs (2-way softmax per head, relu(c0 + sum_h w_i P_i + w_t P_t), hid1 -> hid2 as one ascending-k fp32
+ * FMA chain on v_mfma_f32_16x16x4_f32, hid2 -> 1, 0.5 * tanh).  The dot products differ from the dense route's (which takes them
+ * from the bf16-split similarity kernel) in the last bits, so scores agree with kemr_cross_attention_pairs to rounding, not bit
+ * for bit.  out_scores fp32 [nq, ld]: columns < depth are each written exactly once, columns >= depth are not touched; the result
+ * is a pure function of the input (same bits on every run).  1 <= depth <= KEMR_MAX_DEEP_K, depth <= ld; nq == 0 or depth == 0 is a no-op. */
+int kemr_cross_attention_rerank(const float* q_dev, const float* k_i_dev, const float* k_t_dev, const float* p_i_dev,
+                                const float* p_t_dev, const float* c0_dev, const float* w2t_dev, const float* b2_dev,
+                                const float* w3_dev, float b3, int heads, int nq, int ng, int dim, int hid1, int hid2,
+                                const int32_t* cand_idx_dev, int depth, int64_t ld, float* out_scores_dev, void* stream);
 
 /* Optional per-kernel-class timing with hipEvents recorded on the launch stream (bench.py's roofline line).
  * Classes: 0 GEMM, 1 LayerNorm, 2 attention, 3 embed/tail, 4 similarity tile kernel.  Not thread-safe;

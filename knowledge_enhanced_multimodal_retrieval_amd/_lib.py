@@ -37,7 +37,7 @@ TOWER_VISION, TOWER_TEXT = 0, 1
 SIDE_QUERY, SIDE_GALLERY = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RESID_F32 = 0, 1, 2
 EPI_BIAS_RESADD_BF16 = 4
-MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused
+MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused / kemr_cross_attention_rerank
 
 
 class KemrCfg(C.Structure):
@@ -79,6 +79,7 @@ SIGNATURES = {
     "kemr_linear_head": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "kemr_gate_rows": (_i, [_vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "kemr_cross_attention_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp]),
+    "kemr_cross_attention_rerank": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp]),
     "kemr_profile_begin": (_i, [_i]),
     "kemr_profile_end": (_i, [C.POINTER(C.c_double), C.POINTER(_i64), _i]),
     "kemr_op_gemm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -493,6 +493,44 @@ def sim_topk_deep(qp: Panel, gp: Panel, k: int, gallery_offset: int = 0, query_b
     return top_s, top_i
 
 
+def cross_attention_rerank(q: torch.Tensor, k_i: torch.Tensor, k_t: torch.Tensor, p_i: torch.Tensor, p_t: torch.Tensor,
+                           c0: torch.Tensor, w2t: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: float,
+                           cand_idx: torch.Tensor, depth: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The cross_attention head on listed pairs (``kemr_cross_attention_rerank``): fp32 [nq, ld] scores of query ``q`` against the
+    candidates ``cand_idx`` (int32 [nq, ld], row stride ld, ids < 0 = padding -> -inf) in the first ``depth`` (default: all) columns.
+    q [nq, dim] scaled attention queries, k_x [ng, dim], p_x [ng, heads, hid1], c0 [hid1], w2t [hid1, hid2], b2 / w3 [hid2]: what
+    ``FusionModel`` precomputes per query / per candidate.  ``out`` (fp32 [nq, ld], contiguous): written in place in its first
+    ``depth`` columns, the rest is left as it is; without it a new tensor whose columns >= depth hold -inf."""
+    L = _lib.lib()
+    _require_cuda(q, "attention queries")
+    dev = q.device
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+    q, k_i, k_t, p_i, p_t, c0, w2t, b2, w3 = (f32(t) for t in (q, k_i, k_t, p_i, p_t, c0, w2t, b2, w3))
+    cand_idx = cand_idx.to(device=dev, dtype=torch.int32).contiguous()
+    if q.dim() != 2 or cand_idx.dim() != 2 or cand_idx.shape[0] != q.shape[0]:
+        raise RuntimeError("cross_attention_rerank: q [nq, dim] and cand_idx [nq, ld] must describe the same queries")
+    nq, dim = q.shape
+    ld = cand_idx.shape[1]
+    depth = ld if depth is None else int(depth)
+    ng, heads, hid1 = p_i.shape
+    hid2 = w2t.shape[1]
+    if tuple(k_i.shape) != (ng, dim) or tuple(k_t.shape) != (ng, dim) or tuple(p_t.shape) != (ng, heads, hid1) or \
+            tuple(w2t.shape) != (hid1, hid2) or c0.numel() != hid1 or b2.numel() != hid2 or w3.numel() != hid2:
+        raise RuntimeError("cross_attention_rerank: candidate-side tensors do not fit together")
+    if out is None:
+        out = torch.full((nq, ld), float("-inf"), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (nq, ld) or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError("cross_attention_rerank: out must be a contiguous fp32 [nq, ld] tensor on the queries' device")
+    if nq and depth:
+        with torch.cuda.device(dev):
+            _lib.check(L.kemr_cross_attention_rerank(
+                C.c_void_p(q.data_ptr()), C.c_void_p(k_i.data_ptr()), C.c_void_p(k_t.data_ptr()), C.c_void_p(p_i.data_ptr()),
+                C.c_void_p(p_t.data_ptr()), C.c_void_p(c0.data_ptr()), C.c_void_p(w2t.data_ptr()), C.c_void_p(b2.data_ptr()),
+                C.c_void_p(w3.data_ptr()), float(b3), heads, nq, ng, dim, hid1, hid2, C.c_void_p(cand_idx.data_ptr()), depth, ld,
+                C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(dev))), "cross_attention_rerank")
+    return out
+
+
 def scores_dense(qp: Panel, gp: Panel) -> torch.Tensor:
     """Dense fp32 score matrix [nq, ng] (fusion heads that need every pair; debugging)."""
     L = _lib.lib()

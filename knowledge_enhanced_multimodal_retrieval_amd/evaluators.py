@@ -399,25 +399,63 @@ def main_baseline(argv=None):
 
 
 # ------------------------------------------------------------------------------------------------ learned fusion heads
+RERANK_DEPTH_MIN = 20       # every reported Recall@K has K <= 20: with at least 20 listed candidates each is exact for the two-stage route
+
+
+def _check_rerank_depth(fusion_type: str, rerank_depth: int) -> None:
+    if not RERANK_DEPTH_MIN <= rerank_depth <= _lib.MAX_DEEP_K:
+        raise ValueError(f"rerank_depth={rerank_depth} not in {RERANK_DEPTH_MIN}..{_lib.MAX_DEEP_K}")
+    if fusion_type not in ("linear", "cross_attention"):
+        raise ValueError(f"rerank_depth is for the linear and cross_attention heads; the {fusion_type!r} head ranks the whole "
+                         "gallery in one fused pass already (FusionModel.rank)")
+
+
 @torch.no_grad()
 def evaluate_fusion_model(fusion_model, dataset, batch_size: int = 64, device: str = "cuda", seed: int = 42,
-                          tokenize_fn: Optional[Callable] = None, num_workers: Optional[int] = 4) -> Dict[str, float]:
+                          tokenize_fn: Optional[Callable] = None, num_workers: Optional[int] = 4,
+                          rerank_depth: Optional[int] = None) -> Dict[str, float]:
     """Counterpart of /root/reference/src/clip/eval/evaluator_fusion.py:28-144 (4 loader workers as at :42).  The reference fills an N x N numpy
     matrix in 50 x 500 blocks with an H2D/D2H round trip and ``empty_cache()`` per block (:76-121); here the head's
-    score is one fused kernel pass over resident embeddings (``FusionModel.rank``)."""
+    score is one fused kernel pass over resident embeddings (``FusionModel.rank``).
+
+    ``rerank_depth`` (None = the above, unchanged; else 20..1024, linear / cross_attention heads only): retrieve-then-rerank
+    (``FusionModel.rerank``) -- every query's ``rerank_depth`` best candidates by 0.5 * T2I + 0.5 * T2T are scored with the head and
+    the metrics come from the ground truth's position in that reranked list, ``rerank_depth + 1`` where it was not shortlisted.
+    Recall@K (K <= 20 <= rerank_depth) is exact for the two-stage pipeline.  Two keys are added: ``Shortlist_Recall`` (percent of
+    queries whose ground truth reached the list) and ``Rerank_Depth``.  Unless ``Shortlist_Recall`` is 100, ``MRR`` is an UPPER and
+    ``Mean_Rank`` a LOWER bound of the pipeline's value: a query whose ground truth missed the list counts with rank
+    ``rerank_depth + 1``, the best it could have."""
+    if rerank_depth is not None:
+        _check_rerank_depth(fusion_model.fusion_type, int(rerank_depth))
     fusion_model.eval()
     image, query, target, _ = encode_dataset(fusion_model.clip_model, dataset, batch_size, seed, num_workers, tokenize_fn)
-    ranks, _, _ = fusion_model.rank(query, image, target, k=0)
     from . import ranking
-    result = ranking.metrics_from_ranks(ranks, [1, 5, 10, 20])
+    if rerank_depth is None:
+        ranks, _, _ = fusion_model.rank(query, image, target, k=0)
+        result = ranking.metrics_from_ranks(ranks, [1, 5, 10, 20])
+    else:
+        depth = int(rerank_depth)
+        ranks = fusion_model.rerank(query, fusion_model.prepare_gallery(image, target), depth=depth, k=1, gt_idx="diag")[0]
+        result = ranking.metrics_from_ranks(ranks, [1, 5, 10, 20])
+        result["Shortlist_Recall"] = float((ranks <= depth).double().mean().item() * 100.0)
+        result["Rerank_Depth"] = depth
     logger.info("Fusion Model Evaluation Results")
     for k, v in result.items():
-        logger.info(f"{k}: {v:.2f}" + ("%" if ("R@" in k or "MRR" in k) else ""))
+        logger.info(f"{k}: {v:.2f}" + ("%" if ("R@" in k or "MRR" in k or "Recall" in k) else ""))
     return result
 
 
-def main_fusion(argv=None):
-    import json
+def _rerank_depth_arg(text: str) -> int:
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not an integer")
+    if not RERANK_DEPTH_MIN <= value <= _lib.MAX_DEEP_K:
+        raise argparse.ArgumentTypeError(f"{value} not in {RERANK_DEPTH_MIN}..{_lib.MAX_DEEP_K}")
+    return value
+
+
+def fusion_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="Evaluate Fusion Model")
     parser.add_argument("--model_name", type=str, default="ViT-L/14")
     parser.add_argument("--clip_checkpoint", type=str, default=None)
@@ -434,7 +472,19 @@ def main_fusion(argv=None):
     parser.add_argument("--output_file", type=str, default=None)
     parser.add_argument("--synthetic", type=int, default=0, metavar="N")
     parser.add_argument("--dataset", type=str, default="xuemduan/reevaluate-image-text-pairs")
+    parser.add_argument("--rerank_depth", type=_rerank_depth_arg, default=None, metavar="N",
+                        help=f"linear / cross_attention heads: retrieve-then-rerank over every query's N ({RERANK_DEPTH_MIN}..{_lib.MAX_DEEP_K}) "
+                             "best candidates by the fused T2I + T2T score instead of the head on every pair")
+    return parser
+
+
+def main_fusion(argv=None):
+    import json
+    parser = fusion_parser()
     args = parser.parse_args(argv)
+    if args.rerank_depth is not None and args.fusion_type not in ("linear", "cross_attention"):
+        parser.error(f"--rerank_depth is for the linear and cross_attention heads; the {args.fusion_type} head ranks the whole "
+                     "gallery in one fused pass already")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     from . import clip_api, tokenizer
     from .clip_model import load_clip_model
@@ -454,7 +504,7 @@ def main_fusion(argv=None):
         from datasets import load_dataset
         ds = load_dataset(args.dataset)
         dataset = CLIPEvalDatasetHF(ds[{"val": "validation"}.get(args.split, args.split)], preprocess, args.max_text_length)
-    result = evaluate_fusion_model(fusion_model, dataset, args.batch_size, args.device)
+    result = evaluate_fusion_model(fusion_model, dataset, args.batch_size, args.device, rerank_depth=args.rerank_depth)
     results = {"model_name": args.model_name, "clip_checkpoint": args.clip_checkpoint,
                "fusion_checkpoint": args.fusion_checkpoint, "fusion_type": args.fusion_type, "split": args.split,
                "num_samples": len(dataset), "metrics": result,

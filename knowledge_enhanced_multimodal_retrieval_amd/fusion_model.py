@@ -18,13 +18,16 @@ inactive) and maps onto the fused similarity kernel:
   the similarity kernel) and ``kemr_cross_attention_pairs`` does ~21 kFLOP per pair instead of ~1.6 MFLOP.
 
 ``rank()`` gives ranks / top-k without ever forming the [N,M] matrix for the gated family and bilinear; linear and
-cross_attention produce the dense matrix on the GPU and rank it with ``kemr_rank_dense``.
+cross_attention produce the dense matrix on the GPU and rank it with ``kemr_rank_dense``.  ``prepare_gallery()`` + ``rerank()`` are
+the two-stage route for those two heads: a deep shortlist by the fused T2I + T2T score, the head on the listed pairs only
+(``kemr_cross_attention_rerank``; ``kemr_pair_scores`` + ``kemr_linear_head``), sorted by ``kemr_select_topk``.
 """
 from __future__ import annotations
 
 import ctypes as C
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -89,6 +92,47 @@ class CrossAttentionFusionHead(nn.Module):
 
 
 _GATED = ("gated", "simple_gated", "simple_gated_with_bias")
+_RERANK_HEADS = ("linear", "cross_attention")          # the pair heads: scored densely by forward(), on shortlists by rerank()
+
+
+class HeadGallery:
+    """A gallery prepared for ``FusionModel.rerank``: everything the two-stage route needs per candidate, on the device, computed
+    once per gallery instead of once per query batch.
+
+    * ``fused_panel``: the fp32x3 panel of ``[image ; target]`` that the shortlist stage scores (``engine.sim_topk_deep``);
+    * linear head: ``image_panel`` / ``target_panel``, the two fp32x3 panels ``engine.pair_scores`` reads;
+    * cross_attention head: ``cand`` = keys Ki, Kt [M, D], folded projections Pi, Pt [M, 8, hid1] (2 * M * 8 * hid1 * 4 bytes:
+      0.7 GB at M = 43 000, hid1 = 256) and the MLP's constants.
+
+    The cross_attention quantities are functions of the head's parameters: a HeadGallery is STALE once they change (an optimizer
+    step, ``load_state_dict``); call ``refresh()`` or prepare a new one.  The linear head's parameters are read at every call."""
+
+    def __init__(self, model: "FusionModel", image_embed, target_embed):
+        self.model, self.fusion_type = model, model.fusion_type
+        self.image = ranking.to_device_f32(image_embed)
+        self.target = ranking.to_device_f32(target_embed, self.image.device)
+        if self.image.dim() != 2 or self.image.shape != self.target.shape:
+            raise ValueError("prepare_gallery: image and target embeddings must share one [M, D] shape")
+        self.refresh()
+
+    def __len__(self):
+        return self.image.shape[0]
+
+    @property
+    def device(self):
+        return self.image.device
+
+    @torch.no_grad()
+    def refresh(self) -> "HeadGallery":
+        """Recompute every per-candidate quantity from the stored embeddings and the head's CURRENT parameters."""
+        self.fused_panel = engine.build_panel([self.image, self.target], _lib.SIDE_GALLERY, 3)
+        self.image_panel = self.target_panel = self.cand = None
+        if self.fusion_type == "linear":
+            self.image_panel = engine.build_panel([self.image], _lib.SIDE_GALLERY, 3)
+            self.target_panel = engine.build_panel([self.target], _lib.SIDE_GALLERY, 3)
+        else:
+            self.cand = self.model._cross_attention_gallery(self.image, self.target)
+        return self
 
 
 class FusionModel(nn.Module):
@@ -169,19 +213,28 @@ class FusionModel(nn.Module):
         return y if bias is None else y + bias.detach().float()
 
     @torch.no_grad()
-    def _cross_attention(self, q, img, tgt) -> torch.Tensor:
-        """Eval-mode CrossAttentionFusionHead.forward (reference fusion_model.py:83-133) -> [N, M] fp32."""
+    def _cross_attention_query(self, q) -> torch.Tensor:
+        """Query side of the cross_attention head: the attention queries Q [N, D], already scaled by hd^-0.5."""
         h = self.fusion_head.to(q.device).eval()
         lin = self._linear
-        N, D = q.shape
-        M = img.shape[0]
+        D = q.shape[1]
+        hd = D // h.cross_attn.num_heads
+        Wqkv, bqkv = h.cross_attn.in_proj_weight.detach(), h.cross_attn.in_proj_bias.detach()
+        qp = lin(q, h.query_proj.weight, h.query_proj.bias)
+        return lin(qp, Wqkv[:D], bqkv[:D]) * (hd ** -0.5)
+
+    @torch.no_grad()
+    def _cross_attention_gallery(self, img, tgt) -> dict:
+        """Candidate side of the cross_attention head, everything that does not depend on the query: the keys Ki, Kt [M, D], the
+        folded projections Pi, Pt [M, H, hid1] = W1.Wo[:, head].V_x and the MLP's constants (c0, w2t, b2, w3, b3)."""
+        h = self.fusion_head.to(img.device).eval()
+        lin = self._linear
+        M, D = img.shape
         H = h.cross_attn.num_heads
         hd = D // H
         Wqkv, bqkv = h.cross_attn.in_proj_weight.detach(), h.cross_attn.in_proj_bias.detach()
-        qp = lin(q, h.query_proj.weight, h.query_proj.bias)
         ip = lin(img, h.image_proj.weight, h.image_proj.bias)
         tp = lin(tgt, h.target_proj.weight, h.target_proj.bias)
-        Q = lin(qp, Wqkv[:D], bqkv[:D]) * (hd ** -0.5)
         Ki, Kt = lin(ip, Wqkv[D:2 * D], bqkv[D:2 * D]), lin(tp, Wqkv[D:2 * D], bqkv[D:2 * D])
         Vi, Vt = lin(ip, Wqkv[2 * D:], bqkv[2 * D:]), lin(tp, Wqkv[2 * D:], bqkv[2 * D:])
         Wo, bo = h.cross_attn.out_proj.weight.detach().float(), h.cross_attn.out_proj.bias.detach().float()
@@ -189,7 +242,7 @@ class FusionModel(nn.Module):
         W2, b2 = h.score_mlp[3].weight.detach().float(), h.score_mlp[3].bias.detach().float()
         W3, b3 = h.score_mlp[6].weight.detach().float().reshape(-1), float(h.score_mlp[6].bias.detach())
         hid1, hid2 = W1.shape[0], W2.shape[0]
-        Pi = torch.empty((M, H, hid1), dtype=torch.float32, device=q.device)
+        Pi = torch.empty((M, H, hid1), dtype=torch.float32, device=img.device)
         Pt = torch.empty_like(Pi)
         for hh in range(H):
             sl = slice(hh * hd, (hh + 1) * hd)
@@ -197,7 +250,20 @@ class FusionModel(nn.Module):
             Pi[:, hh] = lin(Vi[:, sl].contiguous(), G)
             Pt[:, hh] = lin(Vt[:, sl].contiguous(), G)
         c0 = (lin(bo[None, :], W1)[0] + b1).contiguous()
-        w2t = W2.t().contiguous()
+        return {"Ki": Ki, "Kt": Kt, "Pi": Pi, "Pt": Pt, "c0": c0, "w2t": W2.t().contiguous(), "b2": b2.contiguous(),
+                "w3": W3.contiguous(), "b3": b3, "H": H, "hid1": hid1, "hid2": hid2}
+
+    @torch.no_grad()
+    def _cross_attention(self, q, img, tgt) -> torch.Tensor:
+        """Eval-mode CrossAttentionFusionHead.forward (reference fusion_model.py:83-133) -> [N, M] fp32."""
+        lin = self._linear
+        N, D = q.shape
+        M = img.shape[0]
+        Q = self._cross_attention_query(q)
+        c = self._cross_attention_gallery(img, tgt)
+        Ki, Kt, Pi, Pt, c0, w2t, b2, W3, b3 = (c[n] for n in ("Ki", "Kt", "Pi", "Pt", "c0", "w2t", "b2", "w3", "b3"))
+        H, hid1, hid2 = c["H"], c["hid1"], c["hid2"]
+        hd = D // H
         out = torch.empty((N, M), dtype=torch.float32, device=q.device)
         step = max(1, min(N, (256 << 20) // max(1, 2 * H * M * 4)))   # bound the transposed score planes to ~256 MB
         L = _lib.lib()
@@ -215,10 +281,23 @@ class FusionModel(nn.Module):
             with torch.cuda.device(q.device):
                 _lib.check(L.kemr_cross_attention_pairs(
                     C.c_void_p(sti.data_ptr()), C.c_void_p(stt.data_ptr()), C.c_void_p(Pi.data_ptr()), C.c_void_p(Pt.data_ptr()),
-                    C.c_void_p(c0.data_ptr()), C.c_void_p(w2t.data_ptr()), C.c_void_p(b2.contiguous().data_ptr()),
-                    C.c_void_p(W3.contiguous().data_ptr()), b3, H, nc, M, hid1, hid2, C.c_void_p(out_t.data_ptr()),
+                    C.c_void_p(c0.data_ptr()), C.c_void_p(w2t.data_ptr()), C.c_void_p(b2.data_ptr()),
+                    C.c_void_p(W3.data_ptr()), b3, H, nc, M, hid1, hid2, C.c_void_p(out_t.data_ptr()),
                     C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)), "cross_attention_pairs")
             out[s0:s0 + nc] = out_t.t()
+        return out
+
+    def _linear_head(self, t2i: torch.Tensor, t2t: torch.Tensor) -> torch.Tensor:
+        """The linear head's MLP(2 -> hidden -> 1) on every (t2i, t2t) pair of two equally shaped fp32 tensors (kemr_linear_head)."""
+        f = self.fusion_head.fusion.to(t2i.device)
+        w0, b0 = f[0].weight.detach().float().contiguous(), f[0].bias.detach().float().contiguous()
+        w1, b1 = f[3].weight.detach().float().reshape(-1).contiguous(), float(f[3].bias.detach())
+        out = torch.empty_like(t2i)
+        with torch.cuda.device(t2i.device):
+            _lib.check(_lib.lib().kemr_linear_head(
+                C.c_void_p(t2i.data_ptr()), C.c_void_p(t2t.data_ptr()), t2i.numel(), C.c_void_p(w0.data_ptr()),
+                C.c_void_p(b0.data_ptr()), C.c_void_p(w1.data_ptr()), b1, w0.shape[0], C.c_void_p(out.data_ptr()),
+                C.c_void_p(torch.cuda.current_stream(t2i.device).cuda_stream)), "linear_head")
         return out
 
     @torch.no_grad()
@@ -234,16 +313,7 @@ class FusionModel(nn.Module):
             qp = engine.build_panel([q], _lib.SIDE_QUERY, 3)
             t2i = engine.scores_dense(qp, engine.build_panel([img], _lib.SIDE_GALLERY, 3))
             t2t = engine.scores_dense(qp, engine.build_panel([tgt], _lib.SIDE_GALLERY, 3))
-            f = self.fusion_head.fusion.to(q.device)
-            w0, b0 = f[0].weight.detach().float().contiguous(), f[0].bias.detach().float().contiguous()
-            w1, b1 = f[3].weight.detach().float().reshape(-1).contiguous(), float(f[3].bias.detach())
-            out = torch.empty_like(t2i)
-            with torch.cuda.device(q.device):
-                _lib.check(_lib.lib().kemr_linear_head(
-                    C.c_void_p(t2i.data_ptr()), C.c_void_p(t2t.data_ptr()), t2i.numel(), C.c_void_p(w0.data_ptr()),
-                    C.c_void_p(b0.data_ptr()), C.c_void_p(w1.data_ptr()), b1, w0.shape[0], C.c_void_p(out.data_ptr()),
-                    C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)), "linear_head")
-            return out
+            return self._linear_head(t2i, t2t)
         qs, gs, weights, gates = self._parts(query_embed, image_embed, target_embed)
         qp = engine.build_panel(qs, _lib.SIDE_QUERY, 3, part_scale=weights, row_scale=gates)
         gp = engine.build_panel(gs, _lib.SIDE_GALLERY, 3)
@@ -257,3 +327,100 @@ class FusionModel(nn.Module):
             return ranking.ranks_of_matrix(self.forward(query_embed, image_embed, target_embed), k=k, gt_idx=gt_idx)
         qs, gs, weights, gates = self._parts(query_embed, image_embed, target_embed)
         return ranking.ranks_and_topk(qs, gs, weights=weights, row_gate=gates, k=k, gt_idx=gt_idx)
+
+    # ---- retrieve-then-rerank: the pair heads on deep shortlists instead of on the whole [N, M] grid
+    def _require_rerank_head(self, what: str) -> None:
+        if self.fusion_type not in _RERANK_HEADS:
+            raise ValueError(f"{what}: the {self.fusion_type!r} head folds into the fused similarity pass and ranks the WHOLE gallery "
+                             f"already -- use rank(); reranking a shortlist is for {_RERANK_HEADS}")
+
+    @torch.no_grad()
+    def prepare_gallery(self, image_embed, target_embed) -> HeadGallery:
+        """The per-candidate side of ``rerank`` for one gallery (``HeadGallery``; stale after the head's parameters change)."""
+        self._require_rerank_head("prepare_gallery")
+        return HeadGallery(self, image_embed, target_embed)
+
+    @torch.no_grad()
+    def shortlist(self, q: torch.Tensor, gallery_panel: engine.Panel, depth: int, shortlist_weights=(0.5, 0.5)) -> torch.Tensor:
+        """Stage one: the ``depth`` best candidates of every query by w_i * T2I + w_t * T2T against a ``[image ; target]`` gallery
+        panel -- the ids (int32 [N, depth], -1 padded) of ``ranking.ranks_and_topk_deep([q, q], [img, tgt], weights, k=depth)``."""
+        qp = engine.build_panel([q, q], _lib.SIDE_QUERY, gallery_panel.terms, part_scale=list(shortlist_weights))
+        return engine.sim_topk_deep(qp, gallery_panel, depth)[1]
+
+    @torch.no_grad()
+    def list_scores(self, q: torch.Tensor, gallery: HeadGallery, list_idx: torch.Tensor) -> torch.Tensor:
+        """Stage two: this head's score of every listed pair, fp32 [N, depth]; padded slots (id < 0) hold -inf."""
+        n, depth = list_idx.shape
+        if self.fusion_type == "cross_attention":
+            c = gallery.cand
+            return engine.cross_attention_rerank(self._cross_attention_query(q), c["Ki"], c["Kt"], c["Pi"], c["Pt"], c["c0"], c["w2t"],
+                                                 c["b2"], c["w3"], c["b3"], list_idx, depth)
+        # linear: t2i / t2t at the listed pairs with the bits of scores_dense (include/kemr.h, kemr_pair_scores), then the MLP
+        qp = engine.build_panel([q], _lib.SIDE_QUERY, 3)
+        q_rows = torch.arange(n, dtype=torch.int32, device=q.device).repeat_interleave(depth)
+        g_rows = list_idx.clamp(min=0).reshape(-1)
+        t2i = engine.pair_scores(qp, gallery.image_panel, q_rows, g_rows)
+        t2t = engine.pair_scores(qp, gallery.target_panel, q_rows, g_rows)
+        return self._linear_head(t2i, t2t).view(n, depth).masked_fill_(list_idx < 0, float("-inf"))
+
+    @torch.no_grad()
+    def _rerank_lists(self, q: torch.Tensor, gallery: HeadGallery, list_idx: torch.Tensor, k: int, gt: Optional[torch.Tensor]):
+        n, depth = list_idx.shape
+        scores = self.list_scores(q, gallery, list_idx)
+        if gt is None:
+            top_s, top_i = engine.select_topk(scores, k, idx=list_idx)
+            return None, top_s, top_i, scores, list_idx
+        # the whole list in the project's order (score descending, then lower id), by the selection kernel: the ground truth's
+        # 1-based position in it is its rank under the two-stage pipeline, and the first k entries are the top-k
+        hit = list_idx == gt.view(-1, 1)
+        ranking._require_finite(scores[hit], "head scores at the ground truth")
+        order_s, order_i = engine.select_topk(scores, depth, idx=list_idx)
+        at = order_i == gt.view(-1, 1)
+        pos = (at.int() * torch.arange(1, depth + 1, dtype=torch.int32, device=q.device)).sum(dim=1).long()
+        ranks = torch.where(at.any(dim=1), pos, torch.full_like(pos, depth + 1))
+        return ranks, order_s[:, :k].contiguous(), order_i[:, :k].contiguous(), scores, list_idx
+
+    @torch.no_grad()
+    def rerank(self, query_embed, gallery: HeadGallery, depth: int = 200, k: int = 10, gt_idx=None, cand_idx=None,
+               shortlist_weights=(0.5, 0.5)):
+        """Retrieve-then-rerank with the ``linear`` or ``cross_attention`` head: cut a shortlist of ``depth`` candidates per query
+        with the fused score ``w_i * T2I + w_t * T2T`` (``shortlist_weights``; one pass of ``engine.sim_topk_deep`` over the
+        gallery's fused panel), score only those pairs with the head, sort them (score descending, then lower id).
+
+        ``cand_idx`` (int32 [N, depth], -1 = padding, ids < M and distinct within a row) replaces the shortlist stage.
+        ``gt_idx``: None, ``"diag"`` or one gallery id per query.
+
+        Returns ``(ranks, top_scores [N, k], top_idx [N, k], list_scores [N, depth], list_idx [N, depth])``.  ``ranks`` is None
+        without ``gt_idx``; otherwise int64 [N]: the ground truth's 1-based position in the reranked list, or ``depth + 1`` where
+        the shortlist does not hold it -- a LOWER BOUND of the rank the head would give it over the whole gallery.  A rank
+        <= depth is the exact rank of the two-stage pipeline, so Recall@K is exact for every K <= depth.  Linear scores are
+        bit-identical to ``forward()[q, ids]``; cross_attention scores agree with it to fp32 rounding (``include/kemr.h``)."""
+        self._require_rerank_head("rerank")
+        depth, k = int(depth), int(k)
+        if not 1 <= depth <= _lib.MAX_DEEP_K:
+            raise ValueError(f"rerank: depth={depth} not in 1..{_lib.MAX_DEEP_K}")
+        if not 1 <= k <= depth:
+            raise ValueError(f"rerank: k={k} not in 1..depth={depth}")
+        if not isinstance(gallery, HeadGallery) or gallery.model is not self or gallery.fusion_type != self.fusion_type:
+            raise ValueError("rerank: gallery must come from this model's prepare_gallery()")
+        q = ranking.to_device_f32(query_embed, gallery.device)
+        n, m = q.shape[0], len(gallery)
+        if cand_idx is None:
+            list_idx = self.shortlist(q, gallery.fused_panel, depth, shortlist_weights)
+        else:
+            list_idx = torch.as_tensor(cand_idx)
+            if list_idx.dtype != torch.int32 or tuple(list_idx.shape) != (n, depth):
+                raise ValueError(f"rerank: cand_idx must be int32 [{n}, {depth}], got {list_idx.dtype} {tuple(list_idx.shape)}")
+            ids = np.sort(list_idx.cpu().numpy(), axis=1)              # validation of an external list, on the host
+            if ids.size and int(ids.max()) >= m:
+                raise ValueError(f"rerank: cand_idx holds id {int(ids.max())}, the gallery has {m} candidates")
+            if bool(((ids[:, 1:] == ids[:, :-1]) & (ids[:, 1:] >= 0)).any()):
+                raise ValueError("rerank: the ids of a cand_idx row must be distinct")
+            list_idx = list_idx.to(q.device).contiguous()
+        gt = None
+        if gt_idx is not None:
+            gt = torch.arange(n, dtype=torch.int32, device=q.device) if isinstance(gt_idx, str) \
+                else torch.as_tensor(gt_idx).to(device=q.device, dtype=torch.int32).reshape(-1)
+            if gt.numel() != n or bool(((gt < 0) | (gt >= m)).any()):
+                raise ValueError("rerank: gt_idx must hold one gallery id per query")
+        return self._rerank_lists(q, gallery, list_idx, k, gt)

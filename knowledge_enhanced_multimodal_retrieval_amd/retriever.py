@@ -176,6 +176,31 @@ class CLIPRetriever:
         scores, idx = scores[0].cpu().tolist(), idx[0].cpu().tolist()
         return [{"uuid": self.store.uuids[i], "score": float(s)} for s, i in zip(scores, idx) if i >= 0]
 
+    @torch.no_grad()
+    def search_batch_reranked(self, queries: Sequence[str], fusion_model, gallery, depth: int = 200, top_k: int = 10):
+        """The online route of a trained ``linear`` / ``cross_attention`` head (``FusionModel.rerank``): text tower -> the ``depth``
+        best of the store's fused panel by 0.5 * <q, image_i> + 0.5 * <q, text_i> -> the head on those pairs -> its ``top_k`` best,
+        ``(scores [Q, top_k], ids [Q, top_k])`` with the HEAD's scores (score descending, then lower row; -inf / -1 padding).
+        ``gallery``: ``fusion_model.prepare_gallery(store.image, store.text)``, built once.  ``top_k`` may exceed MAX_TOP_K, up to
+        ``depth`` <= MAX_DEEP_TOP_K: the list goes through the deep route."""
+        if not 1 <= depth <= MAX_DEEP_TOP_K:
+            raise ValueError(f"depth must be in 1..{MAX_DEEP_TOP_K}")
+        if not 1 <= top_k <= depth:
+            raise ValueError(f"top_k must be in 1..depth={depth}")
+        fusion_model._require_rerank_head("search_batch_reranked")
+        if len(gallery) != len(self.store):
+            raise ValueError(f"the prepared gallery has {len(gallery)} candidates, the store {len(self.store)}")
+        ids = self.tokenize_fn(list(queries))
+        q = self.model.encode_text(ids, normalize=True)
+        list_idx = fusion_model.shortlist(q, self.store.panel, depth)
+        _, top_s, top_i, _, _ = fusion_model._rerank_lists(q, gallery, list_idx, top_k, None)
+        return top_s, top_i
+
+    def search_reranked(self, query: str, fusion_model, gallery, depth: int = 200, top_k: int = 10) -> List[Dict]:
+        scores, idx = self.search_batch_reranked([query], fusion_model, gallery, depth, top_k)
+        scores, idx = scores[0].cpu().tolist(), idx[0].cpu().tolist()
+        return [{"uuid": self.store.uuids[i], "score": float(s)} for s, i in zip(scores, idx) if i >= 0]
+
 
 class CLIPRetrieval:
     """``CLIPRetrieval(model_name=None).retrieval(query, alpha=0.5)`` (reference src/clip/clip_retrieval.py:10-40),
