@@ -242,7 +242,18 @@ int kemr_scores_dense(const void* q_panel_dev, int nq, const void* g_panel_dev, 
  * candidates ranked ahead of column gt_idx[row] (written, not accumulated) and/or the sorted top-k.
  * Replaces the np.argsort passes when the caller hands over a matrix: compute_recall_at_k,
  * compute_mrr_and_mean_rank (metrics.py:13-76), compute_retrieval_metrics_fusion (metrics.py:165-185),
- * evaluate_retrieval (eval/fusion.py:6-20), evaluator_fusion.py:126.  Either output pair may be NULL. */
+ * evaluate_retrieval (eval/fusion.py:6-20), evaluator_fusion.py:126.  Either output pair may be NULL.
+ * scores_dev may be a row-strided view (ld >= ng; rows need no alignment); columns ng .. ld - 1 are never read.  A gt_idx outside
+ * 0 .. ng - 1 writes ahead = 0.  Lists are padded with -inf / -1 where a row has fewer than k listable candidates.
+ *
+ * -inf and NaN scores on the k <= 32 routes (kemr_rank_dense, kemr_sim_topk, and through it the lists kemr_topk_merge is fed):
+ * -inf is the PAD VALUE of the register-resident lists, and a candidate enters a list only if its score is greater than the
+ * list's last entry, so a candidate whose score is -inf or NaN is NEVER LISTED -- the lists hold the candidates with a score
+ * above -inf in order, then padding.  `ahead` still counts by the order rule on the raw scores (a -inf or NaN candidate is never
+ * ahead of a finite ground truth).  The deep routes (kemr_select_topk, kemr_sim_topk_deep*) differ: they list every candidate with
+ * an id >= 0, -inf ones behind the finite ones and NaN behind -inf.  kemr_topk_merge itself tells padding by the id (< 0), not by
+ * the score: an entry (-inf, id >= 0) handed to it IS listed, behind the finite entries in id order; kemr_sim_topk never produces
+ * one.  A NaN entry is not supported by kemr_topk_merge (where it lands depends on its position in the input). */
 int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t ld, const int32_t* gt_idx_dev,
                     int32_t* ahead_dev, int k, float* top_scores_dev, int32_t* top_idx_dev, void* stream);
 
@@ -250,7 +261,7 @@ int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t ld, const i
  * register-resident lists behind kemr_sim_topk / kemr_rank_dense (k <= 32).  What the online engine needs to let a SPARQL hit
  * that CLIP ranks 57th receive its bonus (reference src/retrieval.py:79-95 fuses over CLIP's own list), the shortlist that
  * kemr_cross_attention_rerank scores with the cross_attention head, Recall@100, deduplication.  Same order rule as everywhere: score descending, then lower id; lists are
- * padded with -inf / -1.  The result is a pure function of the input (same bits on every run).  kemr_select_topk and
+ * padded with -inf / -1.  Unlike the k <= 32 routes, a candidate whose score is -inf or NaN is listed (see kemr_rank_dense).  The result is a pure function of the input (same bits on every run).  kemr_select_topk and
  * kemr_sim_topk_deep take no ground truth, `ahead` or bonus arguments; kemr_sim_topk_deep_fused is the deep route with them. */
 #define KEMR_MAX_DEEP_K 1024
 /* top-k of materialised rows: scores fp32 [nq, ld] (n <= ld valid columns; nothing at or beyond column n is read), idx int32

@@ -547,26 +547,83 @@ def scores_dense(qp: Panel, gp: Panel) -> torch.Tensor:
 
 def rank_dense(scores: torch.Tensor, gt_idx: Optional[torch.Tensor] = None, k: int = 0
                ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """Rank a materialised fp32 score matrix on the GPU: returns (ahead [nq] or None, top scores, top ids)."""
+    """Rank a materialised fp32 score matrix on the GPU: returns (ahead [nq] or None, top scores, top ids).  Row-strided views are
+    read in place (``stride(0)`` is the ABI's ``ld``).  The lists are padded with -inf / -1 where a row has fewer than k candidates
+    (an empty gallery: padding only, ahead = 0); a candidate whose score is -inf or NaN is never listed (include/kemr.h)."""
     L = _lib.lib()
     _require_cuda(scores, "score matrix")
     scores = scores.to(torch.float32)
-    if scores.stride(-1) != 1:
+    if scores.stride(-1) != 1 or (scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]):
         scores = scores.contiguous()
     nq, ng = scores.shape
     dev = scores.device
+    ld = scores.stride(0) if nq > 1 else max(ng, 1)
     ahead = gt = top_s = top_i = None
     if gt_idx is not None:
         gt = gt_idx.to(device=dev, dtype=torch.int32).contiguous()
         ahead = torch.zeros(nq, dtype=torch.int32, device=dev)
     if k > 0:
-        top_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        top_i = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        top_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev) if ng == 0 else \
+            torch.empty((nq, k), dtype=torch.float32, device=dev)
+        top_i = torch.full((nq, k), -1, dtype=torch.int32, device=dev) if ng == 0 else \
+            torch.empty((nq, k), dtype=torch.int32, device=dev)
     if nq and ng:
         with torch.cuda.device(dev):
-            _lib.check(L.kemr_rank_dense(C.c_void_p(scores.data_ptr()), nq, ng, scores.stride(0), _opt_ptr(gt), _opt_ptr(ahead),
+            _lib.check(L.kemr_rank_dense(C.c_void_p(scores.data_ptr()), nq, ng, ld, _opt_ptr(gt), _opt_ptr(ahead),
                                          k, _opt_ptr(top_s), _opt_ptr(top_i), C.c_void_p(_stream_ptr(dev))), "rank_dense")
     return ahead, top_s, top_i
+
+
+def gate_rows(x: torch.Tensor, pre: Optional[torch.Tensor], w: torch.Tensor, bias: float, relu: bool,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``kemr_gate_rows``: sigmoid(sum_c act(x[r, c] + pre[c]) w[c] + bias) per row of the contiguous fp32 x [rows, cols] -> fp32
+    [rows] (``out``: a contiguous fp32 tensor of at least ``rows`` elements, written in its first ``rows``)."""
+    L = _lib.lib()
+    _require_cuda(x, "gate input")
+    rows, cols = x.shape
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(L.kemr_gate_rows(C.c_void_p(x.data_ptr()), rows, cols, _opt_ptr(pre), C.c_void_p(w.data_ptr()), float(bias),
+                                    int(bool(relu)), C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(x.device))), "gate_rows")
+    return out
+
+
+def linear_head(t2i: torch.Tensor, t2t: torch.Tensor, w0: torch.Tensor, b0: torch.Tensor, w1: torch.Tensor, b1: float,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``kemr_linear_head``: b1 + w1 . relu(W0 . [t2i, t2t] + b0) on every element of two equally shaped contiguous fp32 tensors
+    (w0 [hidden, 2], b0 / w1 [hidden], all contiguous fp32 on t2i's device); ``out``: at least ``t2i.numel()`` fp32 elements."""
+    L = _lib.lib()
+    _require_cuda(t2i, "t2i scores")
+    if out is None:
+        out = torch.empty_like(t2i)
+    with torch.cuda.device(t2i.device):
+        _lib.check(L.kemr_linear_head(C.c_void_p(t2i.data_ptr()), C.c_void_p(t2t.data_ptr()), t2i.numel(), C.c_void_p(w0.data_ptr()),
+                                      C.c_void_p(b0.data_ptr()), C.c_void_p(w1.data_ptr()), float(b1), w0.shape[0],
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(t2i.device))), "linear_head")
+    return out
+
+
+def cross_attention_pairs(st_i: torch.Tensor, st_t: torch.Tensor, p_i: torch.Tensor, p_t: torch.Tensor, c0: torch.Tensor,
+                          w2t: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: float, heads: Optional[int] = None,
+                          hid1: Optional[int] = None, hid2: Optional[int] = None, out_t: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``kemr_cross_attention_pairs`` on contiguous fp32 device tensors: st_x [heads, n_c, n_q], p_x [n_c, heads, hid1], c0 [hid1],
+    w2t [hid1, hid2], b2 / w3 [hid2] -> out_t fp32 [n_c, n_q] (``out_t``: at least n_c * n_q fp32 elements).  heads / hid1 / hid2
+    default to the tensors' shapes; the tests pass sizes the ABI refuses."""
+    L = _lib.lib()
+    _require_cuda(st_i, "score planes")
+    n_c, n_q = st_i.shape[1], st_i.shape[2]
+    heads = st_i.shape[0] if heads is None else heads
+    hid1 = w2t.shape[0] if hid1 is None else hid1
+    hid2 = w2t.shape[1] if hid2 is None else hid2
+    if out_t is None:
+        out_t = torch.empty((n_c, n_q), dtype=torch.float32, device=st_i.device)
+    with torch.cuda.device(st_i.device):
+        _lib.check(L.kemr_cross_attention_pairs(
+            C.c_void_p(st_i.data_ptr()), C.c_void_p(st_t.data_ptr()), C.c_void_p(p_i.data_ptr()), C.c_void_p(p_t.data_ptr()),
+            C.c_void_p(c0.data_ptr()), C.c_void_p(w2t.data_ptr()), C.c_void_p(b2.data_ptr()), C.c_void_p(w3.data_ptr()), float(b3),
+            heads, n_q, n_c, hid1, hid2, C.c_void_p(out_t.data_ptr()), C.c_void_p(_stream_ptr(st_i.device))), "cross_attention_pairs")
+    return out_t
 
 
 # ---------------------------------------------------------------------- per-kernel hooks used by tests

@@ -24,7 +24,6 @@ the two-stage route for those two heads: a deep shortlist by the fused T2I + T2T
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple
 
 import numpy as np
@@ -197,12 +196,7 @@ class FusionModel(nn.Module):
             w, bias, relu = f32(h.gate_net[3].weight).reshape(-1), float(h.gate_net[3].bias.detach()), 1
         else:
             x, pre, w, bias, relu = q.float().contiguous(), None, f32(h.query_weight), float(h.bias.detach().reshape(-1)[0]), 0
-        out = torch.empty(x.shape[0], dtype=torch.float32, device=q.device)
-        with torch.cuda.device(q.device):
-            _lib.check(_lib.lib().kemr_gate_rows(C.c_void_p(x.data_ptr()), x.shape[0], x.shape[1], C.c_void_p(pre.data_ptr()) if pre is not None else None,
-                                                 C.c_void_p(w.data_ptr()), bias, relu, C.c_void_p(out.data_ptr()),
-                                                 C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)), "gate_rows")
-        return out
+        return engine.gate_rows(x, pre, w, bias, relu)
 
     @staticmethod
     def _linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -262,11 +256,10 @@ class FusionModel(nn.Module):
         Q = self._cross_attention_query(q)
         c = self._cross_attention_gallery(img, tgt)
         Ki, Kt, Pi, Pt, c0, w2t, b2, W3, b3 = (c[n] for n in ("Ki", "Kt", "Pi", "Pt", "c0", "w2t", "b2", "w3", "b3"))
-        H, hid1, hid2 = c["H"], c["hid1"], c["hid2"]
+        H = c["H"]
         hd = D // H
         out = torch.empty((N, M), dtype=torch.float32, device=q.device)
         step = max(1, min(N, (256 << 20) // max(1, 2 * H * M * 4)))   # bound the transposed score planes to ~256 MB
-        L = _lib.lib()
         for s0 in range(0, N, step):
             Qc = Q[s0:s0 + step]
             nc = Qc.shape[0]
@@ -277,13 +270,7 @@ class FusionModel(nn.Module):
                 qh = Qc[:, sl].contiguous()
                 sti[hh] = lin(Ki[:, sl].contiguous(), qh)               # [M, nc]: candidates x queries (transposed)
                 stt[hh] = lin(Kt[:, sl].contiguous(), qh)
-            out_t = torch.empty((M, nc), dtype=torch.float32, device=q.device)
-            with torch.cuda.device(q.device):
-                _lib.check(L.kemr_cross_attention_pairs(
-                    C.c_void_p(sti.data_ptr()), C.c_void_p(stt.data_ptr()), C.c_void_p(Pi.data_ptr()), C.c_void_p(Pt.data_ptr()),
-                    C.c_void_p(c0.data_ptr()), C.c_void_p(w2t.data_ptr()), C.c_void_p(b2.data_ptr()),
-                    C.c_void_p(W3.data_ptr()), b3, H, nc, M, hid1, hid2, C.c_void_p(out_t.data_ptr()),
-                    C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)), "cross_attention_pairs")
+            out_t = engine.cross_attention_pairs(sti, stt, Pi, Pt, c0, w2t, b2, W3, b3)
             out[s0:s0 + nc] = out_t.t()
         return out
 
@@ -292,13 +279,7 @@ class FusionModel(nn.Module):
         f = self.fusion_head.fusion.to(t2i.device)
         w0, b0 = f[0].weight.detach().float().contiguous(), f[0].bias.detach().float().contiguous()
         w1, b1 = f[3].weight.detach().float().reshape(-1).contiguous(), float(f[3].bias.detach())
-        out = torch.empty_like(t2i)
-        with torch.cuda.device(t2i.device):
-            _lib.check(_lib.lib().kemr_linear_head(
-                C.c_void_p(t2i.data_ptr()), C.c_void_p(t2t.data_ptr()), t2i.numel(), C.c_void_p(w0.data_ptr()),
-                C.c_void_p(b0.data_ptr()), C.c_void_p(w1.data_ptr()), b1, w0.shape[0], C.c_void_p(out.data_ptr()),
-                C.c_void_p(torch.cuda.current_stream(t2i.device).cuda_stream)), "linear_head")
-        return out
+        return engine.linear_head(t2i.contiguous(), t2t.contiguous(), w0, b0, w1, b1)
 
     @torch.no_grad()
     def forward(self, query_embed, image_embed, target_embed) -> torch.Tensor:

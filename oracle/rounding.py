@@ -22,6 +22,9 @@ device the tensors live on:
 * exact statements, compared bit for bit: ``text_tokens_statement`` (the text tower's token rows and packed row starts) and
   ``panel_statement`` (the bf16 similarity panels); ``panel_representation_bound`` bounds what the panels' bf16 split costs
   against fp64 of the fp32 embeddings.
+* fp64 statements of the learned-head kernels (csrc/rank.hip, csrc/rerank.hip): ``linear_head_statement``, ``gate_rows_emulation``,
+  ``cross_attention_pairs_emulation`` and ``cross_attention_rerank_emulation``.  Their budgets use the square-root form of an fp32
+  FMA chain's error (``FUSION_LAMBDA``), derived in ``_chain``.
 """
 from __future__ import annotations
 
@@ -448,3 +451,167 @@ def panel_representation_bound(q_parts, g_parts, terms, q_part_scale=None, q_row
     ref = sum(x @ y.T for x, y in zip(xq, xg))
     bound = sum((c * (1 + a) * (1 + b) + a + b + a * b) * (x.abs() @ y.abs().T) for x, y, a, b in zip(xq, xg, eq, eg))
     return ref, bound
+
+
+# ------------------------------------------------------------------------------------------------ learned fusion heads
+U32 = 2.0 ** -24              # fp32 unit roundoff
+FUSION_LAMBDA = 1.0           # lambda of _chain; measured in tests/test_rounding_budget.py (see cross_attention_pairs_emulation)
+SHORT_CHAIN_LAMBDA = 4.0      # lambda of linear_head_statement and gate_rows_emulation (see linear_head_statement)
+TANH_ULPS = 4.0               # c_tanh: what the device's tanhf may cost, fp32 ulp of the output (tests/test_numerics_heads_gpu.py)
+EXP_ULPS = 4.0                # the same for expf in gate_rows_kernel, ulp of exp(-s)
+_TINY = 2.0 ** -126           # absolute floor: a fast exp that underflows to 0 where exp(-200) = 1e-87
+
+
+def _chain(n, abs_sum, lam=None):
+    """What an n-term fp32 FMA chain may move its sum by: lam sqrt(n) u sum|terms|.  Every step rounds once, by at most u times the
+    partial sum, itself at most sum|terms|; the worst case n u sum|terms| assumes n roundings of one sign and full size, and is
+    useless for a three-layer head (about 5e4 fp32 ulp of the output at hid1 = 256, hid2 = 64, where correct fp32 arithmetic
+    reads 3e-4 of it and a dropped unit passes).  Roundings are independent in sign, so they add in quadrature: sqrt(n) u
+    sum|terms| is an n-step random walk with every step at its largest; lam is the safety factor on top."""
+    return (FUSION_LAMBDA if lam is None else lam) * (float(n) ** 0.5) * U32 * abs_sum
+
+
+def _fusion_mix(d, dd, p_i, p_t, c0, w2t, b2, w3, b3, lam, c_tanh):
+    """The pair arithmetic shared by the dense and the gathered cross_attention kernels, in fp64.  d [B, R, H] = image score - target
+    score per head, dd [B, R, H] what fp32 moved d by before the exponential (0 where the scores are given); p_x [B, H, hid1].
+    Returns (out, extra) [B, R].  See cross_attention_pairs_emulation for the derivation."""
+    heads = d.shape[-1]
+    w_i = torch.sigmoid(d)
+    w_t = torch.sigmoid(-d)                                                   # 1 - w_i without cancellation
+    eps_e = U32 * (2 * d.abs() * 1.4427 + 4) + 3 * U32
+    dw_i = w_i * eps_e + w_i * w_t * dd + _TINY
+    dw_t = w_t * eps_e + w_i * w_t * dd + _TINY
+    pre = c0 + w_i @ p_i + w_t @ p_t                                          # [B, R, hid1]
+    pre_abs = c0.abs() + w_i @ p_i.abs() + w_t @ p_t.abs()
+    dh = dw_i @ p_i.abs() + dw_t @ p_t.abs() + _chain(2 * heads, pre_abs, lam)
+    h = pre.clamp_min(0)
+    z = h @ w2t + b2
+    dz = torch.sqrt((dh * dh) @ (w2t * w2t)) + _chain(w2t.shape[0] + 1, h @ w2t.abs() + b2.abs(), lam)
+    z = z.clamp_min(0)
+    o = z @ w3 + b3
+    do = torch.sqrt((dz * dz) @ (w3 * w3)) + _chain(w3.shape[0], z @ w3.abs() + abs(b3), lam)
+    out = 0.5 * torch.tanh(o)
+    return out, 0.5 * do + c_tanh * ulp(out, "fp32")
+
+
+def _head_consts(c0, w2t, b2, w3, b3):
+    c0, w2t, b2, w3 = (t.double().cpu() for t in (c0, w2t, b2, w3))
+    return c0.reshape(-1), w2t, b2.reshape(-1), w3.reshape(-1), _f32_scale(b3)
+
+
+def cross_attention_pairs_emulation(st_i, st_t, p_i, p_t, c0, w2t, b2, w3, b3, lam=None, c_tanh=None):
+    """fp64 statement of csrc/rank.hip cross_attn_pair_kernel on the fp32 tensors it is given: st_x [H, n_c, n_q] scaled scores, p_x
+    [n_c, H, hid1], c0 [hid1], w2t [hid1, hid2], b2 / w3 [hid2], b3 (passed as fp32).  Per pair and head w_i = sigmoid(st_i - st_t),
+    w_t = 1 - w_i (the kernel's two-way softmax); h = relu(c0 + sum_h w_i P_i + w_t P_t); z = relu(h W2^T + b2);
+    out = 0.5 tanh(z . w3 + b3).  Returns (out, extra) [n_c, n_q], the kernel's transposed layout.  With u = 2^-24:
+    * weights: the kernel takes exp(s_x - max) of both sides (one of them exp(0) = 1), adds, takes the reciprocal and multiplies.  The
+      exponential gets attention_emulation's allowance, u (2 |d| log2 e + 4) relative (the fp32 subtraction and the fast exp), the
+      add, reciprocal and multiply u each: dw_x = w_x (u (2 |d| log2 e + 4) + 3 u), plus 2^-126 for an exp that underflows to 0;
+    * h: 2 H FMAs on c0, _chain(2 H, |c0| + sum w_i |P_i| + w_t |P_t|), plus sum dw_i |P_i| + dw_t |P_t|; ReLU does not grow an error;
+    * z: hid1 FMAs and the add of b2, _chain(hid1 + 1, h |W2^T| + |b2|), plus the errors of h carried through |W2| IN QUADRATURE,
+      sqrt(sum_j (dh_j W2_jk)^2): the roundings of different units are independent (the weights' share of dh is common to the units
+      of a pair; it is small beside the allowance it is given, which the measured ratios below confirm);
+    * o: hid2 FMAs on b3, _chain(hid2, |b3| + z |w3|), plus sqrt(sum_k (dz_k w3_k)^2);
+    * out: tanh is 1-Lipschitz, 0.5 do, plus TANH_ULPS fp32 ulp of the output for the device's tanhf.
+    The final rounding of 0.5 * tanhf is exact (a power of two); check_budget(fmt="fp32") grants its half ulp regardless.
+    lambda (FUSION_LAMBDA) = 1: the CPU fp32 stand-in of tests/test_rounding_budget.py, which follows the kernel's order with a
+    separate multiply and add per FMA, reads 0.032 .. 0.050 of the budget on the four named cases (hid1 x hid2 7x1, 260x17, 256x64, 500x64; bar 0.25; the rerank
+    stand-in 0.017); W2 rounded
+    to bf16 reads above 100.  The kernels on an MI355X read at most 0.19 (dense) and 0.15 (gathered) over the cases of
+    tests/test_numerics_heads_gpu.py (bar 1); on exact arguments their 0.5 tanhf lies within 1.22 fp32 ulp of the fp64 value, so
+    TANH_ULPS stays at 4."""
+    sti, stt = st_i.double().cpu(), st_t.double().cpu()
+    d = (sti - stt).permute(1, 2, 0)                                          # [n_c, n_q, H]
+    c0, w2t, b2, w3, b3 = _head_consts(c0, w2t, b2, w3, b3)
+    return _fusion_mix(d, torch.zeros_like(d), p_i.double().cpu(), p_t.double().cpu(), c0, w2t, b2, w3, b3, lam,
+                       TANH_ULPS if c_tanh is None else c_tanh)
+
+
+def rerank_dots(q, k_i, k_t, heads, cand, depth):
+    """The gathered route's per-head dot products in fp64: (a_i, a_t, |q|.|k_i| + |q|.|k_t|, valid), each [nq, depth, heads]
+    (valid [nq, depth]: the slots whose id lies in 0 .. ng - 1; the others read candidate 0 and are to be ignored)."""
+    q, k_i, k_t = q.double().cpu(), k_i.double().cpu(), k_t.double().cpu()
+    nq, dim = q.shape
+    ng = k_i.shape[0]
+    ids = cand.long().cpu()[:, :depth]
+    valid = (ids >= 0) & (ids < ng)
+    ids = torch.where(valid, ids, torch.zeros_like(ids))
+    per_head = lambda x: x.view(nq, depth, heads, dim // heads).sum(-1)       # noqa: E731
+    qq = q[:, None, :]
+    ki, kt = k_i[ids], k_t[ids]                                               # [nq, depth, dim]
+    return per_head(qq * ki), per_head(qq * kt), per_head(qq.abs() * ki.abs()) + per_head(qq.abs() * kt.abs()), valid
+
+
+def cross_attention_rerank_emulation(q, k_i, k_t, p_i, p_t, c0, w2t, b2, w3, b3, cand, depth, lam=None, c_tanh=None):
+    """fp64 statement of csrc/rerank.hip cross_attn_rerank_kernel: for every slot (row, j < depth) of cand [nq, ld] with an id c in
+    0 .. ng - 1, the pair statement of cross_attention_pairs_emulation behind the per-head dot products s_x[h] = Q[row, head h] .
+    K_x[c, head h] (q [nq, dim] already scaled, k_x [ng, dim], head h = columns h dim / H .. (h + 1) dim / H - 1, H = p_i.shape[1]).
+    Every other slot (padding, an id outside the gallery) is -inf with extra 0.  Returns (out, extra) [nq, depth].
+    The kernel sums a head's dim / H products per lane (an FMA chain of 4, or single products) and over the wave in 6 butterfly
+    adds: _chain(dim / H + 6, |q| . |k|) per dot product.  The two errors of a head move d = s_i - s_t by at most their sum, and the
+    softmax weight by w_i w_t (the sigmoid's slope) times that, on top of the pair statement's dw.  The rest is the pair statement:
+    the kernel keeps the dense kernel's FMA order for h, one ascending-k accumulator chain per MFMA tile for z and the same tail."""
+    heads = p_i.shape[1]
+    a_i, a_t, ab, valid = rerank_dots(q, k_i, k_t, heads, cand, depth)
+    nq = a_i.shape[0]
+    ids = torch.where(valid, cand.long().cpu()[:, :depth], torch.zeros_like(valid, dtype=torch.int64)).reshape(-1)
+    d = (a_i - a_t).reshape(nq * depth, 1, heads)
+    dd = _chain(q.shape[1] // heads + 6, ab, lam).reshape(nq * depth, 1, heads)
+    c0, w2t, b2, w3, b3 = _head_consts(c0, w2t, b2, w3, b3)
+    out, extra = _fusion_mix(d, dd, p_i.double().cpu()[ids], p_t.double().cpu()[ids], c0, w2t, b2, w3, b3, lam,
+                             TANH_ULPS if c_tanh is None else c_tanh)
+    out, extra = out.reshape(nq, depth), extra.reshape(nq, depth)
+    return out.masked_fill(~valid, float("-inf")), extra.masked_fill(~valid, 0.0)
+
+
+def linear_head_statement(t2i, t2t, w0, b0, w1, b1, lam=None):
+    """fp64 statement of csrc/rank.hip linear_head_kernel: out = b1 + sum_h w1[h] relu(w0[h, 0] t2i + w0[h, 1] t2t + b0[h]) for every
+    element of the two equally shaped fp32 tensors (w0 [hidden, 2], b0 / w1 [hidden], b1 passed as fp32).  Returns (out, extra) in
+    the inputs' shape.  A unit is two FMAs on b0[h]: at most 2 u (|w0 t2i| + |w0 t2t| + |b0|), the worst case (two terms need no
+    statistics); ReLU does not grow it.  The output is a chain of `hidden` FMAs on b1 in ascending h: _chain(hidden, |b1| +
+    sum |w1| relu(.)), plus the units' errors through |w1| in quadrature.  The last FMA's rounding is the half ulp of
+    check_budget(fmt="fp32").  Evaluated in row blocks of at most 2^24 / hidden elements.
+    lambda is SHORT_CHAIN_LAMBDA = 4 here and in gate_rows_emulation, not FUSION_LAMBDA: where the chain is a handful of steps the final
+    rounding's half ulp is most of the error, and a stand-in can only stay at a quarter of (half an ulp + extra) if extra is at least
+    1.5 ulp.  The FMA-exact CPU stand-ins of tests/test_rounding_budget.py read up to 0.35 (linear, hidden = 1) and 0.45 (gate, cols =
+    1) at lambda = 1, 0.27 and 0.45 at 2, 0.17 and 0.15 at 4: the next power of two that meets 0.25 on every case.  The kernels on an MI355X read at
+    most 0.24 (linear head) and 0.14 (gate); 1 / (1 + expf(-s)) on exact integer s lies within 0.92 fp32 ulp of the fp64 value."""
+    shape = t2i.shape
+    a, b = t2i.double().cpu().reshape(-1, 1), t2t.double().cpu().reshape(-1, 1)
+    w0, b0, w1 = w0.double().cpu().reshape(-1, 2), b0.double().cpu().reshape(-1), w1.double().cpu().reshape(-1)
+    b1 = _f32_scale(b1)
+    hidden = w0.shape[0]
+    step = max(1, (1 << 24) // hidden)
+    outs, extras = [], []
+    for s in range(0, a.shape[0], step):
+        x, y = a[s:s + step] * w0[:, 0], b[s:s + step] * w0[:, 1]
+        t = (x + y + b0).clamp_min(0)
+        dt = 2 * U32 * (x.abs() + y.abs() + b0.abs())
+        outs.append(t @ w1 + b1)
+        extras.append(torch.sqrt((dt * dt) @ (w1 * w1)) + _chain(hidden, t @ w1.abs() + abs(b1), SHORT_CHAIN_LAMBDA if lam is None else lam))
+    return torch.cat(outs).reshape(shape), torch.cat(extras).reshape(shape)
+
+
+def gate_rows_emulation(x, pre, w, bias, relu, lam=None, c_exp=None):
+    """fp64 statement of csrc/rank.hip gate_rows_kernel: out[r] = sigmoid(sum_c act(x[r, c] + pre[c]) w[c] + bias), act = ReLU when
+    relu else the identity; x fp32 [rows, cols], pre [cols] or None, w [cols], bias passed as fp32.  Returns (out, extra) [rows].
+    The kernel adds pre in fp32 (u |v|, nothing without pre), sums ceil(cols / 64) FMAs per lane, 6 butterfly adds over the wave
+    and the add of the bias: _chain(ceil(cols / 64) + 7, sum |v w| + |bias|), plus the errors of v through |w| in quadrature; that
+    is ds.  out = 1 / (1 + expf(-s)): the sigmoid's slope out (1 - out) carries ds and expf's EXP_ULPS ulp (2 u EXP_ULPS relative on
+    exp(-s), i.e. out (1 - out) times that); the add and the division round once each, lambda 2 u out.  2^-126 absolute covers an
+    exponential that overflows (s < -88: out is 0, never NaN) where the exact value is below every normal number.
+    lambda is SHORT_CHAIN_LAMBDA (linear_head_statement), on the two output roundings as well: for out in [0.5, 1) one ulp IS u, so
+    the add's u and the division's half ulp alone read 0.6 of a budget of half an ulp + 2 u (measured: 0.45 at cols = 1)."""
+    x64, w64 = x.double().cpu(), w.double().cpu().reshape(-1)
+    v = x64 if pre is None else x64 + pre.double().cpu().reshape(-1)
+    dv = torch.zeros_like(v) if pre is None else U32 * v.abs()
+    if relu:
+        v = v.clamp_min(0)
+    bias = _f32_scale(bias)
+    s = v @ w64 + bias
+    lam = SHORT_CHAIN_LAMBDA if lam is None else lam
+    ds = torch.sqrt((dv * dv) @ (w64 * w64)) + _chain((x.shape[1] + 63) // 64 + 7, v.abs() @ w64.abs() + abs(bias), lam)
+    out = torch.sigmoid(s)
+    slope = out * torch.sigmoid(-s)
+    c = EXP_ULPS if c_exp is None else c_exp
+    return out, slope * (ds + 2 * U32 * c) + lam * 2 * U32 * out + _TINY

@@ -248,6 +248,53 @@ def test_module_repacks_after_in_place_weight_edits_and_refuses_nan(device):
         ranking.ranks_of_matrix(S)
 
 
+def _head_budget_at_larger_weights(ft, D, device, seed=15):
+    """The fixed tolerances of the two tests below are bars for small pre-activations: at randn * 0.15 parameters correct fp32
+    arithmetic leaves them.  What holds at any parameters is the head kernel's rounding budget (oracle/rounding.py): the kernel's
+    output against the fp64 statement of its arithmetic ON THE fp32 TENSORS IT IS GIVEN, ratio <= 1 on every element.  Checked here
+    at randn * 0.15 for the head kernel behind `ft` (bilinear has none: it is one weighted contraction)."""
+    from knowledge_enhanced_multimodal_retrieval_amd import _lib, engine
+    from oracle import rounding as R
+    from src.clip.models import FusionModel
+    g = torch.Generator().manual_seed(seed)
+    fm = FusionModel(torch.nn.Linear(1, 1), fusion_type=ft, embed_dim=D)
+    with torch.no_grad():
+        for p_ in fm.fusion_head.parameters():
+            p_.copy_(torch.randn(p_.shape, generator=g) * 0.15)
+    fm = fm.to(device).eval()
+    q, im, tg = (torch.nn.functional.normalize(torch.randn(n, D, generator=g), dim=-1).to(device) for n in (37, 53, 53))
+    h = fm.fusion_head
+    if ft == "cross_attention":
+        Q, c = fm._cross_attention_query(q), fm._cross_attention_gallery(im, tg)
+        hd = D // c["H"]
+        planes = lambda K: torch.stack([fm._linear(K[:, i * hd:(i + 1) * hd].contiguous(), Q[:, i * hd:(i + 1) * hd].contiguous())  # noqa: E731
+                                        for i in range(c["H"])]).contiguous()
+        st_i, st_t = planes(c["Ki"]), planes(c["Kt"])
+        got = engine.cross_attention_pairs(st_i, st_t, c["Pi"], c["Pt"], c["c0"], c["w2t"], c["b2"], c["w3"], c["b3"])
+        assert torch.equal(got.t(), fm(q, im, tg))                           # the matrix forward() returns, bit for bit
+        ref, extra = R.cross_attention_pairs_emulation(st_i, st_t, c["Pi"], c["Pt"], c["c0"], c["w2t"], c["b2"], c["w3"], c["b3"])
+    elif ft == "linear":
+        qp = engine.build_panel([q], _lib.SIDE_QUERY, 3)
+        t2i = engine.scores_dense(qp, engine.build_panel([im], _lib.SIDE_GALLERY, 3))
+        t2t = engine.scores_dense(qp, engine.build_panel([tg], _lib.SIDE_GALLERY, 3))
+        got = fm._linear_head(t2i, t2t)
+        assert torch.equal(got, fm(q, im, tg))
+        f = h.fusion
+        ref, extra = R.linear_head_statement(t2i, t2t, f[0].weight.detach(), f[0].bias.detach(), f[3].weight.detach(), float(f[3].bias.detach()))
+    elif ft == "gated":
+        x = fm._linear(q, h.gate_net[0].weight)
+        got = fm._gate(q)
+        ref, extra = R.gate_rows_emulation(x, h.gate_net[0].bias.detach(), h.gate_net[3].weight.detach(), float(h.gate_net[3].bias.detach()), 1)
+    elif ft in ("simple_gated", "simple_gated_with_bias"):
+        got = fm._gate(q)
+        ref, extra = R.gate_rows_emulation(q, None, h.query_weight.detach(), float(h.bias.detach().reshape(-1)[0]), 0)
+    else:
+        return None
+    top, _ = R.check_budget(got.reshape(1, -1), ref.reshape(1, -1), extra.reshape(1, -1), fmt="fp32", what=f"{ft} head at randn * 0.15, D = {D}")
+    print(f"{ft} head at randn * 0.15, D = {D}: worst budget ratio {top:.4f}")
+    return top
+
+
 @pytest.mark.parametrize("ft", ["linear", "gated", "simple_gated", "simple_gated_with_bias", "bilinear", "cross_attention"])
 def test_fusion_heads_match_reference_golden(device, golden_dir, ft):
     from src.clip.models import FusionModel
@@ -272,6 +319,7 @@ def test_fusion_heads_match_reference_golden(device, golden_dir, ft):
     clear = d.min(axis=1) > 1e-5
     assert np.array_equal(ranks.cpu().numpy()[clear], metrics_ref.ranks_by_count(want, gt)[clear])
     assert np.array_equal(top_i.cpu().numpy()[:, 0], want.argmax(axis=1))
+    _head_budget_at_larger_weights(ft, 64, device)
 
 
 def test_cross_attention_head_at_clip_width(device):
@@ -290,6 +338,7 @@ def test_cross_attention_head_at_clip_width(device):
     want = fusion_ref.head_scores("cross_attention", sd, q, im, tg)
     got = fm.to(device)(q, im, tg).cpu().numpy()
     np.testing.assert_allclose(got, want, rtol=1e-3, atol=2e-5)
+    _head_budget_at_larger_weights("cross_attention", D, device)
     with pytest.raises(ValueError):
         FusionModel(torch.nn.Linear(1, 1), fusion_type="bogus")
 

@@ -496,3 +496,19 @@ def test_encode_dataset_groups_text_calls_by_token_rows(monkeypatch):
     assert torch.equal(qry, ids_q[:, :4].float()) and torch.equal(tgt, ids_t[:, :4].float()) and img.shape[0] == n
     assert sum(c[0] for c in calls) == 2 * n and len(calls) > 3
     assert all(rows <= 120 or texts == 2 for texts, rows in calls)        # a call stays inside the budget (one pair may exceed it alone)
+
+
+def test_rank_dense_of_an_empty_gallery_returns_padding(monkeypatch):
+    """ng == 0: no kernel runs, so the wrapper itself has to fill the lists (-inf / -1) and the counts (0); the launch is skipped,
+    which lets host tensors stand in for device ones here."""
+    from knowledge_enhanced_multimodal_retrieval_amd import engine
+    monkeypatch.setattr(engine, "_require_cuda", lambda t, what: None)
+    for nq in (3, 1):
+        ahead, top_s, top_i = engine.rank_dense(torch.empty(nq, 0), torch.zeros(nq, dtype=torch.int64), k=4)
+        assert ahead.dtype == torch.int32 and ahead.tolist() == [0] * nq
+        assert top_s.dtype == torch.float32 and tuple(top_s.shape) == (nq, 4) and bool(torch.isneginf(top_s).all())
+        assert top_i.dtype == torch.int32 and top_i.tolist() == [[-1] * 4] * nq
+    ahead, top_s, top_i = engine.rank_dense(torch.empty(2, 0), None, k=0)
+    assert ahead is None and top_s is None and top_i is None
+    ahead, top_s, top_i = engine.rank_dense(torch.empty(0, 5), torch.zeros(0, dtype=torch.int64), k=3)
+    assert tuple(ahead.shape) == (0,) and tuple(top_s.shape) == (0, 3) and tuple(top_i.shape) == (0, 3)

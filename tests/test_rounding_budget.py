@@ -655,3 +655,209 @@ def test_representation_bound_is_tight_enough_to_matter(scores_case):
     err = (s1 - rep).abs()
     assert float((err / (b1 + extra1)).max()) <= 1.0
     assert float((err / (b3 + extra1)).max()) > 4.0
+
+
+# ------------------------------------------------------------------------------------------------ learned fusion heads
+HEAD_STAND_IN_BAR = 0.25       # the CPU stand-ins must leave a factor of four to the GPU's FMA contraction, exp, tanh and division
+HEAD_DEFECT_SHARE = 0.02       # a planted defect must break the budget on at least this share of the outputs
+
+
+def _head_ratio(got, ref, extra):
+    """Budget ratio over the finite slots of the statement; padded slots (-inf) must be -inf in `got`."""
+    pad = torch.isinf(ref)
+    assert bool(torch.isinf(got.double()[pad]).all())
+    return torch.nan_to_num(R.budget_ratio(got, ref, extra, "fp32")[~pad], nan=float("inf"))
+
+
+def _head_check(name, defect, got, ref, extra):
+    ratio = _head_ratio(got, ref, extra)
+    top, share = float(ratio.max()), float((ratio > 1).double().mean())
+    print(f"{name} defect={defect}: worst ratio {top:.4g}, share above 1: {share:.3f}")
+    if defect is None:
+        assert top <= HEAD_STAND_IN_BAR, (name, top)
+    else:
+        assert share >= HEAD_DEFECT_SHARE, (name, defect, top, share)
+    return top
+
+
+def _fma(a, b, c):
+    """fmaf: the product of two fp32 values is exact in fp64, so one fp64 add and one rounding to fp32 is the fused result (up to
+    a double rounding 2^-29 of an ulp away from a tie)."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _mix_cpu(a, b, p_i, p_t, c0, w2t, b2, w3, b3, defect=None):
+    """fp32 stand-in of the pair arithmetic in the kernels' order, FMA for FMA (torch's exp, tanh and division in place of the
+    device's): a, b [B, R, H] scores, p_x [B, H, hid1] -> [B, R]."""
+    heads, hid1, hid2 = a.shape[-1], w2t.shape[0], w2t.shape[1]
+    mx = torch.maximum(a, b)
+    ea, eb = torch.exp(a - mx), torch.exp(b - mx)
+    inv = 1.0 / (ea + eb)
+    wi, wt = ea * inv, eb * inv
+    if defect == "weights_swapped_in_one_head":
+        wi, wt = wi.clone(), wt.clone()
+        wi[..., 3], wt[..., 3] = wt[..., 3].clone(), wi[..., 3].clone()
+    hs = (torch.zeros_like(c0) if defect == "c0_dropped" else c0).expand(a.shape[0], a.shape[1], hid1)
+    for h in range(heads):
+        hs = _fma(wi[..., h, None], p_i[:, None, h, :], _fma(wt[..., h, None], p_t[:, None, h, :], hs))
+    hs = hs.clamp_min(0)
+    if defect == "last_hid1_unit_dropped":
+        hs = hs.clone()
+        hs[..., -1] = 0
+    w2 = w2t.to(torch.bfloat16).float() if defect == "w2_bf16" else w2t
+    acc = torch.zeros(a.shape[0], a.shape[1], hid2)
+    for j in range(hid1):
+        acc = _fma(hs[..., j, None], w2[j], acc)
+    z = acc.clamp_min(0) + b2 if defect == "b2_after_relu" else (acc + b2).clamp_min(0)
+    o = torch.full(a.shape[:2], b3, dtype=torch.float32)
+    for k in range(hid2 - 1 if defect == "chain_stops_at_hid2-1" else hid2):
+        o = _fma(z[..., k], w3[k], o)
+    return torch.tanh(o) if defect == "tanh_without_half" else 0.5 * torch.tanh(o)
+
+
+def _pairs_cpu(st_i, st_t, p_i, p_t, c0, w2t, b2, w3, b3, defect=None):
+    return _mix_cpu(st_i.permute(1, 2, 0), st_t.permute(1, 2, 0), p_i, p_t, c0, w2t, b2, w3, b3, defect)
+
+
+def _head_params(g, heads, n_c, hid1, hid2, scale):
+    r = lambda *s: torch.randn(*s, generator=g) * scale                       # noqa: E731
+    return dict(p_i=r(n_c, heads, hid1), p_t=r(n_c, heads, hid1), c0=r(hid1), w2t=r(hid1, hid2), b2=r(hid2), w3=r(hid2),
+                b3=float(r(1)[0]))
+
+
+PAIR_CASES = {"7x1": (7, 1, 1.0), "260x17": (260, 17, 0.3), "256x64": (256, 64, 0.1), "500x64": (500, 64, 0.05)}
+
+
+@pytest.fixture(scope="module")
+def pair_cases():
+    out = {}
+    for i, (name, (hid1, hid2, scale)) in enumerate(PAIR_CASES.items()):
+        g = torch.Generator().manual_seed(100 + i)
+        prm = _head_params(g, 8, 3, hid1, hid2, scale)
+        st_i, st_t = torch.randn(8, 3, 200, generator=g) * 2, torch.randn(8, 3, 200, generator=g) * 2
+        out[name] = (st_i, st_t, prm, R.cross_attention_pairs_emulation(st_i, st_t, **prm))
+    return out
+
+
+PAIR_DEFECTS = ["weights_swapped_in_one_head", "c0_dropped", "b2_after_relu", "chain_stops_at_hid2-1", "last_hid1_unit_dropped", "w2_bf16",
+                "tanh_without_half"]
+
+
+@pytest.mark.parametrize("case", list(PAIR_CASES))
+@pytest.mark.parametrize("defect", [None] + PAIR_DEFECTS)
+def test_cross_attention_pair_budget(pair_cases, case, defect):
+    st_i, st_t, prm, (ref, extra) = pair_cases[case]
+    _head_check(f"pairs {case}", defect, _pairs_cpu(st_i, st_t, defect=defect, **prm), ref, extra)
+
+
+def _rerank_cpu(q, k_i, k_t, cand, depth, prm, defect=None):
+    """fp32 stand-in of the gathered route: per-head dot products of the gathered rows, then the pair arithmetic."""
+    heads = prm["p_i"].shape[1]
+    nq, dim = q.shape
+    ng, hd = k_i.shape[0], dim // heads
+    ids = cand[:, :depth].long()
+    valid = (ids >= 0) & (ids < ng)
+    ids = torch.where(valid, ids, torch.zeros_like(ids))
+    used = dim // 4 * 4 if defect == "last_dim%4_elements_dropped" else dim
+    keep = (torch.arange(dim) < used).float()
+
+    def dots(k):
+        prod = (q[:, None, :] * k[ids] * keep).view(nq, depth, heads, hd)
+        if defect == "neighbouring_heads_columns":
+            prod = prod.clone()
+            prod[:, :, 0] = prod[:, :, 1]
+        return prod.sum(-1)
+
+    flat = lambda x: x.reshape(nq * depth, 1, heads)                         # noqa: E731
+    p = {n: (v[ids.reshape(-1)] if n in ("p_i", "p_t") else v) for n, v in prm.items()}
+    out = _mix_cpu(flat(dots(k_i)), flat(dots(k_t)), **p).reshape(nq, depth)
+    return out.masked_fill(~valid, float("-inf"))
+
+
+def _rerank_case(seed, heads, dim, hid1, hid2, scale, ng=40, nq=3, depth=100):
+    g = torch.Generator().manual_seed(seed)
+    prm = _head_params(g, heads, ng, hid1, hid2, scale)
+    amp = (2.0 / (dim // heads) ** 0.5) ** 0.5                               # per-head dot products ~ randn * 2
+    q, k_i, k_t = (torch.randn(n, dim, generator=g) * amp for n in (nq, ng, ng))
+    cand = torch.randint(0, ng, (nq, depth + 3), generator=g, dtype=torch.int32)
+    cand[0, 5], cand[1, 0], cand[2, depth - 1] = -1, ng, 2 ** 31 - 1
+    return q, k_i, k_t, cand, depth, prm
+
+
+@pytest.mark.parametrize("defect", [None, "neighbouring_heads_columns"])
+def test_cross_attention_rerank_budget(defect):
+    q, k_i, k_t, cand, depth, prm = _rerank_case(7, 8, 72, 260, 17, 0.3)
+    ref, extra = R.cross_attention_rerank_emulation(q, k_i, k_t, cand=cand, depth=depth, **prm)
+    assert tuple(ref.shape) == (3, depth) and int(torch.isinf(ref).sum()) == 3          # the three slots outside the gallery
+    _head_check("rerank dim 72", defect, _rerank_cpu(q, k_i, k_t, cand, depth, prm, defect), ref, extra)
+
+
+@pytest.mark.parametrize("defect", [None, "last_dim%4_elements_dropped"])
+def test_cross_attention_rerank_budget_catches_a_dropped_vector_tail(defect):
+    """dim % 4 != 0 needs a head count that does not divide by four: the statement takes the heads from p_i (the kernel serves
+    8 heads, where dim % 8 == 0 leaves no such tail -- its scalar instance is for dim % 32 != 0)."""
+    q, k_i, k_t, cand, depth, prm = _rerank_case(8, 2, 6, 8, 4, 1.0)
+    ref, extra = R.cross_attention_rerank_emulation(q, k_i, k_t, cand=cand, depth=depth, **prm)
+    _head_check("rerank dim 6", defect, _rerank_cpu(q, k_i, k_t, cand, depth, prm, defect), ref, extra)
+
+
+def _linear_cpu(t2i, t2t, w0, b0, w1, b1, defect=None):
+    a, b = (t2t, t2i) if defect == "inputs_swapped" else (t2i, t2t)
+    acc = torch.full_like(a, b1)
+    for h in range(w0.shape[0]):
+        t = _fma(w0[h, 0], a, _fma(w0[h, 1], b, b0[h]))
+        acc = _fma(w1[h], t if defect == "relu_dropped" else t.clamp_min(0), acc)
+    if defect == "last_element_not_written":
+        acc[-1] = -7.0                                                       # the test's sentinel
+    return acc
+
+
+@pytest.mark.parametrize("hidden", [1, 128, 2048])
+@pytest.mark.parametrize("defect", [None, "relu_dropped", "inputs_swapped", "last_element_not_written"])
+def test_linear_head_budget(hidden, defect):
+    g = torch.Generator().manual_seed(200 + hidden)
+    n = 33 if defect == "last_element_not_written" else 2000                 # one unwritten element of 33 is 3 % of the outputs
+    t2i, t2t = torch.randn(n, generator=g) * 0.3, torch.randn(n, generator=g) * 0.3
+    w0, b0, w1 = torch.randn(hidden, 2, generator=g), torch.randn(hidden, generator=g) * 0.3, torch.randn(hidden, generator=g) * hidden ** -0.5
+    b1 = float(torch.randn(1, generator=g)[0])
+    ref, extra = R.linear_head_statement(t2i, t2t, w0, b0, w1, b1)
+    _head_check(f"linear hidden {hidden}", defect, _linear_cpu(t2i, t2t, w0, b0, w1, b1, defect), ref, extra)
+
+
+def _gate_cpu(x, pre, w, bias, relu, defect=None):
+    rows, cols = x.shape
+    used = cols // 64 * 64 if defect == "last_cols%64_dropped" else cols
+    v = x if pre is None or defect == "pre_ignored" else x + pre
+    if relu or defect == "relu_when_off":
+        v = v.clamp_min(0)
+    pad = (cols + 63) // 64 * 64
+    s = torch.zeros(rows, 64)
+    vp, wp = torch.zeros(rows, pad), torch.zeros(pad)
+    vp[:, :used], wp[:used] = v[:, :used], w[:used]
+    for c in range(0, pad, 64):                                              # lane l sums columns l, l + 64, ...
+        s = _fma(vp[:, c:c + 64], wp[c:c + 64], s)
+    return 1.0 / (1.0 + torch.exp(-(s.sum(-1) + bias)))
+
+
+def _gate_case(cols, with_pre):
+    g = torch.Generator().manual_seed(300 + cols)
+    x = torch.randn(400, cols, generator=g)
+    pre = torch.randn(cols, generator=g) * 0.5 if with_pre else None
+    return x, pre, torch.randn(cols, generator=g) * cols ** -0.5
+
+
+@pytest.mark.parametrize("cols", [1, 64, 65, 1000])
+@pytest.mark.parametrize("relu,with_pre", [(0, True), (1, True), (0, False)])
+def test_gate_rows_budget_passes_the_stand_in(cols, relu, with_pre):
+    x, pre, w = _gate_case(cols, with_pre)
+    ref, extra = R.gate_rows_emulation(x, pre, w, 0.25, relu)
+    _head_check(f"gate cols {cols} relu {relu} pre {with_pre}", None, _gate_cpu(x, pre, w, 0.25, relu), ref, extra)
+
+
+@pytest.mark.parametrize("cols", [65, 1000])
+@pytest.mark.parametrize("relu,with_pre,defect", [(0, True, "relu_when_off"), (1, True, "pre_ignored"), (0, True, "pre_ignored"),
+                                                  (1, True, "last_cols%64_dropped"), (0, False, "last_cols%64_dropped")])
+def test_gate_rows_budget_catches_planted_defects(cols, relu, with_pre, defect):
+    x, pre, w = _gate_case(cols, with_pre)
+    ref, extra = R.gate_rows_emulation(x, pre, w, 0.25, relu)
+    _head_check(f"gate cols {cols} relu {relu} pre {with_pre}", defect, _gate_cpu(x, pre, w, 0.25, relu, defect), ref, extra)
