@@ -38,7 +38,9 @@ extern "C" {
  *    to the vision tower only and scale the e4m3 A operand per channel; kemr_preprocess_u8_batch accepts 0 x 0 items (an undecodable
  *    image: zeros after normalisation); kemr_debug_set refuses the experiment kernels the library was built without.
  *    Still 4: kemr_select_topk, kemr_sim_topk_deep, kemr_sim_topk_deep_workspace_bytes and kemr_sim_topk_deep_fused are additions, no
- *    existing entry point changed. */
+ *    existing entry point changed.  Option "activation" of kemr_model_set_option / kemr_model_get_option and the epilogue value
+ *    KEMR_EPI_BIAS_GELU_BF16 (kemr_op_gemm, kemr_op_gemm_fp8) are additions as well: the default, 0, is the QuickGELU every existing
+ *    caller gets; no entry point was added. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -135,7 +137,12 @@ int kemr_model_destroy(kemr_model* m);
  *                      4 bytes per element in the HBM-bound LayerNorm passes (+2 % on the ViT-L/14 step); every statistic and add
  *                      stays fp32 arithmetic.  The default because it meets every bar the 4-byte stream meets (1 - cos against the
  *                      fp32 oracle on plain and heavy-tailed weights, the fixed 0.2-point Recall@10 bar on ViT-B/32 and ViT-L/14,
- *                      the end-to-end margin rule: DESIGN.md section 2); 0 = the 4-byte stream (python: precision "bf16"). */
+ *                      the end-to-end margin rule: DESIGN.md section 2); 0 = the 4-byte stream (python: precision "bf16").
+ *   "activation"       the MLP's activation between fc1 and fc2, in both towers: 0 (default) QuickGELU x sigmoid(1.702 x), what the
+ *                      OpenAI checkpoints were trained with; 1 exact GELU 0.5 x (1 + erf(x / sqrt 2)) = torch.nn.GELU(), what the
+ *                      OpenCLIP / LAION ViT-B/32, B/16 and L/14 checkpoints and Hugging Face configs with hidden_act "gelu" use.
+ *                      It selects the epilogue of the fc1 GEMMs (bf16 and fp8 operands, the pooled-row last block) and nothing
+ *                      else; the weights are not touched, so it may be flipped between encode calls without a finalize. */
 int kemr_model_set_option(kemr_model* m, const char* key, int value);
 int kemr_model_get_option(const kemr_model* m, const char* key, int* value);
 /* number of required tensor names; name i via kemr_model_tensor_name (for strict-load diagnostics) */
@@ -348,8 +355,9 @@ typedef enum kemr_epilogue {
     KEMR_EPI_BIAS_QGELU_BF16 = 1,  /* C_bf16 = quickgelu(A.W^T + bias)                       */
     KEMR_EPI_BIAS_RESID_F32 = 2,   /* X_f32 += A.W^T + bias   (in place on the residual; from 128 output tiles of 256 x 256 and more
                                       than 512 rows up the persistent kernel: C with ceil256(m) rows) */
-    KEMR_EPI_BIAS_RESADD_BF16 = 4  /* X_bf16 = bf16(bf16(A.W^T + bias) + X_bf16), in place; persistent 256 x 256 kernel only:
+    KEMR_EPI_BIAS_RESADD_BF16 = 4, /* X_bf16 = bf16(bf16(A.W^T + bias) + X_bf16), in place; persistent 256 x 256 kernel only:
                                       N % 256 == 0, m > 512, C with ceil256(m) rows                              */
+    KEMR_EPI_BIAS_GELU_BF16 = 5    /* C_bf16 = gelu(A.W^T + bias), exact GELU 0.5 x erfc(-x / sqrt 2) in fp32 (3 is internal) */
 } kemr_epilogue;
 /* A bf16 [m_alloc, k] and C [m_alloc, n] with m_alloc = m rounded up to 256 rows (pad rows of A are read; pad rows of C
  * may be written by the bf16 epilogues), W bf16 [n, k], bias fp32 [n] */
@@ -377,7 +385,7 @@ int kemr_op_gemm(const void* a_dev, const void* w_dev, const float* bias_dev, vo
 int kemr_op_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev, void* y_dev,
                       int rows, int width, int out_dtype /*KEMR_BF16|KEMR_F32*/, void* stream);
 /* fp8 operands: a e4m3 [ceil256(m), k] and w e4m3 [n, k] (bytes), wscale fp32 [n] multiplies the accumulators per output
- * channel before the bias; c bf16 [ceil256(m), n]; n % 256 == 0, k % 128 == 0, k >= 256; epilogue BIAS_BF16 | BIAS_QGELU_BF16 */
+ * channel before the bias; c bf16 [ceil256(m), n]; n % 256 == 0, k % 128 == 0, k >= 256; epilogue BIAS_BF16 | BIAS_QGELU_BF16 | BIAS_GELU_BF16 */
 int kemr_op_gemm_fp8(const void* a_dev, const void* w_dev, const float* wscale_dev, const float* bias_dev, void* c_dev,
                      int m, int n, int k, int epilogue, void* stream);
 /* the host-side fp32 -> e4m3 conversion used when weights are packed (round to nearest even, saturating at +-448); no GPU */

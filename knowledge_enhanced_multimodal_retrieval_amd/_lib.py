@@ -37,6 +37,9 @@ TOWER_VISION, TOWER_TEXT = 0, 1
 SIDE_QUERY, SIDE_GALLERY = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RESID_F32 = 0, 1, 2
 EPI_BIAS_RESADD_BF16 = 4
+EPI_BIAS_GELU_BF16 = 5      # exact (erf) GELU; 3 is internal to the library
+# model option "activation" (include/kemr.h): the MLP's activation, by the name Hugging Face configs give it (`hidden_act`)
+ACTIVATIONS = {"quick_gelu": 0, "gelu": 1}
 MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused / kemr_cross_attention_rerank
 
 
@@ -141,6 +144,12 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"libkemr.so ABI version {handle.kemr_abi_version()} != {ABI_VERSION}; rebuild the library")
         _lib = handle
         return _lib
+
+
+def check_activation(activation: str) -> str:
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be one of 'quick_gelu' (OpenAI CLIP) or 'gelu' (OpenCLIP / LAION, exact erf GELU), got {activation!r}")
+    return activation
 
 
 def check(status: int, what: str = "") -> None:

@@ -10,9 +10,16 @@ Weights: upstream ``clip.load(name)`` downloads a checkpoint, which is impossibl
   matched first, so ``"ViT-L/14@336px"`` is that model and ``"ViT-L/14@336px@/path/file"`` its checkpoint;
 * or a known model name: ``$KEMR_CLIP_WEIGHTS/<name with / and @ -> ->.pt|.safetensors`` is used when present (upstream's
   file names: ``ViT-L-14.pt``, ``ViT-L-14-336px.pt``);
+* or a Hugging Face ``save_pretrained`` DIRECTORY on the local disk (``config.json`` + ``model.safetensors`` |
+  ``pytorch_model.bin``): architecture and activation come from its config, the weights through ``hf_checkpoint``;
 * otherwise ``load`` raises: a run on random weights looks like any other run in its metrics file.  Synthetic-data runs
   opt in explicitly with ``allow_random_weights()`` (what ``--synthetic`` does) or ``KEMR_ALLOW_RANDOM_WEIGHTS=1``; the
   model then records ``weights_source = "random(seed 0)"``, which the evaluators write into their results JSON.
+
+Activation: the OpenAI checkpoints use QuickGELU, the OpenCLIP / LAION ViT-B/32, B/16 and L/14 ones (same architecture, same key
+names) exact GELU -- a file does not say which, and the wrong one gives embeddings that are silently off.  ``load(...,
+activation="gelu")`` or ``KEMR_CLIP_ACTIVATION=gelu`` in the environment (so that the reference's scripts stay unchanged; the
+keyword wins) selects it; the default is ``quick_gelu``.  A Hugging Face directory states its own (``hidden_act``).
 """
 from __future__ import annotations
 
@@ -22,6 +29,8 @@ from typing import List, Tuple, Union
 
 import torch
 
+from . import hf_checkpoint
+from ._lib import check_activation
 from .clip_module import CLIP, build_model
 from .config import ARCHS, get_arch
 from .preprocess import ClipPreprocess, gpu_preprocessing_enabled
@@ -72,8 +81,20 @@ def _weights_for(name: str):
     return None
 
 
+def _load_hf_directory(directory: str, device, activation) -> Tuple[CLIP, ClipPreprocess]:
+    arch, act, sd = hf_checkpoint.read_hf_directory(directory)
+    if activation is not None and check_activation(activation) != act:
+        raise ValueError(f"clip.load({directory!r}, activation={activation!r}): its config.json says hidden_act = {act!r}")
+    model = CLIP(arch, hf_checkpoint.registered_name(arch), act)
+    model.load_state_dict(sd, strict=True)
+    model.weights_source = os.path.abspath(directory)
+    model = model.to(device).eval()
+    on_gpu = torch.device(device).type == "cuda"
+    return model, ClipPreprocess(arch.image_size, defer_to_gpu=on_gpu and gpu_preprocessing_enabled())
+
+
 def load(name: str, device: Union[str, torch.device, None] = None,
-         jit: bool = False, download_root: str = None) -> Tuple[CLIP, ClipPreprocess]:
+         jit: bool = False, download_root: str = None, activation: str = None) -> Tuple[CLIP, ClipPreprocess]:
     """device None = "cuda" when a GPU is visible, else "cpu" (upstream's default), decided at CALL time: evaluating
     torch.cuda.is_available() in the signature initialised the HIP runtime in every process that merely imported this module --
     the loader processes included (round 3: 13 processes with the GPU open)."""
@@ -81,6 +102,11 @@ def load(name: str, device: Union[str, torch.device, None] = None,
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if jit:
         raise RuntimeError("clip.load(jit=True) is not supported by the HIP engine")
+    if name not in ARCHS and hf_checkpoint.is_hf_directory(name):
+        return _load_hf_directory(name, device, activation)
+    if activation is None:
+        activation = os.environ.get("KEMR_CLIP_ACTIVATION") or "quick_gelu"
+    check_activation(activation)
     path = None
     if name not in ARCHS:
         # "<registered name>@<path>" -- the longest registered name first: "ViT-L/14@336px@/x.pt" is not "ViT-L/14" + "336px@/x.pt"
@@ -104,7 +130,7 @@ def load(name: str, device: Union[str, torch.device, None] = None,
     seed_state = torch.random.get_rng_state()
     torch.manual_seed(0)                     # reproducible random init when no weights are available
     try:
-        model = build_model(name, device="cpu")
+        model = build_model(name, device="cpu", activation=activation)
     finally:
         torch.random.set_rng_state(seed_state)
     if path:

@@ -33,24 +33,25 @@ class QuickGELU(nn.Module):
 class ResidualAttentionBlock(nn.Module):
     """Parameter container with OpenAI-CLIP names (ln_1, attn.in_proj_*, attn.out_proj.*, ln_2, mlp.c_fc, mlp.c_proj)."""
 
-    def __init__(self, d_model: int, n_head: int):
+    def __init__(self, d_model: int, n_head: int, activation: str = "quick_gelu"):
         super().__init__()
         self.attn = nn.MultiheadAttention(d_model, n_head)
         self.ln_1 = nn.LayerNorm(d_model)
-        self.mlp = nn.Sequential(OrderedDict([("c_fc", nn.Linear(d_model, d_model * 4)), ("gelu", QuickGELU()),
+        self.mlp = nn.Sequential(OrderedDict([("c_fc", nn.Linear(d_model, d_model * 4)), ("gelu", nn.GELU() if activation == "gelu" else QuickGELU()),
                                               ("c_proj", nn.Linear(d_model * 4, d_model))]))
         self.ln_2 = nn.LayerNorm(d_model)
 
 
 class Transformer(nn.Module):
-    def __init__(self, width: int, layers: int, heads: int):
+    def __init__(self, width: int, layers: int, heads: int, activation: str = "quick_gelu"):
         super().__init__()
         self.width, self.layers = width, layers
-        self.resblocks = nn.Sequential(*[ResidualAttentionBlock(width, heads) for _ in range(layers)])
+        self.resblocks = nn.Sequential(*[ResidualAttentionBlock(width, heads, activation) for _ in range(layers)])
 
 
 class VisionTransformer(nn.Module):
-    def __init__(self, input_resolution: int, patch_size: int, width: int, layers: int, heads: int, output_dim: int):
+    def __init__(self, input_resolution: int, patch_size: int, width: int, layers: int, heads: int, output_dim: int,
+                 activation: str = "quick_gelu"):
         super().__init__()
         self.input_resolution, self.output_dim = input_resolution, output_dim
         self.conv1 = nn.Conv2d(3, width, kernel_size=patch_size, stride=patch_size, bias=False)
@@ -58,7 +59,7 @@ class VisionTransformer(nn.Module):
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
         self.positional_embedding = nn.Parameter(scale * torch.randn((input_resolution // patch_size) ** 2 + 1, width))
         self.ln_pre = nn.LayerNorm(width)
-        self.transformer = Transformer(width, layers, heads)
+        self.transformer = Transformer(width, layers, heads, activation)
         self.ln_post = nn.LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
 
@@ -69,13 +70,17 @@ def _lib_default_precision() -> str:
 
 
 class CLIP(nn.Module):
-    def __init__(self, arch: ClipArch, name: str = ""):
+    def __init__(self, arch: ClipArch, name: str = "", activation: str = "quick_gelu"):
+        """activation: the MLP's activation, a property of the CHECKPOINT, not of the architecture: "quick_gelu" (OpenAI) or "gelu"
+        (exact GELU: OpenCLIP / LAION, Hugging Face `hidden_act: gelu`).  It has no parameters: state dicts are the same."""
         super().__init__()
+        from ._lib import check_activation
+        self.activation = check_activation(activation)
         self.arch, self.model_name = arch, name
         self.context_length, self.vocab_size = arch.ctx, arch.vocab
         self.visual = VisionTransformer(arch.image_size, arch.patch, arch.v_width, arch.v_layers, arch.v_width // 64,
-                                        arch.embed_dim)
-        self.transformer = Transformer(arch.t_width, arch.t_layers, arch.t_width // 64)
+                                        arch.embed_dim, activation)
+        self.transformer = Transformer(arch.t_width, arch.t_layers, arch.t_width // 64, activation)
         self.token_embedding = nn.Embedding(arch.vocab, arch.t_width)
         self.positional_embedding = nn.Parameter(torch.empty(arch.ctx, arch.t_width))
         self.ln_final = nn.LayerNorm(arch.t_width)
@@ -108,7 +113,8 @@ class CLIP(nn.Module):
 
     # ------------------------------------------------------------------ engine plumbing
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        sd = {k: v for k, v in state_dict.items() if k not in ("input_resolution", "context_length", "vocab_size")}
+        # the scalars OpenAI's files carry, and the causal-mask buffer of OpenCLIP files (not persistent in newer releases)
+        sd = {k: v for k, v in state_dict.items() if k not in ("input_resolution", "context_length", "vocab_size", "attn_mask")}
         res = super().load_state_dict(sd, strict=strict, assign=assign)
         self._dirty = True
         return res
@@ -164,7 +170,10 @@ class CLIP(nn.Module):
         if self._engine is None or self._engine.device != dev:
             # encoder precision of the packed copy: "bf16" (fp32 residual stream) unless KEMR_PRECISION says otherwise (bf16-res16 | fp8 | fp8-res16 | fp8-mlp,
             # kemr_precision in include/kemr.h) -- an environment switch so that the reference's scripts stay unchanged
-            self._engine, self._dirty = ClipEngine(self.arch, dev, precision=os.environ.get("KEMR_PRECISION", _lib_default_precision())), True
+            self._engine, self._dirty = ClipEngine(self.arch, dev, precision=os.environ.get("KEMR_PRECISION", _lib_default_precision()),
+                                                    activation=self.activation), True
+        if self._engine.activation != self.activation:
+            self._engine.set_activation(self.activation)
         fp = self._fingerprint()
         if self._dirty or fp != getattr(self, "_packed_fp", None):
             self._engine.load_state_dict({k: v for k, v in self.state_dict().items() if k != "logit_scale"})
@@ -194,6 +203,31 @@ class CLIP(nn.Module):
         caller passes ``lens`` (``engine.text_lengths(host_tokens)``)."""
         return self.engine().encode_text(text, normalize=normalize, lens=lens)
 
+    # ------------------------------------------------------------------ the calls made on a transformers.CLIPModel
+    @classmethod
+    def from_pretrained(cls, directory: str, device=None) -> "CLIP":
+        """A ``save_pretrained`` directory on the LOCAL disk (``config.json`` + ``model.safetensors`` | ``pytorch_model.bin``);
+        nothing is ever fetched."""
+        from .clip_api import load
+        return load(directory, device=device)[0]
+
+    @torch.no_grad()
+    def get_image_features(self, pixel_values: torch.Tensor = None, **_) -> torch.Tensor:
+        """``CLIPModel.get_image_features(pixel_values=...)``: the projected embeddings, not normalised."""
+        return self.encode_image(pixel_values)
+
+    @torch.no_grad()
+    def get_text_features(self, input_ids: torch.Tensor = None, attention_mask=None, **_) -> torch.Tensor:
+        """``CLIPModel.get_text_features(**processor(text=...))``: the projected embeddings, not normalised.  A processor pads to the
+        batch's longest text: shorter rows are zero-padded to the context length here (the mask is causal and the pooled row is
+        the first end-of-text token's, so neither the padding nor ``attention_mask`` can reach the result)."""
+        ctx = self.context_length
+        if input_ids.dim() != 2 or input_ids.shape[1] > ctx:
+            raise ValueError(f"get_text_features: input_ids must be [B, <= {ctx}], got {tuple(input_ids.shape)}")
+        if input_ids.shape[1] < ctx:
+            input_ids = torch.nn.functional.pad(input_ids, (0, ctx - input_ids.shape[1]), value=0)
+        return self.encode_text(input_ids)
+
     @torch.no_grad()
     def forward(self, image: torch.Tensor, text: torch.Tensor):
         """logits_per_image, logits_per_text (cosine similarities times exp(logit_scale)), as upstream CLIP.forward."""
@@ -207,7 +241,7 @@ class CLIP(nn.Module):
         return logits, logits.t()
 
 
-def build_model(name_or_arch, device="cuda") -> CLIP:
+def build_model(name_or_arch, device="cuda", activation: str = "quick_gelu") -> CLIP:
     arch = name_or_arch if isinstance(name_or_arch, ClipArch) else get_arch(name_or_arch)
     name = name_or_arch if isinstance(name_or_arch, str) else ""
-    return CLIP(arch, name).to(device).eval()
+    return CLIP(arch, name, activation).to(device).eval()

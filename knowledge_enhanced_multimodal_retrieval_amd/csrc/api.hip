@@ -75,6 +75,7 @@ struct kemr_model {
     int fp8 = 0;                                    // bit 0: QKV on fp8 operands (KEMR_PREC_FP8), bit 1: fc1 too (KEMR_PREC_FP8_MLP)
     int resadd = 1;                                 // option "residual_fusion": residual add inside the out-proj / fc2 epilogues
     int last_pooled = 1;                            // option "last_block_pooled_row": the last block's query path on the pooled row only
+    int activation = 0;                             // option "activation": 0 = QuickGELU, 1 = exact GELU (the fc1 epilogue of run_blocks)
     int stream24 = 1;                               // option "residual_stream_24bit" (before finalize; default on since round 4): the fp32-class stream stored in 3 bytes
     // vision
     TowerW vis;
@@ -438,7 +439,8 @@ int carve(Workspace& w, void* base, size_t bytes, int width, int64_t rows, int i
 // row's attention) but the query, the attention output, out-proj, ln_2 and the MLP for the pooled rows alone: compact [items, W]
 // buffers, 2 of the block's 12 W^2 of GEMM work per token row instead of 12.  The pooled rows see the same arithmetic (their GEMMs
 // are smaller launches, routed to the skinny / 128-row kernels, with their summation order).  *compact = the tail reads xc / d1c / d2c.
-int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int fp8, int want_resadd, hipStream_t s, bool* pending,
+// epi_act: the fc1 epilogue (option "activation"), EPI_BIAS_QGELU_BF16 or EPI_BIAS_GELU_BF16; nothing else depends on the activation.
+int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int fp8, int want_resadd, int epi_act, hipStream_t s, bool* pending,
                const int* row_start = nullptr, int rows = 0, int last_pooled = 0, const int32_t* ids = nullptr, bool* compact = nullptr) {
     const int W = t.width, M = row_start ? rows : batch * t.tokens;
     const bool fq = fp8 & 1, f1 = fp8 & 2;          // LayerNorm output = A operand of QKV / fc1: e4m3 where that GEMM runs in fp8
@@ -475,7 +477,7 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int f
             KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
             KEMR_TRY(launch_layernorm(w.xc, w.x_dtype, w.d1c, nullptr, 0, L.ln2_g, L.ln2_b, w.hc, batch, W, KEMR_BF16, s));
             g.A = w.hc; g.W = L.w1; g.bias = L.b1; g.C = w.gc; g.ldc = 4 * W; g.N = 4 * W;
-            KEMR_TRY(launch_gemm(g, EPI_BIAS_QGELU_BF16, s));
+            KEMR_TRY(launch_gemm(g, epi_act, s));
             g.A = w.gc; g.lda = 4 * W; g.W = L.w2; g.ldw = 4 * W; g.bias = L.b2; g.C = w.d2c; g.ldc = W; g.N = W; g.K = 4 * W;
             KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
             break;
@@ -501,10 +503,10 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int f
         g.A = w.h; g.lda = W; g.W = L.w1; g.ldw = W; g.bias = L.b1; g.C = w.big; g.ldc = 4 * W; g.N = 4 * W; g.K = W;
         if (f1) {
             g.W = (const bf16_t*)L.w18; g.wscale = L.s1;
-            KEMR_TRY(launch_gemm256u_fp8(g, EPI_BIAS_QGELU_BF16, s));
+            KEMR_TRY(launch_gemm256u_fp8(g, epi_act, s));
             g.wscale = nullptr;
         } else {
-            KEMR_TRY(launch_gemm(g, EPI_BIAS_QGELU_BF16, s));
+            KEMR_TRY(launch_gemm(g, epi_act, s));
         }
         g.A = w.big; g.lda = 4 * W; g.W = L.w2; g.ldw = 4 * W; g.bias = L.b2; g.C = resadd ? w.x : (void*)w.delta2; g.ldc = W; g.N = W; g.K = 4 * W;
         KEMR_TRY(launch_gemm(g, resadd ? epi_res : EPI_BIAS_BF16, s));
@@ -558,6 +560,8 @@ int text_front(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, i
     return launch_text_embed(ids_dev, m->tok, m->tpos, w.x, w.x_dtype, batch, T, W, m->cfg.vocab, s, *row_start, rows);
 }
 
+int fc1_epilogue(const kemr_model* m) { return m->activation == 1 ? EPI_BIAS_GELU_BF16 : EPI_BIAS_QGELU_BF16; }
+
 }  // namespace
 
 extern "C" size_t kemr_workspace_bytes(const kemr_model* m, int tower, int batch) {
@@ -582,7 +586,7 @@ extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int bat
     const int W = m->cfg.v_width, T = m->patches + 1;
     KEMR_TRY(launch_layernorm(w.x32, KEMR_F32, nullptr, nullptr, 0, m->lnpre_g, m->lnpre_b, w.x, batch * T, W, w.x_dtype, s));
     bool vb = false, vc = false;
-    KEMR_TRY(run_blocks(m->vis, w, batch, 0, m->fp8, m->resadd, s, &vb, nullptr, 0, m->last_pooled, nullptr, &vc));
+    KEMR_TRY(run_blocks(m->vis, w, batch, 0, m->fp8, m->resadd, fc1_epilogue(m), s, &vb, nullptr, 0, m->last_pooled, nullptr, &vc));
     if (vc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnpost_g, m->lnpost_b, m->vproj, m->cfg.embed_dim, normalize, out_dev, s));
     else KEMR_TRY(launch_tail(w.x, w.x_dtype, vb ? w.delta : nullptr, vb ? w.delta2 : nullptr, nullptr, batch, T, W, m->lnpost_g, m->lnpost_b, m->vproj, m->cfg.embed_dim, normalize, out_dev, s));
     return KEMR_OK;
@@ -597,7 +601,7 @@ extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch
     if (batch == 0) return KEMR_OK;
     const int W = m->cfg.t_width, T = m->cfg.ctx;
     bool tb = false, tc = false;
-    KEMR_TRY(run_blocks(m->txt, w, batch, 1, 0, m->resadd, s, &tb, nullptr, 0, m->last_pooled, ids_dev, &tc));
+    KEMR_TRY(run_blocks(m->txt, w, batch, 1, 0, m->resadd, fc1_epilogue(m), s, &tb, nullptr, 0, m->last_pooled, ids_dev, &tc));
     if (tc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
     else KEMR_TRY(launch_tail(w.x, w.x_dtype, tb ? w.delta : nullptr, tb ? w.delta2 : nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
     return KEMR_OK;
@@ -621,7 +625,7 @@ extern "C" int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, co
     if (batch == 0) return KEMR_OK;
     const int W = m->cfg.t_width, T = m->cfg.ctx;
     bool tb = false, tc = false;
-    KEMR_TRY(run_blocks(m->txt, w, batch, 1, 0, m->resadd, s, &tb, row_start, rows, m->last_pooled, ids_dev, &tc));
+    KEMR_TRY(run_blocks(m->txt, w, batch, 1, 0, m->resadd, fc1_epilogue(m), s, &tb, row_start, rows, m->last_pooled, ids_dev, &tc));
     if (tc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
     else KEMR_TRY(launch_tail(w.x, w.x_dtype, tb ? w.delta : nullptr, tb ? w.delta2 : nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s, row_start));
     return KEMR_OK;
@@ -646,6 +650,11 @@ extern "C" int kemr_model_set_option(kemr_model* m, const char* key, int value) 
         m->last_pooled = value;
         return KEMR_OK;
     }
+    if (!strcmp(key, "activation")) {
+        if (value < 0 || value > 1) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(activation): 0 (QuickGELU) or 1 (GELU), got %d", value);
+        m->activation = value;
+        return KEMR_OK;
+    }
     KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option: unknown key '%s'", key);
 }
 
@@ -654,6 +663,7 @@ extern "C" int kemr_model_get_option(const kemr_model* m, const char* key, int* 
     if (!strcmp(key, "residual_fusion")) { *value = m->resadd; return KEMR_OK; }
     if (!strcmp(key, "last_block_pooled_row")) { *value = m->last_pooled; return KEMR_OK; }
     if (!strcmp(key, "residual_stream_24bit")) { *value = m->finalized ? (m->res_dtype == KEMR_F24) : m->stream24; return KEMR_OK; }
+    if (!strcmp(key, "activation")) { *value = m->activation; return KEMR_OK; }
     if (!strcmp(key, "precision_residual_bf16")) { *value = m->res_dtype == KEMR_BF16; return KEMR_OK; }
     KEMR_FAIL(KEMR_ERR_INVALID, "model_get_option: unknown key '%s'", key);
 }
@@ -676,7 +686,7 @@ const DebugKnob* debug_knobs(int* n) {
         {"gemm_flags", &g_gemm_dbg, 0, 255, 1u << 0},  // timing-experiment flags of the DBG instantiation (1 drop stores, 4 plain stores, 32 / 64 / 128 stamps): A/B builds
         {"gemm_order", &g_gemm_order, 0, 8, ~0u},     // gemm256u tile order (0 = N fastest, else log2(column-group width) + 1)
         {"gemm_grid", &g_gemm_grid, 0, 1024, ~0u},    // tools: cap on the persistent GEMM's grid (0 = one workgroup per CU); results do not depend on it
-        {"gemm_conc", &g_gemm_conc, 0, 2, ~0u},       // both wave halves' epilogues in one barrier interval: 0 never, 1 always, 2 = QuickGELU only
+        {"gemm_conc", &g_gemm_conc, 0, 2, ~0u},       // both wave halves' epilogues in one barrier interval: 0 never, 1 always, 2 = QuickGELU / GELU only
         {"gemm_kl", &g_gemm_kl, 0, 1, 1u << 0},       // 0 = eight 256-cycle barrier intervals per K-tile (the product loop), 1 = four of 512 (round-3 experiment): A/B builds
         {"attn_v", &g_attn_v, 0, 5, 1u << 0},         // 0 = the product kernel, 1..4 = attention_ab.hip: A/B builds
         {"attn_xcd", &g_attn_xcd, 0, 1, ~0u},         // attention: images dealt to the XCDs
@@ -807,7 +817,7 @@ extern "C" int kemr_profile_end(double* ms_per_class, int64_t* launches_per_clas
 extern "C" int kemr_op_gemm(const void* a_dev, const void* w_dev, const float* bias_dev, void* c_dev, int m, int n, int k,
                             int epilogue, void* stream) {
     if (!a_dev || !w_dev || !c_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_gemm: null argument");
-    if (epilogue < 0 || (epilogue > KEMR_EPI_BIAS_RESID_F32 && epilogue != KEMR_EPI_BIAS_RESADD_BF16)) KEMR_FAIL(KEMR_ERR_INVALID, "op_gemm: bad epilogue %d", epilogue);
+    if (epilogue < 0 || (epilogue > KEMR_EPI_BIAS_RESID_F32 && epilogue != KEMR_EPI_BIAS_RESADD_BF16 && epilogue != KEMR_EPI_BIAS_GELU_BF16)) KEMR_FAIL(KEMR_ERR_INVALID, "op_gemm: bad epilogue %d", epilogue);
     GemmParams g{};
     g.A = (const bf16_t*)a_dev; g.lda = k; g.W = (const bf16_t*)w_dev; g.ldw = k; g.bias = bias_dev; g.C = c_dev; g.ldc = n;
     g.M = m; g.N = n; g.K = k;

@@ -92,6 +92,32 @@ __device__ __forceinline__ f32x2_t quick_gelu2(f32x2_t v) {
     r.y = __builtin_amdgcn_rcpf(d.y);
     return v * r;
 }
+// Exact GELU 0.5 x (1 + erf(x / sqrt 2)) in its erfc form 0.5 x erfc(-x / sqrt 2): erfc keeps RELATIVE accuracy where 1 + erf cancels
+// (x < -3: the erf form is off by up to 1.4 |x| 2^-24 absolute, hundreds of bf16 ulps of the result).  erfcf is the device library's
+// (branches over literal-coefficient polynomials, no table: nothing enters the vector-memory counter).  The tail of erfc amplifies an
+// error of its argument z by erfc'/erfc ~ 2 z, so the argument is carried as z + e: z = fl(x c_hi), e = the product's exact
+// remainder + x c_lo (c_hi + c_lo = -1 / sqrt 2 to 2^-49), and erfc(z + e) = erfc(z) (1 - r(z) e) with r = 2 z for z > 0 (true r in
+// [2 z, 2 z + 1.13]: what is left of the argument's rounding is <= 1.5 x 2^-24 relative) and r = 0 for z <= 0 (erfc in [1, 2]: <=
+// 0.7 x 2^-24).  Relative error of the result in units of 2^-24: 2 per ulp of erfcf + 1.5 (argument) + 3 (the correction's fma and
+// the two products; 0.5 x is exact).  x >= 5.9: erfcf = 2 and the result is x itself, bit for bit; the result keeps the sign of x.
+__device__ __forceinline__ float gelu_erf(float v) {
+    const float z = v * -0.70710677f;
+    const float e = fmaf(v, -1.2101617e-8f, fmaf(v, -0.70710677f, -z));
+    const float c = fmaf(-2.0f * fmaxf(z, 0.0f), e, 1.0f);
+    return (0.5f * v) * (erfcf(z) * c);
+}
+// two at a time: the scalings and products as packed fp32 instructions (same IEEE results), erfcf per element
+__device__ __forceinline__ f32x2_t gelu_erf2(f32x2_t v) {
+    const f32x2_t z = v * -0.70710677f;
+    f32x2_t e, c, t;
+    e.x = fmaf(v.x, -1.2101617e-8f, fmaf(v.x, -0.70710677f, -z.x));
+    e.y = fmaf(v.y, -1.2101617e-8f, fmaf(v.y, -0.70710677f, -z.y));
+    c.x = fmaf(-2.0f * fmaxf(z.x, 0.0f), e.x, 1.0f);
+    c.y = fmaf(-2.0f * fmaxf(z.y, 0.0f), e.y, 1.0f);
+    t.x = erfcf(z.x);
+    t.y = erfcf(z.y);
+    return (v * 0.5f) * (t * c);
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -117,6 +143,7 @@ enum GemmEpi : int {
     EPI_BIAS_QGELU_BF16 = KEMR_EPI_BIAS_QGELU_BF16,
     EPI_BIAS_RESID_F32 = KEMR_EPI_BIAS_RESID_F32,
     EPI_PATCH_F32 = 3,
+    EPI_BIAS_GELU_BF16 = KEMR_EPI_BIAS_GELU_BF16,       // C_bf16 = gelu(A.W^T + bias), exact (erf) GELU: the same class as EPI_BIAS_QGELU_BF16 everywhere
     EPI_BIAS_RESADD_BF16 = KEMR_EPI_BIAS_RESADD_BF16,   // X_bf16 = bf16(bf16(A.W^T + bias) + X_bf16), in place (gemm256u only)     // X_f32[remap(m)] = acc + pos[1 + m % tokens_per_img]   (patch embedding)
 };
 struct GemmParams {
@@ -158,7 +185,7 @@ extern int g_attn_v;        // attention.hip: 0 = the product kernel; 1..4 = att
 extern int g_gemm_kl;       // gemm256u: 0 = eight barrier intervals per K-tile (the product loop), 1 = the long-interval K loop (A/B builds only)
 extern int g_ln_nt;         // layernorm.hip: cache-hint level of the residual forms, 3 = the product kernel; 0 / 1 / 2 in A/B builds only
 extern int g_gemm_grid;     // tools: cap on the persistent GEMM's grid (0 = one workgroup per CU)
-extern int g_gemm_conc;     // gemm256u: both wave halves run their epilogues in the same barrier interval (0 never, 1 always, 2 = QuickGELU epilogue only)
+extern int g_gemm_conc;     // gemm256u: both wave halves run their epilogues in the same barrier interval (0 never, 1 always, 2 = QuickGELU / GELU epilogues only)
 int gemm_read_stamps(unsigned* host_out, int n_words);
 int launch_gemm256u_simgmax(const bf16_t* q_panel, int nq, const bf16_t* g_panel, int ng, int kdim, int stride, float* out,
                             hipStream_t stream, bool* used);

@@ -130,7 +130,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_kernel(const GemmPa
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = quick_gelu(v[r]);
             }
-            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16) {
+            if constexpr (EPI == EPI_BIAS_GELU_BF16) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+            }
+            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16) {
                 uint2 o;
                 o.x = pack_bf16x2(v[0], v[1]);
                 o.y = pack_bf16x2(v[2], v[3]);
@@ -187,7 +191,7 @@ int launch_gemm(const GemmParams& p, int epi, hipStream_t stream) {
     // 256x256 tiles (one workgroup per CU, deep LDS-DMA pipeline) once there is at least ~half a wave of them
     const bool can256 = p.N % 256 == 0 && p.K >= 128;
     const long tiles256 = (long)((p.M + 255) / 256) * (p.N / 256);
-    const bool bf16_epi = epi == EPI_BIAS_BF16 || epi == EPI_BIAS_QGELU_BF16;
+    const bool bf16_epi = epi == EPI_BIAS_BF16 || epi == EPI_BIAS_QGELU_BF16 || epi == EPI_BIAS_GELU_BF16;
     if (epi == EPI_BIAS_RESADD_BF16) {        // read-modify-write of the bf16 residual stream: only the persistent kernel has it
         if (!(can256 && p.c_rows_padded && p.M > 512 && gemm256u_fits(p, 2)))
             KEMR_FAIL(KEMR_ERR_INVALID, "gemm: the residual-add epilogue needs N %% 256 == 0, more than 512 rows and a row-padded C (M=%d N=%d K=%d)", p.M, p.N, p.K);
@@ -237,6 +241,7 @@ int launch_gemm(const GemmParams& p, int epi, hipStream_t stream) {
     switch (epi) {
         case EPI_BIAS_BF16:       return launch_cfg<128, 128, 2, 2, EPI_BIAS_BF16>(p, stream);
         case EPI_BIAS_QGELU_BF16: return launch_cfg<128, 128, 2, 2, EPI_BIAS_QGELU_BF16>(p, stream);
+        case EPI_BIAS_GELU_BF16:  return launch_cfg<128, 128, 2, 2, EPI_BIAS_GELU_BF16>(p, stream);
         case EPI_BIAS_RESID_F32:  return launch_cfg<128, 128, 2, 2, EPI_BIAS_RESID_F32>(p, stream);
         case EPI_PATCH_F32:       return launch_cfg<128, 128, 2, 2, EPI_PATCH_F32>(p, stream);
     }

@@ -189,7 +189,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_bf16_nt_kernel(const GemmParam
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = quick_gelu(v[r]);
             }
-            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16) {
+            if constexpr (EPI == EPI_BIAS_GELU_BF16) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+            }
+            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16) {
                 uint2 o;
                 o.x = pack_bf16x2(v[0], v[1]);
                 o.y = pack_bf16x2(v[2], v[3]);
@@ -359,7 +363,11 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_nt_kernel(const GemmPara
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = quick_gelu(v[r]);
             }
-            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16) {
+            if constexpr (EPI == EPI_BIAS_GELU_BF16) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+            }
+            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16) {
                 uint2 o;
                 o.x = pack_bf16x2(v[0], v[1]);
                 o.y = pack_bf16x2(v[2], v[3]);
@@ -410,6 +418,7 @@ int launch_gemm256(const GemmParams& p, int epi, hipStream_t stream) {
     switch (epi) {
         case EPI_BIAS_BF16:       return launch256<EPI_BIAS_BF16>(p, stream);
         case EPI_BIAS_QGELU_BF16: return launch256<EPI_BIAS_QGELU_BF16>(p, stream);
+        case EPI_BIAS_GELU_BF16:  return launch256<EPI_BIAS_GELU_BF16>(p, stream);
         case EPI_BIAS_RESID_F32:  return launch256<EPI_BIAS_RESID_F32>(p, stream);
         case EPI_PATCH_F32:       return launch256<EPI_PATCH_F32>(p, stream);
     }

@@ -69,11 +69,15 @@ def _require_cuda(t: torch.Tensor, what: str) -> None:
 class ClipEngine:
     """One packed CLIP model (both towers) in HBM."""
 
-    def __init__(self, arch: ClipArch, device: torch.device | str = "cuda:0", precision: str = _lib.DEFAULT_PRECISION):
+    def __init__(self, arch: ClipArch, device: torch.device | str = "cuda:0", precision: str = _lib.DEFAULT_PRECISION,
+                 activation: str = "quick_gelu"):
         """precision: "bf16-x24" (default: bf16 operands, fp32 accumulation, the fp32 residual stream stored as 24-bit floats -- model
         option residual_stream_24bit), "bf16" (the stream as 4-byte fp32), "bf16-res16" (bf16 residual stream, opt-in), "fp8" / "fp8-x24"
         (the vision tower's QKV GEMMs on fp8 operands, BASELINE config 5), "fp8-res16" or "fp8-mlp" (fc1 too).  See kemr_precision in
-        include/kemr.h and _lib.DEFAULT_PRECISION."""
+        include/kemr.h and _lib.DEFAULT_PRECISION.
+        activation: "quick_gelu" (the OpenAI checkpoints) or "gelu" (exact GELU: OpenCLIP / LAION and Hugging Face `hidden_act: gelu`
+        checkpoints) -- model option "activation"."""
+        _lib.check_activation(activation)
         if precision not in _lib.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {precision!r}")
         self.precision = precision
@@ -87,6 +91,9 @@ class ClipEngine:
         h = C.c_void_p()
         _lib.check(self._L.kemr_model_create(C.byref(cfg), C.byref(h)), "model_create")
         self._h = h
+        self.activation = "quick_gelu"                   # the library's default; the option is only touched when something else is asked for
+        if activation != self.activation:
+            self.set_activation(activation)
         self._ws: Dict[object, torch.Tensor] = {}
         self.ready = False
         self.pack_text = os.environ.get("KEMR_TEXT_PACKED", "1") != "0"     # encode_text: only the positions up to the end-of-text token
@@ -98,6 +105,13 @@ class ClipEngine:
                 self._L.kemr_model_destroy(h)
             except Exception:
                 pass
+
+    def set_activation(self, activation: str) -> None:
+        """Option "activation" of THIS model: "quick_gelu" or "gelu", the epilogue of the fc1 GEMMs from the next encode call on (the
+        packed weights do not depend on it)."""
+        code = _lib.ACTIVATIONS[_lib.check_activation(activation)]
+        _lib.check(self._L.kemr_model_set_option(self._h, b"activation", code), "model_set_option")
+        self.activation = activation
 
     def set_residual_fusion(self, level) -> None:
         """Option "residual_fusion" of THIS model (include/kemr.h kemr_model_set_option): 0 / False = the out-proj / fc2 GEMMs store
