@@ -75,8 +75,28 @@ typedef enum kemr_dtype { KEMR_F32 = 0, KEMR_BF16 = 1, KEMR_I32 = 2, KEMR_FP8 = 
  *                       near-duplicate retrieval test this costs about one point of Recall@10 where bf16 is below 90 %
  *                       (the MLP update goes straight into the residual stream, the QKV error is averaged by the softmax),
  *                       so it is outside config 5's bar and opt-in.
- * KEMR_PREC_FP8_RES16:  KEMR_PREC_FP8 with the bf16 residual stream of KEMR_PREC_BF16_RES16 (the two savings add). */
-typedef enum kemr_precision { KEMR_PREC_BF16 = 1, KEMR_PREC_BF16_RES16 = 2, KEMR_PREC_FP8 = 3, KEMR_PREC_FP8_MLP = 4, KEMR_PREC_FP8_RES16 = 5 } kemr_precision;
+ * KEMR_PREC_FP8_RES16:  KEMR_PREC_FP8 with the bf16 residual stream of KEMR_PREC_BF16_RES16 (the two savings add).
+ * KEMR_PREC_FP32X3:     the fp32-grade mode ("fp32x3"): what the reference's `.float()` model computes, for practical purposes, at a
+ *                       quarter to a third of the default's rate -- for evaluation runs, for validating a faster precision on one's
+ *                       own checkpoint (python: engine.precision_gap), and for towers the bf16 class cannot hold to the 1e-3 bar
+ *                       (uncompensated LayerNorm gains of 30-100).  Numerical contract:
+ *                       - every GEMM operand, activation and weight, enters v_mfma_f32_16x16x32_bf16 as the pair hi = rne_bf16(a),
+ *                         lo = rne_bf16(a - hi); every product is hi.hi + lo.hi + hi.lo with fp32 accumulation -- the convention
+ *                         of the terms == 3 similarity panels: the A side is [hi | lo | hi], the W side [hi | hi | lo], both
+ *                         concatenated along k, so K becomes 3K (finalize packs every matrix as [N, 3K], conv1 over 3 kpad);
+ *                       - nothing between kernels is stored below fp32 except as such a pair: the residual stream is plain 4-byte
+ *                         fp32 (option "residual_stream_24bit" has no effect; its stored value is still what get_option returns),
+ *                         q | k | v are fp32, the LayerNorm outputs, the attention output and the MLP hidden are A-side triples;
+ *                       - the out-proj and fc2 epilogues add acc + bias into the stream in fp32 (option "residual_fusion" has no
+ *                         meaning here); the attention scale 1/8 stays folded into W_q and b_q (exact);
+ *                       - attention splits Q, K, V and P into pairs and contracts with the same three products; LayerNorm
+ *                         statistics, softmax, QuickGELU and the erfc-form GELU are fp32 arithmetic as in every mode; option
+ *                         "activation" works as in every mode;
+ *                       - option "last_block_pooled_row" is ignored: every row runs through every block, as the reference does;
+ *                       - every GEMM runs on one kernel family (the 128 x 128 tile kernel), whatever the shape; fp8 is not involved.
+ *                       Workspace: 46 instead of 18 bytes per token row and width element (kemr_workspace_bytes knows). */
+typedef enum kemr_precision { KEMR_PREC_BF16 = 1, KEMR_PREC_BF16_RES16 = 2, KEMR_PREC_FP8 = 3, KEMR_PREC_FP8_MLP = 4, KEMR_PREC_FP8_RES16 = 5,
+                              KEMR_PREC_FP32X3 = 6 } kemr_precision;
 
 typedef enum kemr_tower { KEMR_TOWER_VISION = 0, KEMR_TOWER_TEXT = 1 } kemr_tower;
 
@@ -401,6 +421,23 @@ int kemr_op_layernorm_rows(void* x_dev, int x_dtype, const void* delta_dev, cons
 /* qkv bf16 [batch*t, 3*width] (q pre-scaled by 1/8) -> out bf16 [batch*t, width]; t <= 288, or non-causal
  * t <= KEMR_MAX_VISION_TOKENS (streaming kernel); longer causal sequences are KEMR_ERR_INVALID */
 int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, int t, int width, int causal, void* stream);
+/* The kernels of KEMR_PREC_FP32X3.  Panels are what kemr_panel_build(nparts = 1, terms = 3, side) builds: bf16 [ceil256(rows), 3 ceil64(d)],
+ * KEMR_SIDE_QUERY = the A side [hi | lo | hi], KEMR_SIDE_GALLERY = the W side [hi | hi | lo].
+ * layernorm_x3: x fp32 [rows, width] -> y_panel, the A-side triple of kemr_op_layernorm(..., KEMR_F32)'s output, bit for bit;
+ *   [ceil256(rows), 3 width], pad rows zero-filled. */
+int kemr_op_layernorm_x3(const float* x_dev, const float* gamma_dev, const float* beta_dev, void* y_panel_dev, int rows, int width,
+                         void* stream);
+/* gemm_x3: a_panel [ceil256(m), k3] (A side), w_panel [n, k3] (W side), k3 = 3 k with k % 64 == 0, n % 128 == 0, bias fp32 [n] or NULL.
+ *   mode 0: c fp32 [m, n] = acc + bias; 1: c fp32 [m, n] += acc + bias; 2 / 3: c = the A-side triple [ceil256(m), 3 n] bf16 of
+ *   quick_gelu(acc + bias) / gelu(acc + bias), the activation in fp32 (rows m .. are not written).  One kernel family: 128 x 128 tiles. */
+int kemr_op_gemm_x3(const void* a_panel_dev, const void* w_panel_dev, const float* bias_dev, void* c_dev, int m, int n, int k3,
+                    int mode /*0 store f32, 1 add into f32 C, 2 quick_gelu -> triple, 3 gelu -> triple*/, void* stream);
+/* attention_x3: qkv fp32 [rows, 3 width] (q pre-scaled by 1/8; heads of 64) -> out_panel, the A-side triple [rows, 3 width] bf16 of
+ *   softmax(q k^T) v; rows of the panel that hold no query are not written.  row_start == NULL: batch items of t rows each, t <=
+ *   KEMR_MAX_VISION_TOKENS non-causal, t <= KEMR_MAX_TEXT_CTX causal.  row_start (device int32 [batch + 1], causal only): packed
+ *   items, item b = rows row_start[b] .. row_start[b + 1] - 1, at most t of them.  Same bits on every launch. */
+int kemr_op_attention_x3(const float* qkv_dev, void* out_panel_dev, const int* row_start_dev, int batch, int t, int width, int causal,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ PREC_BF16_RES16 = 2
 PREC_FP8 = 3
 PREC_FP8_MLP = 4
 PREC_FP8_RES16 = 5
+PREC_FP32X3 = 6             # split-bf16 operand pairs, fp32 between the kernels: the fp32-grade reference mode (include/kemr.h)
 # default of the product (round 4): bf16 GEMM / attention operands, fp32 accumulation, and the fp32 residual stream STORED as 24-bit
 # floats (15-bit mantissa, 128 x finer than bf16: "bf16-x24"; every LayerNorm statistic and residual add is fp32 arithmetic).  It meets
 # every bar the 4-byte stream ("bf16") meets -- 1 - cos against the fp32 oracle 3e-6 / 3e-5 (image / text) on plain AND heavy-tailed
@@ -32,7 +33,9 @@ PREC_FP8_RES16 = 5
 DEFAULT_PRECISION = "bf16-x24"
 PRECISIONS = {"bf16": PREC_BF16, "bf16-res16": PREC_BF16_RES16, "fp8": PREC_FP8, "fp8-mlp": PREC_FP8_MLP, "fp8-res16": PREC_FP8_RES16,
               # "-x24": the same arithmetic with the fp32 residual stream stored as 24-bit floats (model option residual_stream_24bit)
-              "bf16-x24": PREC_BF16, "fp8-x24": PREC_FP8}
+              "bf16-x24": PREC_BF16, "fp8-x24": PREC_FP8,
+              # every GEMM / attention operand as a bf16 pair, three products each: the reference's fp32 numbers at a third of the rate
+              "fp32x3": PREC_FP32X3}
 TOWER_VISION, TOWER_TEXT = 0, 1
 SIDE_QUERY, SIDE_GALLERY = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RESID_F32 = 0, 1, 2
@@ -96,6 +99,9 @@ SIGNATURES = {
     "kemr_op_layernorm_resid": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "kemr_op_layernorm_rows": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "kemr_op_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "kemr_op_layernorm_x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "kemr_op_gemm_x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "kemr_op_attention_x3": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 # include/kemr_debug.h: experiment switches and diagnostics for tools/ and tests/ (process-wide; not the product ABI)
@@ -144,6 +150,15 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"libkemr.so ABI version {handle.kemr_abi_version()} != {ABI_VERSION}; rebuild the library")
         _lib = handle
         return _lib
+
+
+def env_precision(environ=None) -> str:
+    """The encoder precision the environment asks for: KEMR_PRECISION (a key of PRECISIONS), else DEFAULT_PRECISION.  What `clip.load`,
+    `load_clip_model` and the evaluator CLIs pack their model with and record under "precision" in their result JSON."""
+    name = (os.environ if environ is None else environ).get("KEMR_PRECISION", "") or DEFAULT_PRECISION
+    if name not in PRECISIONS:
+        raise ValueError(f"KEMR_PRECISION must be one of {sorted(PRECISIONS)}, got {name!r}")
+    return name
 
 
 def check_activation(activation: str) -> str:

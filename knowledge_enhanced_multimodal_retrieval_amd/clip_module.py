@@ -168,10 +168,10 @@ class CLIP(nn.Module):
             raise RuntimeError("CLIP: the model sits on %s; the encoders run only on a GPU (model.to('cuda')); there is no "
                                "CPU fallback" % dev)
         if self._engine is None or self._engine.device != dev:
-            # encoder precision of the packed copy: "bf16" (fp32 residual stream) unless KEMR_PRECISION says otherwise (bf16-res16 | fp8 | fp8-res16 | fp8-mlp,
-            # kemr_precision in include/kemr.h) -- an environment switch so that the reference's scripts stay unchanged
-            self._engine, self._dirty = ClipEngine(self.arch, dev, precision=os.environ.get("KEMR_PRECISION", _lib_default_precision()),
-                                                    activation=self.activation), True
+            # encoder precision of the packed copy: _lib.DEFAULT_PRECISION unless KEMR_PRECISION says otherwise (bf16 | bf16-res16 | fp8 | fp8-res16 |
+            # fp8-mlp | fp32x3, kemr_precision in include/kemr.h) -- an environment switch so that the reference's scripts stay unchanged
+            from ._lib import env_precision
+            self._engine, self._dirty = ClipEngine(self.arch, dev, precision=env_precision(), activation=self.activation), True
         if self._engine.activation != self.activation:
             self._engine.set_activation(self.activation)
         fp = self._fingerprint()

@@ -76,6 +76,7 @@ struct kemr_model {
     int resadd = 1;                                 // option "residual_fusion": residual add inside the out-proj / fc2 epilogues
     int last_pooled = 1;                            // option "last_block_pooled_row": the last block's query path on the pooled row only
     int activation = 0;                             // option "activation": 0 = QuickGELU, 1 = exact GELU (the fc1 epilogue of run_blocks)
+    int x3 = 0;                                     // KEMR_PREC_FP32X3: split-bf16 operand triples, fp32 between the kernels (run_blocks_x3)
     int stream24 = 1;                               // option "residual_stream_24bit" (before finalize; default on since round 4): the fp32-class stream stored in 3 bytes
     // vision
     TowerW vis;
@@ -200,13 +201,24 @@ extern "C" int kemr_model_load_tensor(kemr_model* m, const char* name, const voi
 
 extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
     if (!m) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: null model");
-    if (precision < KEMR_PREC_BF16 || precision > KEMR_PREC_FP8_RES16)
+    if (precision < KEMR_PREC_BF16 || precision > KEMR_PREC_FP32X3)
         KEMR_FAIL(KEMR_ERR_INVALID, "finalize: unsupported precision %d", precision);
     const int fp8 = (precision == KEMR_PREC_FP8 || precision == KEMR_PREC_FP8_RES16) ? 1 : precision == KEMR_PREC_FP8_MLP ? 3 : 0;
     if (fp8 && ((m->cfg.v_width % 128) || (m->cfg.t_width % 128) || m->cfg.v_width < 256 || m->cfg.t_width < 256))
         KEMR_FAIL(KEMR_ERR_INVALID, "finalize: fp8 needs tower widths that are multiples of 128 and >= 256");
     for (const auto& n : m->names)
         if (!m->tensors[n].loaded) KEMR_FAIL(KEMR_ERR_STATE, "finalize: missing key '%s' (strict load)", n.c_str());
+    // KEMR_PREC_FP32X3: every matrix [N, K] is packed as the W-side triple [N, 3K] = [hi | hi | lo] (conv1 over 3 kpad); vectors stay fp32
+    const bool x3 = precision == KEMR_PREC_FP32X3;
+    const size_t mat_bytes = x3 ? 6 : 2;
+    auto put_x3 = [](bf16_t* d, size_t row, size_t K, size_t k, float v) {
+        const bf16_t hi = f32_to_bf16_host(v);
+        uint32_t u = (uint32_t)hi << 16;
+        float hf; memcpy(&hf, &u, 4);
+        d[row * 3 * K + k] = hi;
+        d[row * 3 * K + K + k] = hi;
+        d[row * 3 * K + 2 * K + k] = f32_to_bf16_host(v - hf);
+    };
 
     // plan the device arena: f32 tensors verbatim, matrices as bf16
     ArenaPlan plan;
@@ -226,9 +238,9 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
     for (const auto& n : m->names) {
         const HostTensor& t = m->tensors[n];
         size_t bytes;
-        if (n == "visual.conv1.weight") bytes = (size_t)m->cfg.v_width * m->kpad * 2;
+        if (n == "visual.conv1.weight") bytes = (size_t)m->cfg.v_width * m->kpad * mat_bytes;
         else if (is_fp8_matrix(n)) { bytes = t.data.size(); off[n + "#scale"] = plan.take((size_t)t.shape[0] * 4); }
-        else if (is_matrix(n)) bytes = t.data.size() * 2;
+        else if (is_matrix(n)) bytes = t.data.size() * mat_bytes;
         else bytes = t.data.size() * 4;
         off[n] = plan.take(bytes);
     }
@@ -267,7 +279,17 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
             const int kv = 3 * m->cfg.patch * m->cfg.patch;
             bf16_t* d = (bf16_t*)dst;
             for (int r = 0; r < m->cfg.v_width; ++r)
-                for (int k = 0; k < kv; ++k) d[(size_t)r * m->kpad + k] = f32_to_bf16_host(t.data[(size_t)r * kv + k]);
+                for (int k = 0; k < kv; ++k) {
+                    if (x3) put_x3(d, r, m->kpad, k, t.data[(size_t)r * kv + k]);
+                    else d[(size_t)r * m->kpad + k] = f32_to_bf16_host(t.data[(size_t)r * kv + k]);
+                }
+        } else if (x3 && is_matrix(n)) {
+            // the attention scale 1/8 in the query rows is a power of two: it commutes with the split
+            const int64_t rows = t.shape[0], cols = t.shape[1];
+            const bool qkv = n.find("in_proj_weight") != std::string::npos;
+            for (int64_t r = 0; r < rows; ++r)
+                for (int64_t c = 0; c < cols; ++c)
+                    put_x3((bf16_t*)dst, r, cols, c, (qkv && r < cols) ? t.data[r * cols + c] * 0.125f : t.data[r * cols + c]);
         } else if (is_fp8_matrix(n)) {
             // e4m3 with one scale per output channel (row): scale = amax / 448; the attention scale 1/8 goes into the q rows
             const int64_t rows = t.shape[0], cols = t.shape[1];
@@ -343,8 +365,9 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
 
     for (auto& kv : m->tensors) { std::vector<float>().swap(kv.second.data); kv.second.loaded = false; }
     m->res_dtype = (precision == KEMR_PREC_BF16_RES16 || precision == KEMR_PREC_FP8_RES16) ? KEMR_BF16 : KEMR_F32;
-    if (m->stream24 && m->res_dtype == KEMR_F32) m->res_dtype = KEMR_F24;      // option "residual_stream_24bit" (common.h f24_t)
+    if (m->stream24 && m->res_dtype == KEMR_F32 && !x3) m->res_dtype = KEMR_F24;      // option "residual_stream_24bit" (common.h f24_t)
     m->fp8 = fp8;
+    m->x3 = x3 ? 1 : 0;
     m->finalized = true;
     return KEMR_OK;
 }
@@ -523,6 +546,7 @@ int image_front(kemr_model* m, const float* pixels_dev, int batch, const void* o
                 hipStream_t s, const char* what, Workspace& w) {
     if (!m || !pixels_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
     if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
+    if (m->x3) KEMR_FAIL(KEMR_ERR_STATE, "%s: not available for a KEMR_PREC_FP32X3 model", what);
     if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
     if ((int64_t)batch * (m->patches + 1) > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
     const int W = m->cfg.v_width, T = m->patches + 1;
@@ -542,6 +566,7 @@ int text_front(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, i
                void* workspace_dev, size_t workspace_bytes, hipStream_t s, const char* what, Workspace& w, int** row_start) {
     if (!m || !ids_dev || !out_dev || (packed && !lens_dev)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
     if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
+    if (m->x3) KEMR_FAIL(KEMR_ERR_STATE, "%s: not available for a KEMR_PREC_FP32X3 model", what);
     if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
     if ((int64_t)batch * m->cfg.ctx > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
     const int W = m->cfg.t_width, T = m->cfg.ctx;
@@ -560,12 +585,110 @@ int text_front(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, i
     return launch_text_embed(ids_dev, m->tok, m->tpos, w.x, w.x_dtype, batch, T, W, m->cfg.vocab, s, *row_start, rows);
 }
 
+// ---- KEMR_PREC_FP32X3: its own workspace and tower driver (nothing of the bf16 path is shared but the kernels that are fp32 already) ----
+// Per token row of the Mp = ceil256(rows) allocated: x [Mp, W] fp32 (the residual stream, plain 4-byte), h [Mp, 3W] bf16 (LayerNorm
+// output, then the attention output: A-side triples), qkv [Mp, 3W] fp32, big [Mp, 12W] bf16 (the MLP hidden as an A-side triple;
+// the tripled im2col rows, 3 kpad <= 12W, before the blocks).  46 W bytes per row; no pooled-row area: every row runs through every
+// block (option "last_block_pooled_row" is ignored in this mode).
+struct WorkspaceX3 { float* x; bf16_t* h; float* qkv; bf16_t* big; };
+
+size_t ws_bytes_x3(int width, int64_t rows) {
+    const int64_t Mp = round_up(rows, 256);
+    return (size_t)(Mp * width * 4 + Mp * width * 6 + Mp * width * 12 + Mp * width * 24);
+}
+
+int carve_x3(WorkspaceX3& w, void* base, size_t bytes, int width, int64_t rows, size_t extra = 0) {
+    const size_t need = ws_bytes_x3(width, rows) + extra;
+    if (!base || bytes < need) KEMR_FAIL(KEMR_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", bytes, need);
+    if ((uintptr_t)base % 256) KEMR_FAIL(KEMR_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    const int64_t Mp = round_up(rows, 256);
+    char* p = (char*)base;
+    w.x = (float*)p; p += Mp * width * 4;
+    w.h = (bf16_t*)p; p += Mp * width * 6;
+    w.qkv = (float*)p; p += Mp * width * 12;
+    w.big = (bf16_t*)p;
+    return KEMR_OK;
+}
+
+// Every GEMM contracts over the tripled K on gemm.hip's 128 x 128 kernel (launch_gemm_x3); the out-proj and fc2 epilogues add
+// acc + bias into x in fp32 (EPI_BIAS_RESID_F32: nothing pending for the tail, option "residual_fusion" has no meaning here).
+int run_blocks_x3(const TowerW& t, const WorkspaceX3& w, int M, int batch, int causal, const int* row_start, int activation, hipStream_t s) {
+    const int W = t.width;
+    const int epi_act = activation == 1 ? EPI_X3_GELU : EPI_X3_QGELU;
+    for (int l = 0; l < t.layers; ++l) {
+        const LayerW& L = t.layer[l];
+        KEMR_TRY(launch_layernorm_x3(w.x, L.ln1_g, L.ln1_b, w.h, M, W, s));
+        GemmParams g{};
+        g.M = M; g.c_rows_padded = 1;
+        g.A = w.h; g.lda = 3 * W; g.W = L.wqkv; g.ldw = 3 * W; g.bias = L.bqkv; g.C = w.qkv; g.ldc = 3 * W; g.N = 3 * W; g.K = 3 * W;
+        KEMR_TRY(launch_gemm_x3(g, EPI_X3_F32, s));
+        KEMR_TRY(launch_attention_x3(w.qkv, w.h, row_start, batch, t.tokens, W, causal, s));
+        g.W = L.wo; g.bias = L.bo; g.C = w.x; g.ldc = W; g.N = W;
+        KEMR_TRY(launch_gemm_x3(g, EPI_BIAS_RESID_F32, s));
+        KEMR_TRY(launch_layernorm_x3(w.x, L.ln2_g, L.ln2_b, w.h, M, W, s));
+        g.W = L.w1; g.bias = L.b1; g.C = w.big; g.ldc = 12 * W; g.N = 4 * W;
+        KEMR_TRY(launch_gemm_x3(g, epi_act, s));
+        g.A = w.big; g.lda = 12 * W; g.W = L.w2; g.ldw = 12 * W; g.bias = L.b2; g.C = w.x; g.ldc = W; g.N = W; g.K = 12 * W;
+        KEMR_TRY(launch_gemm_x3(g, EPI_BIAS_RESID_F32, s));
+    }
+    return KEMR_OK;
+}
+
+int encode_image_x3(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize, void* workspace_dev,
+                    size_t workspace_bytes, hipStream_t s) {
+    if (!pixels_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: null argument");
+    if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("encode_image: negative batch"), KEMR_ERR_INVALID);
+    if ((int64_t)batch * (m->patches + 1) > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: batch %d too large", batch);
+    const int W = m->cfg.v_width, T = m->patches + 1, M = batch * T;
+    WorkspaceX3 w;
+    KEMR_TRY(carve_x3(w, workspace_dev, workspace_bytes, W, M));
+    KEMR_TRY(launch_im2col_x3(pixels_dev, w.big, batch, m->cfg.image_size, m->cfg.patch, m->kpad, s));
+    GemmParams g{};
+    g.A = w.big; g.lda = 3 * m->kpad; g.W = m->conv_w; g.ldw = 3 * m->kpad; g.bias = nullptr; g.C = w.x; g.ldc = W;
+    g.pos = m->vpos; g.patches = m->patches; g.M = batch * m->patches; g.N = W; g.K = 3 * m->kpad;
+    KEMR_TRY(launch_gemm_x3(g, EPI_PATCH_F32, s));
+    KEMR_TRY(launch_cls_rows(w.x, m->cls, m->vpos, batch, T, W, s));
+    KEMR_TRY(launch_layernorm(w.x, KEMR_F32, nullptr, nullptr, 0, m->lnpre_g, m->lnpre_b, w.x, M, W, KEMR_F32, s));
+    KEMR_TRY(run_blocks_x3(m->vis, w, M, batch, 0, nullptr, m->activation, s));
+    return launch_tail(w.x, KEMR_F32, nullptr, nullptr, nullptr, batch, T, W, m->lnpost_g, m->lnpost_b, m->vproj, m->cfg.embed_dim, normalize, out_dev, s);
+}
+
+int encode_text_x3(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, bool packed, float* out_dev,
+                   int normalize, void* workspace_dev, size_t workspace_bytes, hipStream_t s) {
+    const char* what = packed ? "encode_text_packed" : "encode_text";
+    if (!ids_dev || !out_dev || (packed && !lens_dev)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
+    if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
+    if ((int64_t)batch * m->cfg.ctx > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
+    const int W = m->cfg.t_width, T = m->cfg.ctx;
+    WorkspaceX3 w;
+    int* row_start = nullptr;
+    int M = batch * T;
+    if (packed) {
+        if (T > 128) KEMR_FAIL(KEMR_ERR_INVALID, "%s: context length %d > 128", what, T);
+        if (rows < batch || (int64_t)rows > (int64_t)batch * T) KEMR_FAIL(KEMR_ERR_INVALID, "%s: %d rows for %d texts of 1 .. %d positions", what, rows, batch, T);
+        KEMR_TRY(carve_x3(w, workspace_dev, workspace_bytes, W, rows, (size_t)round_up(((int64_t)batch + 1) * 4, 256)));
+        row_start = (int*)((char*)workspace_dev + ws_bytes_x3(W, rows));
+        KEMR_TRY(launch_row_starts(lens_dev, batch, T, rows, row_start, s));
+        KEMR_TRY(launch_text_embed(ids_dev, m->tok, m->tpos, w.x, KEMR_F32, batch, T, W, m->cfg.vocab, s, row_start, rows));
+        M = rows;
+    } else {
+        KEMR_TRY(carve_x3(w, workspace_dev, workspace_bytes, W, M));
+        KEMR_TRY(launch_text_embed(ids_dev, m->tok, m->tpos, w.x, KEMR_F32, batch, T, W, m->cfg.vocab, s));
+    }
+    KEMR_TRY(run_blocks_x3(m->txt, w, M, batch, 1, row_start, m->activation, s));
+    return launch_tail(w.x, KEMR_F32, nullptr, nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s, row_start);
+}
+
 int fc1_epilogue(const kemr_model* m) { return m->activation == 1 ? EPI_BIAS_GELU_BF16 : EPI_BIAS_QGELU_BF16; }
 
 }  // namespace
 
 extern "C" size_t kemr_workspace_bytes(const kemr_model* m, int tower, int batch) {
     if (!m || batch <= 0) return 0;
+    if (m->x3) {
+        if (tower == KEMR_TOWER_VISION) return ws_bytes_x3(m->cfg.v_width, (int64_t)batch * (m->patches + 1));
+        return tower == KEMR_TOWER_TEXT ? ws_bytes_x3(m->cfg.t_width, (int64_t)batch * m->cfg.ctx) : 0;
+    }
     if (tower == KEMR_TOWER_VISION) return ws_bytes(m->cfg.v_width, m->patches + 1, batch, m->res_dtype) + compact_bytes(m->cfg.v_width, batch);
     if (tower == KEMR_TOWER_TEXT) return ws_bytes(m->cfg.t_width, m->cfg.ctx, batch, m->res_dtype) + compact_bytes(m->cfg.t_width, batch);
     return 0;
@@ -573,6 +696,7 @@ extern "C" size_t kemr_workspace_bytes(const kemr_model* m, int tower, int batch
 
 extern "C" size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows, int batch) {
     if (!m || batch <= 0 || rows < batch) return 0;
+    if (m->x3) return ws_bytes_x3(m->cfg.t_width, rows) + (size_t)round_up(((int64_t)batch + 1) * 4, 256);
     return ws_bytes_rows(m->cfg.t_width, rows, m->res_dtype) + compact_bytes(m->cfg.t_width, batch) +
            (size_t)round_up(((int64_t)batch + 1) * 4, 256);                                        // buffers + pooled-row area + row_start
 }
@@ -580,6 +704,7 @@ extern "C" size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows
 extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize,
                                  void* workspace_dev, size_t workspace_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
+    if (m && m->finalized && m->x3) return encode_image_x3(m, pixels_dev, batch, out_dev, normalize, workspace_dev, workspace_bytes, s);
     Workspace w;
     KEMR_TRY(image_front(m, pixels_dev, batch, out_dev, workspace_dev, workspace_bytes, s, "encode_image", w));
     if (batch == 0) return KEMR_OK;
@@ -595,6 +720,7 @@ extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int bat
 extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch, float* out_dev, int normalize,
                                 void* workspace_dev, size_t workspace_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
+    if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, nullptr, 0, batch, false, out_dev, normalize, workspace_dev, workspace_bytes, s);
     Workspace w;
     int* no_rows = nullptr;
     KEMR_TRY(text_front(m, ids_dev, nullptr, 0, batch, false, out_dev, workspace_dev, workspace_bytes, s, "encode_text", w, &no_rows));
@@ -619,6 +745,7 @@ extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch
 extern "C" int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
                                        int normalize, void* workspace_dev, size_t workspace_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
+    if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, lens_dev, rows, batch, true, out_dev, normalize, workspace_dev, workspace_bytes, s);
     Workspace w;
     int* row_start = nullptr;
     KEMR_TRY(text_front(m, ids_dev, lens_dev, rows, batch, true, out_dev, workspace_dev, workspace_bytes, s, "encode_text_packed", w, &row_start));
@@ -662,7 +789,7 @@ extern "C" int kemr_model_get_option(const kemr_model* m, const char* key, int* 
     if (!m || !key || !value) KEMR_FAIL(KEMR_ERR_INVALID, "model_get_option: null argument");
     if (!strcmp(key, "residual_fusion")) { *value = m->resadd; return KEMR_OK; }
     if (!strcmp(key, "last_block_pooled_row")) { *value = m->last_pooled; return KEMR_OK; }
-    if (!strcmp(key, "residual_stream_24bit")) { *value = m->finalized ? (m->res_dtype == KEMR_F24) : m->stream24; return KEMR_OK; }
+    if (!strcmp(key, "residual_stream_24bit")) { *value = (m->finalized && !m->x3) ? (m->res_dtype == KEMR_F24) : m->stream24; return KEMR_OK; }
     if (!strcmp(key, "activation")) { *value = m->activation; return KEMR_OK; }
     if (!strcmp(key, "precision_residual_bf16")) { *value = m->res_dtype == KEMR_BF16; return KEMR_OK; }
     KEMR_FAIL(KEMR_ERR_INVALID, "model_get_option: unknown key '%s'", key);
@@ -864,4 +991,30 @@ extern "C" int kemr_op_layernorm_rows(void* x_dev, int x_dtype, const void* delt
 extern "C" int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, int t, int width, int causal, void* stream) {
     if (!qkv_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention: null argument");
     return launch_attention((const bf16_t*)qkv_dev, (bf16_t*)out_dev, batch, t, width, causal, (hipStream_t)stream);
+}
+
+// ---- KEMR_PREC_FP32X3 building blocks (panels: kemr_panel_build with nparts = 1, terms = 3) ----
+extern "C" int kemr_op_layernorm_x3(const float* x_dev, const float* gamma_dev, const float* beta_dev, void* y_panel_dev, int rows,
+                                    int width, void* stream) {
+    if (!x_dev || !gamma_dev || !beta_dev || !y_panel_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_layernorm_x3: null argument");
+    return launch_layernorm_x3(x_dev, gamma_dev, beta_dev, (bf16_t*)y_panel_dev, rows, width, (hipStream_t)stream);
+}
+
+extern "C" int kemr_op_gemm_x3(const void* a_panel_dev, const void* w_panel_dev, const float* bias_dev, void* c_dev, int m, int n,
+                               int k3, int mode, void* stream) {
+    if (!a_panel_dev || !w_panel_dev || !c_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_gemm_x3: null argument");
+    if (mode < 0 || mode > 3) KEMR_FAIL(KEMR_ERR_INVALID, "op_gemm_x3: mode %d not in 0..3", mode);
+    if (k3 <= 0 || k3 % 192) KEMR_FAIL(KEMR_ERR_INVALID, "op_gemm_x3: k3 = %d is not three blocks of a multiple of 64", k3);
+    static const int epi[4] = {EPI_X3_F32, EPI_BIAS_RESID_F32, EPI_X3_QGELU, EPI_X3_GELU};
+    GemmParams g{};
+    g.A = (const bf16_t*)a_panel_dev; g.lda = k3; g.W = (const bf16_t*)w_panel_dev; g.ldw = k3; g.bias = bias_dev; g.C = c_dev;
+    g.ldc = mode >= 2 ? 3 * n : n; g.M = m; g.N = n; g.K = k3;
+    g.c_rows_padded = 1;
+    return launch_gemm_x3(g, epi[mode], (hipStream_t)stream);
+}
+
+extern "C" int kemr_op_attention_x3(const float* qkv_dev, void* out_panel_dev, const int* row_start_dev, int batch, int t, int width,
+                                    int causal, void* stream) {
+    if (!qkv_dev || !out_panel_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_x3: null argument");
+    return launch_attention_x3(qkv_dev, (bf16_t*)out_panel_dev, row_start_dev, batch, t, width, causal, (hipStream_t)stream);
 }

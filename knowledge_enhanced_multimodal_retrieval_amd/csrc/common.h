@@ -74,6 +74,11 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     const kemr_f32x2_t v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, kemr_bf16x2_t));
 }
+// the bf16 pair of KEMR_PREC_FP32X3 and of the terms == 3 panels, two values at a time: hi = rne(v), lo = rne(v - hi) (v - hi is exact)
+__device__ __forceinline__ void split_bf16x2(float a, float b, uint32_t& hi, uint32_t& lo) {
+    hi = pack_bf16x2(a, b);
+    lo = pack_bf16x2(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
+}
 // QuickGELU x * sigmoid(1.702 x) with v_exp_f32 / v_rcp_f32 (exp2 with the constant folded; rcp is 1 ulp)
 __device__ __forceinline__ float quick_gelu(float v) {
     return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * v));
@@ -144,6 +149,11 @@ enum GemmEpi : int {
     EPI_BIAS_RESID_F32 = KEMR_EPI_BIAS_RESID_F32,
     EPI_PATCH_F32 = 3,
     EPI_BIAS_GELU_BF16 = KEMR_EPI_BIAS_GELU_BF16,       // C_bf16 = gelu(A.W^T + bias), exact (erf) GELU: the same class as EPI_BIAS_QGELU_BF16 everywhere
+    // KEMR_PREC_FP32X3 (gemm.hip launch_gemm_x3; A [M, 3K] = [hi | lo | hi], W [N, 3K] = [hi | hi | lo], p.K = 3K): fp32 stores, or the
+    // activation in fp32 stored as the next GEMM's A-side triple [M, 3N] (ldc = 3N)
+    EPI_X3_F32 = 16,                                    // C_f32 = acc + bias
+    EPI_X3_QGELU = 17,                                  // C = [hi | lo | hi] of quickgelu(acc + bias)
+    EPI_X3_GELU = 18,                                   // C = [hi | lo | hi] of gelu(acc + bias)
     EPI_BIAS_RESADD_BF16 = KEMR_EPI_BIAS_RESADD_BF16,   // X_bf16 = bf16(bf16(A.W^T + bias) + X_bf16), in place (gemm256u only)     // X_f32[remap(m)] = acc + pos[1 + m % tokens_per_img]   (patch embedding)
 };
 struct GemmParams {
@@ -207,6 +217,8 @@ int launch_gemm256u_fp8(const GemmParams& p, int epi, hipStream_t stream);  // g
 int launch_gemm256r(const GemmParams& p, int epi, hipStream_t stream);  // gemm256r.hip: persistent, 4 waves x 128x128, register-staged operands
 int launch_gemm_skinny(const GemmParams& p, int epi, hipStream_t stream);   // gemm_skinny.hip: M <= 512 rows (online queries), split-K over 8 waves
 int launch_gemm256w(const GemmParams& p, int epi, hipStream_t stream);  // gemm256w.hip: persistent, 4 waves x 128x128 (AGPR accumulators)
+// KEMR_PREC_FP32X3: the 128 x 128 kernel of gemm.hip over the tripled K; epi EPI_X3_F32 | EPI_BIAS_RESID_F32 | EPI_X3_QGELU | EPI_X3_GELU | EPI_PATCH_F32
+int launch_gemm_x3(const GemmParams& p, int epi, hipStream_t stream);
 extern int g_gemm_variant;   // 0 auto, 1 = 128x128 (gemm.hip), 2 / 3 = 256x256 lockstep / staggered, 4 = persistent 256x256 (bf16 epilogues)
 
 // ---- other launchers --------------------------------------------------------------------------
@@ -221,6 +233,13 @@ int launch_select_topk(const float* scores, const int32_t* idx, int nq, int n, l
 // delta2 (needs delta and writeback) is added as well; writeback == 0 leaves x as it is and normalises x + delta
 int launch_layernorm(void* x, int x_dtype, const bf16_t* delta, const bf16_t* delta2, int writeback, const float* gamma,
                      const float* beta, void* y, int rows, int width, int out_dtype, hipStream_t stream);
+// KEMR_PREC_FP32X3: y = LayerNorm(x) of fp32 rows stored as the A-side triple [hi | lo | hi] into [ceil256(rows), 3 width] bf16, pad rows zero
+int launch_layernorm_x3(const float* x, const float* gamma, const float* beta, bf16_t* y_panel, int rows, int width, hipStream_t stream);
+// KEMR_PREC_FP32X3 (fp32x3.hip): fp32 q | k | v rows [*, 3 width] -> the attention output as an A-side triple [*, 3 width] bf16; streaming
+// softmax, any t <= KEMR_MAX_VISION_TOKENS, causal or not; row_start != nullptr: packed items of lengths <= t (device ints, batch + 1)
+int launch_attention_x3(const float* qkv, bf16_t* out_panel, const int* row_start, int batch, int t, int width, int causal, hipStream_t stream);
+// im2col whose rows are A-side triples [B * P, 3 kpad]
+int launch_im2col_x3(const float* pixels, bf16_t* patches, int batch, int image_size, int patch, int kpad, hipStream_t stream);
 int launch_attention(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, int causal, hipStream_t stream);
 // non-causal, t up to KEMR_MAX_VISION_TOKENS: K / V streamed through LDS with an online softmax (attention_long.hip)
 int launch_attention_long(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, hipStream_t stream);

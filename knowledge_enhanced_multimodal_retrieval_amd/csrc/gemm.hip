@@ -134,6 +134,14 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_kernel(const GemmPa
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
             }
+            if constexpr (EPI == EPI_X3_QGELU) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = quick_gelu(v[r]);
+            }
+            if constexpr (EPI == EPI_X3_GELU) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+            }
             if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16) {
                 uint2 o;
                 o.x = pack_bf16x2(v[0], v[1]);
@@ -144,6 +152,16 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_kernel(const GemmPa
                 float4 x = *dst;
                 x.x += v[0]; x.y += v[1]; x.z += v[2]; x.w += v[3];
                 *dst = x;
+            } else if constexpr (EPI == EPI_X3_F32) {
+                *(float4*)((float*)p.C + (size_t)m * p.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
+            } else if constexpr (EPI == EPI_X3_QGELU || EPI == EPI_X3_GELU) {   // A-side triple [hi | lo | hi], blocks of N columns
+                uint2 hi, lo;
+                split_bf16x2(v[0], v[1], hi.x, lo.x);
+                split_bf16x2(v[2], v[3], hi.y, lo.y);
+                bf16_t* dst = (bf16_t*)p.C + (size_t)m * p.ldc + n;
+                *(uint2*)dst = hi;
+                *(uint2*)(dst + p.N) = lo;
+                *(uint2*)(dst + 2 * p.N) = hi;
             } else {  // EPI_PATCH_F32: token row = image * (patches + 1) + 1 + patch, plus positional embedding
                 const int img = m / p.patches, pi = m - img * p.patches;
                 const float4 pe = *(const float4*)(p.pos + (size_t)(pi + 1) * p.N + n);
@@ -181,6 +199,24 @@ int g_gemm_grid = 0;       // tools: > 0 caps the persistent GEMM's grid (workgr
 // region is read until two intervals before -- and the stall eats the gain: 402 -> 414 us on fc2, 106 -> 111 on out-proj, same
 // device, bit-identical results; tools/bench_gemm_r3.py)
 int g_gemm_kl = 0;
+
+// KEMR_PREC_FP32X3: every GEMM of the mode runs on this file's 128 x 128 kernel, whatever the shape (one family: a reference mode
+// needs one summation order, not four).  K is the tripled K of the operand panels; the kernel itself does not know.
+int launch_gemm_x3(const GemmParams& p, int epi, hipStream_t stream) {
+    if (p.M <= 0) return KEMR_OK;
+    if (p.N % 128 != 0 || p.K % BK != 0 || p.K <= 0)
+        KEMR_FAIL(KEMR_ERR_INVALID, "gemm_x3: need N %% 128 == 0 and K %% 64 == 0 (got M=%d N=%d K=%d)", p.M, p.N, p.K);
+    if ((p.lda % 8) || (p.ldw % 8) || (p.ldc % 4))
+        KEMR_FAIL(KEMR_ERR_INVALID, "gemm_x3: leading dimensions must keep 16-byte alignment");
+    switch (epi) {
+        case EPI_X3_F32:         return launch_cfg<128, 128, 2, 2, EPI_X3_F32>(p, stream);
+        case EPI_BIAS_RESID_F32: return launch_cfg<128, 128, 2, 2, EPI_BIAS_RESID_F32>(p, stream);
+        case EPI_X3_QGELU:       return launch_cfg<128, 128, 2, 2, EPI_X3_QGELU>(p, stream);
+        case EPI_X3_GELU:        return launch_cfg<128, 128, 2, 2, EPI_X3_GELU>(p, stream);
+        case EPI_PATCH_F32:      return launch_cfg<128, 128, 2, 2, EPI_PATCH_F32>(p, stream);
+    }
+    KEMR_FAIL(KEMR_ERR_INVALID, "gemm_x3: unknown epilogue %d", epi);
+}
 
 int launch_gemm(const GemmParams& p, int epi, hipStream_t stream) {
     if (p.M <= 0) return KEMR_OK;

@@ -92,6 +92,17 @@ __device__ __forceinline__ void store_row4(fp8_t* r, int i, float4 v, int) {
     ((int*)r)[i] = pk;
 }
 
+struct __attribute__((packed)) x3_t { bf16_t v[3]; };   // output tag of KEMR_PREC_FP32X3: a row of W values is the A-side triple [hi | lo | hi], 3 W bf16
+__device__ __forceinline__ void store_row4(x3_t* r, int i, float4 v, int W) {
+    uint2 hi, lo;
+    split_bf16x2(v.x, v.y, hi.x, lo.x);
+    split_bf16x2(v.z, v.w, hi.y, lo.y);
+    bf16_t* dst = (bf16_t*)r + 4 * i;
+    *(uint2*)dst = hi;
+    *(uint2*)(dst + W) = lo;
+    *(uint2*)(dst + 2 * W) = hi;
+}
+
 // NTD (round 4; 3 = the product kernel): cache hints for bytes that are touched exactly once here.  The deltas are dead after this read; the
 // residual row is next read a millisecond and 1.5 GB of traffic later; as ordinary loads / stores they pushed what IS reused soon -- the
 // GEMM operand h this kernel writes, the q | k | v rows the next kernels produce -- out of L2 / Infinity Cache.  Measured in the chain,
@@ -202,6 +213,31 @@ static int launch_xt(XT* x, const bf16_t* d1, const bf16_t* d2, int writeback, c
         case 1280: return launch_nv<5>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream);
     }
     KEMR_FAIL(KEMR_ERR_INVALID, "layernorm: width %d not in {256,512,768,1024,1280}", width);
+}
+
+// KEMR_PREC_FP32X3: the fp32-output form's arithmetic (the same template, so the same bits) with the split store; the pad rows up to
+// ceil256(rows), which the GEMM's 128-row tiles read, are zero-filled
+template <int NV>
+static int launch_x3_nv(const float* x, const float* g, const float* b, bf16_t* y, int rows, hipStream_t s) {
+    ProfScope prof(PROF_LAYERNORM, s);
+    hipLaunchKernelGGL((layernorm_kernel<NV, float, x3_t, 0>), dim3((rows + 3) / 4), dim3(256), 0, s, (float*)x, (const bf16_t*)nullptr,
+                       (const bf16_t*)nullptr, g, b, (x3_t*)y, rows, 1e-5f);
+    KEMR_CHECK_LAUNCH("layernorm_kernel (x3)");
+    return KEMR_OK;
+}
+
+int launch_layernorm_x3(const float* x, const float* gamma, const float* beta, bf16_t* y_panel, int rows, int width, hipStream_t stream) {
+    if (rows <= 0) return KEMR_OK;
+    const int64_t pad = round_up(rows, 256) - rows;
+    if (pad) KEMR_CHECK_HIP(hipMemsetAsync(y_panel + (size_t)rows * 3 * width, 0, (size_t)pad * 3 * width * 2, stream));
+    switch (width) {
+        case 256:  return launch_x3_nv<1>(x, gamma, beta, y_panel, rows, stream);
+        case 512:  return launch_x3_nv<2>(x, gamma, beta, y_panel, rows, stream);
+        case 768:  return launch_x3_nv<3>(x, gamma, beta, y_panel, rows, stream);
+        case 1024: return launch_x3_nv<4>(x, gamma, beta, y_panel, rows, stream);
+        case 1280: return launch_x3_nv<5>(x, gamma, beta, y_panel, rows, stream);
+    }
+    KEMR_FAIL(KEMR_ERR_INVALID, "layernorm_x3: width %d not in {256,512,768,1024,1280}", width);
 }
 
 // x_dtype: KEMR_F32 or KEMR_BF16 rows.  delta != nullptr: LN(x + delta [+ delta2]); with `writeback` the sum replaces x

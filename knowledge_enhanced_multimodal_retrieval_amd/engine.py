@@ -74,7 +74,9 @@ class ClipEngine:
         """precision: "bf16-x24" (default: bf16 operands, fp32 accumulation, the fp32 residual stream stored as 24-bit floats -- model
         option residual_stream_24bit), "bf16" (the stream as 4-byte fp32), "bf16-res16" (bf16 residual stream, opt-in), "fp8" / "fp8-x24"
         (the vision tower's QKV GEMMs on fp8 operands, BASELINE config 5), "fp8-res16" or "fp8-mlp" (fc1 too).  See kemr_precision in
-        include/kemr.h and _lib.DEFAULT_PRECISION.
+        include/kemr.h and _lib.DEFAULT_PRECISION.  "fp32x3": every GEMM / attention operand as a bf16 pair (hi, lo) with three products
+        each, fp32 between the kernels -- the reference's fp32 numbers for practical purposes at a quarter to a third of the default's
+        rate; what `precision_gap` measures the faster precisions against.
         activation: "quick_gelu" (the OpenAI checkpoints) or "gelu" (exact GELU: OpenCLIP / LAION and Hugging Face `hidden_act: gelu`
         checkpoints) -- model option "activation"."""
         _lib.check_activation(activation)
@@ -95,6 +97,7 @@ class ClipEngine:
         if activation != self.activation:
             self.set_activation(activation)
         self._ws: Dict[object, torch.Tensor] = {}
+        self._state: Optional[Mapping[str, torch.Tensor]] = None
         self.ready = False
         self.pack_text = os.environ.get("KEMR_TEXT_PACKED", "1") != "0"     # encode_text: only the positions up to the end-of-text token
 
@@ -139,8 +142,8 @@ class ClipEngine:
 
     def residual_fusion_active(self) -> bool:
         """Whether large calls of THIS engine add the residual inside the GEMM epilogues (option and stream type together)."""
-        if self.precision.endswith("-x24"):
-            return False                                   # 24-bit stream rows: store-only epilogues, whatever the option says
+        if self.precision.endswith("-x24") or self.precision == "fp32x3":
+            return False                                   # 24-bit stream rows: store-only epilogues, whatever the option says; fp32x3: the option has no meaning
         return self.residual_fusion() >= (1 if self.precision.endswith("res16") else 2)
 
     # ------------------------------------------------------------------ weights
@@ -150,6 +153,7 @@ class ClipEngine:
 
     def load_state_dict(self, sd: Mapping[str, torch.Tensor]) -> None:
         """Strict load of an OpenAI-CLIP style state dict (any float dtype, any device) + pack to HBM."""
+        self._state = dict(sd)          # references, not copies: what `precision_gap` packs a second engine from
         for name, t in sd.items():
             if not torch.is_tensor(t):
                 continue
@@ -261,6 +265,44 @@ class ClipEngine:
                                                            C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)), "encode_text_packed")
                 s0, base = s1, csum[s1 - 1]
         return out
+
+
+def precision_gap(model_or_engine, pixels: Optional[torch.Tensor], ids: Optional[torch.Tensor], fast: str = _lib.DEFAULT_PRECISION,
+                  exact: str = "fp32x3") -> Dict[str, Dict[str, object]]:
+    """Is `fast` safe for THIS checkpoint on THIS data?  Packs the same weights twice, at precision `fast` and at `exact` (the
+    fp32-grade "fp32x3"), encodes `pixels` ([B, 3, S, S] normalised) and `ids` ([B, ctx] token ids; either may be None) with both and
+    returns, per tower, the per-embedding 1 - cos between the two:
+
+        {"image": {"one_minus_cos": fp64 tensor [B] (CPU), "worst": float, "median": float, "argmax": int}, "text": {...},
+         "fast": fast, "exact": exact}
+
+    `model_or_engine`: a `CLIP` module (its state dict and activation) or a `ClipEngine` that has loaded one.  Two engines of its
+    own are built and dropped; the one handed in is not touched.  The path's bar is 1e-3: a worst value near
+    or above it means the checkpoint is in the regime bf16 operands cannot hold (LayerNorm gains of 30-100 that the following
+    weights do not compensate) and should be served at `exact`."""
+    if isinstance(model_or_engine, ClipEngine):
+        if model_or_engine._state is None:
+            raise RuntimeError("precision_gap: the engine has not loaded a state dict")
+        arch, device, activation, sd = model_or_engine.arch, model_or_engine.device, model_or_engine.activation, model_or_engine._state
+    else:
+        arch, activation = model_or_engine.arch, model_or_engine.activation
+        device = next(model_or_engine.parameters()).device
+        sd = {k: v for k, v in model_or_engine.state_dict().items() if k != "logit_scale"}
+    embs = {}
+    for prec in (fast, exact):
+        eng = ClipEngine(arch, device, precision=prec, activation=activation)
+        eng.load_state_dict(sd)
+        embs[prec] = (eng.encode_image(pixels.to(device)).double().cpu() if pixels is not None else None,
+                      eng.encode_text(ids).double().cpu() if ids is not None else None)
+        del eng
+    out: Dict[str, Dict[str, object]] = {"fast": fast, "exact": exact}
+    for i, tower in enumerate(("image", "text")):
+        a, b = embs[fast][i], embs[exact][i]
+        if a is None:
+            continue
+        gap = 1.0 - torch.nn.functional.cosine_similarity(a, b, dim=-1)      # fp64 on the CPU, the expression the tests measure with
+        out[tower] = {"one_minus_cos": gap, "worst": float(gap.max()), "median": float(gap.median()), "argmax": int(gap.argmax())}
+    return out
 
 
 # ====================================================================== similarity / ranking ops
@@ -756,4 +798,46 @@ def op_attention(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool
     with torch.cuda.device(qkv.device):
         _lib.check(L.kemr_op_attention(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), batch, t, width,
                                        1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))), "op_attention")
+    return out
+
+
+def op_layernorm_x3(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
+    """fp32 [rows, width] -> the A-side triple [hi | lo | hi] of LayerNorm(x): bf16 [ceil256(rows), 3 width], pad rows zero."""
+    L = _lib.lib()
+    rows, width = x.shape
+    y = torch.full((rows_alloc(rows), 3 * width), float("nan"), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(L.kemr_op_layernorm_x3(C.c_void_p(x.data_ptr()), C.c_void_p(gamma.data_ptr()), C.c_void_p(beta.data_ptr()),
+                                          C.c_void_p(y.data_ptr()), rows, width, C.c_void_p(_stream_ptr(x.device))), "op_layernorm_x3")
+    return y
+
+
+def op_gemm_x3(a_panel: torch.Tensor, w_panel: torch.Tensor, bias: Optional[torch.Tensor], m: int, mode: int,
+               c: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a_panel bf16 [ceil256(m), 3k] (build_panel(..., SIDE_QUERY, 3).data), w_panel bf16 [>= n, 3k] (SIDE_GALLERY; n = its row count
+    unless `c` says otherwise).  mode 0: fp32 [m, n] = acc + bias; 1: c += acc + bias (c required); 2 / 3: the A-side triple
+    bf16 [ceil256(m), 3n] of quick_gelu / gelu(acc + bias), rows m .. left as allocated (zero)."""
+    L = _lib.lib()
+    n, k3 = w_panel.shape
+    if c is None:
+        if mode == 1:
+            raise RuntimeError("op_gemm_x3: mode 1 accumulates into a given c")
+        c = (torch.zeros((m, n), dtype=torch.float32, device=a_panel.device) if mode == 0 else
+             torch.zeros((rows_alloc(m), 3 * n), dtype=torch.bfloat16, device=a_panel.device))
+    elif mode < 2:
+        n = c.shape[1]
+    with torch.cuda.device(a_panel.device):
+        _lib.check(L.kemr_op_gemm_x3(C.c_void_p(a_panel.data_ptr()), C.c_void_p(w_panel.data_ptr()), _opt_ptr(bias), C.c_void_p(c.data_ptr()),
+                                     m, n, k3, mode, C.c_void_p(_stream_ptr(a_panel.device))), "op_gemm_x3")
+    return c
+
+
+def op_attention_x3(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool, row_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qkv fp32 [rows, 3 width] (q pre-scaled) -> the A-side triple bf16 [rows, 3 width] of the attention output.  row_start (int32
+    [batch + 1] on the device): packed causal items of at most t rows."""
+    L = _lib.lib()
+    out = torch.zeros((qkv.shape[0], 3 * width), dtype=torch.bfloat16, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(L.kemr_op_attention_x3(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), _opt_ptr(row_start), batch, t, width,
+                                          1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))), "op_attention_x3")
     return out

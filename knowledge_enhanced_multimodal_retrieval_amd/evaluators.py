@@ -375,7 +375,7 @@ def _run(args, baseline: bool, log_name: str):
                "num_samples": len(dataset), "seed": args.seed, "metrics": metrics,
                # provenance (not in the reference's file): what the numbers were computed with
                "weights_source": getattr(model, "weights_source", "unknown"), "tokenizer": tokenizer.tokenizer_name(),
-               "precision": os.environ.get("KEMR_PRECISION", _lib.DEFAULT_PRECISION), "data": "synthetic" if args.synthetic > 0 else args.dataset,
+               "precision": _lib.env_precision(), "data": "synthetic" if args.synthetic > 0 else args.dataset,
                "image_transform": {"RawRGB": "gpu (batched kernels, bit-identical to the host transform)", "ClipPreprocess": "host (PIL, per sample)"}.get(
                    type(getattr(dataset, "preprocessor", None)).__name__, "none (pre-normalised tensors)"),
                "loader_workers": workers}
@@ -509,7 +509,7 @@ def main_fusion(argv=None):
                "fusion_checkpoint": args.fusion_checkpoint, "fusion_type": args.fusion_type, "split": args.split,
                "num_samples": len(dataset), "metrics": result,
                "weights_source": getattr(clip_model, "weights_source", "unknown"), "tokenizer": tokenizer.tokenizer_name(),
-               "precision": os.environ.get("KEMR_PRECISION", _lib.DEFAULT_PRECISION), "data": "synthetic" if args.synthetic > 0 else args.dataset}
+               "precision": _lib.env_precision(), "data": "synthetic" if args.synthetic > 0 else args.dataset}
     if args.output_file:
         Path(args.output_file).parent.mkdir(parents=True, exist_ok=True)
         with open(args.output_file, "w") as f:
