@@ -360,6 +360,28 @@ int kemr_cross_attention_rerank(const float* q_dev, const float* k_i_dev, const 
                                 const float* w3_dev, float b3, int heads, int nq, int ng, int dim, int hid1, int hid2,
                                 const int32_t* cand_idx_dev, int depth, int64_t ld, float* out_scores_dev, void* stream);
 
+/* The knowledge side on a learned head's lists (knowledge-fused rerank: CLIP shortlist -> head on the listed pairs -> this): for
+ * every slot (q, j), j < depth, of list_scores fp32 [nq, ld] / list_idx int32 [nq, ld] with id c = list_idx[q, j]
+ *   c < 0 (the deep lists' padding): out = -inf;
+ *   otherwise f = score_scale * s as ONE fp32 multiply (score_scale == 1.0f: the output has the input's own bits), then every entry
+ *   of bonus row q whose column equals c is added to f, one after the other in list order, in fp32 -- the rule of
+ *   kemr_sim_topk_deep_fused, whose CSR layout the bonus has (rowptr int32 [nq + 1], col int32 GLOBAL ids ascending within a row, val
+ *   fp32; all three or none).  A column may repeat, lie outside the list or outside any gallery; a row may be empty or hold many
+ *   thousands of entries (it is binary-searched; the result does not depend on its length).
+ * Only columns < depth are read or written: columns >= depth of out_scores are not touched.  out_scores may alias list_scores.
+ * Ground truth (gt_idx int32 [nq], ahead int32 [nq], found int32 [nq], gt_score fp32 [nq]; all four or none; WRITTEN, not accumulated):
+ *   found[q] = 1 if gt_idx[q] is among the row's ids, else 0; gt_score[q] = that slot's fused score where found, -inf otherwise;
+ *   ahead[q] = the slots with id >= 0 and id != gt_idx[q] that rank before (gt_score[q], gt_idx[q]) by the order rule of
+ *   kemr_select_topk (score descending, -0.0 ties +0.0, lower id first on equal scores, NaN behind -inf); where the ground truth is
+ *   absent, every slot with id >= 0.  So where found, ahead + 1 is the ground truth's position in kemr_select_topk(out, idx, k = depth).
+ * A partial triple or quadruple is KEMR_ERR_INVALID; 1 <= depth <= KEMR_MAX_DEEP_K, ld >= depth; nq == 0 is a no-op; with both groups
+ * NULL the call is scale + padding only.  One workgroup per query row, every output element has one owner, no atomics: the result is
+ * a pure function of the input (same bits on every run). */
+int kemr_list_fuse(const float* list_scores_dev, const int32_t* list_idx_dev, int nq, int depth, int64_t ld, float score_scale,
+                   const int32_t* bonus_rowptr_dev, const int32_t* bonus_col_dev, const float* bonus_val_dev,   /* all three or none */
+                   const int32_t* gt_idx_dev, int32_t* ahead_dev, int32_t* found_dev, float* gt_score_dev,      /* all four or none  */
+                   float* out_scores_dev, void* stream);
+
 /* Optional per-kernel-class timing with hipEvents recorded on the launch stream (bench.py's roofline line).
  * Classes: 0 GEMM, 1 LayerNorm, 2 attention, 3 embed/tail, 4 similarity tile kernel.  Not thread-safe;
  * profile_end synchronises the device.  Off by default: no events are recorded on the normal path. */

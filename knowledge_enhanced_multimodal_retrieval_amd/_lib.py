@@ -43,7 +43,7 @@ EPI_BIAS_RESADD_BF16 = 4
 EPI_BIAS_GELU_BF16 = 5      # exact (erf) GELU; 3 is internal to the library
 # model option "activation" (include/kemr.h): the MLP's activation, by the name Hugging Face configs give it (`hidden_act`)
 ACTIVATIONS = {"quick_gelu": 0, "gelu": 1}
-MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused / kemr_cross_attention_rerank
+MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused / kemr_cross_attention_rerank / kemr_list_fuse
 
 
 class KemrCfg(C.Structure):
@@ -86,6 +86,7 @@ SIGNATURES = {
     "kemr_gate_rows": (_i, [_vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp]),
     "kemr_cross_attention_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp]),
     "kemr_cross_attention_rerank": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp]),
+    "kemr_list_fuse": (_i, [_vp, _vp, _i, _i, _i64, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kemr_profile_begin": (_i, [_i]),
     "kemr_profile_end": (_i, [C.POINTER(C.c_double), C.POINTER(_i64), _i]),
     "kemr_op_gemm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -167,9 +167,11 @@ class ShardedGallery:
             gates = [None if g is None else all_gather_rows(g.reshape(-1, 1), self.group).reshape(-1) for g in row_gate]
         return self.ops.build_panel(qs, _lib.SIDE_QUERY, self.terms, part_scale=weights, row_scale=gates), qs[0].shape[0]
 
-    def _local_topk(self, qp, nq, k, dev, *rank_args):
+    def _local_topk(self, qp, nq, k, dev, *rank_args, bonus=None):
         if self.panel is not None:
-            return self.ops.sim_topk(qp, self.panel, k, self.lo, *rank_args)
+            if bonus is None:
+                return self.ops.sim_topk(qp, self.panel, k, self.lo, *rank_args)
+            return self.ops.sim_topk(qp, self.panel, k, self.lo, *rank_args, bonus=bonus)
         return (torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev),
                 torch.full((nq, k), -1, dtype=torch.int32, device=dev))
 
@@ -183,17 +185,19 @@ class ShardedGallery:
         return PendingSearch(merge, [w1, w2], (ss, ii))
 
     def search_async(self, local_query_parts: Sequence[torch.Tensor], weights: Optional[Sequence[float]] = None, k: int = 10,
-                     row_gate=None) -> PendingSearch:
+                     row_gate=None, bonus=None) -> PendingSearch:
         """``search`` with the candidate exchange left in flight: encode the next query batch, then call ``result()``."""
         qp, nq = self._query_panel(local_query_parts, weights, row_gate)
-        s, i = self._local_topk(qp, nq, k, local_query_parts[0].device)
+        s, i = self._local_topk(qp, nq, k, local_query_parts[0].device, bonus=bonus)
         return self._exchange(s, i, k)
 
     def search(self, local_query_parts: Sequence[torch.Tensor], weights: Optional[Sequence[float]] = None, k: int = 10,
-               row_gate=None) -> Tuple[torch.Tensor, torch.Tensor]:
+               row_gate=None, bonus=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Every rank passes its slice of the query batch (same row count on all ranks) and receives the merged
-        top-k of the WHOLE batch against the WHOLE gallery: (scores [Q, k], global ids [Q, k])."""
-        return self.search_async(local_query_parts, weights, k, row_gate).result()
+        top-k of the WHOLE batch against the WHOLE gallery: (scores [Q, k], global ids [Q, k]).
+        ``bonus``: a CSR ``(rowptr, col, val)`` over the WHOLE gathered query batch with GLOBAL column ids, the same on every rank;
+        each shard adds the entries that fall into its own id range (``kemr_sim_topk``) and the lists hold fused scores."""
+        return self.search_async(local_query_parts, weights, k, row_gate, bonus).result()
 
     def search_deep(self, local_query_parts: Sequence[torch.Tensor], weights: Optional[Sequence[float]] = None, k: int = 100,
                     row_gate=None, bonus=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -233,9 +237,10 @@ class ShardedGallery:
             yield prev.result()
 
     def ranks(self, local_query_parts: Sequence[torch.Tensor], local_gt: torch.Tensor,
-              weights: Optional[Sequence[float]] = None, k: int = 10, row_gate=None
+              weights: Optional[Sequence[float]] = None, k: int = 10, row_gate=None, bonus=None
               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """As ``search`` plus the 1-based rank of each query's ground-truth candidate (GLOBAL id in ``local_gt``)."""
+        """As ``search`` plus the 1-based rank of each query's ground-truth candidate (GLOBAL id in ``local_gt``).  With ``bonus``
+        (as in ``search``) the rank is counted on the fused scores: the ground-truth pair's own bonus is added to its score."""
         qp, nq = self._query_panel(local_query_parts, weights, row_gate)
         dev = local_query_parts[0].device
         gt = all_gather_rows(local_gt.to(device=dev, dtype=torch.int32).reshape(-1, 1), self.group).reshape(-1)
@@ -248,10 +253,69 @@ class ShardedGallery:
             every = self.ops.pair_scores(qp, self.panel, torch.arange(nq, dtype=torch.int32, device=dev), local)
             sgt = torch.where(mine, every, sgt)
         all_reduce_sum(sgt, self.group)                            # exactly one rank contributed a non-zero per query
+        if bonus is not None:                                      # the ground-truth pair's own bonus, the same on every rank
+            sgt = sgt + ranking._bonus_of_pairs(bonus, gt, dev)
         ahead = torch.zeros(nq, dtype=torch.int32, device=dev)
-        s, i = self._local_topk(qp, nq, k, dev, gt, sgt, ahead)
+        s, i = self._local_topk(qp, nq, k, dev, gt, sgt, ahead, bonus=bonus)
         pending = self._exchange(s, i, k) if k > 0 else None       # k == 0: ranks only (what Recall@K / MRR need), nothing to merge
         all_reduce_sum(ahead, self.group)                          # rides while the candidates are gathered
         if pending is not None:
             s, i = pending.result()
         return ahead.long() + 1, s, i
+
+    def rerank(self, fusion_model, local_head_gallery, local_query_embed: torch.Tensor, depth: int = 200, k: int = 10,
+               local_gt: Optional[torch.Tensor] = None, bonus=None, head_weight: float = 1.0, shortlist_weights=(0.5, 0.5),
+               score_lists: Optional[Callable] = None):
+        """``FusionModel.rerank`` over a gallery sharded as ``[image, target]`` parts, with or without the knowledge side.
+
+        1. ``search_deep(k=depth, bonus=...)`` gives every rank the same global shortlist (ids [Q, depth], -1 padded);
+        2. every rank scores, against its LOCAL ``HeadGallery`` (``fusion_model.prepare_gallery`` of this rank's shard), only the slots
+           whose id lies in its own ``[lo, hi)``; the other slots are handed to the head as -1, which scores -inf;
+        3. the non-owners contribute 0 and ONE ``all_reduce_sum`` assembles the list: exactly one rank owns a slot (the trick
+           ``ranks`` uses for the ground-truth score), so a score arrives with its own bits (a head score of -0.0 as +0.0, which
+           ties with it).  No folded projection and no key row crosses the wire: depth floats per query do;
+        4. ``ops.list_fuse`` (``head_weight * head + bonus``, the ground truth's place, ``found``) and ``ops.select_topk`` run on every
+           rank on identical inputs, so every rank ends with the same answer.
+
+        ``local_gt``: this rank's queries' GLOBAL ground-truth ids, or None.  ``bonus``: CSR over the WHOLE gathered query batch, GLOBAL
+        column ids, the same on every rank.  ``score_lists(q, local_head_gallery, local_idx) -> fp32 [Q, depth]`` defaults to
+        ``fusion_model.list_scores`` (the gloo rehearsal substitutes an oracle).  Returns the 5-tuple of ``FusionModel.rerank`` with
+        GLOBAL ids; at world size 1 it has that call's bits."""
+        depth, k = int(depth), int(k)
+        if self.nparts != 2:
+            raise ValueError(f"ShardedGallery.rerank: the gallery must be built from [image, target] parts, this one has {self.nparts}")
+        if not 1 <= depth <= _lib.MAX_DEEP_K:
+            raise ValueError(f"ShardedGallery.rerank: depth={depth} not in 1..{_lib.MAX_DEEP_K}")
+        if not 1 <= k <= depth:
+            raise ValueError(f"ShardedGallery.rerank: k={k} not in 1..depth={depth}")
+        if bonus is None and float(head_weight) != 1.0:
+            raise ValueError("ShardedGallery.rerank: head_weight scales the head against a bonus; without bonus it must stay 1.0")
+        if self.panel is not None and (local_head_gallery is None or len(local_head_gallery) != self.hi - self.lo):
+            raise ValueError(f"ShardedGallery.rerank: rank {self.rank} needs the HeadGallery of its own {self.hi - self.lo} candidates")
+        if score_lists is None:
+            score_lists = fusion_model.list_scores
+        q_local = local_query_embed
+        dev = q_local.device
+        if bonus is not None and len(bonus[0]) != q_local.shape[0] * self.world + 1:      # every rank brings the same number of rows
+            raise ValueError(f"ShardedGallery.rerank: the bonus row pointer must have {q_local.shape[0] * self.world + 1} entries "
+                             f"(one row per query of the whole batch), got {len(bonus[0])}")
+        _, gi = self.search_deep([q_local, q_local], list(shortlist_weights), depth, bonus=bonus)
+        q = all_gather_rows(q_local, self.group)
+        nq = q.shape[0]
+        lists = torch.zeros((nq, depth), dtype=torch.float32, device=dev)
+        if self.panel is not None:
+            mine = (gi >= self.lo) & (gi < self.hi)
+            local_idx = torch.where(mine, gi - self.lo, torch.full_like(gi, -1)).to(torch.int32).contiguous()
+            lists = torch.where(mine, score_lists(q, local_head_gallery, local_idx), lists).contiguous()
+        all_reduce_sum(lists, self.group)                          # exactly one rank contributed a non-zero per listed slot
+        gt = None
+        if local_gt is not None:
+            gt = all_gather_rows(local_gt.to(device=dev, dtype=torch.int32).reshape(-1, 1), self.group).reshape(-1)
+        fused, ahead, found, gt_score = self.ops.list_fuse(lists, gi, depth, float(head_weight), bonus, gt, out=lists)
+        top_s, top_i = self.ops.select_topk(fused, k, idx=gi)
+        if gt is None:
+            return None, top_s, top_i, fused, gi
+        present = found != 0
+        ranking._require_finite(gt_score[present], "fused scores at the ground truth")
+        ranks = torch.where(present, ahead.long() + 1, torch.full_like(ahead, depth + 1, dtype=torch.int64))
+        return ranks, top_s, top_i, fused, gi

@@ -587,6 +587,62 @@ def cross_attention_rerank(q: torch.Tensor, k_i: torch.Tensor, k_t: torch.Tensor
     return out
 
 
+def list_fuse(scores: torch.Tensor, idx: torch.Tensor, depth: Optional[int] = None, scale: float = 1.0,
+              bonus: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, gt_idx: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None
+              ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """The knowledge side on listed scores (``kemr_list_fuse``): ``scale * scores + bonus`` in the first ``depth`` (default: all)
+    columns of the contiguous fp32 [nq, ld] ``scores`` whose candidates are ``idx`` (int32 [nq, ld], ids < 0 = padding -> -inf).
+    ``bonus``: the CSR ``(rowptr [nq + 1], col, val)`` of ``sim_topk_deep`` (GLOBAL column ids ascending within a row).  ``gt_idx``
+    (one id per query): also the ground truth's place in the fused list.  ``out`` (contiguous fp32 [nq, ld], may be ``scores``
+    itself): written in its first ``depth`` columns, the rest is left as it is; without it a new tensor whose columns >= depth hold
+    -inf.  Returns ``(fused, ahead, found, gt_score)``, the last three None without ``gt_idx``: int32 [nq] slots ranked before the
+    ground truth (every listed slot where it is absent), int32 [nq] 1 where the row lists it, fp32 [nq] its fused score (-inf where
+    absent) -- where found, ``ahead + 1`` is its position in ``select_topk(fused, depth, idx=idx)``."""
+    L = _lib.lib()
+    _require_cuda(scores, "listed scores")
+    dev = scores.device
+    if scores.dim() != 2 or idx.dim() != 2 or tuple(idx.shape) != tuple(scores.shape):
+        raise RuntimeError("list_fuse: scores and idx must share one [nq, ld] shape")
+    if scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise RuntimeError("list_fuse: scores must be a contiguous fp32 tensor")
+    idx = idx.to(device=dev, dtype=torch.int32).contiguous()
+    nq, ld = scores.shape
+    depth = ld if depth is None else int(depth)
+    if nq and not 1 <= depth <= min(ld, _lib.MAX_DEEP_K):
+        raise RuntimeError(f"list_fuse: depth={depth} not in 1..min(ld={ld}, {_lib.MAX_DEEP_K})")
+    if out is None:
+        out = torch.full((nq, ld), float("-inf"), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (nq, ld) or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError("list_fuse: out must be a contiguous fp32 [nq, ld] tensor on the scores' device")
+    b_ptr = b_col = b_val = None
+    if bonus is not None and len(bonus[1]) == 0:      # no hit at all: same as no bonus (empty tensors have no address)
+        bonus = None
+    if bonus is not None:
+        b_ptr, b_col, b_val = (torch.as_tensor(bonus[0]).to(device=dev, dtype=torch.int32).contiguous(),
+                               torch.as_tensor(bonus[1]).to(device=dev, dtype=torch.int32).contiguous(),
+                               torch.as_tensor(bonus[2]).to(device=dev, dtype=torch.float32).contiguous())
+        if b_ptr.numel() != nq + 1:
+            raise RuntimeError("list_fuse: bonus row pointer must have nq + 1 entries")
+        if b_val.numel() != b_col.numel():
+            raise RuntimeError("list_fuse: bonus col and val must have one entry per hit")
+    gt = ahead = found = gt_score = None
+    if gt_idx is not None:
+        gt = torch.as_tensor(gt_idx).to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+        if gt.numel() != nq:
+            raise RuntimeError("list_fuse: gt_idx must have one entry per query")
+        ahead = torch.empty(nq, dtype=torch.int32, device=dev)
+        found = torch.empty(nq, dtype=torch.int32, device=dev)
+        gt_score = torch.empty(nq, dtype=torch.float32, device=dev)
+    if nq:
+        with torch.cuda.device(dev):
+            _lib.check(L.kemr_list_fuse(C.c_void_p(scores.data_ptr()), C.c_void_p(idx.data_ptr()), nq, depth, ld, float(scale),
+                                        _opt_ptr(b_ptr), _opt_ptr(b_col), _opt_ptr(b_val),
+                                        _opt_ptr(gt), _opt_ptr(ahead), _opt_ptr(found), _opt_ptr(gt_score),
+                                        C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(dev))), "list_fuse")
+    return out, ahead, found, gt_score
+
+
 def scores_dense(qp: Panel, gp: Panel) -> torch.Tensor:
     """Dense fp32 score matrix [nq, ng] (fusion heads that need every pair; debugging)."""
     L = _lib.lib()

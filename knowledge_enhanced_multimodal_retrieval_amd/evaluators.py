@@ -402,6 +402,11 @@ def main_baseline(argv=None):
 RERANK_DEPTH_MIN = 20       # every reported Recall@K has K <= 20: with at least 20 listed candidates each is exact for the two-stage route
 
 
+_SPARQL_NEEDS_RERANK = ("the SPARQL bonus of the learned heads is applied to the reranked shortlist (FusionModel.rerank(bonus=...), "
+                        "kemr_list_fuse): the dense route scores every pair with the head and has no bonus stage -- give a "
+                        "rerank depth as well (rerank_depth / --rerank_depth N)")
+
+
 def _check_rerank_depth(fusion_type: str, rerank_depth: int) -> None:
     if not RERANK_DEPTH_MIN <= rerank_depth <= _lib.MAX_DEEP_K:
         raise ValueError(f"rerank_depth={rerank_depth} not in {RERANK_DEPTH_MIN}..{_lib.MAX_DEEP_K}")
@@ -413,7 +418,8 @@ def _check_rerank_depth(fusion_type: str, rerank_depth: int) -> None:
 @torch.no_grad()
 def evaluate_fusion_model(fusion_model, dataset, batch_size: int = 64, device: str = "cuda", seed: int = 42,
                           tokenize_fn: Optional[Callable] = None, num_workers: Optional[int] = 4,
-                          rerank_depth: Optional[int] = None) -> Dict[str, float]:
+                          rerank_depth: Optional[int] = None, text2sparql_results: Optional[Dict[str, List[str]]] = None,
+                          fusion_strategy: str = "weighted", fusion_params: Optional[dict] = None) -> Dict[str, float]:
     """Counterpart of /root/reference/src/clip/eval/evaluator_fusion.py:28-144 (4 loader workers as at :42).  The reference fills an N x N numpy
     matrix in 50 x 500 blocks with an H2D/D2H round trip and ``empty_cache()`` per block (:76-121); here the head's
     score is one fused kernel pass over resident embeddings (``FusionModel.rank``).
@@ -424,24 +430,39 @@ def evaluate_fusion_model(fusion_model, dataset, batch_size: int = 64, device: s
     Recall@K (K <= 20 <= rerank_depth) is exact for the two-stage pipeline.  Two keys are added: ``Shortlist_Recall`` (percent of
     queries whose ground truth reached the list) and ``Rerank_Depth``.  Unless ``Shortlist_Recall`` is 100, ``MRR`` is an UPPER and
     ``Mean_Rank`` a LOWER bound of the pipeline's value: a query whose ground truth missed the list counts with rank
-    ``rerank_depth + 1``, the best it could have."""
+    ``rerank_depth + 1``, the best it could have.
+
+    ``text2sparql_results`` (query uuid -> listed URIs, with ``rerank_depth``): the knowledge-fused rerank.  The bonus comes from
+    ``sparql_fusion.sparql_bonus(text2sparql_results, uuids, uuids, fusion_strategy, fusion_params)``; its ``clip_scale`` becomes
+    the ``head_weight`` of ``FusionModel.rerank(bonus=...)``: hits join the shortlist wherever CLIP ranks them and the list is
+    ranked by ``head_weight * head + bonus``.  ``Head_Weight`` and ``SPARQL_Strategy`` are added to the result."""
+    if text2sparql_results is not None and rerank_depth is None:
+        raise ValueError(_SPARQL_NEEDS_RERANK)
     if rerank_depth is not None:
         _check_rerank_depth(fusion_model.fusion_type, int(rerank_depth))
     fusion_model.eval()
-    image, query, target, _ = encode_dataset(fusion_model.clip_model, dataset, batch_size, seed, num_workers, tokenize_fn)
+    image, query, target, uuids = encode_dataset(fusion_model.clip_model, dataset, batch_size, seed, num_workers, tokenize_fn)
     from . import ranking
     if rerank_depth is None:
         ranks, _, _ = fusion_model.rank(query, image, target, k=0)
         result = ranking.metrics_from_ranks(ranks, [1, 5, 10, 20])
     else:
         depth = int(rerank_depth)
-        ranks = fusion_model.rerank(query, fusion_model.prepare_gallery(image, target), depth=depth, k=1, gt_idx="diag")[0]
+        fused = {}
+        if text2sparql_results is not None:
+            from . import sparql_fusion
+            head_weight, bonus = sparql_fusion.sparql_bonus(text2sparql_results, uuids, uuids, fusion_strategy, fusion_params)
+            fused = {"bonus": bonus, "head_weight": head_weight}
+        ranks = fusion_model.rerank(query, fusion_model.prepare_gallery(image, target), depth=depth, k=1, gt_idx="diag", **fused)[0]
         result = ranking.metrics_from_ranks(ranks, [1, 5, 10, 20])
         result["Shortlist_Recall"] = float((ranks <= depth).double().mean().item() * 100.0)
         result["Rerank_Depth"] = depth
+        if fused:
+            result["Head_Weight"] = float(fused["head_weight"])
+            result["SPARQL_Strategy"] = fusion_strategy
     logger.info("Fusion Model Evaluation Results")
     for k, v in result.items():
-        logger.info(f"{k}: {v:.2f}" + ("%" if ("R@" in k or "MRR" in k or "Recall" in k) else ""))
+        logger.info(f"{k}: {v}" if isinstance(v, str) else f"{k}: {v:.2f}" + ("%" if ("R@" in k or "MRR" in k or "Recall" in k) else ""))
     return result
 
 
@@ -475,6 +496,11 @@ def fusion_parser() -> argparse.ArgumentParser:
     parser.add_argument("--rerank_depth", type=_rerank_depth_arg, default=None, metavar="N",
                         help=f"linear / cross_attention heads: retrieve-then-rerank over every query's N ({RERANK_DEPTH_MIN}..{_lib.MAX_DEEP_K}) "
                              "best candidates by the fused T2I + T2T score instead of the head on every pair")
+    parser.add_argument("--sparql_results", type=str, default=None, metavar="DIR",
+                        help="with --rerank_depth: directory of Text2SPARQL result files (load_text2sparql_results); the hits join the "
+                             "shortlist and the list is ranked by head_weight * head + bonus")
+    parser.add_argument("--sparql_strategy", type=str, default="weighted", choices=["weighted", "additive", "adaptive"],
+                        help="how --sparql_results become a bonus (sparql_fusion.sparql_bonus); its clip_scale is the head's weight")
     return parser
 
 
@@ -485,6 +511,14 @@ def main_fusion(argv=None):
     if args.rerank_depth is not None and args.fusion_type not in ("linear", "cross_attention"):
         parser.error(f"--rerank_depth is for the linear and cross_attention heads; the {args.fusion_type} head ranks the whole "
                      "gallery in one fused pass already")
+    if args.sparql_results is not None:
+        if args.fusion_type not in ("linear", "cross_attention"):
+            parser.error(f"--sparql_results is for the linear and cross_attention heads (with --rerank_depth); the {args.fusion_type} head "
+                         "folds into the fused similarity pass: fuse its ranking with sparql_fusion.fused_ranks")
+        if args.rerank_depth is None:
+            parser.error("--sparql_results needs --rerank_depth: " + _SPARQL_NEEDS_RERANK)
+    elif args.sparql_strategy != "weighted":
+        parser.error("--sparql_strategy has no effect without --sparql_results DIR")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     from . import clip_api, tokenizer
     from .clip_model import load_clip_model
@@ -504,7 +538,9 @@ def main_fusion(argv=None):
         from datasets import load_dataset
         ds = load_dataset(args.dataset)
         dataset = CLIPEvalDatasetHF(ds[{"val": "validation"}.get(args.split, args.split)], preprocess, args.max_text_length)
-    result = evaluate_fusion_model(fusion_model, dataset, args.batch_size, args.device, rerank_depth=args.rerank_depth)
+    t2s = load_text2sparql_results(args.sparql_results) if args.sparql_results is not None else None
+    result = evaluate_fusion_model(fusion_model, dataset, args.batch_size, args.device, rerank_depth=args.rerank_depth,
+                                   text2sparql_results=t2s, fusion_strategy=args.sparql_strategy)
     results = {"model_name": args.model_name, "clip_checkpoint": args.clip_checkpoint,
                "fusion_checkpoint": args.fusion_checkpoint, "fusion_type": args.fusion_type, "split": args.split,
                "num_samples": len(dataset), "metrics": result,

@@ -20,7 +20,9 @@ inactive) and maps onto the fused similarity kernel:
 ``rank()`` gives ranks / top-k without ever forming the [N,M] matrix for the gated family and bilinear; linear and
 cross_attention produce the dense matrix on the GPU and rank it with ``kemr_rank_dense``.  ``prepare_gallery()`` + ``rerank()`` are
 the two-stage route for those two heads: a deep shortlist by the fused T2I + T2T score, the head on the listed pairs only
-(``kemr_cross_attention_rerank``; ``kemr_pair_scores`` + ``kemr_linear_head``), sorted by ``kemr_select_topk``.
+(``kemr_cross_attention_rerank``; ``kemr_pair_scores`` + ``kemr_linear_head``), sorted by ``kemr_select_topk``.  With ``bonus=`` the
+knowledge side rides along: the SPARQL bonus joins the shortlist score and ``kemr_list_fuse`` ranks the list by
+``head_weight * head + bonus``.
 """
 from __future__ import annotations
 
@@ -322,11 +324,15 @@ class FusionModel(nn.Module):
         return HeadGallery(self, image_embed, target_embed)
 
     @torch.no_grad()
-    def shortlist(self, q: torch.Tensor, gallery_panel: engine.Panel, depth: int, shortlist_weights=(0.5, 0.5)) -> torch.Tensor:
+    def shortlist(self, q: torch.Tensor, gallery_panel: engine.Panel, depth: int, shortlist_weights=(0.5, 0.5), bonus=None) -> torch.Tensor:
         """Stage one: the ``depth`` best candidates of every query by w_i * T2I + w_t * T2T against a ``[image ; target]`` gallery
-        panel -- the ids (int32 [N, depth], -1 padded) of ``ranking.ranks_and_topk_deep([q, q], [img, tgt], weights, k=depth)``."""
+        panel -- the ids (int32 [N, depth], -1 padded) of ``ranking.ranks_and_topk_deep([q, q], [img, tgt], weights, k=depth)``.
+        ``bonus`` (CSR, as ``engine.sim_topk_deep`` takes it) is added to that score before the cut, so a hit reaches the list
+        wherever CLIP alone ranks it."""
         qp = engine.build_panel([q, q], _lib.SIDE_QUERY, gallery_panel.terms, part_scale=list(shortlist_weights))
-        return engine.sim_topk_deep(qp, gallery_panel, depth)[1]
+        if bonus is None:
+            return engine.sim_topk_deep(qp, gallery_panel, depth)[1]
+        return engine.sim_topk_deep(qp, gallery_panel, depth, bonus=bonus)[1]
 
     @torch.no_grad()
     def list_scores(self, q: torch.Tensor, gallery: HeadGallery, list_idx: torch.Tensor) -> torch.Tensor:
@@ -362,8 +368,36 @@ class FusionModel(nn.Module):
         return ranks, order_s[:, :k].contiguous(), order_i[:, :k].contiguous(), scores, list_idx
 
     @torch.no_grad()
+    def _rerank_lists_fused(self, q: torch.Tensor, gallery: HeadGallery, list_idx: torch.Tensor, k: int, gt: Optional[torch.Tensor],
+                            bonus, head_weight: float):
+        """``_rerank_lists`` with the knowledge side: ``head_weight * head + bonus`` on the listed pairs, the ground truth's place in
+        the fused list and ``found`` in the same kernel (``engine.list_fuse``), the top-k by ``engine.select_topk``."""
+        depth = list_idx.shape[1]
+        scores = self.list_scores(q, gallery, list_idx)
+        fused, ahead, found, gt_score = engine.list_fuse(scores, list_idx, depth, head_weight, bonus, gt, out=scores)
+        top_s, top_i = engine.select_topk(fused, k, idx=list_idx)
+        if gt is None:
+            return None, top_s, top_i, fused, list_idx
+        present = found != 0
+        ranking._require_finite(gt_score[present], "fused scores at the ground truth")
+        ranks = torch.where(present, ahead.long() + 1, torch.full_like(ahead, depth + 1, dtype=torch.int64))
+        return ranks, top_s, top_i, fused, list_idx
+
+    @staticmethod
+    def _check_bonus(bonus, n: Optional[int], what: str):
+        """A bonus CSR ``(rowptr [n + 1], col, val)`` as the kernels take it, checked on the host before anything is launched
+        (``n`` None: the row count is not known yet)."""
+        if not isinstance(bonus, (tuple, list)) or len(bonus) != 3:
+            raise ValueError(f"{what}: bonus must be the CSR triple (rowptr, col, val)")
+        if n is not None and len(bonus[0]) != n + 1:
+            raise ValueError(f"{what}: the bonus row pointer must have {n + 1} entries (one row per query), got {len(bonus[0])}")
+        if len(bonus[1]) != len(bonus[2]):
+            raise ValueError(f"{what}: bonus col and val must have one entry per hit")
+        return tuple(bonus)
+
+    @torch.no_grad()
     def rerank(self, query_embed, gallery: HeadGallery, depth: int = 200, k: int = 10, gt_idx=None, cand_idx=None,
-               shortlist_weights=(0.5, 0.5)):
+               shortlist_weights=(0.5, 0.5), bonus=None, head_weight: float = 1.0, shortlist_bonus: bool = True):
         """Retrieve-then-rerank with the ``linear`` or ``cross_attention`` head: cut a shortlist of ``depth`` candidates per query
         with the fused score ``w_i * T2I + w_t * T2T`` (``shortlist_weights``; one pass of ``engine.sim_topk_deep`` over the
         gallery's fused panel), score only those pairs with the head, sort them (score descending, then lower id).
@@ -375,8 +409,19 @@ class FusionModel(nn.Module):
         without ``gt_idx``; otherwise int64 [N]: the ground truth's 1-based position in the reranked list, or ``depth + 1`` where
         the shortlist does not hold it -- a LOWER BOUND of the rank the head would give it over the whole gallery.  A rank
         <= depth is the exact rank of the two-stage pipeline, so Recall@K is exact for every K <= depth.  Linear scores are
-        bit-identical to ``forward()[q, ids]``; cross_attention scores agree with it to fp32 rounding (``include/kemr.h``)."""
+        bit-identical to ``forward()[q, ids]``; cross_attention scores agree with it to fp32 rounding (``include/kemr.h``).
+
+        ``bonus`` (CSR ``(rowptr [N + 1], col, val)``, gallery ids ascending within a row: ``sparql_fusion.sparql_bonus``,
+        ``EmbeddingStore.hits_csr``) is the knowledge-fused rerank: the shortlist is cut by the fused score PLUS the bonus (unless
+        ``shortlist_bonus=False``), so a hit reaches the list wherever CLIP ranks it; the listed pairs are scored by the head; the
+        list is ranked by ``head_weight * head + bonus`` (``kemr_list_fuse``: one fp32 multiply, the bonus entries added in list
+        order).  ``list_scores`` then holds the fused scores and ``ranks`` the ground truth's place in the fused list.  Without
+        ``bonus`` the call is the plain rerank, and ``head_weight`` must be left at 1."""
         self._require_rerank_head("rerank")
+        if bonus is None and float(head_weight) != 1.0:
+            raise ValueError("rerank: head_weight scales the head against a bonus; without bonus it must stay 1.0")
+        if bonus is not None:
+            bonus = self._check_bonus(bonus, None, "rerank")
         depth, k = int(depth), int(k)
         if not 1 <= depth <= _lib.MAX_DEEP_K:
             raise ValueError(f"rerank: depth={depth} not in 1..{_lib.MAX_DEEP_K}")
@@ -386,8 +431,10 @@ class FusionModel(nn.Module):
             raise ValueError("rerank: gallery must come from this model's prepare_gallery()")
         q = ranking.to_device_f32(query_embed, gallery.device)
         n, m = q.shape[0], len(gallery)
+        if bonus is not None:
+            bonus = self._check_bonus(bonus, n, "rerank")
         if cand_idx is None:
-            list_idx = self.shortlist(q, gallery.fused_panel, depth, shortlist_weights)
+            list_idx = self.shortlist(q, gallery.fused_panel, depth, shortlist_weights, bonus if shortlist_bonus else None)
         else:
             list_idx = torch.as_tensor(cand_idx)
             if list_idx.dtype != torch.int32 or tuple(list_idx.shape) != (n, depth):
@@ -404,4 +451,6 @@ class FusionModel(nn.Module):
                 else torch.as_tensor(gt_idx).to(device=q.device, dtype=torch.int32).reshape(-1)
             if gt.numel() != n or bool(((gt < 0) | (gt >= m)).any()):
                 raise ValueError("rerank: gt_idx must hold one gallery id per query")
+        if bonus is not None:
+            return self._rerank_lists_fused(q, gallery, list_idx, k, gt, bonus, float(head_weight))
         return self._rerank_lists(q, gallery, list_idx, k, gt)

@@ -201,6 +201,35 @@ class CLIPRetriever:
         scores, idx = scores[0].cpu().tolist(), idx[0].cpu().tolist()
         return [{"uuid": self.store.uuids[i], "score": float(s)} for s, i in zip(scores, idx) if i >= 0]
 
+    @torch.no_grad()
+    def search_batch_reranked_fused(self, queries: Sequence[str], hits_per_query: Sequence[Sequence[str]], fusion_model, gallery,
+                                    depth: int = 200, top_k: int = 10, head_weight: float = 0.8, hit_bonus: float = 0.2):
+        """``search_batch_reranked`` with the knowledge graph kept (``FusionModel.rerank(bonus=...)``): text tower -> the ``depth``
+        best of the store's fused panel by 0.5 * <q, image_i> + 0.5 * <q, text_i> + hit_bonus * [uuid_i in hits], so a hit reaches
+        the list wherever CLIP ranks it -> the head on those pairs -> ``head_weight * head + hit_bonus * [uuid_i in hits]``
+        (``engine.list_fuse``) -> its ``top_k`` best, ``(scores [Q, top_k], ids [Q, top_k])`` with the fused scores."""
+        if not 1 <= depth <= MAX_DEEP_TOP_K:
+            raise ValueError(f"depth must be in 1..{MAX_DEEP_TOP_K}")
+        if not 1 <= top_k <= depth:
+            raise ValueError(f"top_k must be in 1..depth={depth}")
+        if len(hits_per_query) != len(queries):
+            raise ValueError("search_batch_reranked_fused: one hit list per query")
+        fusion_model._require_rerank_head("search_batch_reranked_fused")
+        if len(gallery) != len(self.store):
+            raise ValueError(f"the prepared gallery has {len(gallery)} candidates, the store {len(self.store)}")
+        bonus = self.store.hits_csr(hits_per_query, hit_bonus)
+        ids = self.tokenize_fn(list(queries))
+        q = self.model.encode_text(ids, normalize=True)
+        list_idx = fusion_model.shortlist(q, self.store.panel, depth, bonus=bonus)
+        _, top_s, top_i, _, _ = fusion_model._rerank_lists_fused(q, gallery, list_idx, top_k, None, bonus, float(head_weight))
+        return top_s, top_i
+
+    def search_reranked_fused(self, query: str, hits: Sequence[str], fusion_model, gallery, depth: int = 200, top_k: int = 10,
+                              head_weight: float = 0.8, hit_bonus: float = 0.2) -> List[Dict]:
+        scores, idx = self.search_batch_reranked_fused([query], [hits], fusion_model, gallery, depth, top_k, head_weight, hit_bonus)
+        scores, idx = scores[0].cpu().tolist(), idx[0].cpu().tolist()
+        return [{"uuid": self.store.uuids[i], "score": float(s)} for s, i in zip(scores, idx) if i >= 0]
+
 
 class CLIPRetrieval:
     """``CLIPRetrieval(model_name=None).retrieval(query, alpha=0.5)`` (reference src/clip/clip_retrieval.py:10-40),
@@ -221,6 +250,13 @@ class CLIPRetrieval:
                         depth: int = 200):
         """The ``depth`` best by the fused score ``clip_weight * clip + hit_bonus * [uuid in hits]`` over the whole gallery."""
         return self.retriever.search_fused(query, hits, alpha=alpha, clip_weight=clip_weight, hit_bonus=hit_bonus, top_k=depth)
+
+    def retrieval_reranked_fused(self, query: str, hits: Sequence[str], fusion_model, gallery, head_weight: float = 0.8,
+                                 hit_bonus: float = 0.2, depth: int = 200):
+        """The ``depth`` best by ``head_weight * head + hit_bonus * [uuid in hits]``, the trained head scored on a shortlist that
+        the hits are part of (``CLIPRetriever.search_reranked_fused``)."""
+        return self.retriever.search_reranked_fused(query, hits, fusion_model, gallery, depth=depth, top_k=depth,
+                                                    head_weight=head_weight, hit_bonus=hit_bonus)
 
 
 class NoText2SPARQL:
@@ -275,6 +311,18 @@ class RetrievalEngine:
         descending, then gallery row), cut at ``threshold``.  (This build's addition; the reference has no counterpart.)"""
         t2s_results = self.t2s_retriever.retrieval(query)
         fused = self.clip_retriever.retrieval_fused(query, t2s_results, alpha=alpha_clip, clip_weight=alpha, hit_bonus=beta, depth=depth)
+        return [{"uuid": it["uuid"], "score": round(it["score"], 4)} for it in fused if round(it["score"], 4) >= threshold]
+
+    def retrieve_text_reranked(self, query: str, fusion_model, gallery, alpha: float = 0.8, beta: float = 0.2, threshold: float = 0,
+                               depth: int = 200):
+        """``retrieve_text_fused`` with a trained ``linear`` / ``cross_attention`` head in CLIP's place: the SPARQL retriever is
+        asked first, its hits join the ``depth``-deep shortlist wherever CLIP ranks them, the head scores the listed pairs and the
+        list is ordered by ``alpha * head + beta * [uuid in sparql]``.  ``gallery``: ``fusion_model.prepare_gallery(store.image,
+        store.text)``.  ``{"uuid", "score": round(score, 4)}`` in the kernel's order, cut at ``threshold``.  (This build's
+        addition; the reference has no counterpart.)"""
+        t2s_results = self.t2s_retriever.retrieval(query)
+        fused = self.clip_retriever.retrieval_reranked_fused(query, t2s_results, fusion_model, gallery, head_weight=alpha,
+                                                             hit_bonus=beta, depth=depth)
         return [{"uuid": it["uuid"], "score": round(it["score"], 4)} for it in fused if round(it["score"], 4) >= threshold]
 
     def retrieve_text_noknowledge(self, query: str, alpha: float = 0.8, beta: float = 0.2, alpha_clip: float = 0.5,

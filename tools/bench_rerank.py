@@ -1,6 +1,6 @@
 """Retrieve-then-rerank timings (tools only): the cross_attention head on deep shortlists against the dense route, in one process.
 
-    python tools/bench_rerank.py [--out profiles/rerank_bench.txt] [--calls 12] [--only offline|online]
+    python tools/bench_rerank.py [--out profiles/rerank_bench.txt] [--calls 12] [--only offline|online|fused]
 
 offline  N = M = 4 096, dim 768, a cross_attention head with seeded random parameters:
   dense        FusionModel.rank(q, img, tgt, k=10): the head on all N x M pairs, then kemr_rank_dense
@@ -9,6 +9,11 @@ offline  N = M = 4 096, dim 768, a cross_attention head with seeded random param
   kernel_d*    engine.cross_attention_rerank alone on those lists (the gathered pair-scoring kernel)
   shortlist_d* the shortlist stage alone (query panel + engine.sim_topk_deep)
   prepare      FusionModel.prepare_gallery(img, tgt): once per gallery, timed apart
+fused    N = M = 4 096, depth 200, gt_idx given, a bonus of ~50 hits per query (knowledge-fused rerank):
+  rerank_ms        FusionModel.rerank(q, gallery, depth=200, k=10, gt_idx="diag"): the plain ranked rerank, for comparison
+  fused_rerank_ms  the same call with bonus=..., head_weight=0.8: shortlist with bonus + head + kemr_list_fuse + kemr_select_topk
+  list_fuse_ms     engine.list_fuse alone on those lists (scale + bonus + ranks), select_ms: engine.select_topk(k=10) on them,
+  shortlist*_ms    the shortlist stage with and without the bonus, head_ms: FusionModel.list_scores on the lists
 online   nq = 1, M = 43 000, depth 200, k = 10: the whole rerank call behind the text tower, its kernel and its shortlist stage.
 hipEvents around every call, median of >= 10 calls after >= 100 ms (and 3 calls) of warm-up; per-pair times are the median
 divided by the pairs the route scores.  One JSON line per case.
@@ -77,6 +82,34 @@ def rerank_legs(fm, gal, q, depth, calls):
             "kernel_gathered_TB_per_s": gathered / (kern * 1e-3) / 1e12}
 
 
+def fused_legs(fm, gal, q, depth, hits, calls):
+    """The knowledge-fused route beside the plain ranked rerank at the same shape, and where its time goes."""
+    import numpy as np
+    n, m = q.shape[0], len(gal)
+    rng = np.random.default_rng(11)
+    cols = np.sort(rng.integers(0, m, (n, hits)), axis=1).astype(np.int32)
+    dev = q.device
+    bonus = (torch.arange(0, n * hits + 1, hits, dtype=torch.int32, device=dev), torch.from_numpy(cols.reshape(-1)).to(dev),
+             torch.full((n * hits,), 0.2, dtype=torch.float32, device=dev))
+    gt = torch.arange(n, dtype=torch.int32, device=dev)
+    lists = fm.shortlist(q, gal.fused_panel, depth, bonus=bonus)
+    scores = fm.list_scores(q, gal, lists)
+    out = torch.empty_like(scores)
+    res = {"depth": depth, "pairs": n * depth, "bonus_hits_per_query": hits,
+           "rerank_ms": timed(lambda: fm.rerank(q, gal, depth=depth, k=10, gt_idx="diag"), calls),
+           "fused_rerank_ms": timed(lambda: fm.rerank(q, gal, depth=depth, k=10, gt_idx="diag", bonus=bonus, head_weight=0.8), calls),
+           "list_fuse_ms": timed(lambda: engine.list_fuse(scores, lists, depth, 0.8, bonus, gt, out=out), calls),
+           "select_ms": timed(lambda: engine.select_topk(out, 10, idx=lists), calls),
+           "select_depth_ms": timed(lambda: engine.select_topk(out, depth, idx=lists), calls),
+           "head_ms": timed(lambda: fm.list_scores(q, gal, lists), calls),
+           "shortlist_ms": timed(lambda: fm.shortlist(q, gal.fused_panel, depth), calls),
+           "shortlist_bonus_ms": timed(lambda: fm.shortlist(q, gal.fused_panel, depth, bonus=bonus), calls)}
+    res["list_fuse_MB"] = (3 * n * depth * 4 + bonus[1].numel() * 8 + (n + 1) * 4 + 4 * n * 4) / 1e6
+    res["list_fuse_GB_per_s"] = res["list_fuse_MB"] / res["list_fuse_ms"]
+    res["fused_over_plain"] = res["fused_rerank_ms"] / res["rerank_ms"]
+    return res
+
+
 def rounded(res):
     return {key: (round(v, 4) if isinstance(v, float) else v) for key, v in res.items()}
 
@@ -88,7 +121,7 @@ def main():
     ap.add_argument("--n", type=int, default=4096, help="offline: queries = candidates")
     ap.add_argument("--ng", type=int, default=43000, help="online: gallery size")
     ap.add_argument("--d", type=int, default=768)
-    ap.add_argument("--only", default=None, choices=["offline", "online"])
+    ap.add_argument("--only", default=None, choices=["offline", "online", "fused"])
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     fm = head(args.d, dev)
@@ -116,6 +149,13 @@ def main():
                         # with the same candidates ahead of it or fewer: a listed ground truth never ranks behind its dense rank
                         "listed_ranks_le_dense": bool((ranks[listed] <= d_ranks[listed]).all())})
             emit(res)
+        del gal
+    if args.only in (None, "fused"):
+        q, img, tgt = embeddings(args.n, args.n, args.d, dev)
+        gal = fm.prepare_gallery(img, tgt)
+        res = {"case": "offline_fused_rerank_d200", "nq": args.n, "ng": args.n, "dim": args.d}
+        res.update(fused_legs(fm, gal, q, 200, 50, args.calls))
+        emit(res)
         del gal
     if args.only in (None, "online"):
         q, img, tgt = embeddings(args.ng, 1, args.d, dev)
