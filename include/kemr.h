@@ -40,7 +40,8 @@ extern "C" {
  *    Still 4: kemr_select_topk, kemr_sim_topk_deep, kemr_sim_topk_deep_workspace_bytes and kemr_sim_topk_deep_fused are additions, no
  *    existing entry point changed.  Option "activation" of kemr_model_set_option / kemr_model_get_option and the epilogue value
  *    KEMR_EPI_BIAS_GELU_BF16 (kemr_op_gemm, kemr_op_gemm_fp8) are additions as well: the default, 0, is the QuickGELU every existing
- *    caller gets; no entry point was added. */
+ *    caller gets; no entry point was added.  Still 4: option "vision_head_dim" (64, the default every existing caller gets, or 80: the
+ *    vision tower of ViT-H-14) and the entry points kemr_op_attention_hd / kemr_op_attention_x3_hd are additions; kemr_cfg did not grow. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -88,7 +89,8 @@ typedef enum kemr_dtype { KEMR_F32 = 0, KEMR_BF16 = 1, KEMR_I32 = 2, KEMR_FP8 = 
  *                         fp32 (option "residual_stream_24bit" has no effect; its stored value is still what get_option returns),
  *                         q | k | v are fp32, the LayerNorm outputs, the attention output and the MLP hidden are A-side triples;
  *                       - the out-proj and fc2 epilogues add acc + bias into the stream in fp32 (option "residual_fusion" has no
- *                         meaning here); the attention scale 1/8 stays folded into W_q and b_q (exact);
+ *                         meaning here); the attention scale 1/8 stays folded into W_q and b_q (exact; at "vision_head_dim" 80 the
+ *                         vision tower's 1/sqrt(80) is applied in fp32 before the split);
  *                       - attention splits Q, K, V and P into pairs and contracts with the same three products; LayerNorm
  *                         statistics, softmax, QuickGELU and the erfc-form GELU are fp32 arithmetic as in every mode; option
  *                         "activation" works as in every mode;
@@ -107,7 +109,8 @@ typedef enum kemr_tower { KEMR_TOWER_VISION = 0, KEMR_TOWER_TEXT = 1 } kemr_towe
 #define KEMR_MAX_VISION_TOKENS 1025
 #define KEMR_MAX_TEXT_CTX 288
 
-/* Architecture numbers of an OpenAI-CLIP style model (heads are width/64, MLP is 4*width).
+/* Architecture numbers of an OpenAI-CLIP style model (MLP is 4*width; heads are width/64, except a vision tower under option
+ * "vision_head_dim" = 80, whose heads are v_width/80: OpenCLIP's ViT-H-14 {1024,224,14,1280,32,1024,24,49408,77}).
  * ViT-L/14: {768,224,14,1024,24,768,12,49408,77}; ViT-L/14@336px: {768,336,14,1024,24,768,12,49408,77};
  * ViT-B/32: {512,224,32,768,12,512,12,49408,77}. */
 typedef struct kemr_cfg {
@@ -132,7 +135,8 @@ int kemr_abi_version(void);
  * strict=True)` (reference: src/clip/model/clip_model.py:41-64).
  *   create -> load_tensor (once per state-dict entry, OpenAI-CLIP names, fp32 host memory)
  *          -> finalize (checks every required tensor is present = "strict", packs bf16 weights
- *             into device memory: q-scale folded into W_q, conv1 flattened/padded to a GEMM panel)
+ *             into device memory: the q-scale 1/sqrt(head dim) folded into W_q and b_q in fp32 before the rounding -- 1/8 for
+ *             heads of 64, exact --, conv1 flattened/padded to a GEMM panel)
  *   load_tensor may be called again after finalize (fine-tuned checkpoint): call finalize again.
  * ------------------------------------------------------------------------------------------- */
 int kemr_model_create(const kemr_cfg* cfg, kemr_model** out);
@@ -162,7 +166,13 @@ int kemr_model_destroy(kemr_model* m);
  *                      OpenAI checkpoints were trained with; 1 exact GELU 0.5 x (1 + erf(x / sqrt 2)) = torch.nn.GELU(), what the
  *                      OpenCLIP / LAION ViT-B/32, B/16 and L/14 checkpoints and Hugging Face configs with hidden_act "gelu" use.
  *                      It selects the epilogue of the fc1 GEMMs (bf16 and fp8 operands, the pooled-row last block) and nothing
- *                      else; the weights are not touched, so it may be flipped between encode calls without a finalize. */
+ *                      else; the weights are not touched, so it may be flipped between encode calls without a finalize.
+ *   "vision_head_dim"  (set BEFORE kemr_model_finalize) the head dim of the VISION tower: 64 (default) or 80, which needs v_width % 80 == 0
+ *                      (1280 = 16 heads of 80: OpenCLIP / LAION ViT-H-14; the text tower keeps heads of 64).  Finalize then folds
+ *                      1/sqrt(80) instead of 1/8 into the vision tower's query rows and the encoders run the head-dim-80 attention
+ *                      kernels (csrc/attention80.hip).  Refused at finalize with 80: the fp8 precisions, and vision towers of more than
+ *                      288 tokens (the streaming attention kernel serves heads of 64 only).  Not served at all: ViT-g / bigG (head dim
+ *                      88 / widths that are no multiple of 256, MLP not 4 x width), SigLIP. */
 int kemr_model_set_option(kemr_model* m, const char* key, int value);
 int kemr_model_get_option(const kemr_model* m, const char* key, int* value);
 /* number of required tensor names; name i via kemr_model_tensor_name (for strict-load diagnostics) */
@@ -440,9 +450,12 @@ int kemr_op_layernorm_resid(float* x_dev, const void* delta_dev, const float* ga
 int kemr_op_layernorm_rows(void* x_dev, int x_dtype, const void* delta_dev, const void* delta2_dev, int writeback,
                            const float* gamma_dev, const float* beta_dev, void* y_dev, int rows, int width, int out_dtype,
                            void* stream);
-/* qkv bf16 [batch*t, 3*width] (q pre-scaled by 1/8) -> out bf16 [batch*t, width]; t <= 288, or non-causal
+/* qkv bf16 [batch*t, 3*width] (heads of 64; q pre-scaled by 1/sqrt(64) = 1/8) -> out bf16 [batch*t, width]; t <= 288, or non-causal
  * t <= KEMR_MAX_VISION_TOKENS (streaming kernel); longer causal sequences are KEMR_ERR_INVALID */
 int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, int t, int width, int causal, void* stream);
+/* the same with the head dim an argument: 64 = kemr_op_attention; 80 (q pre-scaled by 1/sqrt(80), width % 80 == 0): non-causal, t <= 288.
+ * A width that is no multiple of the head dim, another head dim, causal or t > 288 at 80: KEMR_ERR_INVALID, nothing is launched. */
+int kemr_op_attention_hd(const void* qkv_dev, void* out_dev, int batch, int t, int width, int head_dim, int causal, void* stream);
 /* The kernels of KEMR_PREC_FP32X3.  Panels are what kemr_panel_build(nparts = 1, terms = 3, side) builds: bf16 [ceil256(rows), 3 ceil64(d)],
  * KEMR_SIDE_QUERY = the A side [hi | lo | hi], KEMR_SIDE_GALLERY = the W side [hi | hi | lo].
  * layernorm_x3: x fp32 [rows, width] -> y_panel, the A-side triple of kemr_op_layernorm(..., KEMR_F32)'s output, bit for bit;
@@ -454,12 +467,16 @@ int kemr_op_layernorm_x3(const float* x_dev, const float* gamma_dev, const float
  *   quick_gelu(acc + bias) / gelu(acc + bias), the activation in fp32 (rows m .. are not written).  One kernel family: 128 x 128 tiles. */
 int kemr_op_gemm_x3(const void* a_panel_dev, const void* w_panel_dev, const float* bias_dev, void* c_dev, int m, int n, int k3,
                     int mode /*0 store f32, 1 add into f32 C, 2 quick_gelu -> triple, 3 gelu -> triple*/, void* stream);
-/* attention_x3: qkv fp32 [rows, 3 width] (q pre-scaled by 1/8; heads of 64) -> out_panel, the A-side triple [rows, 3 width] bf16 of
+/* attention_x3: qkv fp32 [rows, 3 width] (q pre-scaled by 1/sqrt(head dim) = 1/8; heads of 64) -> out_panel, the A-side triple [rows, 3 width] bf16 of
  *   softmax(q k^T) v; rows of the panel that hold no query are not written.  row_start == NULL: batch items of t rows each, t <=
  *   KEMR_MAX_VISION_TOKENS non-causal, t <= KEMR_MAX_TEXT_CTX causal.  row_start (device int32 [batch + 1], causal only): packed
  *   items, item b = rows row_start[b] .. row_start[b + 1] - 1, at most t of them.  Same bits on every launch. */
 int kemr_op_attention_x3(const float* qkv_dev, void* out_panel_dev, const int* row_start_dev, int batch, int t, int width, int causal,
                          void* stream);
+/* attention_x3 with the head dim an argument: 64 = kemr_op_attention_x3; 80: non-causal, row_start NULL, t <= 288 (d padded to 96 with
+ *   zeros the kernel makes, 5 output d-tiles; same three-product convention, same bits on every launch); else KEMR_ERR_INVALID. */
+int kemr_op_attention_x3_hd(const float* qkv_dev, void* out_panel_dev, const int* row_start_dev, int batch, int t, int width,
+                            int head_dim, int causal, void* stream);
 
 #ifdef __cplusplus
 }

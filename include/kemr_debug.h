@@ -41,6 +41,8 @@ extern "C" {
  *   "attn_waves"    [A/B] waves per workgroup at T = 257: 0 = default (4 for attn_v 0, 16 for attn_v 3), 6 (attn_v 0), 8 (attn_v 3);
  *                   2 (attn_v 0) = the build with s_memtime stamps, which writes 8 counters per wave BEHIND the output
  *                   (tools/prof_attention.py allocates the room; nothing else may select it)
+ *   "attn80_waves"  waves per workgroup of the head-dim-80 attention kernel at T = 257 (csrc/attention80.hip): 0 or 8 = eight (two per
+ *                   SIMD, the default), 4 = four (one per SIMD); both instantiations are in the product library, same results bit for bit
  *   "sim_lists"     kemr_sim_topk: 0 = never the candidate-list route (nor the fast rank pass for bonus lists), 1 = where it pays
  *                   (default: from 2 048 gallery rows, 256 queries and 1.2e10 multiply-adds up), 3 = wherever it fits, 2 = as 3 and
  *                   the exact fallback forced to run after the lists
@@ -72,6 +74,12 @@ int kemr_debug_op_attention_packed(const void* qkv_dev, void* out_dev, const int
  * 1088-key instantiation even for tokens <= 320 */
 int kemr_debug_op_attention_pooled(const void* q_dev, const void* qkv_dev, void* out_dev, const int* pool_idx_dev,
                                    const int* row_start_dev, int items, int tokens, int width, int causal, int force_long, void* stream);
+/* the same with the head dim an argument: 64 = the call above; 80 (q pre-scaled by 1/sqrt(80), width a multiple of 80): the vision form
+ * only -- causal 0, pool_idx_dev, row_start_dev NULL, force_long 0, tokens <= 288; anything else, and any other head dim, is
+ * KEMR_ERR_INVALID and launches nothing */
+int kemr_debug_op_attention_pooled_hd(const void* q_dev, const void* qkv_dev, void* out_dev, const int* pool_idx_dev,
+                                      const int* row_start_dev, int items, int tokens, int width, int head_dim, int causal, int force_long,
+                                      void* stream);
 /* the pooling tail: x rows of x_dtype (KEMR_F32, KEMR_BF16 or 24 = the 24-bit rows of the residual stream, W bf16 upper halves
  * then W third bytes per row) [+ delta [+ delta2]] (bf16, may be NULL) at the pooled row -- b * tokens (ids NULL) or the first
  * arg-max of ids [batch, tokens], inside row_start's rows when given (clamped to the item's last row) -- LayerNorm(gamma, beta)

@@ -100,9 +100,11 @@ SIGNATURES = {
     "kemr_op_layernorm_resid": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "kemr_op_layernorm_rows": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "kemr_op_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "kemr_op_attention_hd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "kemr_op_layernorm_x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "kemr_op_gemm_x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "kemr_op_attention_x3": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "kemr_op_attention_x3_hd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
 # include/kemr_debug.h: experiment switches and diagnostics for tools/ and tests/ (process-wide; not the product ABI)
@@ -113,6 +115,7 @@ DEBUG_SIGNATURES = {
     "kemr_debug_gemm_stamps": (_i, [_vp, _i]),
     "kemr_debug_op_attention_packed": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "kemr_debug_op_attention_pooled": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "kemr_debug_op_attention_pooled_hd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "kemr_debug_op_tail": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "kemr_debug_image_tokens": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "kemr_debug_text_tokens": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -36,7 +36,7 @@ from .config import ARCHS, get_arch
 from .preprocess import ClipPreprocess, gpu_preprocessing_enabled
 from .tokenizer import tokenize  # noqa: F401  (re-exported)
 
-_PUBLIC = ("ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px")
+_PUBLIC = ("ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px", "ViT-H-14")
 _allow_random = False
 
 

@@ -78,9 +78,9 @@ class CLIP(nn.Module):
         self.activation = check_activation(activation)
         self.arch, self.model_name = arch, name
         self.context_length, self.vocab_size = arch.ctx, arch.vocab
-        self.visual = VisionTransformer(arch.image_size, arch.patch, arch.v_width, arch.v_layers, arch.v_width // 64,
+        self.visual = VisionTransformer(arch.image_size, arch.patch, arch.v_width, arch.v_layers, arch.v_heads,
                                         arch.embed_dim, activation)
-        self.transformer = Transformer(arch.t_width, arch.t_layers, arch.t_width // 64, activation)
+        self.transformer = Transformer(arch.t_width, arch.t_layers, arch.t_heads, activation)
         self.token_embedding = nn.Embedding(arch.vocab, arch.t_width)
         self.positional_embedding = nn.Parameter(torch.empty(arch.ctx, arch.t_width))
         self.ln_final = nn.LayerNorm(arch.t_width)

@@ -56,6 +56,7 @@ struct LayerW {
 
 struct TowerW {
     int width = 0, layers = 0, tokens = 0;
+    int head_dim = 64;                              // 64, or 80 for the vision tower under option "vision_head_dim" (attention80.hip)
     std::vector<LayerW> layer;
 };
 
@@ -77,6 +78,7 @@ struct kemr_model {
     int last_pooled = 1;                            // option "last_block_pooled_row": the last block's query path on the pooled row only
     int activation = 0;                             // option "activation": 0 = QuickGELU, 1 = exact GELU (the fc1 epilogue of run_blocks)
     int x3 = 0;                                     // KEMR_PREC_FP32X3: split-bf16 operand triples, fp32 between the kernels (run_blocks_x3)
+    int v_head_dim = 64;                            // option "vision_head_dim" (before finalize): 64, or 80 (ViT-H-14: 1280 = 16 heads of 80)
     int stream24 = 1;                               // option "residual_stream_24bit" (before finalize; default on since round 4): the fp32-class stream stored in 3 bytes
     // vision
     TowerW vis;
@@ -206,8 +208,19 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
     const int fp8 = (precision == KEMR_PREC_FP8 || precision == KEMR_PREC_FP8_RES16) ? 1 : precision == KEMR_PREC_FP8_MLP ? 3 : 0;
     if (fp8 && ((m->cfg.v_width % 128) || (m->cfg.t_width % 128) || m->cfg.v_width < 256 || m->cfg.t_width < 256))
         KEMR_FAIL(KEMR_ERR_INVALID, "finalize: fp8 needs tower widths that are multiples of 128 and >= 256");
+    if (m->v_head_dim == 80) {
+        if (m->cfg.v_width % 80) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: vision_head_dim 80 needs a vision width that is a multiple of 80, got %d", m->cfg.v_width);
+        if (fp8) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: the fp8 precisions are not served at vision_head_dim 80 (the e4m3 QKV path is validated for heads of 64 only)");
+        if (m->patches + 1 > 288)
+            KEMR_FAIL(KEMR_ERR_INVALID, "finalize: vision_head_dim 80 serves towers of at most 288 tokens, this one has %d (the streaming attention kernel is head-dim-64 only)", m->patches + 1);
+    }
     for (const auto& n : m->names)
         if (!m->tensors[n].loaded) KEMR_FAIL(KEMR_ERR_STATE, "finalize: missing key '%s' (strict load)", n.c_str());
+    // the attention scale 1 / sqrt(head dim), folded into the query rows of in_proj_weight / in_proj_bias in fp32 BEFORE the values are
+    // rounded to bf16 (or split into hi and lo): exactly 0.125f for heads of 64 (a power of two: it commutes with every rounding), the
+    // fp32 nearest to 1 / sqrt(80) for the vision tower at head dim 80
+    const float v_qscale = m->v_head_dim == 80 ? (float)(1.0 / sqrt(80.0)) : 0.125f;
+    auto qscale_of = [&](const std::string& n) { return n.rfind("visual.", 0) == 0 ? v_qscale : 0.125f; };
     // KEMR_PREC_FP32X3: every matrix [N, K] is packed as the W-side triple [N, 3K] = [hi | hi | lo] (conv1 over 3 kpad); vectors stay fp32
     const bool x3 = precision == KEMR_PREC_FP32X3;
     const size_t mat_bytes = x3 ? 6 : 2;
@@ -284,12 +297,13 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
                     else d[(size_t)r * m->kpad + k] = f32_to_bf16_host(t.data[(size_t)r * kv + k]);
                 }
         } else if (x3 && is_matrix(n)) {
-            // the attention scale 1/8 in the query rows is a power of two: it commutes with the split
+            // the attention scale in the query rows: 1/8 is a power of two and commutes with the split; 1 / sqrt(80) is applied in fp32 first
             const int64_t rows = t.shape[0], cols = t.shape[1];
             const bool qkv = n.find("in_proj_weight") != std::string::npos;
+            const float qs = qscale_of(n);
             for (int64_t r = 0; r < rows; ++r)
                 for (int64_t c = 0; c < cols; ++c)
-                    put_x3((bf16_t*)dst, r, cols, c, (qkv && r < cols) ? t.data[r * cols + c] * 0.125f : t.data[r * cols + c]);
+                    put_x3((bf16_t*)dst, r, cols, c, (qkv && r < cols) ? t.data[r * cols + c] * qs : t.data[r * cols + c]);
         } else if (is_fp8_matrix(n)) {
             // e4m3 with one scale per output channel (row): scale = amax / 448; the attention scale 1/8 goes into the q rows
             const int64_t rows = t.shape[0], cols = t.shape[1];
@@ -306,15 +320,17 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
                 for (int64_t c = 0; c < cols; ++c) d[r * cols + c] = f32_to_e4m3_host(t.data[r * cols + c] * pre * as[c] / scale);
             }
         } else if (n.find("in_proj_weight") != std::string::npos) {
-            // fold the attention scale 1/sqrt(64) = 0.125 (exact in bf16) into the query rows
+            // fold the attention scale 1/sqrt(64) = 0.125 (exact in bf16; 1/sqrt(80) at vision_head_dim 80) into the query rows
             const int64_t w = t.shape[1];
+            const float qs = qscale_of(n);
             bf16_t* d = (bf16_t*)dst;
             for (int64_t i = 0; i < (int64_t)t.data.size(); ++i)
-                d[i] = f32_to_bf16_host(i < w * w ? t.data[i] * 0.125f : t.data[i]);
+                d[i] = f32_to_bf16_host(i < w * w ? t.data[i] * qs : t.data[i]);
         } else if (n.find("in_proj_bias") != std::string::npos) {
             const int64_t w = t.shape[0] / 3;
+            const float qs = qscale_of(n);
             float* d = (float*)dst;
-            for (int64_t i = 0; i < (int64_t)t.data.size(); ++i) d[i] = i < w ? t.data[i] * 0.125f : t.data[i];
+            for (int64_t i = 0; i < (int64_t)t.data.size(); ++i) d[i] = i < w ? t.data[i] * qs : t.data[i];
         } else if (is_matrix(n)) {
             bf16_t* d = (bf16_t*)dst;
             for (size_t i = 0; i < t.data.size(); ++i) d[i] = f32_to_bf16_host(t.data[i]);
@@ -355,6 +371,7 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
     };
     tower(m->vis, "visual.transformer", m->cfg.v_width, m->cfg.v_layers, m->patches + 1, fp8);
     tower(m->txt, "transformer", m->cfg.t_width, m->cfg.t_layers, m->cfg.ctx, 0);
+    m->vis.head_dim = m->v_head_dim;
     m->conv_w = H("visual.conv1.weight");
     m->cls = F("visual.class_embedding"); m->vpos = F("visual.positional_embedding");
     m->lnpre_g = F("visual.ln_pre.weight"); m->lnpre_b = F("visual.ln_pre.bias");
@@ -495,7 +512,8 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int f
             g.M = batch; g.A = w.hc; g.bias = L.bqkv; g.C = w.qc; g.ldc = W; g.N = W;
             if (fq) { g.W = (const bf16_t*)L.wqkv8; g.wscale = L.sqkv; KEMR_TRY(launch_gemm256u_fp8(g, EPI_BIAS_BF16, s)); g.wscale = nullptr; }
             else { g.W = L.wqkv; KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s)); }
-            KEMR_TRY(launch_attention_pooled(w.qc, w.big, w.ac, w.pool_idx, row_start, batch, t.tokens, W, causal, s));
+            if (t.head_dim == 80) KEMR_TRY(launch_attention80_pooled(w.qc, w.big, w.ac, batch, t.tokens, W, causal, s));
+            else KEMR_TRY(launch_attention_pooled(w.qc, w.big, w.ac, w.pool_idx, row_start, batch, t.tokens, W, causal, s));
             g.A = w.ac; g.W = L.wo; g.bias = L.bo; g.C = w.d1c;
             KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
             KEMR_TRY(launch_layernorm(w.xc, w.x_dtype, w.d1c, nullptr, 0, L.ln2_g, L.ln2_b, w.hc, batch, W, KEMR_BF16, s));
@@ -519,6 +537,7 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int f
             KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
         }
         if (row_start) KEMR_TRY(launch_attention_packed(w.big, w.h, row_start, batch, t.tokens, W, s));
+        else if (t.head_dim == 80) KEMR_TRY(launch_attention80(w.big, w.h, batch, t.tokens, W, causal, s));
         else KEMR_TRY(launch_attention(w.big, w.h, batch, t.tokens, W, causal, s));
         g.A = w.h; g.lda = W; g.W = L.wo; g.ldw = W; g.bias = L.bo; g.C = resadd ? w.x : (void*)w.delta; g.ldc = W; g.N = W; g.K = W;
         KEMR_TRY(launch_gemm(g, resadd ? epi_res : EPI_BIAS_BF16, s));
@@ -622,7 +641,8 @@ int run_blocks_x3(const TowerW& t, const WorkspaceX3& w, int M, int batch, int c
         g.M = M; g.c_rows_padded = 1;
         g.A = w.h; g.lda = 3 * W; g.W = L.wqkv; g.ldw = 3 * W; g.bias = L.bqkv; g.C = w.qkv; g.ldc = 3 * W; g.N = 3 * W; g.K = 3 * W;
         KEMR_TRY(launch_gemm_x3(g, EPI_X3_F32, s));
-        KEMR_TRY(launch_attention_x3(w.qkv, w.h, row_start, batch, t.tokens, W, causal, s));
+        if (t.head_dim == 80) KEMR_TRY(launch_attention80_x3(w.qkv, w.h, batch, t.tokens, W, causal, s));
+        else KEMR_TRY(launch_attention_x3(w.qkv, w.h, row_start, batch, t.tokens, W, causal, s));
         g.W = L.wo; g.bias = L.bo; g.C = w.x; g.ldc = W; g.N = W;
         KEMR_TRY(launch_gemm_x3(g, EPI_BIAS_RESID_F32, s));
         KEMR_TRY(launch_layernorm_x3(w.x, L.ln2_g, L.ln2_b, w.h, M, W, s));
@@ -772,6 +792,13 @@ extern "C" int kemr_model_set_option(kemr_model* m, const char* key, int value) 
         m->stream24 = value;
         return KEMR_OK;
     }
+    if (!strcmp(key, "vision_head_dim")) {
+        if (value != 64 && value != 80) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): 64 or 80, got %d", value);
+        if (m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "model_set_option(vision_head_dim): set it before kemr_model_finalize");
+        if (m->cfg.v_width % value) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): the vision width %d is not a multiple of %d", m->cfg.v_width, value);
+        m->v_head_dim = value;
+        return KEMR_OK;
+    }
     if (!strcmp(key, "last_block_pooled_row")) {
         if (value < 0 || value > 1) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(last_block_pooled_row): 0 or 1, got %d", value);
         m->last_pooled = value;
@@ -791,6 +818,7 @@ extern "C" int kemr_model_get_option(const kemr_model* m, const char* key, int* 
     if (!strcmp(key, "last_block_pooled_row")) { *value = m->last_pooled; return KEMR_OK; }
     if (!strcmp(key, "residual_stream_24bit")) { *value = (m->finalized && !m->x3) ? (m->res_dtype == KEMR_F24) : m->stream24; return KEMR_OK; }
     if (!strcmp(key, "activation")) { *value = m->activation; return KEMR_OK; }
+    if (!strcmp(key, "vision_head_dim")) { *value = m->v_head_dim; return KEMR_OK; }
     if (!strcmp(key, "precision_residual_bf16")) { *value = m->res_dtype == KEMR_BF16; return KEMR_OK; }
     KEMR_FAIL(KEMR_ERR_INVALID, "model_get_option: unknown key '%s'", key);
 }
@@ -817,6 +845,7 @@ const DebugKnob* debug_knobs(int* n) {
         {"gemm_kl", &g_gemm_kl, 0, 1, 1u << 0},       // 0 = eight 256-cycle barrier intervals per K-tile (the product loop), 1 = four of 512 (round-3 experiment): A/B builds
         {"attn_v", &g_attn_v, 0, 5, 1u << 0},         // 0 = the product kernel, 1..4 = attention_ab.hip: A/B builds
         {"attn_xcd", &g_attn_xcd, 0, 1, ~0u},         // attention: images dealt to the XCDs
+        {"attn80_waves", &g_attn80_waves, 0, 8, 1u << 0 | 1u << 4 | 1u << 8},   // head-dim-80 tile kernel at T = 257: 0 / 8 = eight waves per workgroup (default), 4 = four; both are in the product library
         {"attn_waves", &g_attn_waves, 0, 8, 1u << 0}, // waves per attention workgroup at T = 257 (0 = default; others: A/B builds)
         {"ln_nt", &g_ln_nt, 0, 3, 1u << 3},           // LayerNorm cache hints: 3 = deltas, residual rows and the x write-back non-temporal (the product kernel); 0 / 1 / 2 = earlier levels: A/B builds
         {"sim_lists", sim_lists_knob(), 0, 3, ~0u},   // 0 = never the candidate-list route, 1 = where it pays, 2 = wherever it fits + the fallback forced, 3 = wherever it fits
@@ -858,6 +887,13 @@ extern "C" int kemr_debug_gemm_stamps(unsigned* host_out, int n_words) {
     return gemm_read_stamps(host_out, n_words);
 }
 
+// the head dims the attention kernels serve, and the width they split
+static int check_head_dim(const char* what, int head_dim, int width) {
+    if (head_dim != 64 && head_dim != 80) KEMR_FAIL(KEMR_ERR_INVALID, "%s: head dim %d not served (64 or 80)", what, head_dim);
+    if (width <= 0 || width % head_dim) KEMR_FAIL(KEMR_ERR_INVALID, "%s: width %d is not a multiple of the head dim %d", what, width, head_dim);
+    return KEMR_OK;
+}
+
 // pass-throughs to the launchers of the kernels a tower reaches only inside itself (tests hold them to their rounding budgets)
 extern "C" int kemr_debug_op_attention_packed(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width,
                                               void* stream) {
@@ -871,6 +907,19 @@ extern "C" int kemr_debug_op_attention_pooled(const void* q_dev, const void* qkv
     if (!q_dev || !qkv_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_attention_pooled: null argument");
     return launch_attention_pooled((const bf16_t*)q_dev, (const bf16_t*)qkv_dev, (bf16_t*)out_dev, pool_idx_dev, row_start_dev, items,
                                    tokens, width, causal, (hipStream_t)stream, force_long);
+}
+
+extern "C" int kemr_debug_op_attention_pooled_hd(const void* q_dev, const void* qkv_dev, void* out_dev, const int* pool_idx_dev,
+                                                 const int* row_start_dev, int items, int tokens, int width, int head_dim, int causal,
+                                                 int force_long, void* stream) {
+    if (!q_dev || !qkv_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_attention_pooled_hd: null argument");
+    KEMR_TRY(check_head_dim("debug_op_attention_pooled_hd", head_dim, width));
+    if (head_dim == 64)
+        return launch_attention_pooled((const bf16_t*)q_dev, (const bf16_t*)qkv_dev, (bf16_t*)out_dev, pool_idx_dev, row_start_dev, items,
+                                       tokens, width, causal, (hipStream_t)stream, force_long);
+    if (pool_idx_dev || row_start_dev || force_long)
+        KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_attention_pooled_hd: head dim 80 takes no pooled positions, packed rows or long instantiation (vision towers of at most 288 tokens)");
+    return launch_attention80_pooled((const bf16_t*)q_dev, (const bf16_t*)qkv_dev, (bf16_t*)out_dev, items, tokens, width, causal, (hipStream_t)stream);
 }
 
 extern "C" int kemr_debug_op_tail(const void* x_dev, int x_dtype, const void* delta_dev, const void* delta2_dev, const int32_t* ids_dev,
@@ -993,6 +1042,13 @@ extern "C" int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, 
     return launch_attention((const bf16_t*)qkv_dev, (bf16_t*)out_dev, batch, t, width, causal, (hipStream_t)stream);
 }
 
+extern "C" int kemr_op_attention_hd(const void* qkv_dev, void* out_dev, int batch, int t, int width, int head_dim, int causal, void* stream) {
+    if (!qkv_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_hd: null argument");
+    KEMR_TRY(check_head_dim("op_attention_hd", head_dim, width));
+    if (head_dim == 64) return launch_attention((const bf16_t*)qkv_dev, (bf16_t*)out_dev, batch, t, width, causal, (hipStream_t)stream);
+    return launch_attention80((const bf16_t*)qkv_dev, (bf16_t*)out_dev, batch, t, width, causal, (hipStream_t)stream);
+}
+
 // ---- KEMR_PREC_FP32X3 building blocks (panels: kemr_panel_build with nparts = 1, terms = 3) ----
 extern "C" int kemr_op_layernorm_x3(const float* x_dev, const float* gamma_dev, const float* beta_dev, void* y_panel_dev, int rows,
                                     int width, void* stream) {
@@ -1017,4 +1073,13 @@ extern "C" int kemr_op_attention_x3(const float* qkv_dev, void* out_panel_dev, c
                                     int causal, void* stream) {
     if (!qkv_dev || !out_panel_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_x3: null argument");
     return launch_attention_x3(qkv_dev, (bf16_t*)out_panel_dev, row_start_dev, batch, t, width, causal, (hipStream_t)stream);
+}
+
+extern "C" int kemr_op_attention_x3_hd(const float* qkv_dev, void* out_panel_dev, const int* row_start_dev, int batch, int t, int width,
+                                       int head_dim, int causal, void* stream) {
+    if (!qkv_dev || !out_panel_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_x3_hd: null argument");
+    KEMR_TRY(check_head_dim("op_attention_x3_hd", head_dim, width));
+    if (head_dim == 64) return launch_attention_x3(qkv_dev, (bf16_t*)out_panel_dev, row_start_dev, batch, t, width, causal, (hipStream_t)stream);
+    if (row_start_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_x3_hd: packed rows are causal, and head dim 80 is not served causal");
+    return launch_attention80_x3(qkv_dev, (bf16_t*)out_panel_dev, batch, t, width, causal, (hipStream_t)stream);
 }

@@ -192,6 +192,7 @@ extern int g_sim_lists;     // sim.hip: candidate-list route of kemr_sim_topk (k
 extern int g_attn_xcd;      // attention.hip (tools)
 extern int g_attn_waves;    // attention.hip (tools)
 extern int g_attn_v;        // attention.hip: 0 = the product kernel; 1..4 = attention_ab.hip (A/B builds only)
+extern int g_attn80_waves;  // attention80.hip (tools): waves per workgroup of the head-dim-80 tile kernel at T = 257 (0 = default 8, or 4)
 extern int g_gemm_kl;       // gemm256u: 0 = eight barrier intervals per K-tile (the product loop), 1 = the long-interval K loop (A/B builds only)
 extern int g_ln_nt;         // layernorm.hip: cache-hint level of the residual forms, 3 = the product kernel; 0 / 1 / 2 in A/B builds only
 extern int g_gemm_grid;     // tools: cap on the persistent GEMM's grid (0 = one workgroup per CU)
@@ -245,6 +246,11 @@ int launch_attention(const bf16_t* qkv, bf16_t* out, int batch, int t, int width
 int launch_attention_long(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, hipStream_t stream);
 // causal, items of lengths 1 .. max_t packed one behind the other: item b = rows row_start[b] .. row_start[b + 1] - 1 (device ints)
 int launch_attention_packed(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream);
+// attention80.hip: heads of 80 columns (the vision tower of ViT-H-14), non-causal, t <= 288: the tile kernel, the pooled row of the last
+// block (q [items, width] compact, k / v from the call's qkv buffer, item b = rows b * tokens ..) and the KEMR_PREC_FP32X3 form
+int launch_attention80(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, int causal, hipStream_t stream);
+int launch_attention80_pooled(const bf16_t* q, const bf16_t* qkv, bf16_t* out, int items, int tokens, int width, int causal, hipStream_t stream);
+int launch_attention80_x3(const float* qkv, bf16_t* out_panel, int batch, int t, int width, int causal, hipStream_t stream);
 int launch_im2col(const float* pixels, bf16_t* patches, int batch, int image_size, int patch, int kpad, hipStream_t stream);
 int launch_cls_rows(float* x, const float* class_emb, const float* pos, int batch, int tokens, int width, hipStream_t stream);
 // the pooled row of every item (class token: ids == nullptr; else first argmax of the token ids, inside row_start's rows when packed)

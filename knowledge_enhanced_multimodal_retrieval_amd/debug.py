@@ -11,7 +11,7 @@ import ctypes as C
 
 from . import _lib
 
-KEYS = ("gemm_variant", "gemm_flags", "gemm_order", "gemm_grid", "gemm_conc", "gemm_kl", "attn_v", "attn_xcd", "attn_waves", "sim_lists", "ln_nt")
+KEYS = ("gemm_variant", "gemm_flags", "gemm_order", "gemm_grid", "gemm_conc", "gemm_kl", "attn_v", "attn_xcd", "attn_waves", "attn80_waves", "sim_lists", "ln_nt")
 
 
 def ab_variants() -> bool:
@@ -92,16 +92,21 @@ def op_attention_packed(qkv, row_start, max_t: int, width: int):
     return out
 
 
-def op_attention_pooled(q, qkv, pool_idx, row_start, tokens: int, causal: bool, force_long: bool = False):
+def op_attention_pooled(q, qkv, pool_idx, row_start, tokens: int, causal: bool, force_long: bool = False, head_dim: int = 64):
     """One query row per item: q bf16 [items, width], k / v from qkv bf16 [rows, 3 width], pool_idx / row_start int32 (device, or
-    None) -> bf16 [items, width]."""
+    None) -> bf16 [items, width].  head_dim 64, or 80 (the vision form only: no pool_idx / row_start, tokens <= 288)."""
     import torch
     items, width = q.shape
     out = torch.zeros((items, width), dtype=torch.bfloat16, device=q.device)
     with torch.cuda.device(q.device):
-        _lib.check(_lib.lib().kemr_debug_op_attention_pooled(_ptr(q), _ptr(qkv), _ptr(out), _ptr(pool_idx), _ptr(row_start), items,
-                                                             tokens, width, 1 if causal else 0, 1 if force_long else 0,
-                                                             _stream(q.device)), "debug_op_attention_pooled")
+        if head_dim == 64:
+            _lib.check(_lib.lib().kemr_debug_op_attention_pooled(_ptr(q), _ptr(qkv), _ptr(out), _ptr(pool_idx), _ptr(row_start), items,
+                                                                 tokens, width, 1 if causal else 0, 1 if force_long else 0,
+                                                                 _stream(q.device)), "debug_op_attention_pooled")
+        else:
+            _lib.check(_lib.lib().kemr_debug_op_attention_pooled_hd(_ptr(q), _ptr(qkv), _ptr(out), _ptr(pool_idx), _ptr(row_start), items,
+                                                                    tokens, width, int(head_dim), 1 if causal else 0,
+                                                                    1 if force_long else 0, _stream(q.device)), "debug_op_attention_pooled_hd")
     return out
 
 

@@ -89,10 +89,12 @@ class ClipEngine:
         if self.device.type != "cuda":
             raise RuntimeError("ClipEngine needs a GPU device; the HIP path has no CPU fallback")
         self._L = _lib.lib()
-        cfg = _lib.KemrCfg(**arch.as_dict())
+        cfg = _lib.KemrCfg(**arch.cfg_dict())
         h = C.c_void_p()
         _lib.check(self._L.kemr_model_create(C.byref(cfg), C.byref(h)), "model_create")
         self._h = h
+        if arch.v_head_dim != 64:                        # before finalize: it decides the scale folded into the vision tower's query rows
+            _lib.check(self._L.kemr_model_set_option(self._h, b"vision_head_dim", arch.v_head_dim), "model_set_option")
         self.activation = "quick_gelu"                   # the library's default; the option is only touched when something else is asked for
         if activation != self.activation:
             self.set_activation(activation)
@@ -848,12 +850,18 @@ def op_layernorm_rows_f24(x24: torch.Tensor, width: int, delta: Optional[torch.T
     return y
 
 
-def op_attention(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool) -> torch.Tensor:
+def op_attention(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool, head_dim: int = 64) -> torch.Tensor:
+    """qkv bf16 [batch * t, 3 width] (q pre-scaled by 1 / sqrt(head_dim)) -> bf16 [batch * t, width].  head_dim 64, or 80 (non-causal,
+    t <= 288, width a multiple of 80)."""
     L = _lib.lib()
     out = torch.empty((batch * t, width), dtype=torch.bfloat16, device=qkv.device)
     with torch.cuda.device(qkv.device):
-        _lib.check(L.kemr_op_attention(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), batch, t, width,
-                                       1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))), "op_attention")
+        if head_dim == 64:
+            _lib.check(L.kemr_op_attention(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), batch, t, width,
+                                           1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))), "op_attention")
+        else:
+            _lib.check(L.kemr_op_attention_hd(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), batch, t, width, int(head_dim),
+                                              1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))), "op_attention_hd")
     return out
 
 
@@ -888,12 +896,17 @@ def op_gemm_x3(a_panel: torch.Tensor, w_panel: torch.Tensor, bias: Optional[torc
     return c
 
 
-def op_attention_x3(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool, row_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+def op_attention_x3(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool, row_start: Optional[torch.Tensor] = None,
+                    head_dim: int = 64) -> torch.Tensor:
     """qkv fp32 [rows, 3 width] (q pre-scaled) -> the A-side triple bf16 [rows, 3 width] of the attention output.  row_start (int32
-    [batch + 1] on the device): packed causal items of at most t rows."""
+    [batch + 1] on the device): packed causal items of at most t rows.  head_dim 64, or 80 (non-causal, no packed rows, t <= 288)."""
     L = _lib.lib()
     out = torch.zeros((qkv.shape[0], 3 * width), dtype=torch.bfloat16, device=qkv.device)
     with torch.cuda.device(qkv.device):
-        _lib.check(L.kemr_op_attention_x3(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), _opt_ptr(row_start), batch, t, width,
-                                          1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))), "op_attention_x3")
+        if head_dim == 64:
+            _lib.check(L.kemr_op_attention_x3(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), _opt_ptr(row_start), batch, t, width,
+                                              1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))), "op_attention_x3")
+        else:
+            _lib.check(L.kemr_op_attention_x3_hd(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), _opt_ptr(row_start), batch, t, width,
+                                                 int(head_dim), 1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))), "op_attention_x3_hd")
     return out

@@ -26,6 +26,7 @@ from . import _lib
 from . import engine
 from . import metrics as M
 from . import sparql_fusion as SF
+from .config import get_arch
 from .datasets import CLIPEvalDatasetHF, CollateAndTokenize, SyntheticHFSplit, SyntheticRawImageDataset, SyntheticRetrievalDataset, collate_fn_eval
 from .preprocess import ClipPreprocessGPU, PackedRaw
 from .logging_utils import save_metrics_to_json, setup_logger
@@ -304,7 +305,7 @@ def evaluate_clip_model_baseline(model, dataset, batch_size: int = 64, device: s
 
 # ------------------------------------------------------------------------------------------------ CLIs
 def _common_args(parser, baseline: bool):
-    parser.add_argument("--model_name", type=str, default="ViT-L/14", choices=["ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px"])
+    parser.add_argument("--model_name", type=str, default="ViT-L/14", choices=["ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px", "ViT-H-14"])
     parser.add_argument("--checkpoint", type=str, help="Path to checkpoint, if None uses pretrained model")
     parser.add_argument("--images_dir", type=str, default=None)
     parser.add_argument("--texts_dir", type=str, default=None, help="Directory containing query-target JSON files")
@@ -527,7 +528,7 @@ def main_fusion(argv=None):
         clip_api.allow_random_weights(True)
         tokenizer.allow_hash_tokenizer(True)
     clip_model, preprocess = load_clip_model(model_name=args.model_name, checkpoint_path=args.clip_checkpoint, device=args.device)
-    embed_dim = 768 if "L/14" in args.model_name else 512
+    embed_dim = get_arch(args.model_name).embed_dim       # 768 (ViT-L/14), 512 (ViT-B), 1024 (ViT-H-14)
     fusion_model = FusionModel(clip_model=clip_model, fusion_type=args.fusion_type, embed_dim=embed_dim).to(args.device)
     if args.fusion_checkpoint:
         ckpt = torch.load(args.fusion_checkpoint, map_location="cpu", weights_only=True)

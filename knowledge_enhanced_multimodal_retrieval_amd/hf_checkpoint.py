@@ -45,7 +45,9 @@ def arch_and_activation_from_hf_config(cfg: Mapping) -> Tuple[ClipArch, str]:
             raise ValueError(f"HF config: {side}.hidden_size = {w} is not a multiple of 256 (the kernels' tile)")
         if heads <= 0 or w != 64 * heads:
             raise ValueError(f"HF config: {side}.num_attention_heads = {heads} at hidden_size {w} is a head dim of "
-                             f"{w / max(heads, 1):g}; the attention kernels serve 64 only (ViT-H/14 has 80, ViT-g 88)")
+                             f"{w / max(heads, 1):g}; Hugging Face directories are served at head dim 64 only.  ViT-H/14 (head dim 80) "
+                             "is served from its OpenCLIP file -- clip.load('ViT-H-14@/path/open_clip_pytorch_model.bin', "
+                             "activation='gelu'), which LAION's repositories ship next to the HF weights; ViT-g (88) is not served")
         if int(c["intermediate_size"]) != 4 * w:
             raise ValueError(f"HF config: {side}.intermediate_size = {c['intermediate_size']} is not 4 x hidden_size ({4 * w})")
         if c["hidden_act"] not in _ACTS:
