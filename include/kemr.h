@@ -41,7 +41,9 @@ extern "C" {
  *    existing entry point changed.  Option "activation" of kemr_model_set_option / kemr_model_get_option and the epilogue value
  *    KEMR_EPI_BIAS_GELU_BF16 (kemr_op_gemm, kemr_op_gemm_fp8) are additions as well: the default, 0, is the QuickGELU every existing
  *    caller gets; no entry point was added.  Still 4: option "vision_head_dim" (64, the default every existing caller gets, or 80: the
- *    vision tower of ViT-H-14) and the entry points kemr_op_attention_hd / kemr_op_attention_x3_hd are additions; kemr_cfg did not grow. */
+ *    vision tower of ViT-H-14) and the entry points kemr_op_attention_hd / kemr_op_attention_x3_hd are additions; kemr_cfg did not grow.
+ *    Still 4: option "family" (0 = CLIP, the default every existing caller gets; 1 = SigLIP) and the epilogue value
+ *    KEMR_EPI_BIAS_TGELU_BF16 (kemr_op_gemm) are additions; no entry point changed, kemr_cfg did not grow. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -112,7 +114,10 @@ typedef enum kemr_tower { KEMR_TOWER_VISION = 0, KEMR_TOWER_TEXT = 1 } kemr_towe
 /* Architecture numbers of an OpenAI-CLIP style model (MLP is 4*width; heads are width/64, except a vision tower under option
  * "vision_head_dim" = 80, whose heads are v_width/80: OpenCLIP's ViT-H-14 {1024,224,14,1280,32,1024,24,49408,77}).
  * ViT-L/14: {768,224,14,1024,24,768,12,49408,77}; ViT-L/14@336px: {768,336,14,1024,24,768,12,49408,77};
- * ViT-B/32: {512,224,32,768,12,512,12,49408,77}. */
+ * ViT-B/32: {512,224,32,768,12,512,12,49408,77}.
+ * The SigLIP family (model option "family" = 1) reads the same nine numbers: embed_dim must equal v_width (the image embedding is the
+ * pooling head's row, there is no vision projection), the vision tower has (image_size / patch)^2 tokens (no class token), vocab and ctx
+ * are the model's (32000 / 64).  ViT-B-16-SigLIP: {768,224,16,768,12,768,12,32000,64}; ViT-L-16-SigLIP-384: {1024,384,16,1024,24,1024,24,32000,64}. */
 typedef struct kemr_cfg {
     int32_t embed_dim;    /* joint embedding size D */
     int32_t image_size;   /* input resolution (square) */
@@ -172,7 +177,21 @@ int kemr_model_destroy(kemr_model* m);
  *                      1/sqrt(80) instead of 1/8 into the vision tower's query rows and the encoders run the head-dim-80 attention
  *                      kernels (csrc/attention80.hip).  Refused at finalize with 80: the fp8 precisions, and vision towers of more than
  *                      288 tokens (the streaming attention kernel serves heads of 64 only).  Not served at all: ViT-g / bigG (head dim
- *                      88 / widths that are no multiple of 256, MLP not 4 x width), SigLIP. */
+ *                      88 / widths that are no multiple of 256, MLP not 4 x width).
+ *   "family"           (set BEFORE the first kemr_model_load_tensor: it rebuilds the list of required tensor names) 0 = CLIP (default),
+ *                      1 = SigLIP (ViT-B/16, ViT-L/16; transformers.SiglipModel).  The names are the OpenAI-style ones wherever the tensor
+ *                      exists in both models; in addition visual.conv1.bias, visual.positional_embedding [patches, W] (no class row),
+ *                      visual.attn_pool.{probe [W], in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, ln.weight, ln.bias,
+ *                      mlp.c_fc.*, mlp.c_proj.*}, text_projection [t_width, D] with text_projection_bias [D]; no visual.class_embedding,
+ *                      visual.ln_pre.* or visual.proj; logit_bias is ignored like logit_scale.  What the encoders then do differently:
+ *                      the patch GEMM's epilogue writes x[m] = acc + pos[m % patches] + bias with no class rows and no ln_pre; every
+ *                      LayerNorm uses eps 1e-6; fc1 runs the tanh-GELU epilogue (option "activation" keeps its range and messages and is
+ *                      not consulted); the image embedding is the attention-pooling head over ln_post of ALL tokens (one learned query,
+ *                      then r + mlp(ln(r))), so option "last_block_pooled_row" is ignored by the vision tower; the text tower has no
+ *                      mask, pools position ctx - 1 whatever the ids (its last block honours "last_block_pooled_row") and its head adds
+ *                      text_projection_bias.  Refused for family 1 with the reason in the message: at finalize embed_dim != v_width,
+ *                      the fp8 precisions, KEMR_PREC_FP32X3 and "vision_head_dim" != 64; kemr_encode_text_packed (a pad position is a
+ *                      key and the pooled row is the last one, so no row can be left out). */
 int kemr_model_set_option(kemr_model* m, const char* key, int value);
 int kemr_model_get_option(const kemr_model* m, const char* key, int* value);
 /* number of required tensor names; name i via kemr_model_tensor_name (for strict-load diagnostics) */
@@ -185,7 +204,7 @@ const char* kemr_model_tensor_name(const kemr_model* m, int i);
  * 113-114, 119-120; src/clip/eval/evaluator.py:121-122, 127-128, 133-134;
  * src/clip/model/fusion_model.py:287-303).
  *   pixels_dev : fp32 [B,3,S,S] contiguous NCHW, already mean/std normalised
- *   ids_dev    : int32 [B,ctx]; pooled at the first position of the row maximum (EOT)
+ *   ids_dev    : int32 [B,ctx]; pooled at the first position of the row maximum (EOT); family 1: at position ctx - 1
  *   out_dev    : fp32 [B, embed_dim]; L2-normalised when normalize != 0
  *   workspace  : >= kemr_workspace_bytes(m, tower, B) bytes, 256-byte aligned, contents don't matter
  * ------------------------------------------------------------------------------------------- */
@@ -409,7 +428,9 @@ typedef enum kemr_epilogue {
                                       than 512 rows up the persistent kernel: C with ceil256(m) rows) */
     KEMR_EPI_BIAS_RESADD_BF16 = 4, /* X_bf16 = bf16(bf16(A.W^T + bias) + X_bf16), in place; persistent 256 x 256 kernel only:
                                       N % 256 == 0, m > 512, C with ceil256(m) rows                              */
-    KEMR_EPI_BIAS_GELU_BF16 = 5    /* C_bf16 = gelu(A.W^T + bias), exact GELU 0.5 x erfc(-x / sqrt 2) in fp32 (3 is internal) */
+    KEMR_EPI_BIAS_GELU_BF16 = 5,   /* C_bf16 = gelu(A.W^T + bias), exact GELU 0.5 x erfc(-x / sqrt 2) in fp32 (3 and 7 are internal, 6 is not a value) */
+    KEMR_EPI_BIAS_TGELU_BF16 = 8   /* C_bf16 = gelu_tanh(A.W^T + bias): 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))), computed in fp32 as
+                                      x sigmoid(2 sqrt(2/pi) (x + 0.044715 x^3)) (the SigLIP family's fc1; bf16 operands only) */
 } kemr_epilogue;
 /* A bf16 [m_alloc, k] and C [m_alloc, n] with m_alloc = m rounded up to 256 rows (pad rows of A are read; pad rows of C
  * may be written by the bf16 epilogues), W bf16 [n, k], bias fp32 [n] */

@@ -91,7 +91,7 @@ int kemr_debug_op_tail(const void* x_dev, int x_dtype, const void* delta_dev, co
 /* The token fronts of the encoders (tests/test_numerics_front_gpu.py): the same argument checks, workspace (kemr_workspace_bytes /
  * kemr_text_packed_workspace_bytes) and launches as kemr_encode_image / kemr_encode_text / kemr_encode_text_packed up to the rows
  * the first LayerNorm reads, then a copy of those rows to out_dev.
- * image: im2col, the patch-embedding GEMM and the class rows -> fp32 [batch * tokens, v_width].
+ * image: im2col, the patch-embedding GEMM and the class rows -> fp32 [batch * tokens, v_width] (family 1: no class rows, the conv bias added).
  * text: lens_dev NULL = kemr_encode_text's batch * ctx rows, else kemr_encode_text_packed's `rows` rows and row_start_out_dev gets the
  * batch + 1 row starts; the rows in the residual stream's storage type: fp32, bf16 or 24-bit (3 t_width bytes per row: the bf16
  * upper halves, then the third bytes). */
@@ -99,6 +99,13 @@ int kemr_debug_image_tokens(struct kemr_model* m, const float* pixels_dev, int b
                             size_t workspace_bytes, void* stream);
 int kemr_debug_text_tokens(struct kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, void* out_dev,
                            int* row_start_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The pooling head of a family-1 (SigLIP) model alone (tests/test_siglip_ops_gpu.py): h_dev = bf16 [batch * tokens, v_width], the
+ * ln_post output of every token row, is copied into the workspace (kemr_workspace_bytes of the vision tower), then the head's launches
+ * as kemr_encode_image makes them -- k | v GEMM, the one learned query's attention, out-proj, LayerNorm, fc1 + tanh GELU, fc2, add
+ * [, L2 normalise] -> out_dev fp32 [batch, v_width]; attn_out_dev (may be NULL) gets the attention output rows, bf16 [batch, v_width] */
+int kemr_debug_map_head(struct kemr_model* m, const void* h_dev, int batch, void* attn_out_dev, float* out_dev, int normalize,
+                        void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,7 @@ SIDE_QUERY, SIDE_GALLERY = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RESID_F32 = 0, 1, 2
 EPI_BIAS_RESADD_BF16 = 4
 EPI_BIAS_GELU_BF16 = 5      # exact (erf) GELU; 3 is internal to the library
+EPI_BIAS_TGELU_BF16 = 8     # tanh GELU ("gelu_pytorch_tanh": the SigLIP family's fc1)
 # model option "activation" (include/kemr.h): the MLP's activation, by the name Hugging Face configs give it (`hidden_act`)
 ACTIVATIONS = {"quick_gelu": 0, "gelu": 1}
 MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused / kemr_cross_attention_rerank / kemr_list_fuse
@@ -119,6 +120,7 @@ DEBUG_SIGNATURES = {
     "kemr_debug_op_tail": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "kemr_debug_image_tokens": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "kemr_debug_text_tokens": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "kemr_debug_map_head": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
 }
 ABI_VERSION = 4
 

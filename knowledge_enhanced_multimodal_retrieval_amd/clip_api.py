@@ -31,12 +31,13 @@ import torch
 
 from . import hf_checkpoint
 from ._lib import check_activation
-from .clip_module import CLIP, build_model
+from .clip_module import CLIP, SigLIP, build_model
 from .config import ARCHS, get_arch
-from .preprocess import ClipPreprocess, gpu_preprocessing_enabled
+from .preprocess import ClipPreprocess, SiglipPreprocess, gpu_preprocessing_enabled
 from .tokenizer import tokenize  # noqa: F401  (re-exported)
 
-_PUBLIC = ("ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px", "ViT-H-14")
+_PUBLIC = ("ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px", "ViT-H-14",
+           "ViT-B-16-SigLIP", "ViT-B-16-SigLIP-256", "ViT-B-16-SigLIP-384", "ViT-B-16-SigLIP-512", "ViT-L-16-SigLIP-256", "ViT-L-16-SigLIP-384")
 _allow_random = False
 
 
@@ -83,6 +84,15 @@ def _weights_for(name: str):
 
 def _load_hf_directory(directory: str, device, activation) -> Tuple[CLIP, ClipPreprocess]:
     arch, act, sd = hf_checkpoint.read_hf_directory(directory)
+    if arch.family == "siglip":             # a SiglipModel directory: the activation is the family's
+        if activation is not None:
+            raise ValueError(f"clip.load({directory!r}, activation={activation!r}): a SigLIP model's activation is {act!r}, not an option")
+        model = SigLIP(arch, hf_checkpoint.registered_name(arch))
+        model.load_state_dict(sd, strict=True)
+        model.weights_source = os.path.abspath(directory)
+        # what evaluators.model_tokenize reads when no tokenize_fn is given (encode_dataset, EmbeddingStore.build, CLIPRetriever, the CLIs)
+        model.tokenizer_dir = os.path.abspath(directory) if os.path.isfile(os.path.join(directory, "tokenizer.json")) else None
+        return model.to(device).eval(), SiglipPreprocess(arch.image_size)
     if activation is not None and check_activation(activation) != act:
         raise ValueError(f"clip.load({directory!r}, activation={activation!r}): its config.json says hidden_act = {act!r}")
     model = CLIP(arch, hf_checkpoint.registered_name(arch), act)
@@ -140,5 +150,7 @@ def load(name: str, device: Union[str, torch.device, None] = None,
         warnings.warn(f"clip.load({name!r}): seeded RANDOM weights (explicitly allowed)", RuntimeWarning, stacklevel=2)
         model.weights_source = "random(seed 0)"
     model = model.to(device).eval()
+    if get_arch(name).family == "siglip":   # squash to S x S, mean = std = 0.5; host transform only (no GPU uint8 kernel for it yet)
+        return model, SiglipPreprocess(get_arch(name).image_size)
     on_gpu = torch.device(device).type == "cuda"
     return model, ClipPreprocess(get_arch(name).image_size, defer_to_gpu=on_gpu and gpu_preprocessing_enabled())

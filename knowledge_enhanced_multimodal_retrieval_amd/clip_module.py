@@ -162,8 +162,14 @@ class CLIP(nn.Module):
         state["_gpu_pre"] = None
         return state
 
+    def _device(self) -> torch.device:
+        return self.positional_embedding.device
+
+    def _engine_activation(self) -> str:
+        return self.activation
+
     def engine(self) -> ClipEngine:
-        dev = self.visual.proj.device
+        dev = self._device()
         if dev.type != "cuda":
             raise RuntimeError("CLIP: the model sits on %s; the encoders run only on a GPU (model.to('cuda')); there is no "
                                "CPU fallback" % dev)
@@ -171,12 +177,12 @@ class CLIP(nn.Module):
             # encoder precision of the packed copy: _lib.DEFAULT_PRECISION unless KEMR_PRECISION says otherwise (bf16 | bf16-res16 | fp8 | fp8-res16 |
             # fp8-mlp | fp32x3, kemr_precision in include/kemr.h) -- an environment switch so that the reference's scripts stay unchanged
             from ._lib import env_precision
-            self._engine, self._dirty = ClipEngine(self.arch, dev, precision=env_precision(), activation=self.activation), True
-        if self._engine.activation != self.activation:
-            self._engine.set_activation(self.activation)
+            self._engine, self._dirty = ClipEngine(self.arch, dev, precision=env_precision(), activation=self._engine_activation()), True
+        if self._engine.activation != self._engine_activation():
+            self._engine.set_activation(self._engine_activation())
         fp = self._fingerprint()
         if self._dirty or fp != getattr(self, "_packed_fp", None):
-            self._engine.load_state_dict({k: v for k, v in self.state_dict().items() if k != "logit_scale"})
+            self._engine.load_state_dict({k: v for k, v in self.state_dict().items() if k not in ("logit_scale", "logit_bias")})
             self._dirty, self._packed_fp = False, fp
         return self._engine
 
@@ -187,8 +193,11 @@ class CLIP(nn.Module):
         ``CLIPEvalDatasetHF(split, preprocess)`` yields when the transform is deferred to the GPU -- so the reference's own loop
         (``images.to(device)`` -> ``model.encode_image(images)``, evaluator.py:118-121) runs unchanged on either."""
         from .preprocess import ClipPreprocessGPU, PackedRaw
-        dev = self.visual.proj.device
+        dev = self._device()
         if isinstance(image, PackedRaw):
+            if self.arch.family != "clip":
+                raise RuntimeError("encode_image: the GPU uint8 preprocess kernel implements CLIP's transform only; a SigLIP model takes "
+                                   "the pixels of its host transform (preprocess.SiglipPreprocess)")
             if getattr(self, "_gpu_pre", None) is None or self._gpu_pre.device != dev:
                 self._gpu_pre = ClipPreprocessGPU(self.visual.input_resolution, dev)
             image = self._gpu_pre.batch(image)
@@ -241,7 +250,103 @@ class CLIP(nn.Module):
         return logits, logits.t()
 
 
+class AttentionPool(nn.Module):
+    """Parameter container of SigLIP's attention-pooling head (``visual.attn_pool.*``): a learned probe is the single query of a
+    multi-head attention over the post-LayerNorm tokens; then ``r + mlp(ln(r))``."""
+
+    def __init__(self, width: int):
+        super().__init__()
+        self.probe = nn.Parameter(torch.randn(width) * width ** -0.5)          # Hugging Face's [1, 1, W], flattened
+        self.in_proj_weight = nn.Parameter(torch.randn(3 * width, width) * width ** -0.5)
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * width))
+        self.out_proj = nn.Linear(width, width)
+        self.ln = nn.LayerNorm(width, eps=1e-6)
+        self.mlp = nn.Sequential(OrderedDict([("c_fc", nn.Linear(width, width * 4)), ("gelu", nn.GELU(approximate="tanh")),
+                                              ("c_proj", nn.Linear(width * 4, width))]))
+
+
+class SiglipVisionTransformer(nn.Module):
+    def __init__(self, input_resolution: int, patch_size: int, width: int, layers: int, heads: int):
+        super().__init__()
+        self.input_resolution, self.output_dim = input_resolution, width
+        self.conv1 = nn.Conv2d(3, width, kernel_size=patch_size, stride=patch_size, bias=True)
+        self.positional_embedding = nn.Parameter(width ** -0.5 * torch.randn((input_resolution // patch_size) ** 2, width))
+        self.transformer = Transformer(width, layers, heads, "gelu")          # parameters only: the family's tanh GELU runs in the kernels
+        self.ln_post = nn.LayerNorm(width, eps=1e-6)
+        self.attn_pool = AttentionPool(width)
+
+
+class SigLIP(CLIP):
+    """SigLIP (ViT-B/16, ViT-L/16) with the same duck type as :class:`CLIP`: real ``nn.Parameter``s under the OpenAI-style names wherever
+    the tensor exists in both models, plus ``visual.conv1.bias``, ``visual.attn_pool.*``, ``text_projection_bias`` and ``logit_bias``;
+    no ``visual.class_embedding`` / ``visual.ln_pre`` / ``visual.proj``.  The encoders run in libkemr.so (model option "family" = 1)."""
+
+    accepts_text_lengths = False       # every position is a key and the LAST one is pooled: nothing can be left out
+
+    def __init__(self, arch: ClipArch, name: str = ""):
+        if arch.family != "siglip":
+            raise ValueError(f"SigLIP: arch family {arch.family!r} is not 'siglip'")
+        nn.Module.__init__(self)
+        self.activation = "gelu_pytorch_tanh"          # the family's; model option "activation" is not consulted
+        self.arch, self.model_name = arch, name
+        self.context_length, self.vocab_size = arch.ctx, arch.vocab
+        self.visual = SiglipVisionTransformer(arch.image_size, arch.patch, arch.v_width, arch.v_layers, arch.v_heads)
+        self.transformer = Transformer(arch.t_width, arch.t_layers, arch.t_heads, "gelu")
+        self.token_embedding = nn.Embedding(arch.vocab, arch.t_width)
+        self.positional_embedding = nn.Parameter(torch.empty(arch.ctx, arch.t_width))
+        self.ln_final = nn.LayerNorm(arch.t_width, eps=1e-6)
+        self.text_projection = nn.Parameter(torch.empty(arch.t_width, arch.embed_dim))      # head.weight transposed: y = x @ text_projection + bias
+        self.text_projection_bias = nn.Parameter(torch.zeros(arch.embed_dim))
+        self.logit_scale = nn.Parameter(torch.ones(1) * np.log(10.0))
+        self.logit_bias = nn.Parameter(torch.ones(1) * -10.0)
+        self._engine: Optional[ClipEngine] = None
+        self._gpu_pre = None
+        self._packed_fp = None
+        self._dirty = True
+        self.initialize_parameters()
+
+    def initialize_parameters(self):
+        super().initialize_parameters()
+        w = self.arch.v_width
+        nn.init.normal_(self.visual.attn_pool.mlp.c_fc.weight, std=(2 * w) ** -0.5)
+        nn.init.normal_(self.visual.attn_pool.mlp.c_proj.weight, std=w ** -0.5 * 0.5)
+        nn.init.normal_(self.visual.attn_pool.out_proj.weight, std=w ** -0.5)
+        self._dirty = True
+
+    def _engine_activation(self) -> str:
+        return "quick_gelu"            # the library's default: the option stays untouched
+
+    @classmethod
+    def from_pretrained(cls, directory: str, device=None):
+        """A ``save_pretrained`` directory of a ``transformers.SiglipModel`` on the LOCAL disk -> ``(model, preprocess)``."""
+        from .clip_api import load
+        model, preprocess = load(directory, device=device)
+        if not isinstance(model, cls):
+            raise ValueError(f"SigLIP.from_pretrained({directory!r}): its config.json is not a SigLIP model's")
+        return model, preprocess
+
+    @torch.no_grad()
+    def get_text_features(self, input_ids: torch.Tensor = None, attention_mask=None, **_) -> torch.Tensor:
+        """``SiglipModel.get_text_features``: SigLIP is trained on ``padding="max_length"``; shorter rows are padded to the context
+        length with the pad id 1 here (a pad position is a key like every other, so the padding is part of the input)."""
+        ctx = self.context_length
+        if input_ids.dim() != 2 or input_ids.shape[1] > ctx:
+            raise ValueError(f"get_text_features: input_ids must be [B, <= {ctx}], got {tuple(input_ids.shape)}")
+        if input_ids.shape[1] < ctx:
+            input_ids = torch.nn.functional.pad(input_ids, (0, ctx - input_ids.shape[1]), value=1)
+        return self.encode_text(input_ids)
+
+    @torch.no_grad()
+    def forward(self, image: torch.Tensor, text: torch.Tensor):
+        """logits_per_image, logits_per_text = cos * exp(logit_scale) + logit_bias (``sigmoid`` of it is the pair probability)."""
+        li, _ = super().forward(image, text)
+        li = li + self.logit_bias.to(li.device)
+        return li, li.t()
+
+
 def build_model(name_or_arch, device="cuda", activation: str = "quick_gelu") -> CLIP:
     arch = name_or_arch if isinstance(name_or_arch, ClipArch) else get_arch(name_or_arch)
     name = name_or_arch if isinstance(name_or_arch, str) else ""
+    if arch.family == "siglip":
+        return SigLIP(arch, name).to(device).eval()
     return CLIP(arch, name, activation).to(device).eval()

@@ -1,11 +1,18 @@
 """Architecture presets of the CLIP models the reference evaluates
 (`--model_name` choices at /root/reference/src/clip/eval/evaluator.py:264-266: ViT-B/32, ViT-B/16, ViT-L/14;
 embed_dim rule at src/clip/eval/evaluator_fusion.py:192), plus ViT-L/14@336px, the higher-resolution OpenAI CLIP model, and
-ViT-H-14 (OpenCLIP's spelling), LAION's ViT-H/14: the one served model whose vision heads are 80 wide instead of 64."""
+ViT-H-14 (OpenCLIP's spelling), LAION's ViT-H/14: the one served model whose vision heads are 80 wide instead of 64.
+
+A second model FAMILY rides on the same dataclass: SigLIP (``family="siglip"``, OpenCLIP's names ``ViT-B-16-SigLIP*`` /
+``ViT-L-16-SigLIP-*``): no class token, no ln_pre, tanh GELU, LayerNorm eps 1e-6, an attention-pooling head instead of a projection
+(so ``embed_dim == v_width``), an unmasked text tower pooled at its last position, vocabulary 32000 and 64 text positions."""
 from __future__ import annotations
 
 from dataclasses import dataclass, asdict
 from typing import Dict
+
+
+FAMILIES = {"clip": 0, "siglip": 1}      # model option "family" (include/kemr.h)
 
 
 @dataclass(frozen=True)
@@ -20,8 +27,14 @@ class ClipArch:
     vocab: int = 49408
     ctx: int = 77
     v_head_dim: int = 64          # head dim of the vision tower: 64, or 80 (ViT-H-14: 1280 = 16 heads of 80); text heads are always 64
+    family: str = "clip"          # "clip", or "siglip" (model option "family" = 1 of the library; kemr_cfg did not grow)
 
     def __post_init__(self):
+        if self.family not in FAMILIES:
+            raise ValueError(f"ClipArch: family {self.family!r}; served: {list(FAMILIES)}")
+        if self.family == "siglip" and (self.v_head_dim != 64 or self.embed_dim != self.v_width):
+            raise ValueError(f"ClipArch: a siglip arch has vision heads of 64 and no vision projection (embed_dim {self.embed_dim} must "
+                             f"equal v_width {self.v_width})")
         if self.v_head_dim not in (64, 80) or self.v_width % self.v_head_dim:
             raise ValueError(f"ClipArch: vision head dim {self.v_head_dim} at width {self.v_width}: served are heads of 64, or of 80 "
                              "at a width that is a multiple of 80")
@@ -40,7 +53,7 @@ class ClipArch:
 
     @property
     def v_tokens(self) -> int:
-        return self.grid * self.grid + 1
+        return self.grid * self.grid + (0 if self.family == "siglip" else 1)      # SigLIP has no class token
 
     @property
     def sot(self) -> int:
@@ -57,24 +70,35 @@ class ClipArch:
         d = asdict(self)
         if d["v_head_dim"] == 64:
             del d["v_head_dim"]
+        if d["family"] == "clip":         # likewise "family": only where it is not the default
+            del d["family"]
         return d
 
     def cfg_dict(self) -> Dict[str, int]:
         """Exactly the fields of kemr_cfg, for every arch: what `_lib.KemrCfg(**...)`, oracle.clip_ref and the tools take."""
         d = asdict(self)
-        del d["v_head_dim"]
+        del d["v_head_dim"], d["family"]
         return d
 
     # algorithmic FLOPs per item (SURVEY.md section 8(d))
     def image_flops(self) -> float:
         t, w, p = self.v_tokens, self.v_width, self.grid * self.grid
         per_layer = t * w * 3 * w + t * w * w + 2 * t * t * w + 2 * t * w * 4 * w
-        return 2.0 * (p * 3 * self.patch * self.patch * w + self.v_layers * per_layer + w * self.embed_dim)
+        tail = w * self.embed_dim
+        if self.family == "siglip":       # the pooling head: k | v of every token, one query row's attention, out-proj and the MLP
+            tail = t * w * 2 * w + 2 * t * w + w * w + 2 * w * 4 * w
+        return 2.0 * (p * 3 * self.patch * self.patch * w + self.v_layers * per_layer + tail)
 
     def text_flops(self) -> float:
         t, w = self.ctx, self.t_width
         per_layer = t * w * 3 * w + t * w * w + 2 * t * t * w + 2 * t * w * 4 * w
         return 2.0 * (self.t_layers * per_layer + w * self.embed_dim)
+
+
+def _siglip(image_size: int, width: int, layers: int, **kw) -> ClipArch:
+    """A SigLIP arch: both towers `width` wide and `layers` deep, patch 16, joint dim = width, vocabulary 32000, 64 positions."""
+    kw = {"vocab": 32000, "ctx": 64, **kw}
+    return ClipArch(width, image_size, 16, width, layers, width, layers, family="siglip", **kw)
 
 
 ARCHS: Dict[str, ClipArch] = {
@@ -91,6 +115,18 @@ ARCHS: Dict[str, ClipArch] = {
     # the structure of ViT-H-14 (vision heads of 80 at width 1280, the only width that is a multiple of 256 and of 80): 5 and 257 tokens
     "tiny-h": ClipArch(128, 28, 14, 1280, 2, 256, 2, vocab=512, ctx=16, v_head_dim=80),
     "tiny-h-257": ClipArch(128, 224, 14, 1280, 2, 256, 2, vocab=512, ctx=16, v_head_dim=80),
+    # SigLIP under OpenCLIP's names: B/16 (768 wide, 12 layers) at 224 / 256 / 384 / 512 px = 196 / 256 / 576 / 1024 tokens, L/16 (1024
+    # wide, 24 layers) at 256 / 384 px
+    "ViT-B-16-SigLIP": _siglip(224, 768, 12),
+    "ViT-B-16-SigLIP-256": _siglip(256, 768, 12),
+    "ViT-B-16-SigLIP-384": _siglip(384, 768, 12),
+    "ViT-B-16-SigLIP-512": _siglip(512, 768, 12),
+    "ViT-L-16-SigLIP-256": _siglip(256, 1024, 24),
+    "ViT-L-16-SigLIP-384": _siglip(384, 1024, 24),
+    # the same structure for tests: 16, 196 and 576 tokens (tile kernel, its 7-tile form, the streaming kernel)
+    "tiny-siglip": _siglip(64, 256, 2, vocab=512, ctx=16),
+    "tiny-siglip-196": _siglip(224, 256, 2, vocab=512, ctx=16),
+    "tiny-siglip-576": _siglip(384, 256, 2, vocab=512, ctx=16),
 }
 
 

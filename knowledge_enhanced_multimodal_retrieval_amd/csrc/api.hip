@@ -80,6 +80,10 @@ struct kemr_model {
     int x3 = 0;                                     // KEMR_PREC_FP32X3: split-bf16 operand triples, fp32 between the kernels (run_blocks_x3)
     int v_head_dim = 64;                            // option "vision_head_dim" (before finalize): 64, or 80 (ViT-H-14: 1280 = 16 heads of 80)
     int stream24 = 1;                               // option "residual_stream_24bit" (before finalize; default on since round 4): the fp32-class stream stored in 3 bytes
+    int family = 0;                                 // option "family" (before the first load_tensor): 0 = CLIP, 1 = SigLIP (no class token / ln_pre, tanh GELU, eps 1e-6, pooling head, unmasked text)
+    bool any_loaded = false;                        // a tensor was loaded: the name list is fixed from then on
+    float eps = 1e-5f;                              // every LayerNorm's epsilon: 1e-6 for family 1
+    int vtokens = 0;                                // token rows per image: patches + 1 (class token), patches for family 1
     // vision
     TowerW vis;
     const bf16_t* conv_w = nullptr;
@@ -88,6 +92,11 @@ struct kemr_model {
     // text
     TowerW txt;
     const float *tok = nullptr, *tpos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr, *tproj = nullptr;
+    // family 1: the text head's bias; the vision tower's pooling head (visual.attn_pool.*): its one query row (probe . Wq^T + bq) / 8
+    // made at finalize, the k | v rows of in_proj (wkv = in_proj_weight + W * W), out_proj, LayerNorm and MLP
+    const float* tproj_b = nullptr;
+    const bf16_t *mh_q = nullptr, *mh_wkv = nullptr, *mh_wo = nullptr, *mh_w1 = nullptr, *mh_w2 = nullptr;
+    const float *mh_bkv = nullptr, *mh_bo = nullptr, *mh_ln_g = nullptr, *mh_ln_b = nullptr, *mh_b1 = nullptr, *mh_b2 = nullptr;
 };
 
 namespace {
@@ -127,6 +136,52 @@ int check_cfg(const kemr_cfg& c) {
     return KEMR_OK;
 }
 
+// the required tensors of a model family, in load order (kemr_model_create; option "family" rebuilds the list)
+void build_names(kemr_model* m) {
+    const kemr_cfg* cfg = &m->cfg;
+    m->names.clear();
+    m->tensors.clear();
+    auto add = [&](const std::string& n, std::vector<int64_t> shape) { m->names.push_back(n); m->tensors[n].shape = std::move(shape); };
+    const int vw = cfg->v_width, tw = cfg->t_width, D = cfg->embed_dim;
+    const bool sig = m->family == 1;
+    m->vtokens = sig ? m->patches : m->patches + 1;
+    m->eps = sig ? 1e-6f : 1e-5f;
+    add("visual.conv1.weight", {vw, 3, cfg->patch, cfg->patch});
+    if (sig) add("visual.conv1.bias", {vw});
+    else add("visual.class_embedding", {vw});
+    add("visual.positional_embedding", {m->vtokens, vw});
+    if (!sig) {
+        add("visual.ln_pre.weight", {vw});
+        add("visual.ln_pre.bias", {vw});
+    }
+    add_block_names(m->names, m->tensors, "visual.transformer", vw, cfg->v_layers);
+    add("visual.ln_post.weight", {vw});
+    add("visual.ln_post.bias", {vw});
+    if (sig) {
+        const std::string h = "visual.attn_pool";
+        add(h + ".probe", {vw});
+        add(h + ".in_proj_weight", {3 * vw, vw});
+        add(h + ".in_proj_bias", {3 * vw});
+        add(h + ".out_proj.weight", {vw, vw});
+        add(h + ".out_proj.bias", {vw});
+        add(h + ".ln.weight", {vw});
+        add(h + ".ln.bias", {vw});
+        add(h + ".mlp.c_fc.weight", {4 * vw, vw});
+        add(h + ".mlp.c_fc.bias", {4 * vw});
+        add(h + ".mlp.c_proj.weight", {vw, 4 * vw});
+        add(h + ".mlp.c_proj.bias", {vw});
+    } else {
+        add("visual.proj", {vw, D});
+    }
+    add("token_embedding.weight", {cfg->vocab, tw});
+    add("positional_embedding", {cfg->ctx, tw});
+    add_block_names(m->names, m->tensors, "transformer", tw, cfg->t_layers);
+    add("ln_final.weight", {tw});
+    add("ln_final.bias", {tw});
+    add("text_projection", {tw, D});
+    if (sig) add("text_projection_bias", {D});
+}
+
 struct ArenaPlan {
     size_t bytes = 0;
     size_t take(size_t n) { size_t o = bytes; bytes += (size_t)round_up((int64_t)n, 256); return o; }
@@ -149,23 +204,7 @@ extern "C" int kemr_model_create(const kemr_cfg* cfg, kemr_model** out) {
     m->grid = cfg->image_size / cfg->patch;
     m->patches = m->grid * m->grid;
     m->kpad = (int)round_up(3 * cfg->patch * cfg->patch, 64);
-    auto add = [&](const std::string& n, std::vector<int64_t> shape) { m->names.push_back(n); m->tensors[n].shape = std::move(shape); };
-    const int vw = cfg->v_width, tw = cfg->t_width, D = cfg->embed_dim;
-    add("visual.conv1.weight", {vw, 3, cfg->patch, cfg->patch});
-    add("visual.class_embedding", {vw});
-    add("visual.positional_embedding", {m->patches + 1, vw});
-    add("visual.ln_pre.weight", {vw});
-    add("visual.ln_pre.bias", {vw});
-    add_block_names(m->names, m->tensors, "visual.transformer", vw, cfg->v_layers);
-    add("visual.ln_post.weight", {vw});
-    add("visual.ln_post.bias", {vw});
-    add("visual.proj", {vw, D});
-    add("token_embedding.weight", {cfg->vocab, tw});
-    add("positional_embedding", {cfg->ctx, tw});
-    add_block_names(m->names, m->tensors, "transformer", tw, cfg->t_layers);
-    add("ln_final.weight", {tw});
-    add("ln_final.bias", {tw});
-    add("text_projection", {tw, D});
+    build_names(m);
     *out = m;
     return KEMR_OK;
 }
@@ -182,6 +221,7 @@ extern "C" int kemr_model_load_tensor(kemr_model* m, const char* name, const voi
     if (dtype != KEMR_F32) KEMR_FAIL(KEMR_ERR_INVALID, "load_tensor(%s): only fp32 host tensors are accepted", name);
     const std::string n(name);
     if (n == "logit_scale" || n == "input_resolution" || n == "context_length" || n == "vocab_size") return KEMR_OK;  // not on the encode path
+    if (m->family == 1 && n == "logit_bias") return KEMR_OK;                    // SigLIP's second loss parameter: not on the encode path either
     auto it = m->tensors.find(n);
     if (it == m->tensors.end()) KEMR_FAIL(KEMR_ERR_INVALID, "load_tensor: unexpected key '%s' (strict load)", name);
     HostTensor& t = it->second;
@@ -197,6 +237,7 @@ extern "C" int kemr_model_load_tensor(kemr_model* m, const char* name, const voi
     for (auto s : t.shape) numel *= s;
     t.data.assign((const float*)host_ptr, (const float*)host_ptr + numel);
     t.loaded = true;
+    m->any_loaded = true;
     m->finalized = false;
     return KEMR_OK;
 }
@@ -213,6 +254,13 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
         if (fp8) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: the fp8 precisions are not served at vision_head_dim 80 (the e4m3 QKV path is validated for heads of 64 only)");
         if (m->patches + 1 > 288)
             KEMR_FAIL(KEMR_ERR_INVALID, "finalize: vision_head_dim 80 serves towers of at most 288 tokens, this one has %d (the streaming attention kernel is head-dim-64 only)", m->patches + 1);
+    }
+    if (m->family == 1) {
+        if (m->cfg.embed_dim != m->cfg.v_width)
+            KEMR_FAIL(KEMR_ERR_INVALID, "finalize: family 1 (SigLIP) has no vision projection: embed_dim %d must equal v_width %d", m->cfg.embed_dim, m->cfg.v_width);
+        if (fp8) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: the fp8 precisions are not served for family 1 (SigLIP): the e4m3 path is validated on the CLIP towers only");
+        if (precision == KEMR_PREC_FP32X3) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: KEMR_PREC_FP32X3 is not served for family 1 (SigLIP): the split-bf16 towers have no pooling head");
+        if (m->v_head_dim != 64) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: family 1 (SigLIP) serves vision_head_dim 64 only, got %d", m->v_head_dim);
     }
     for (const auto& n : m->names)
         if (!m->tensors[n].loaded) KEMR_FAIL(KEMR_ERR_STATE, "finalize: missing key '%s' (strict load)", n.c_str());
@@ -234,6 +282,9 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
     };
 
     // plan the device arena: f32 tensors verbatim, matrices as bf16
+    // (family 1: visual.attn_pool.in_proj_weight / in_proj_bias take the generic in_proj_* branches below like a block's, so the q rows
+    // of their device copies carry the 1/8 too.  Nothing reads those q rows: the head's one query is made from the host fp32 tensors
+    // -- the "visual.attn_pool.probe" branch -- and mh_wkv / mh_bkv start behind them.)
     ArenaPlan plan;
     std::map<std::string, size_t> off;
     auto is_matrix = [](const std::string& n) {
@@ -256,6 +307,7 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
         else if (is_matrix(n)) bytes = t.data.size() * mat_bytes;
         else bytes = t.data.size() * 4;
         off[n] = plan.take(bytes);
+        if (n == "visual.attn_pool.probe") off[n + "#q"] = plan.take(t.data.size() * 2);
     }
     // fp8 A operand (the LayerNorm output in front of an e4m3 GEMM): per-CHANNEL power-of-two scales s_c = 2^ceil(log2 max(|gamma_c|,
     // |beta_c|)) move the LayerNorm's gain out of the e4m3 values and into the weight columns -- gamma' = gamma / s, beta' = beta / s
@@ -296,6 +348,24 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
                     if (x3) put_x3(d, r, m->kpad, k, t.data[(size_t)r * kv + k]);
                     else d[(size_t)r * m->kpad + k] = f32_to_bf16_host(t.data[(size_t)r * kv + k]);
                 }
+        } else if (m->family == 1 && n == "visual.positional_embedding") {
+            // family 1: the patch embedding's bias rides in the positional table (x[m] = acc + pos[m % patches] + bias: one add per element)
+            const std::vector<float>& cb = m->tensors["visual.conv1.bias"].data;
+            float* d = (float*)dst;
+            const size_t w = cb.size();
+            for (size_t i = 0; i < t.data.size(); ++i) d[i] = t.data[i] + cb[i % w];
+        } else if (n == "visual.attn_pool.probe") {
+            // the pooling head's single query, the same for every image: (probe . Wq^T + bq) / 8 in fp32 (double accumulation), rounded to
+            // bf16 once -- what the q rows of a block's QKV GEMM are, with the scale folded in before the rounding
+            memcpy(dst, t.data.data(), t.data.size() * 4);
+            const std::vector<float>&wq = m->tensors["visual.attn_pool.in_proj_weight"].data, &bq = m->tensors["visual.attn_pool.in_proj_bias"].data;
+            const size_t w = t.data.size();
+            bf16_t* q = (bf16_t*)(host.data() + off[n + "#q"]);
+            for (size_t r = 0; r < w; ++r) {
+                double acc = 0.0;
+                for (size_t c = 0; c < w; ++c) acc += (double)t.data[c] * (double)wq[r * w + c];
+                q[r] = f32_to_bf16_host(((float)acc + bq[r]) * 0.125f);
+            }
         } else if (x3 && is_matrix(n)) {
             // the attention scale in the query rows: 1/8 is a power of two and commutes with the split; 1 / sqrt(80) is applied in fp32 first
             const int64_t rows = t.shape[0], cols = t.shape[1];
@@ -369,14 +439,29 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
             L.w2 = H(b + ".mlp.c_proj.weight"); L.b2 = F(b + ".mlp.c_proj.bias");
         }
     };
-    tower(m->vis, "visual.transformer", m->cfg.v_width, m->cfg.v_layers, m->patches + 1, fp8);
+    tower(m->vis, "visual.transformer", m->cfg.v_width, m->cfg.v_layers, m->vtokens, fp8);
     tower(m->txt, "transformer", m->cfg.t_width, m->cfg.t_layers, m->cfg.ctx, 0);
     m->vis.head_dim = m->v_head_dim;
     m->conv_w = H("visual.conv1.weight");
-    m->cls = F("visual.class_embedding"); m->vpos = F("visual.positional_embedding");
-    m->lnpre_g = F("visual.ln_pre.weight"); m->lnpre_b = F("visual.ln_pre.bias");
+    m->vpos = F("visual.positional_embedding");
     m->lnpost_g = F("visual.ln_post.weight"); m->lnpost_b = F("visual.ln_post.bias");
-    m->vproj = F("visual.proj");
+    if (m->family == 1) {
+        const std::string h = "visual.attn_pool";
+        const size_t vw = (size_t)m->cfg.v_width;
+        m->cls = m->lnpre_g = m->lnpre_b = m->vproj = nullptr;
+        m->mh_q = H(h + ".probe#q");
+        m->mh_wkv = H(h + ".in_proj_weight") + vw * vw; m->mh_bkv = F(h + ".in_proj_bias") + vw;
+        m->mh_wo = H(h + ".out_proj.weight"); m->mh_bo = F(h + ".out_proj.bias");
+        m->mh_ln_g = F(h + ".ln.weight"); m->mh_ln_b = F(h + ".ln.bias");
+        m->mh_w1 = H(h + ".mlp.c_fc.weight"); m->mh_b1 = F(h + ".mlp.c_fc.bias");
+        m->mh_w2 = H(h + ".mlp.c_proj.weight"); m->mh_b2 = F(h + ".mlp.c_proj.bias");
+        m->tproj_b = F("text_projection_bias");
+    } else {
+        m->cls = F("visual.class_embedding");
+        m->lnpre_g = F("visual.ln_pre.weight"); m->lnpre_b = F("visual.ln_pre.bias");
+        m->vproj = F("visual.proj");
+        m->tproj_b = nullptr;
+    }
     m->tok = F("token_embedding.weight"); m->tpos = F("positional_embedding");
     m->lnf_g = F("ln_final.weight"); m->lnf_b = F("ln_final.bias"); m->tproj = F("text_projection");
 
@@ -480,8 +565,11 @@ int carve(Workspace& w, void* base, size_t bytes, int width, int64_t rows, int i
 // buffers, 2 of the block's 12 W^2 of GEMM work per token row instead of 12.  The pooled rows see the same arithmetic (their GEMMs
 // are smaller launches, routed to the skinny / 128-row kernels, with their summation order).  *compact = the tail reads xc / d1c / d2c.
 // epi_act: the fc1 epilogue (option "activation"), EPI_BIAS_QGELU_BF16 or EPI_BIAS_GELU_BF16; nothing else depends on the activation.
+// eps: every LayerNorm's epsilon.  pool_pos (causal == 0 only): the position of the pooled row, 0 = the class token; family 1's text
+// tower is unmasked and pools its LAST position, so its last block runs the pooled-row form with pool_pos = ctx - 1.
 int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int fp8, int want_resadd, int epi_act, hipStream_t s, bool* pending,
-               const int* row_start = nullptr, int rows = 0, int last_pooled = 0, const int32_t* ids = nullptr, bool* compact = nullptr) {
+               const int* row_start = nullptr, int rows = 0, int last_pooled = 0, const int32_t* ids = nullptr, bool* compact = nullptr,
+               float eps = 1e-5f, int pool_pos = 0) {
     const int W = t.width, M = row_start ? rows : batch * t.tokens;
     const bool fq = fp8 & 1, f1 = fp8 & 2;          // LayerNorm output = A operand of QKV / fc1: e4m3 where that GEMM runs in fp8
     bool resadd = want_resadd >= (w.x_dtype == KEMR_BF16 ? 1 : 2) && M > 512 && W % 256 == 0 && w.x_dtype != KEMR_F24;
@@ -496,11 +584,11 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int f
     *pending = !resadd && t.layers > 0;
     const bool pooled = last_pooled && compact && !resadd && !f1 && t.layers > 0 && t.tokens <= KEMR_MAX_VISION_TOKENS;
     if (compact) *compact = pooled;
-    if (pooled) KEMR_TRY(launch_pool_index(causal ? ids : nullptr, row_start, batch, t.tokens, w.pool_idx, s));
+    if (pooled) KEMR_TRY(launch_pool_index(causal ? ids : nullptr, row_start, batch, t.tokens, w.pool_idx, s, pool_pos));
     for (int l = 0; l < t.layers; ++l) {
         const LayerW& L = t.layer[l];
         if (pooled && l == t.layers - 1) {
-            KEMR_TRY(launch_layernorm(w.x, w.x_dtype, l ? w.delta : nullptr, l ? w.delta2 : nullptr, 1, L.ln1_g, L.ln1_b, w.h, M, W, fq ? KEMR_FP8 : KEMR_BF16, s));
+            KEMR_TRY(launch_layernorm(w.x, w.x_dtype, l ? w.delta : nullptr, l ? w.delta2 : nullptr, 1, L.ln1_g, L.ln1_b, w.h, M, W, fq ? KEMR_FP8 : KEMR_BF16, s, eps));
             GemmParams g{};
             g.c_rows_padded = 1;
             // K and V of every row: the weight rows W .. 3W - 1 of in_proj, into the columns W .. 3W - 1 of the qkv buffer; then the query of
@@ -516,15 +604,15 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int f
             else KEMR_TRY(launch_attention_pooled(w.qc, w.big, w.ac, w.pool_idx, row_start, batch, t.tokens, W, causal, s));
             g.A = w.ac; g.W = L.wo; g.bias = L.bo; g.C = w.d1c;
             KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
-            KEMR_TRY(launch_layernorm(w.xc, w.x_dtype, w.d1c, nullptr, 0, L.ln2_g, L.ln2_b, w.hc, batch, W, KEMR_BF16, s));
+            KEMR_TRY(launch_layernorm(w.xc, w.x_dtype, w.d1c, nullptr, 0, L.ln2_g, L.ln2_b, w.hc, batch, W, KEMR_BF16, s, eps));
             g.A = w.hc; g.W = L.w1; g.bias = L.b1; g.C = w.gc; g.ldc = 4 * W; g.N = 4 * W;
             KEMR_TRY(launch_gemm(g, epi_act, s));
             g.A = w.gc; g.lda = 4 * W; g.W = L.w2; g.ldw = 4 * W; g.bias = L.b2; g.C = w.d2c; g.ldc = W; g.N = W; g.K = 4 * W;
             KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
             break;
         }
-        if (resadd) KEMR_TRY(launch_layernorm(w.x, w.x_dtype, nullptr, nullptr, 0, L.ln1_g, L.ln1_b, w.h, M, W, fq ? KEMR_FP8 : KEMR_BF16, s));
-        else KEMR_TRY(launch_layernorm(w.x, w.x_dtype, l ? w.delta : nullptr, l ? w.delta2 : nullptr, 1, L.ln1_g, L.ln1_b, w.h, M, W, fq ? KEMR_FP8 : KEMR_BF16, s));
+        if (resadd) KEMR_TRY(launch_layernorm(w.x, w.x_dtype, nullptr, nullptr, 0, L.ln1_g, L.ln1_b, w.h, M, W, fq ? KEMR_FP8 : KEMR_BF16, s, eps));
+        else KEMR_TRY(launch_layernorm(w.x, w.x_dtype, l ? w.delta : nullptr, l ? w.delta2 : nullptr, 1, L.ln1_g, L.ln1_b, w.h, M, W, fq ? KEMR_FP8 : KEMR_BF16, s, eps));
         GemmParams g{};
         g.M = M;
         g.c_rows_padded = 1;       // every workspace buffer has ceil256(M) rows
@@ -541,7 +629,7 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, int causal, int f
         else KEMR_TRY(launch_attention(w.big, w.h, batch, t.tokens, W, causal, s));
         g.A = w.h; g.lda = W; g.W = L.wo; g.ldw = W; g.bias = L.bo; g.C = resadd ? w.x : (void*)w.delta; g.ldc = W; g.N = W; g.K = W;
         KEMR_TRY(launch_gemm(g, resadd ? epi_res : EPI_BIAS_BF16, s));
-        KEMR_TRY(launch_layernorm(w.x, w.x_dtype, resadd ? nullptr : w.delta, nullptr, 0, L.ln2_g, L.ln2_b, w.h, M, W, f1 ? KEMR_FP8 : KEMR_BF16, s));
+        KEMR_TRY(launch_layernorm(w.x, w.x_dtype, resadd ? nullptr : w.delta, nullptr, 0, L.ln2_g, L.ln2_b, w.h, M, W, f1 ? KEMR_FP8 : KEMR_BF16, s, eps));
         g.A = w.h; g.lda = W; g.W = L.w1; g.ldw = W; g.bias = L.b1; g.C = w.big; g.ldc = 4 * W; g.N = 4 * W; g.K = W;
         if (f1) {
             g.W = (const bf16_t*)L.w18; g.wscale = L.s1;
@@ -567,15 +655,39 @@ int image_front(kemr_model* m, const float* pixels_dev, int batch, const void* o
     if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
     if (m->x3) KEMR_FAIL(KEMR_ERR_STATE, "%s: not available for a KEMR_PREC_FP32X3 model", what);
     if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
-    if ((int64_t)batch * (m->patches + 1) > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
-    const int W = m->cfg.v_width, T = m->patches + 1;
+    if ((int64_t)batch * m->vtokens > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
+    const int W = m->cfg.v_width, T = m->vtokens;
     KEMR_TRY(carve(w, workspace_dev, workspace_bytes, W, (int64_t)batch * T, batch, m->res_dtype));
     KEMR_TRY(launch_im2col(pixels_dev, w.big, batch, m->cfg.image_size, m->cfg.patch, m->kpad, s));
     GemmParams g{};
     g.A = w.big; g.lda = m->kpad; g.W = m->conv_w; g.ldw = m->kpad; g.bias = nullptr; g.C = w.x32; g.ldc = W;
     g.pos = m->vpos; g.patches = m->patches; g.M = batch * m->patches; g.N = W; g.K = m->kpad;
+    // family 1: no class token -- row m is patch m % patches of image m / patches; vpos holds pos + the conv bias
+    if (m->family == 1) return launch_gemm(g, EPI_PATCH_ROWS_F32, s);
     KEMR_TRY(launch_gemm(g, EPI_PATCH_F32, s));
     return launch_cls_rows(w.x32, m->cls, m->vpos, batch, T, W, s);
+}
+
+// Family 1's vision pooling (SiglipMultiheadAttentionPoolingHead) on h = ln_post of EVERY token row [batch * T, W]: k | v of every row
+// into the k and v planes of w.big (ld 3 W), the one learned query against them (the pooled-row attention kernel's vision form),
+// r = out_proj(attn), out = r + fc2(gelu_tanh(fc1(layernorm(r)))), optionally L2-normalised.  The M = batch launches take the skinny
+// GEMM route; r and the MLP update are bf16 GEMM outputs like every block's updates and are summed in fp32.
+int map_head(const kemr_model* m, const Workspace& w, const bf16_t* h, int batch, int normalize, float* out, hipStream_t s) {
+    const int W = m->cfg.v_width, T = m->vtokens;
+    GemmParams g{};
+    g.c_rows_padded = 1;
+    g.M = batch * T; g.A = h; g.lda = W; g.W = m->mh_wkv; g.ldw = W; g.bias = m->mh_bkv; g.C = w.big + W; g.ldc = 3 * W; g.N = 2 * W; g.K = W;
+    KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
+    KEMR_TRY(launch_broadcast_row(m->mh_q, w.qc, batch, W, s));
+    KEMR_TRY(launch_attention_pooled(w.qc, w.big, w.ac, nullptr, nullptr, batch, T, W, 0, s));
+    g.M = batch; g.A = w.ac; g.W = m->mh_wo; g.bias = m->mh_bo; g.C = w.d1c; g.ldc = W; g.N = W;
+    KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
+    KEMR_TRY(launch_layernorm(w.d1c, KEMR_BF16, nullptr, nullptr, 0, m->mh_ln_g, m->mh_ln_b, w.hc, batch, W, KEMR_BF16, s, m->eps));
+    g.A = w.hc; g.W = m->mh_w1; g.bias = m->mh_b1; g.C = w.gc; g.ldc = 4 * W; g.N = 4 * W;
+    KEMR_TRY(launch_gemm(g, EPI_BIAS_TGELU_BF16, s));
+    g.A = w.gc; g.lda = 4 * W; g.W = m->mh_w2; g.ldw = 4 * W; g.bias = m->mh_b2; g.C = w.d2c; g.ldc = W; g.N = W; g.K = 4 * W;
+    KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
+    return launch_add_rows_out(w.d1c, w.d2c, batch, W, normalize, out, s);
 }
 
 // Text: the token + positional embedding rows of the residual stream (w.x, the model's storage type).  packed: lens_dev gives the
@@ -699,7 +811,8 @@ int encode_text_x3(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_de
     return launch_tail(w.x, KEMR_F32, nullptr, nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s, row_start);
 }
 
-int fc1_epilogue(const kemr_model* m) { return m->activation == 1 ? EPI_BIAS_GELU_BF16 : EPI_BIAS_QGELU_BF16; }
+// family 1's activation is the family's (tanh GELU); option "activation" is not consulted there
+int fc1_epilogue(const kemr_model* m) { return m->family == 1 ? EPI_BIAS_TGELU_BF16 : m->activation == 1 ? EPI_BIAS_GELU_BF16 : EPI_BIAS_QGELU_BF16; }
 
 }  // namespace
 
@@ -709,7 +822,7 @@ extern "C" size_t kemr_workspace_bytes(const kemr_model* m, int tower, int batch
         if (tower == KEMR_TOWER_VISION) return ws_bytes_x3(m->cfg.v_width, (int64_t)batch * (m->patches + 1));
         return tower == KEMR_TOWER_TEXT ? ws_bytes_x3(m->cfg.t_width, (int64_t)batch * m->cfg.ctx) : 0;
     }
-    if (tower == KEMR_TOWER_VISION) return ws_bytes(m->cfg.v_width, m->patches + 1, batch, m->res_dtype) + compact_bytes(m->cfg.v_width, batch);
+    if (tower == KEMR_TOWER_VISION) return ws_bytes(m->cfg.v_width, m->vtokens, batch, m->res_dtype) + compact_bytes(m->cfg.v_width, batch);
     if (tower == KEMR_TOWER_TEXT) return ws_bytes(m->cfg.t_width, m->cfg.ctx, batch, m->res_dtype) + compact_bytes(m->cfg.t_width, batch);
     return 0;
 }
@@ -728,9 +841,17 @@ extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int bat
     Workspace w;
     KEMR_TRY(image_front(m, pixels_dev, batch, out_dev, workspace_dev, workspace_bytes, s, "encode_image", w));
     if (batch == 0) return KEMR_OK;
-    const int W = m->cfg.v_width, T = m->patches + 1;
-    KEMR_TRY(launch_layernorm(w.x32, KEMR_F32, nullptr, nullptr, 0, m->lnpre_g, m->lnpre_b, w.x, batch * T, W, w.x_dtype, s));
+    const int W = m->cfg.v_width, T = m->vtokens;
     bool vb = false, vc = false;
+    if (m->family == 1) {
+        // no ln_pre: the front's fp32 rows enter block 0 in the stream's storage type; every row of the last block feeds the pooling
+        // head, so option "last_block_pooled_row" cannot apply; ln_post (applying the last block's pending updates) runs over all rows
+        KEMR_TRY(launch_stream_cast(w.x32, w.x, w.x_dtype, (int64_t)batch * T, W, s));
+        KEMR_TRY(run_blocks(m->vis, w, batch, 0, 0, m->resadd, fc1_epilogue(m), s, &vb, nullptr, 0, 0, nullptr, nullptr, m->eps));
+        KEMR_TRY(launch_layernorm(w.x, w.x_dtype, vb ? w.delta : nullptr, vb ? w.delta2 : nullptr, vb ? 1 : 0, m->lnpost_g, m->lnpost_b, w.h, batch * T, W, KEMR_BF16, s, m->eps));
+        return map_head(m, w, w.h, batch, normalize, out_dev, s);
+    }
+    KEMR_TRY(launch_layernorm(w.x32, KEMR_F32, nullptr, nullptr, 0, m->lnpre_g, m->lnpre_b, w.x, batch * T, W, w.x_dtype, s));
     KEMR_TRY(run_blocks(m->vis, w, batch, 0, m->fp8, m->resadd, fc1_epilogue(m), s, &vb, nullptr, 0, m->last_pooled, nullptr, &vc));
     if (vc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnpost_g, m->lnpost_b, m->vproj, m->cfg.embed_dim, normalize, out_dev, s));
     else KEMR_TRY(launch_tail(w.x, w.x_dtype, vb ? w.delta : nullptr, vb ? w.delta2 : nullptr, nullptr, batch, T, W, m->lnpost_g, m->lnpost_b, m->vproj, m->cfg.embed_dim, normalize, out_dev, s));
@@ -747,6 +868,12 @@ extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch
     if (batch == 0) return KEMR_OK;
     const int W = m->cfg.t_width, T = m->cfg.ctx;
     bool tb = false, tc = false;
+    if (m->family == 1) {
+        // no mask (pads are keys like every other position), the LAST position pooled whatever the ids, the head a Linear with bias
+        KEMR_TRY(run_blocks(m->txt, w, batch, 0, 0, m->resadd, fc1_epilogue(m), s, &tb, nullptr, 0, m->last_pooled, nullptr, &tc, m->eps, T - 1));
+        if (tc) return launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s, nullptr, m->eps, 0, m->tproj_b);
+        return launch_tail(w.x, w.x_dtype, tb ? w.delta : nullptr, tb ? w.delta2 : nullptr, nullptr, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s, nullptr, m->eps, T - 1, m->tproj_b);
+    }
     KEMR_TRY(run_blocks(m->txt, w, batch, 1, 0, m->resadd, fc1_epilogue(m), s, &tb, nullptr, 0, m->last_pooled, ids_dev, &tc));
     if (tc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
     else KEMR_TRY(launch_tail(w.x, w.x_dtype, tb ? w.delta : nullptr, tb ? w.delta2 : nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
@@ -765,6 +892,8 @@ extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch
 extern "C" int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
                                        int normalize, void* workspace_dev, size_t workspace_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
+    if (m && m->family == 1)
+        KEMR_FAIL(KEMR_ERR_INVALID, "encode_text_packed: not available for family 1 (SigLIP): its text tower is unmasked and pools the last position, so a pad position is a key and no row can be left out");
     if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, lens_dev, rows, batch, true, out_dev, normalize, workspace_dev, workspace_bytes, s);
     Workspace w;
     int* row_start = nullptr;
@@ -792,7 +921,16 @@ extern "C" int kemr_model_set_option(kemr_model* m, const char* key, int value) 
         m->stream24 = value;
         return KEMR_OK;
     }
+    if (!strcmp(key, "family")) {
+        if (value < 0 || value > 1) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): 0 (CLIP) or 1 (SigLIP), got %d", value);
+        if (m->any_loaded || m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "model_set_option(family): set it before the first kemr_model_load_tensor (it decides the tensor names)");
+        if (value == 1 && m->v_head_dim != 64) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): family 1 (SigLIP) serves vision_head_dim 64 only, got %d", m->v_head_dim);
+        m->family = value;
+        build_names(m);
+        return KEMR_OK;
+    }
     if (!strcmp(key, "vision_head_dim")) {
+        if (m->family == 1 && value != 64) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): family 1 (SigLIP) serves vision_head_dim 64 only, got %d", value);
         if (value != 64 && value != 80) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): 64 or 80, got %d", value);
         if (m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "model_set_option(vision_head_dim): set it before kemr_model_finalize");
         if (m->cfg.v_width % value) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): the vision width %d is not a multiple of %d", m->cfg.v_width, value);
@@ -819,6 +957,7 @@ extern "C" int kemr_model_get_option(const kemr_model* m, const char* key, int* 
     if (!strcmp(key, "residual_stream_24bit")) { *value = (m->finalized && !m->x3) ? (m->res_dtype == KEMR_F24) : m->stream24; return KEMR_OK; }
     if (!strcmp(key, "activation")) { *value = m->activation; return KEMR_OK; }
     if (!strcmp(key, "vision_head_dim")) { *value = m->v_head_dim; return KEMR_OK; }
+    if (!strcmp(key, "family")) { *value = m->family; return KEMR_OK; }
     if (!strcmp(key, "precision_residual_bf16")) { *value = m->res_dtype == KEMR_BF16; return KEMR_OK; }
     KEMR_FAIL(KEMR_ERR_INVALID, "model_get_option: unknown key '%s'", key);
 }
@@ -938,8 +1077,27 @@ extern "C" int kemr_debug_image_tokens(kemr_model* m, const float* pixels_dev, i
     Workspace w;
     KEMR_TRY(image_front(m, pixels_dev, batch, out_dev, workspace_dev, workspace_bytes, s, "debug_image_tokens", w));
     if (batch == 0) return KEMR_OK;
-    const size_t bytes = (size_t)batch * (m->patches + 1) * m->cfg.v_width * 4;
+    const size_t bytes = (size_t)batch * m->vtokens * m->cfg.v_width * 4;
     KEMR_CHECK_HIP(hipMemcpyAsync(out_dev, w.x32, bytes, hipMemcpyDeviceToDevice, s));
+    return KEMR_OK;
+}
+
+// family 1's pooling head alone: h_dev = bf16 [batch * tokens, v_width] post-LayerNorm token rows (copied into the workspace, whose
+// buffers have the pad rows the GEMMs read); attn_out_dev (optional) receives the attention output rows bf16 [batch, v_width]
+extern "C" int kemr_debug_map_head(kemr_model* m, const void* h_dev, int batch, void* attn_out_dev, float* out_dev, int normalize,
+                                   void* workspace_dev, size_t workspace_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!m || !h_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_map_head: null argument");
+    if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "debug_map_head: model not finalized");
+    if (m->family != 1) KEMR_FAIL(KEMR_ERR_INVALID, "debug_map_head: only family 1 (SigLIP) has a pooling head");
+    if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("debug_map_head: negative batch"), KEMR_ERR_INVALID);
+    if ((int64_t)batch * m->vtokens > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "debug_map_head: batch %d too large", batch);
+    const int W = m->cfg.v_width, T = m->vtokens;
+    Workspace w;
+    KEMR_TRY(carve(w, workspace_dev, workspace_bytes, W, (int64_t)batch * T, batch, m->res_dtype));
+    KEMR_CHECK_HIP(hipMemcpyAsync(w.h, h_dev, (size_t)batch * T * W * 2, hipMemcpyDeviceToDevice, s));
+    KEMR_TRY(map_head(m, w, w.h, batch, normalize, out_dev, s));
+    if (attn_out_dev) KEMR_CHECK_HIP(hipMemcpyAsync(attn_out_dev, w.ac, (size_t)batch * W * 2, hipMemcpyDeviceToDevice, s));
     return KEMR_OK;
 }
 
@@ -993,7 +1151,7 @@ extern "C" int kemr_profile_end(double* ms_per_class, int64_t* launches_per_clas
 extern "C" int kemr_op_gemm(const void* a_dev, const void* w_dev, const float* bias_dev, void* c_dev, int m, int n, int k,
                             int epilogue, void* stream) {
     if (!a_dev || !w_dev || !c_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_gemm: null argument");
-    if (epilogue < 0 || (epilogue > KEMR_EPI_BIAS_RESID_F32 && epilogue != KEMR_EPI_BIAS_RESADD_BF16 && epilogue != KEMR_EPI_BIAS_GELU_BF16)) KEMR_FAIL(KEMR_ERR_INVALID, "op_gemm: bad epilogue %d", epilogue);
+    if (epilogue < 0 || (epilogue > KEMR_EPI_BIAS_RESID_F32 && epilogue != KEMR_EPI_BIAS_RESADD_BF16 && epilogue != KEMR_EPI_BIAS_GELU_BF16 && epilogue != KEMR_EPI_BIAS_TGELU_BF16)) KEMR_FAIL(KEMR_ERR_INVALID, "op_gemm: bad epilogue %d", epilogue);
     GemmParams g{};
     g.A = (const bf16_t*)a_dev; g.lda = k; g.W = (const bf16_t*)w_dev; g.ldw = k; g.bias = bias_dev; g.C = c_dev; g.ldc = n;
     g.M = m; g.N = n; g.K = k;

@@ -97,6 +97,29 @@ __device__ __forceinline__ f32x2_t quick_gelu2(f32x2_t v) {
     r.y = __builtin_amdgcn_rcpf(d.y);
     return v * r;
 }
+// tanh GELU 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) (torch's approximate="tanh", Hugging Face "gelu_pytorch_tanh": SigLIP) in its
+// sigmoid form x sigmoid(2 sqrt(2 / pi) (x + 0.044715 x^3)) -- the same function (1 + tanh(u) = 2 sigmoid(2 u)), so the QuickGELU
+// epilogue with a cubic argument: one v_exp_f32 and one v_rcp_f32 per element.  Large |x| as there: the cube overflows to +-inf only
+// beyond |x| ~ 4e12, exp2 gives 0 or +inf, rcp 1 or 0, and the result is x or -0.
+__device__ __forceinline__ float gelu_tanh(float v) {
+    const float u = v * fmaf(v * v, 0.044715f, 1.0f);
+    return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.5957691216057308f * 1.4426950408889634f * u));
+}
+// two at a time, like quick_gelu2
+__device__ __forceinline__ f32x2_t gelu_tanh2(f32x2_t v) {
+    f32x2_t c;
+    c.x = fmaf(v.x * v.x, 0.044715f, 1.0f);
+    c.y = fmaf(v.y * v.y, 0.044715f, 1.0f);
+    const f32x2_t t = (v * c) * (-1.5957691216057308f * 1.4426950408889634f);
+    f32x2_t e;
+    e.x = __builtin_amdgcn_exp2f(t.x);
+    e.y = __builtin_amdgcn_exp2f(t.y);
+    const f32x2_t d = e + 1.0f;
+    f32x2_t r;
+    r.x = __builtin_amdgcn_rcpf(d.x);
+    r.y = __builtin_amdgcn_rcpf(d.y);
+    return v * r;
+}
 // Exact GELU 0.5 x (1 + erf(x / sqrt 2)) in its erfc form 0.5 x erfc(-x / sqrt 2): erfc keeps RELATIVE accuracy where 1 + erf cancels
 // (x < -3: the erf form is off by up to 1.4 |x| 2^-24 absolute, hundreds of bf16 ulps of the result).  erfcf is the device library's
 // (branches over literal-coefficient polynomials, no table: nothing enters the vector-memory counter).  The tail of erfc amplifies an
@@ -149,6 +172,8 @@ enum GemmEpi : int {
     EPI_BIAS_RESID_F32 = KEMR_EPI_BIAS_RESID_F32,
     EPI_PATCH_F32 = 3,
     EPI_BIAS_GELU_BF16 = KEMR_EPI_BIAS_GELU_BF16,       // C_bf16 = gelu(A.W^T + bias), exact (erf) GELU: the same class as EPI_BIAS_QGELU_BF16 everywhere
+    EPI_BIAS_TGELU_BF16 = KEMR_EPI_BIAS_TGELU_BF16,     // C_bf16 = gelu_tanh(A.W^T + bias) (SigLIP), the same class again
+    EPI_PATCH_ROWS_F32 = 7,                             // X_f32[m] = acc + pos[m % patches] (patch embedding of a tower without a class token; the dispatch of EPI_PATCH_F32: 128 x 128 or 256 x 256 tiles)
     // KEMR_PREC_FP32X3 (gemm.hip launch_gemm_x3; A [M, 3K] = [hi | lo | hi], W [N, 3K] = [hi | hi | lo], p.K = 3K): fp32 stores, or the
     // activation in fp32 stored as the next GEMM's A-side triple [M, 3N] (ldc = 3N)
     EPI_X3_F32 = 16,                                    // C_f32 = acc + bias
@@ -162,7 +187,7 @@ struct GemmParams {
     const float* bias;   // [N] or nullptr
     const float* wscale; // fp8 operands only: [N] per-output-channel scale applied to the accumulators before the bias
     void* C;             // bf16 [m_alloc, ldc] or fp32 [*, ldc] depending on the epilogue
-    const float* pos;    // EPI_PATCH_F32: positional embedding [1 + patches, N]
+    const float* pos;    // EPI_PATCH_F32: positional embedding [1 + patches, N]; EPI_PATCH_ROWS_F32: [patches, N]
     int M, N, K;         // M = valid rows (stores are guarded), N % 128 == 0, K % 64 == 0
     int lda, ldw, ldc;
     int patches;         // EPI_PATCH_F32: patches per image (row remap m -> m + m / patches + 1)
@@ -232,8 +257,9 @@ int launch_select_topk(const float* scores, const int32_t* idx, int nq, int n, l
 // delta != nullptr: x += delta (bf16 [rows, width], the previous GEMM's output) is applied first and written back
 // x_dtype (KEMR_F32 / KEMR_BF16) is the storage type of the residual rows
 // delta2 (needs delta and writeback) is added as well; writeback == 0 leaves x as it is and normalises x + delta
+// eps: 1e-5 (CLIP), 1e-6 for the SigLIP family
 int launch_layernorm(void* x, int x_dtype, const bf16_t* delta, const bf16_t* delta2, int writeback, const float* gamma,
-                     const float* beta, void* y, int rows, int width, int out_dtype, hipStream_t stream);
+                     const float* beta, void* y, int rows, int width, int out_dtype, hipStream_t stream, float eps = 1e-5f);
 // KEMR_PREC_FP32X3: y = LayerNorm(x) of fp32 rows stored as the A-side triple [hi | lo | hi] into [ceil256(rows), 3 width] bf16, pad rows zero
 int launch_layernorm_x3(const float* x, const float* gamma, const float* beta, bf16_t* y_panel, int rows, int width, hipStream_t stream);
 // KEMR_PREC_FP32X3 (fp32x3.hip): fp32 q | k | v rows [*, 3 width] -> the attention output as an A-side triple [*, 3 width] bf16; streaming
@@ -253,8 +279,14 @@ int launch_attention80_pooled(const bf16_t* q, const bf16_t* qkv, bf16_t* out, i
 int launch_attention80_x3(const float* qkv, bf16_t* out_panel, int batch, int t, int width, int causal, hipStream_t stream);
 int launch_im2col(const float* pixels, bf16_t* patches, int batch, int image_size, int patch, int kpad, hipStream_t stream);
 int launch_cls_rows(float* x, const float* class_emb, const float* pos, int batch, int tokens, int width, hipStream_t stream);
-// the pooled row of every item (class token: ids == nullptr; else first argmax of the token ids, inside row_start's rows when packed)
-int launch_pool_index(const int32_t* ids, const int* row_start, int batch, int tokens, int* pool_idx, hipStream_t stream);
+// the pooled row of every item (ids == nullptr: position pool_pos, 0 = the class token; else first argmax of the token ids, inside
+// row_start's rows when packed)
+int launch_pool_index(const int32_t* ids, const int* row_start, int batch, int tokens, int* pool_idx, hipStream_t stream, int pool_pos = 0);
+// SigLIP (embed.hip): fp32 token rows -> the residual stream's storage type (no ln_pre does it there); one row [width] copied to `rows`
+// rows (the pooling head's one query); out = a + b (bf16 rows) in fp32, optionally L2-normalised (the pooling head's last step)
+int launch_stream_cast(const float* x32, void* x, int x_dtype, int64_t rows, int width, hipStream_t stream);
+int launch_broadcast_row(const bf16_t* row, bf16_t* out, int rows, int width, hipStream_t stream);
+int launch_add_rows_out(const bf16_t* a, const bf16_t* b, int rows, int width, int normalize, float* out, hipStream_t stream);
 // x[pool_idx[b]] -> xc[b], h[pool_idx[b]] -> hc[b]: compact copies of the pooled rows
 int launch_gather_pooled(const void* x, int x_dtype, const void* h, int h_dtype /* KEMR_BF16 | KEMR_FP8 */, const int* pool_idx, int batch,
                          int width, void* xc, void* hc, hipStream_t stream);
@@ -268,9 +300,10 @@ int launch_row_starts(const int32_t* lens, int batch, int max_len, int rows, int
 // positions, `rows` in total
 int launch_text_embed(const int32_t* ids, const float* tok_emb, const float* pos, void* x, int x_dtype, int batch, int ctx,
                       int width, int vocab, hipStream_t stream, const int* row_start = nullptr, int rows = 0);
-// pooled row -> LayerNorm -> @ proj [width, d] -> optional L2 normalise.  ids == nullptr: row = b * tokens (CLS)
+// pooled row -> LayerNorm -> @ proj [width, d] (+ proj_bias [d]) -> optional L2 normalise.  ids == nullptr: row = b * tokens + pool_pos (0: CLS)
 // delta, delta2 (optional): the last block's pending residual updates, added to the pooled row
 int launch_tail(const void* x, int x_dtype, const bf16_t* delta, const bf16_t* delta2, const int32_t* ids, int batch, int tokens, int width, const float* gamma,
-                const float* beta, const float* proj, int d, int normalize, float* out, hipStream_t stream, const int* row_start = nullptr);
+                const float* beta, const float* proj, int d, int normalize, float* out, hipStream_t stream, const int* row_start = nullptr,
+                float eps = 1e-5f, int pool_pos = 0, const float* proj_bias = nullptr);
 
 }  // namespace kemr

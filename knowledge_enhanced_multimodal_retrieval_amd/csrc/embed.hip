@@ -167,10 +167,10 @@ int launch_text_embed(const int32_t* ids, const float* tok_emb, const float* pos
 // row maximum of its token ids (end-of-text token, torch.argmax semantics) -- inside the rows row_start gives the text when the
 // rows are packed (clamped to its last row, see kemr_encode_text_packed).  One wave per item.
 __global__ __launch_bounds__(256) void pool_index_kernel(const int32_t* __restrict__ ids, const int* __restrict__ row_start, int batch,
-                                                         int tokens, int* __restrict__ pool_idx) {
+                                                         int tokens, int* __restrict__ pool_idx, int pool_pos) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= batch) return;
-    int best_t = 0;
+    int best_t = pool_pos;
     if (ids) {
         int best_v = INT_MIN;
         best_t = INT_MAX;
@@ -194,10 +194,11 @@ __global__ __launch_bounds__(256) void pool_index_kernel(const int32_t* __restri
     }
 }
 
-int launch_pool_index(const int32_t* ids, const int* row_start, int batch, int tokens, int* pool_idx, hipStream_t stream) {
+int launch_pool_index(const int32_t* ids, const int* row_start, int batch, int tokens, int* pool_idx, hipStream_t stream, int pool_pos) {
     if (batch <= 0) return KEMR_OK;
+    if (pool_pos < 0 || pool_pos >= tokens) KEMR_FAIL(KEMR_ERR_INVALID, "pool_index: position %d outside 0 .. %d", pool_pos, tokens - 1);
     ProfScope prof(PROF_OTHER, stream);
-    hipLaunchKernelGGL(pool_index_kernel, dim3((batch + 3) / 4), dim3(256), 0, stream, ids, row_start, batch, tokens, pool_idx);
+    hipLaunchKernelGGL(pool_index_kernel, dim3((batch + 3) / 4), dim3(256), 0, stream, ids, row_start, batch, tokens, pool_idx, pool_pos);
     KEMR_CHECK_LAUNCH("pool_index_kernel");
     return KEMR_OK;
 }
@@ -245,7 +246,8 @@ __global__ __launch_bounds__(256) void tail_proj_kernel(const XT* __restrict__ x
                                                         const bf16_t* __restrict__ delta2, const int32_t* __restrict__ ids,
                                                         int tokens, int width, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, const float* __restrict__ proj,
-                                                        int d, float* __restrict__ out, const int* __restrict__ row_start) {
+                                                        int d, float* __restrict__ out, const int* __restrict__ row_start,
+                                                        float eps, int pool_pos, const float* __restrict__ proj_bias) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* y = (float*)smem;          // [width] normalised row
     float* red = y + width;           // [4]
@@ -253,7 +255,7 @@ __global__ __launch_bounds__(256) void tail_proj_kernel(const XT* __restrict__ x
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
 
     if (tid < 64) {
-        int best_t = 0;
+        int best_t = pool_pos;
         if (ids) {                    // first position of the row maximum (torch.argmax semantics)
             int best_v = INT_MIN;
             best_t = INT_MAX;
@@ -295,7 +297,7 @@ __global__ __launch_bounds__(256) void tail_proj_kernel(const XT* __restrict__ x
     const float mean = block_sum(s, red) / width;
     float q = 0.f;
     for (int i = tid; i < width; i += 256) { const float c = y[i] - mean; q += c * c; }
-    const float rstd = 1.0f / sqrtf(block_sum(q, red) / width + 1e-5f);
+    const float rstd = 1.0f / sqrtf(block_sum(q, red) / width + eps);
     for (int i = tid; i < width; i += 256) y[i] = (y[i] - mean) * rstd * gamma[i] + beta[i];
     __syncthreads();
 
@@ -316,7 +318,13 @@ __global__ __launch_bounds__(256) void tail_proj_kernel(const XT* __restrict__ x
         acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
         acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
     }
-    if (g == 0 && j < d) *(float4*)(out + (size_t)b * d + j) = acc;
+    if (g == 0 && j < d) {
+        if (proj_bias) {               // uniform: the SigLIP text head (a Linear with bias)
+            const float4 pb = *(const float4*)(proj_bias + j);
+            acc.x += pb.x; acc.y += pb.y; acc.z += pb.z; acc.w += pb.w;
+        }
+        *(float4*)(out + (size_t)b * d + j) = acc;
+    }
 }
 
 // Pooling tail, part 2: x / ||x||_2 per row, in place (one wave per row; no eps, like the reference's `x / x.norm()`).
@@ -331,22 +339,100 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(float* __restrict__ x,
 }
 
 int launch_tail(const void* x, int x_dtype, const bf16_t* delta, const bf16_t* delta2, const int32_t* ids, int batch, int tokens, int width, const float* gamma,
-                const float* beta, const float* proj, int d, int normalize, float* out, hipStream_t stream, const int* row_start) {
+                const float* beta, const float* proj, int d, int normalize, float* out, hipStream_t stream, const int* row_start,
+                float eps, int pool_pos, const float* proj_bias) {
     if (batch <= 0) return KEMR_OK;
+    if (pool_pos < 0 || pool_pos >= tokens) KEMR_FAIL(KEMR_ERR_INVALID, "tail: pooled position %d outside 0 .. %d", pool_pos, tokens - 1);
     if (d % 4 != 0 || d <= 0) KEMR_FAIL(KEMR_ERR_INVALID, "tail: embed_dim %d must be a positive multiple of 4", d);
     if (batch > 65535) KEMR_FAIL(KEMR_ERR_INVALID, "tail: batch %d > 65535", batch);
     const size_t smem = (size_t)width * 4 + 32;
     ProfScope prof(PROF_OTHER, stream);
     const dim3 grid((d + 63) / 64, batch);
     if (x_dtype == KEMR_BF16)
-        hipLaunchKernelGGL(tail_proj_kernel<bf16_t>, grid, dim3(256), smem, stream, (const bf16_t*)x, delta, delta2, ids, tokens, width, gamma, beta, proj, d, out, row_start);
+        hipLaunchKernelGGL(tail_proj_kernel<bf16_t>, grid, dim3(256), smem, stream, (const bf16_t*)x, delta, delta2, ids, tokens, width, gamma, beta, proj, d, out, row_start, eps, pool_pos, proj_bias);
     else if (x_dtype == KEMR_F24)
-        hipLaunchKernelGGL(tail_proj_kernel<f24_t>, grid, dim3(256), smem, stream, (const f24_t*)x, delta, delta2, ids, tokens, width, gamma, beta, proj, d, out, row_start);
+        hipLaunchKernelGGL(tail_proj_kernel<f24_t>, grid, dim3(256), smem, stream, (const f24_t*)x, delta, delta2, ids, tokens, width, gamma, beta, proj, d, out, row_start, eps, pool_pos, proj_bias);
     else
-        hipLaunchKernelGGL(tail_proj_kernel<float>, grid, dim3(256), smem, stream, (const float*)x, delta, delta2, ids, tokens, width, gamma, beta, proj, d, out, row_start);
+        hipLaunchKernelGGL(tail_proj_kernel<float>, grid, dim3(256), smem, stream, (const float*)x, delta, delta2, ids, tokens, width, gamma, beta, proj, d, out, row_start, eps, pool_pos, proj_bias);
     KEMR_CHECK_LAUNCH("tail_proj_kernel");
     if (normalize) {
         hipLaunchKernelGGL(l2norm_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, stream, out, batch, d);
+        KEMR_CHECK_LAUNCH("l2norm_rows_kernel");
+    }
+    return KEMR_OK;
+}
+
+// ---- SigLIP: a vision tower without class token and ln_pre, pooled by an attention head ----------------------------------------------
+// fp32 token rows (the patch GEMM's output) -> the residual stream's storage type: what ln_pre's store does in the CLIP towers
+template <typename XT>
+__global__ __launch_bounds__(256) void stream_cast_kernel(const float* __restrict__ x32, XT* __restrict__ x, int width, long long total4) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total4) return;
+    const int w4 = width >> 2;
+    const long long row = gid / w4;
+    const int c4 = (int)(gid - row * w4);
+    const float4 a = ((const float4*)(x32 + (size_t)row * width))[c4];
+    if constexpr (sizeof(XT) == 3) {                   // 24-bit rows: W upper halves, then W third bytes (common.h f24_t)
+        const uint32_t e0 = f32_to_f24_bits(a.x), e1 = f32_to_f24_bits(a.y), e2 = f32_to_f24_bits(a.z), e3 = f32_to_f24_bits(a.w);
+        uint8_t* r = (uint8_t*)(x + (size_t)row * width);
+        uint2 h;
+        h.x = (e0 >> 16) | (e1 & 0xffff0000u);
+        h.y = (e2 >> 16) | (e3 & 0xffff0000u);
+        ((uint2*)r)[c4] = h;
+        ((uint32_t*)(r + 2 * (size_t)width))[c4] = ((e0 >> 8) & 0xff) | (e1 & 0xff00) | ((e2 << 8) & 0xff0000) | ((e3 << 16) & 0xff000000u);
+    } else {
+        uint2 pk;
+        pk.x = pack_bf16x2(a.x, a.y);
+        pk.y = pack_bf16x2(a.z, a.w);
+        ((uint2*)(x + (size_t)row * width))[c4] = pk;
+    }
+}
+
+int launch_stream_cast(const float* x32, void* x, int x_dtype, int64_t rows, int width, hipStream_t stream) {
+    if (rows <= 0 || x_dtype == KEMR_F32) return KEMR_OK;      // an fp32 stream IS the front's rows (Workspace::x32 == x)
+    if (width % 4) KEMR_FAIL(KEMR_ERR_INVALID, "stream_cast: width %d must be a multiple of 4", width);
+    const long long total4 = (long long)rows * (width / 4);
+    ProfScope prof(PROF_OTHER, stream);
+    const dim3 grid((unsigned)((total4 + 255) / 256));
+    if (x_dtype == KEMR_BF16) hipLaunchKernelGGL(stream_cast_kernel<bf16_t>, grid, dim3(256), 0, stream, x32, (bf16_t*)x, width, total4);
+    else hipLaunchKernelGGL(stream_cast_kernel<f24_t>, grid, dim3(256), 0, stream, x32, (f24_t*)x, width, total4);
+    KEMR_CHECK_LAUNCH("stream_cast_kernel");
+    return KEMR_OK;
+}
+
+// the pooling head's one query row (probe . Wq^T + bq, scaled, made at finalize) for every item: the pooled-row attention kernel reads
+// q as compact [items, width] rows
+__global__ __launch_bounds__(256) void broadcast_row_kernel(const bf16_t* __restrict__ row, bf16_t* __restrict__ out, int width) {
+    const uint32_t* src = (const uint32_t*)row;
+    uint32_t* dst = (uint32_t*)(out + (size_t)blockIdx.x * width);
+    for (int i = threadIdx.x; i < (width >> 1); i += 256) dst[i] = src[i];
+}
+
+int launch_broadcast_row(const bf16_t* row, bf16_t* out, int rows, int width, hipStream_t stream) {
+    if (rows <= 0) return KEMR_OK;
+    if (width % 2) KEMR_FAIL(KEMR_ERR_INVALID, "broadcast_row: odd width %d", width);
+    ProfScope prof(PROF_OTHER, stream);
+    hipLaunchKernelGGL(broadcast_row_kernel, dim3(rows), dim3(256), 0, stream, row, out, width);
+    KEMR_CHECK_LAUNCH("broadcast_row_kernel");
+    return KEMR_OK;
+}
+
+// the pooling head's last step: out = r + mlp(layernorm(r)) from the two bf16 GEMM outputs, summed in fp32 (one wave per row)
+__global__ __launch_bounds__(256) void add_rows_out_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, int rows, int width,
+                                                           float* __restrict__ out) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    for (int i = lane; i < width; i += 64)
+        out[(size_t)row * width + i] = bf16_to_f32(a[(size_t)row * width + i]) + bf16_to_f32(b[(size_t)row * width + i]);
+}
+
+int launch_add_rows_out(const bf16_t* a, const bf16_t* b, int rows, int width, int normalize, float* out, hipStream_t stream) {
+    if (rows <= 0) return KEMR_OK;
+    ProfScope prof(PROF_OTHER, stream);
+    hipLaunchKernelGGL(add_rows_out_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, a, b, rows, width, out);
+    KEMR_CHECK_LAUNCH("add_rows_out_kernel");
+    if (normalize) {
+        hipLaunchKernelGGL(l2norm_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, out, rows, width);
         KEMR_CHECK_LAUNCH("l2norm_rows_kernel");
     }
     return KEMR_OK;

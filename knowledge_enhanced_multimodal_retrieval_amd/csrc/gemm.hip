@@ -134,6 +134,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_kernel(const GemmPa
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
             }
+            if constexpr (EPI == EPI_BIAS_TGELU_BF16) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = gelu_tanh(v[r]);
+            }
             if constexpr (EPI == EPI_X3_QGELU) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = quick_gelu(v[r]);
@@ -142,7 +146,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_kernel(const GemmPa
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
             }
-            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16) {
+            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16 || EPI == EPI_BIAS_TGELU_BF16) {
                 uint2 o;
                 o.x = pack_bf16x2(v[0], v[1]);
                 o.y = pack_bf16x2(v[2], v[3]);
@@ -162,6 +166,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt_kernel(const GemmPa
                 *(uint2*)dst = hi;
                 *(uint2*)(dst + p.N) = lo;
                 *(uint2*)(dst + 2 * p.N) = hi;
+            } else if constexpr (EPI == EPI_PATCH_ROWS_F32) {   // no class token: row m stays row m; pos [patches, N] (the conv bias folded in)
+                const float4 pe = *(const float4*)(p.pos + (size_t)(m % p.patches) * p.N + n);
+                *(float4*)((float*)p.C + (size_t)m * p.ldc + n) = make_float4(v[0] + pe.x, v[1] + pe.y, v[2] + pe.z, v[3] + pe.w);
             } else {  // EPI_PATCH_F32: token row = image * (patches + 1) + 1 + patch, plus positional embedding
                 const int img = m / p.patches, pi = m - img * p.patches;
                 const float4 pe = *(const float4*)(p.pos + (size_t)(pi + 1) * p.N + n);
@@ -227,7 +234,7 @@ int launch_gemm(const GemmParams& p, int epi, hipStream_t stream) {
     // 256x256 tiles (one workgroup per CU, deep LDS-DMA pipeline) once there is at least ~half a wave of them
     const bool can256 = p.N % 256 == 0 && p.K >= 128;
     const long tiles256 = (long)((p.M + 255) / 256) * (p.N / 256);
-    const bool bf16_epi = epi == EPI_BIAS_BF16 || epi == EPI_BIAS_QGELU_BF16 || epi == EPI_BIAS_GELU_BF16;
+    const bool bf16_epi = epi == EPI_BIAS_BF16 || epi == EPI_BIAS_QGELU_BF16 || epi == EPI_BIAS_GELU_BF16 || epi == EPI_BIAS_TGELU_BF16;
     if (epi == EPI_BIAS_RESADD_BF16) {        // read-modify-write of the bf16 residual stream: only the persistent kernel has it
         if (!(can256 && p.c_rows_padded && p.M > 512 && gemm256u_fits(p, 2)))
             KEMR_FAIL(KEMR_ERR_INVALID, "gemm: the residual-add epilogue needs N %% 256 == 0, more than 512 rows and a row-padded C (M=%d N=%d K=%d)", p.M, p.N, p.K);
@@ -278,8 +285,10 @@ int launch_gemm(const GemmParams& p, int epi, hipStream_t stream) {
         case EPI_BIAS_BF16:       return launch_cfg<128, 128, 2, 2, EPI_BIAS_BF16>(p, stream);
         case EPI_BIAS_QGELU_BF16: return launch_cfg<128, 128, 2, 2, EPI_BIAS_QGELU_BF16>(p, stream);
         case EPI_BIAS_GELU_BF16:  return launch_cfg<128, 128, 2, 2, EPI_BIAS_GELU_BF16>(p, stream);
+        case EPI_BIAS_TGELU_BF16: return launch_cfg<128, 128, 2, 2, EPI_BIAS_TGELU_BF16>(p, stream);
         case EPI_BIAS_RESID_F32:  return launch_cfg<128, 128, 2, 2, EPI_BIAS_RESID_F32>(p, stream);
         case EPI_PATCH_F32:       return launch_cfg<128, 128, 2, 2, EPI_PATCH_F32>(p, stream);
+        case EPI_PATCH_ROWS_F32:  return launch_cfg<128, 128, 2, 2, EPI_PATCH_ROWS_F32>(p, stream);
     }
     KEMR_FAIL(KEMR_ERR_INVALID, "gemm: unknown epilogue %d", epi);
 }

@@ -193,7 +193,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_bf16_nt_kernel(const GemmParam
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
             }
-            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16) {
+            if constexpr (EPI == EPI_BIAS_TGELU_BF16) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = gelu_tanh(v[r]);
+            }
+            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16 || EPI == EPI_BIAS_TGELU_BF16) {
                 uint2 o;
                 o.x = pack_bf16x2(v[0], v[1]);
                 o.y = pack_bf16x2(v[2], v[3]);
@@ -203,6 +207,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_bf16_nt_kernel(const GemmParam
                 float4 x = *dst;
                 x.x += v[0]; x.y += v[1]; x.z += v[2]; x.w += v[3];
                 *dst = x;
+            } else if constexpr (EPI == EPI_PATCH_ROWS_F32) {   // no class token: row m stays row m; pos [patches, N] (the conv bias folded in)
+                const float4 pe = *(const float4*)(p.pos + (size_t)(m % p.patches) * p.N + n);
+                *(float4*)((float*)p.C + (size_t)m * p.ldc + n) = make_float4(v[0] + pe.x, v[1] + pe.y, v[2] + pe.z, v[3] + pe.w);
             } else {
                 const int img = m / p.patches, pi = m - img * p.patches;
                 const float4 pe = *(const float4*)(p.pos + (size_t)(pi + 1) * p.N + n);
@@ -367,7 +374,11 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_nt_kernel(const GemmPara
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
             }
-            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16) {
+            if constexpr (EPI == EPI_BIAS_TGELU_BF16) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = gelu_tanh(v[r]);
+            }
+            if constexpr (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16 || EPI == EPI_BIAS_TGELU_BF16) {
                 uint2 o;
                 o.x = pack_bf16x2(v[0], v[1]);
                 o.y = pack_bf16x2(v[2], v[3]);
@@ -377,6 +388,9 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_nt_kernel(const GemmPara
                 float4 x = *dst;
                 x.x += v[0]; x.y += v[1]; x.z += v[2]; x.w += v[3];
                 *dst = x;
+            } else if constexpr (EPI == EPI_PATCH_ROWS_F32) {   // no class token: row m stays row m; pos [patches, N] (the conv bias folded in)
+                const float4 pe = *(const float4*)(p.pos + (size_t)(m % p.patches) * p.N + n);
+                *(float4*)((float*)p.C + (size_t)m * p.ldc + n) = make_float4(v[0] + pe.x, v[1] + pe.y, v[2] + pe.z, v[3] + pe.w);
             } else {
                 const int img = m / p.patches, pi = m - img * p.patches;
                 const float4 pe = *(const float4*)(p.pos + (size_t)(pi + 1) * p.N + n);
@@ -419,8 +433,10 @@ int launch_gemm256(const GemmParams& p, int epi, hipStream_t stream) {
         case EPI_BIAS_BF16:       return launch256<EPI_BIAS_BF16>(p, stream);
         case EPI_BIAS_QGELU_BF16: return launch256<EPI_BIAS_QGELU_BF16>(p, stream);
         case EPI_BIAS_GELU_BF16:  return launch256<EPI_BIAS_GELU_BF16>(p, stream);
+        case EPI_BIAS_TGELU_BF16: return launch256<EPI_BIAS_TGELU_BF16>(p, stream);
         case EPI_BIAS_RESID_F32:  return launch256<EPI_BIAS_RESID_F32>(p, stream);
         case EPI_PATCH_F32:       return launch256<EPI_PATCH_F32>(p, stream);
+        case EPI_PATCH_ROWS_F32:  return launch256<EPI_PATCH_ROWS_F32>(p, stream);
     }
     KEMR_FAIL(KEMR_ERR_INVALID, "gemm256: unknown epilogue %d", epi);
 }

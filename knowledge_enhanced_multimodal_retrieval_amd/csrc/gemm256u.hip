@@ -679,7 +679,7 @@ __global__ __launch_bounds__(512, 2) void gemm256u_bf16_nt_kernel(const GemmPara
     // its first K-tile; their LDS region, the last K-tile's A half, is free behind that K-tile's M3) BEFORE its stores, the first K-tile
     // skips them, and its two waits let the 16 stores stay in flight: W(1) is followed by 4 A pieces + 16 stores + W0(2) = 22
     // operations, A(1) by 16 stores + W(2) = 20.  The next wait that covers the stores is K-tile 1's, fourteen intervals behind them.
-    constexpr bool PRE_OK = KEMR_GEMM_PRESTAGE && !LONGK && SIM == 0 && (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16);
+    constexpr bool PRE_OK = KEMR_GEMM_PRESTAGE && !LONGK && SIM == 0 && (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16 || EPI == EPI_BIAS_TGELU_BF16);
     // The counts behind those two waits.  An epilogue, staging plan or store pass that issues a different number of operations must
     // change them: the static_asserts here and in KEMR_STORE_PASS_ fail to compile until it does.
     constexpr int PIECES_PER_STAGE = 2;                                  // KEMR_GLDS per stage_a / stage_w call
@@ -1057,6 +1057,10 @@ __global__ __launch_bounds__(512, 2) void gemm256u_bf16_nt_kernel(const GemmPara
                         const f32x2_t g0 = gelu_erf2(f32x2_t{v[0], v[1]}), g1 = gelu_erf2(f32x2_t{v[2], v[3]});
                         v[0] = g0.x; v[1] = g0.y; v[2] = g1.x; v[3] = g1.y;
                     }
+                    if constexpr (EPI == EPI_BIAS_TGELU_BF16) {     // arithmetic only as well
+                        const f32x2_t g0 = gelu_tanh2(f32x2_t{v[0], v[1]}), g1 = gelu_tanh2(f32x2_t{v[2], v[3]});
+                        v[0] = g0.x; v[1] = g0.y; v[2] = g1.x; v[3] = g1.y;
+                    }
                     o[ni][0] = pack_bf16x2(v[0], v[1]);
                     o[ni][1] = pack_bf16x2(v[2], v[3]);
                 }
@@ -1276,7 +1280,7 @@ static int launch256u(const GemmParams& p, hipStream_t stream) {
     // Epilogues of the two halves in one barrier interval: measured (round 2, same device, sustained) +1.8 % on fc1 + QuickGELU
     // (the VALU-heavy epilogue: 11.1 k -> 9.2 k cycles per tile for both halves), +-0 on the plain store epilogue (single-
     // buffered 3.3 k for both against 2.1 k + 2.9 k one after the other).  g_gemm_conc: 0 never, 1 always, 2 = where it pays.
-    const bool conc = g_gemm_conc == 1 || (g_gemm_conc == 2 && (EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16));
+    const bool conc = g_gemm_conc == 1 || (g_gemm_conc == 2 && (EPI == EPI_BIAS_QGELU_BF16 || EPI == EPI_BIAS_GELU_BF16 || EPI == EPI_BIAS_TGELU_BF16));
     if constexpr (FP8) {
         if (conc) return launch256u_a<EPI, true, false, true>(p, stream);
         return launch256u_a<EPI, true, false, false>(p, stream);
@@ -1442,6 +1446,7 @@ int launch_gemm256u(const GemmParams& p, int epi, hipStream_t stream) {
         case EPI_BIAS_BF16:       return launch256u<EPI_BIAS_BF16, false>(p, stream);
         case EPI_BIAS_QGELU_BF16: return launch256u<EPI_BIAS_QGELU_BF16, false>(p, stream);
         case EPI_BIAS_GELU_BF16:  return launch256u<EPI_BIAS_GELU_BF16, false>(p, stream);
+        case EPI_BIAS_TGELU_BF16: return launch256u<EPI_BIAS_TGELU_BF16, false>(p, stream);
         case EPI_BIAS_RESADD_BF16: return launch256u_a<EPI_BIAS_RESADD_BF16, false, false, false>(p, stream);
         case EPI_BIAS_RESID_F32:
 #ifdef KEMR_AB_VARIANTS

@@ -77,6 +77,10 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(const GemmParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
         }
+        if constexpr (EPI == EPI_BIAS_TGELU_BF16) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = gelu_tanh(v[r]);
+        }
         if (row < p.M) {
             uint2 o;
             o.x = pack_bf16x2(v[0], v[1]);
@@ -96,6 +100,7 @@ int launch_gemm_skinny(const GemmParams& p, int epi, hipStream_t stream) {
         case EPI_BIAS_BF16:       hipLaunchKernelGGL(gemm_skinny_kernel<EPI_BIAS_BF16>, grid, dim3(512), 0, stream, p); break;
         case EPI_BIAS_QGELU_BF16: hipLaunchKernelGGL(gemm_skinny_kernel<EPI_BIAS_QGELU_BF16>, grid, dim3(512), 0, stream, p); break;
         case EPI_BIAS_GELU_BF16:  hipLaunchKernelGGL(gemm_skinny_kernel<EPI_BIAS_GELU_BF16>, grid, dim3(512), 0, stream, p); break;
+        case EPI_BIAS_TGELU_BF16: hipLaunchKernelGGL(gemm_skinny_kernel<EPI_BIAS_TGELU_BF16>, grid, dim3(512), 0, stream, p); break;
         default: KEMR_FAIL(KEMR_ERR_INVALID, "gemm skinny: epilogue %d is not a bf16-store epilogue", epi);
     }
     KEMR_CHECK_LAUNCH("gemm_skinny_kernel");

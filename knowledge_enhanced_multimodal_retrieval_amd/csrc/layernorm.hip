@@ -164,53 +164,53 @@ int g_ln_nt = 3;          // A/B builds: 0 / 1 / 2 = the earlier hint levels (se
 
 template <int NV, typename XT>
 static int launch_nv(XT* x, const bf16_t* d1, const bf16_t* d2, int writeback, const float* g, const float* b, void* y, int rows,
-                     int out_dtype, hipStream_t s) {
+                     int out_dtype, hipStream_t s, float eps) {
     const int blocks = (rows + 3) / 4;
     ProfScope prof(PROF_LAYERNORM, s);
     if (d1 && writeback && out_dtype == KEMR_FP8)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, fp8_t, 1>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (fp8_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, fp8_t, 1>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (fp8_t*)y, rows, eps);
     else if (d1 && out_dtype == KEMR_FP8)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, fp8_t, 2>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (fp8_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, fp8_t, 2>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (fp8_t*)y, rows, eps);
     else if (out_dtype == KEMR_FP8)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, fp8_t, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (fp8_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, fp8_t, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (fp8_t*)y, rows, eps);
 #ifdef KEMR_AB_VARIANTS
     else if (d1 && writeback && g_ln_nt == 0)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 1, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 1, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, eps);
     else if (d1 && g_ln_nt == 0)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 2, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 2, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, eps);
     else if (d1 && writeback && g_ln_nt == 1)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 1, 1>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 1, 1>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, eps);
     else if (d1 && g_ln_nt == 1)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 2, 1>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 2, 1>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, eps);
     else if (d1 && writeback && g_ln_nt == 2)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 1, 2>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 1, 2>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, eps);
 #endif
     else if (d1 && writeback)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 1>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 1>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, eps);
     else if (d1)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 2>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 2>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, eps);
     else if (out_dtype == KEMR_BF16)
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, bf16_t, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (bf16_t*)y, rows, eps);
     else if (out_dtype == KEMR_F24) {                  // ln_pre into a 24-bit stream: fp32 rows in only
         if constexpr (sizeof(XT) == 4)
-            hipLaunchKernelGGL((layernorm_kernel<NV, XT, f24_t, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (f24_t*)y, rows, 1e-5f);
+            hipLaunchKernelGGL((layernorm_kernel<NV, XT, f24_t, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (f24_t*)y, rows, eps);
         else
             KEMR_FAIL(KEMR_ERR_INVALID, "layernorm: 24-bit output rows need fp32 input rows");
     } else
-        hipLaunchKernelGGL((layernorm_kernel<NV, XT, float, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (float*)y, rows, 1e-5f);
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT, float, 0>), dim3(blocks), dim3(256), 0, s, x, d1, d2, g, b, (float*)y, rows, eps);
     KEMR_CHECK_LAUNCH("layernorm_kernel");
     return KEMR_OK;
 }
 
 template <typename XT>
 static int launch_xt(XT* x, const bf16_t* d1, const bf16_t* d2, int writeback, const float* gamma, const float* beta, void* y,
-                     int rows, int width, int out_dtype, hipStream_t stream) {
+                     int rows, int width, int out_dtype, hipStream_t stream, float eps) {
     switch (width) {
-        case 256:  return launch_nv<1>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream);
-        case 512:  return launch_nv<2>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream);
-        case 768:  return launch_nv<3>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream);
-        case 1024: return launch_nv<4>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream);
-        case 1280: return launch_nv<5>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream);
+        case 256:  return launch_nv<1>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream, eps);
+        case 512:  return launch_nv<2>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream, eps);
+        case 768:  return launch_nv<3>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream, eps);
+        case 1024: return launch_nv<4>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream, eps);
+        case 1280: return launch_nv<5>(x, d1, d2, writeback, gamma, beta, y, rows, out_dtype, stream, eps);
     }
     KEMR_FAIL(KEMR_ERR_INVALID, "layernorm: width %d not in {256,512,768,1024,1280}", width);
 }
@@ -243,15 +243,15 @@ int launch_layernorm_x3(const float* x, const float* gamma, const float* beta, b
 // x_dtype: KEMR_F32 or KEMR_BF16 rows.  delta != nullptr: LN(x + delta [+ delta2]); with `writeback` the sum replaces x
 // (delta2 needs writeback); the output is bf16 then.
 int launch_layernorm(void* x, int x_dtype, const bf16_t* delta, const bf16_t* delta2, int writeback, const float* gamma,
-                     const float* beta, void* y, int rows, int width, int out_dtype, hipStream_t stream) {
+                     const float* beta, void* y, int rows, int width, int out_dtype, hipStream_t stream, float eps) {
     if (rows <= 0) return KEMR_OK;
     if (out_dtype != KEMR_BF16 && out_dtype != KEMR_F32 && out_dtype != KEMR_FP8 && out_dtype != KEMR_F24) KEMR_FAIL(KEMR_ERR_INVALID, "layernorm: bad out dtype %d", out_dtype);
     if (x_dtype != KEMR_BF16 && x_dtype != KEMR_F32 && x_dtype != KEMR_F24) KEMR_FAIL(KEMR_ERR_INVALID, "layernorm: bad row dtype %d", x_dtype);
     if (delta && (out_dtype == KEMR_F32 || out_dtype == KEMR_F24)) KEMR_FAIL(KEMR_ERR_INVALID, "layernorm: the residual forms write bf16 or fp8");
     if (delta2 && !(delta && writeback)) KEMR_FAIL(KEMR_ERR_INVALID, "layernorm: a second delta needs the first one and writeback");
-    if (x_dtype == KEMR_BF16) return launch_xt((bf16_t*)x, delta, delta2, writeback, gamma, beta, y, rows, width, out_dtype, stream);
-    if (x_dtype == KEMR_F24) return launch_xt((f24_t*)x, delta, delta2, writeback, gamma, beta, y, rows, width, out_dtype, stream);
-    return launch_xt((float*)x, delta, delta2, writeback, gamma, beta, y, rows, width, out_dtype, stream);
+    if (x_dtype == KEMR_BF16) return launch_xt((bf16_t*)x, delta, delta2, writeback, gamma, beta, y, rows, width, out_dtype, stream, eps);
+    if (x_dtype == KEMR_F24) return launch_xt((f24_t*)x, delta, delta2, writeback, gamma, beta, y, rows, width, out_dtype, stream, eps);
+    return launch_xt((float*)x, delta, delta2, writeback, gamma, beta, y, rows, width, out_dtype, stream, eps);
 }
 
 }  // namespace kemr

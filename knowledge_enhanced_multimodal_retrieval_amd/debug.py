@@ -147,6 +147,21 @@ def image_tokens(eng, pixels, fill: int = 0xff):
     return out
 
 
+def map_head(eng, h, batch: int, normalize: bool = False):
+    """The pooling head of a SigLIP engine on h = bf16 [batch * tokens, v_width] (post-ln_post token rows) -> (out fp32 [batch, v_width],
+    attention output bf16 [batch, v_width])."""
+    import torch
+    a = eng.arch
+    h = h.to(device=eng.device, dtype=torch.bfloat16).contiguous()
+    out = torch.empty((batch, a.v_width), dtype=torch.float32, device=eng.device)
+    attn = torch.empty((batch, a.v_width), dtype=torch.bfloat16, device=eng.device)
+    ws = _front_workspace(eng, int(_lib.lib().kemr_workspace_bytes(eng._h, _lib.TOWER_VISION, batch)), 0)
+    with torch.cuda.device(eng.device):
+        _lib.check(_lib.lib().kemr_debug_map_head(eng._h, _ptr(h), batch, _ptr(attn), _ptr(out), 1 if normalize else 0, _ptr(ws), ws.numel(),
+                                                  _stream(eng.device)), "debug_map_head")
+    return out, attn
+
+
 def residual_dtype(eng) -> int:
     """Storage type of the engine's residual stream: _lib.KEMR_F32, KEMR_BF16 or KEMR_F24."""
     v = C.c_int(0)

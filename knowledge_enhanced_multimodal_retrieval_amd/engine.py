@@ -95,13 +95,19 @@ class ClipEngine:
         self._h = h
         if arch.v_head_dim != 64:                        # before finalize: it decides the scale folded into the vision tower's query rows
             _lib.check(self._L.kemr_model_set_option(self._h, b"vision_head_dim", arch.v_head_dim), "model_set_option")
+        self.family = arch.family
+        if arch.family != "clip":                        # right after create: it decides the tensor names (refused after the first load_tensor)
+            from .config import FAMILIES
+            _lib.check(self._L.kemr_model_set_option(self._h, b"family", FAMILIES[arch.family]), "model_set_option")
         self.activation = "quick_gelu"                   # the library's default; the option is only touched when something else is asked for
-        if activation != self.activation:
+        if activation != self.activation:                # (family "siglip": its tanh GELU is the family's, the option is not consulted)
             self.set_activation(activation)
         self._ws: Dict[object, torch.Tensor] = {}
         self._state: Optional[Mapping[str, torch.Tensor]] = None
         self.ready = False
         self.pack_text = os.environ.get("KEMR_TEXT_PACKED", "1") != "0"     # encode_text: only the positions up to the end-of-text token
+        if arch.family == "siglip":                      # unmasked text tower pooled at the last position: every position counts
+            self.pack_text = False
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -221,7 +227,7 @@ class ClipEngine:
             raise RuntimeError(f"encode_text expects [B,{a.ctx}] token ids, got {tuple(ids.shape)}")
         if not self.ready:
             raise RuntimeError("ClipEngine: load_state_dict() must be called before encoding")
-        pack = self.pack_text and a.ctx <= 128
+        pack = self.pack_text and a.ctx <= 128 and a.family != "siglip"     # never the packed entry point for SigLIP (the library refuses it)
         if pack and not ids.is_cuda:
             # host ids: the lengths are free to compute; caller-supplied ones may only LENGTHEN a text (a length short of the
             # end-of-text token would pool the wrong row: ADVICE r3)

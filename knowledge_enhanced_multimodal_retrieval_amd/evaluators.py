@@ -26,7 +26,6 @@ from . import _lib
 from . import engine
 from . import metrics as M
 from . import sparql_fusion as SF
-from .config import get_arch
 from .datasets import CLIPEvalDatasetHF, CollateAndTokenize, SyntheticHFSplit, SyntheticRawImageDataset, SyntheticRetrievalDataset, collate_fn_eval
 from .preprocess import ClipPreprocessGPU, PackedRaw
 from .logging_utils import save_metrics_to_json, setup_logger
@@ -57,6 +56,30 @@ def load_text2sparql_results(directory: str = TEXT2SPARQL_DIR) -> Dict[str, List
 def default_tokenize(texts: Sequence[str]) -> torch.Tensor:
     from .tokenizer import tokenize
     return tokenize(list(texts), truncate=True)
+
+
+def model_tokenize(model) -> Callable:
+    """The tokenize callable that goes with `model` when the caller names none: CLIP's BPE (`default_tokenize`), or, for a SigLIP
+    model, `tokenizer.siglip_tokenizer` on the directory its `tokenizer_dir` attribute names (`clip.load(<dir>)` sets it to the
+    checkpoint directory; `--tokenizer_dir` / an assignment set it otherwise).  A SigLIP model without one cannot be tokenised for --
+    CLIP's ids are [B, 77] of another vocabulary -- so that is an error here, before any data is read."""
+    arch = getattr(model, "arch", None)
+    if arch is None or getattr(arch, "family", "clip") != "siglip":
+        return default_tokenize
+    directory = getattr(model, "tokenizer_dir", None)
+    if not directory:
+        raise RuntimeError("a SigLIP model needs its own tokenizer and this one names none: it was not loaded from a directory that holds "
+                           "a tokenizer.json.  Set model.tokenizer_dir (evaluator CLIs: --tokenizer_dir DIR) to a directory with the "
+                           "checkpoint's tokenizer.json, or pass tokenize_fn= (pre-tokenised ids [B, %d] always work)" % arch.ctx)
+    from .tokenizer import siglip_tokenizer
+    return siglip_tokenizer(directory, arch.ctx)
+
+
+def model_tokenizer_name(model) -> str:
+    """What the results JSON records under "tokenizer"."""
+    from . import tokenizer
+    fn = model_tokenize(model)
+    return tokenizer.tokenizer_name() if fn is default_tokenize else f"siglip tokenizers ({fn.path})"
 
 
 ENCODE_ITEMS = 255          # items per encoder call in encode_dataset (see there)
@@ -142,6 +165,14 @@ def eval_loader(dataset, batch_size: int, seed: int, num_workers: int, tokenize_
                       multiprocessing_context=loader_context() if num_workers else None)
 
 
+def model_name_arg(value: str) -> str:
+    """`--model_name`: a served model name (clip.available_models()) or a Hugging Face save_pretrained directory on the local disk."""
+    from . import clip_api, hf_checkpoint
+    if value in clip_api.available_models() or hf_checkpoint.is_hf_directory(value):
+        return value
+    raise argparse.ArgumentTypeError(f"{value!r} is neither one of {clip_api.available_models()} nor a directory with a config.json")
+
+
 @torch.no_grad()
 def encode_dataset(model, dataset, batch_size: int = 64, seed: int = 42, num_workers: Optional[int] = 0,
                    tokenize_fn: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, List[str]]:
@@ -151,7 +182,7 @@ def encode_dataset(model, dataset, batch_size: int = 64, seed: int = 42, num_wor
         num_workers = default_loader_workers()
     model.eval()
     device = next(model.parameters()).device
-    tokenize_fn = tokenize_fn or default_tokenize
+    tokenize_fn = tokenize_fn or model_tokenize(model)
     loader = eval_loader(dataset, batch_size, seed, num_workers, tokenize_fn, pin=device.type == "cuda")
     img, qry, tgt, uuids = [], [], [], []
     logger.info(f"Computing embeddings for {len(dataset)} samples...")
@@ -305,7 +336,12 @@ def evaluate_clip_model_baseline(model, dataset, batch_size: int = 64, device: s
 
 # ------------------------------------------------------------------------------------------------ CLIs
 def _common_args(parser, baseline: bool):
-    parser.add_argument("--model_name", type=str, default="ViT-L/14", choices=["ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px", "ViT-H-14"])
+    parser.add_argument("--model_name", type=model_name_arg, default="ViT-L/14",
+                        help="a served model name (clip.available_models(): the CLIP and ViT-*-SigLIP* names), or a Hugging Face "
+                             "save_pretrained directory (CLIP or SigLIP)")
+    parser.add_argument("--tokenizer_dir", type=str, default=None, metavar="DIR",
+                        help="SigLIP models only: the directory whose tokenizer.json tokenises the texts (default: the --model_name "
+                             "directory; a bare ViT-*-SigLIP* name has none and needs this flag)")
     parser.add_argument("--checkpoint", type=str, help="Path to checkpoint, if None uses pretrained model")
     parser.add_argument("--images_dir", type=str, default=None)
     parser.add_argument("--texts_dir", type=str, default=None, help="Directory containing query-target JSON files")
@@ -330,6 +366,16 @@ def _common_args(parser, baseline: bool):
         parser.add_argument("--t2t_weight", type=float, default=0.5)
 
 
+def _bind_tokenizer(model, args) -> None:
+    """--tokenizer_dir onto the model, then the model's tokenize callable built once: a SigLIP model without a tokenizer.json fails
+    here, before the dataset is opened; the flag on a CLIP model is an error, not a silent no-op."""
+    if getattr(args, "tokenizer_dir", None):
+        if model.arch.family != "siglip":
+            raise ValueError(f"--tokenizer_dir is for SigLIP models; {args.model_name!r} is a CLIP model (its BPE vocabulary is built in)")
+        model.tokenizer_dir = args.tokenizer_dir
+    model_tokenize(model)
+
+
 def _run(args, baseline: bool, log_name: str):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
@@ -351,6 +397,7 @@ def _run(args, baseline: bool, log_name: str):
         clip_api.allow_random_weights(True)
         tokenizer.allow_hash_tokenizer(True)
     model, preprocess = load_clip_model(model_name=args.model_name, checkpoint_path=args.checkpoint, device=device)
+    _bind_tokenizer(model, args)
     if args.synthetic > 0 and args.synthetic_images == "float":
         dataset = SyntheticRetrievalDataset(args.synthetic, model.arch.image_size, args.seed)
     elif args.synthetic > 0:
@@ -375,7 +422,7 @@ def _run(args, baseline: bool, log_name: str):
     results = {"model_name": args.model_name, "checkpoint": args.checkpoint, "split": args.split,
                "num_samples": len(dataset), "seed": args.seed, "metrics": metrics,
                # provenance (not in the reference's file): what the numbers were computed with
-               "weights_source": getattr(model, "weights_source", "unknown"), "tokenizer": tokenizer.tokenizer_name(),
+               "weights_source": getattr(model, "weights_source", "unknown"), "tokenizer": model_tokenizer_name(model),
                "precision": _lib.env_precision(), "data": "synthetic" if args.synthetic > 0 else args.dataset,
                "image_transform": {"RawRGB": "gpu (batched kernels, bit-identical to the host transform)", "ClipPreprocess": "host (PIL, per sample)"}.get(
                    type(getattr(dataset, "preprocessor", None)).__name__, "none (pre-normalised tensors)"),
@@ -480,6 +527,7 @@ def _rerank_depth_arg(text: str) -> int:
 def fusion_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="Evaluate Fusion Model")
     parser.add_argument("--model_name", type=str, default="ViT-L/14")
+    parser.add_argument("--tokenizer_dir", type=str, default=None, metavar="DIR", help="SigLIP models only: directory of the tokenizer.json")
     parser.add_argument("--clip_checkpoint", type=str, default=None)
     parser.add_argument("--fusion_checkpoint", type=str, default=None)
     parser.add_argument("--fusion_type", type=str, required=True,
@@ -528,7 +576,8 @@ def main_fusion(argv=None):
         clip_api.allow_random_weights(True)
         tokenizer.allow_hash_tokenizer(True)
     clip_model, preprocess = load_clip_model(model_name=args.model_name, checkpoint_path=args.clip_checkpoint, device=args.device)
-    embed_dim = get_arch(args.model_name).embed_dim       # 768 (ViT-L/14), 512 (ViT-B), 1024 (ViT-H-14)
+    _bind_tokenizer(clip_model, args)
+    embed_dim = clip_model.arch.embed_dim                 # 768 (ViT-L/14), 512 (ViT-B), 1024 (ViT-H-14); a directory states its own
     fusion_model = FusionModel(clip_model=clip_model, fusion_type=args.fusion_type, embed_dim=embed_dim).to(args.device)
     if args.fusion_checkpoint:
         ckpt = torch.load(args.fusion_checkpoint, map_location="cpu", weights_only=True)
@@ -545,7 +594,7 @@ def main_fusion(argv=None):
     results = {"model_name": args.model_name, "clip_checkpoint": args.clip_checkpoint,
                "fusion_checkpoint": args.fusion_checkpoint, "fusion_type": args.fusion_type, "split": args.split,
                "num_samples": len(dataset), "metrics": result,
-               "weights_source": getattr(clip_model, "weights_source", "unknown"), "tokenizer": tokenizer.tokenizer_name(),
+               "weights_source": getattr(clip_model, "weights_source", "unknown"), "tokenizer": model_tokenizer_name(clip_model),
                "precision": _lib.env_precision(), "data": "synthetic" if args.synthetic > 0 else args.dataset}
     if args.output_file:
         Path(args.output_file).parent.mkdir(parents=True, exist_ok=True)

@@ -6,6 +6,9 @@ The reference evaluates its published fine-tuned model through ``transformers.CL
 are transposed), ``pre_layrnorm`` (its spelling) / ``post_layernorm`` / ``final_layer_norm``.  This module maps such a state
 dict onto the OpenAI names the engine loads, and reads ``config.json`` into a :class:`ClipArch` plus the activation.
 
+``transformers.SiglipModel`` directories (``config.json`` with ``model_type: "siglip"``) take the second route of this module:
+:func:`arch_from_siglip_config` and :func:`from_siglip_state_dict` map them onto the names the engine's SigLIP family loads.
+
 Local files only: nothing here (or anywhere in the package) contacts a model hub.
 """
 from __future__ import annotations
@@ -118,6 +121,119 @@ def from_hf_state_dict(sd: Mapping[str, torch.Tensor], arch: ClipArch) -> Dict[s
     return out
 
 
+# what transformers.SiglipTextConfig / SiglipVisionConfig assume for a field that config.json leaves out
+_SIGLIP_TEXT_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_attention_heads=12, num_hidden_layers=12, vocab_size=32000,
+                             max_position_embeddings=64, hidden_act="gelu_pytorch_tanh", layer_norm_eps=1e-6)
+_SIGLIP_VISION_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_attention_heads=12, num_hidden_layers=12, image_size=224,
+                               patch_size=16, hidden_act="gelu_pytorch_tanh", layer_norm_eps=1e-6, vision_use_head=True)
+SIGLIP_ACT = "gelu_pytorch_tanh"
+
+
+def arch_from_siglip_config(cfg: Mapping) -> ClipArch:
+    """``config.json`` of a ``SiglipModel`` (as a dict) -> a ClipArch of family "siglip".  Everything the kernels do not serve is
+    refused with the name of the field: heads of another size than 64 (so400m: 1152 / 16 = 72), an MLP that is not 4 x the width,
+    widths that are not multiples of 256, another activation than ``gelu_pytorch_tanh``, another ``layer_norm_eps`` than 1e-6, a vision
+    tower without the pooling head, a text head that does not project to the vision width."""
+    t, v = _tower(cfg, "text_config", _SIGLIP_TEXT_DEFAULTS), _tower(cfg, "vision_config", _SIGLIP_VISION_DEFAULTS)
+    for side, c in (("text_config", t), ("vision_config", v)):
+        w, heads = int(c["hidden_size"]), int(c["num_attention_heads"])
+        if w <= 0 or w % 256:
+            raise ValueError(f"HF config: {side}.hidden_size = {w} is not a multiple of 256 (the kernels' tile)")
+        if heads <= 0 or w != 64 * heads:
+            raise ValueError(f"HF config: {side}.num_attention_heads = {heads} at hidden_size {w} is a head dim of "
+                             f"{w / max(heads, 1):g}; SigLIP is served at head dim 64 only (B/16 and L/16; so400m has heads of 72)")
+        if int(c["intermediate_size"]) != 4 * w:
+            raise ValueError(f"HF config: {side}.intermediate_size = {c['intermediate_size']} is not 4 x hidden_size ({4 * w})")
+        if c["hidden_act"] != SIGLIP_ACT:
+            raise ValueError(f"HF config: {side}.hidden_act = {c['hidden_act']!r}; the SigLIP family is served with {SIGLIP_ACT!r} only")
+        if float(c["layer_norm_eps"]) != 1e-6:
+            raise ValueError(f"HF config: {side}.layer_norm_eps = {c['layer_norm_eps']!r}; the SigLIP family is served with 1e-06 only")
+    if not v.get("vision_use_head", True):
+        raise ValueError("HF config: vision_config.vision_use_head = false; the engine serves the attention-pooling head only")
+    vw = int(v["hidden_size"])
+    proj = t.get("projection_size")
+    proj = int(t["hidden_size"]) if proj is None else int(proj)
+    if proj != vw:
+        raise ValueError(f"HF config: text_config.projection_size = {proj} differs from vision_config.hidden_size = {vw}: the image "
+                         "embedding is the pooling head's row, there is no vision projection")
+    image, patch = int(v["image_size"]), int(v["patch_size"])
+    if patch <= 0 or image % patch:
+        raise ValueError(f"HF config: vision_config.image_size = {image} is not a multiple of patch_size {patch}")
+    return ClipArch(vw, image, patch, vw, int(v["num_hidden_layers"]), int(t["hidden_size"]), int(t["num_hidden_layers"]),
+                    vocab=int(t["vocab_size"]), ctx=int(t["max_position_embeddings"]), family="siglip")
+
+
+def _siglip_pairs(arch: ClipArch):
+    """(HF key, engine key, how) for every tensor outside the blocks; how: None = as is, "t" = transposed, "flat" = flattened."""
+    h, p = "vision_model.head", "visual.attn_pool"
+    return [("vision_model.embeddings.patch_embedding.weight", "visual.conv1.weight", None),
+            ("vision_model.embeddings.patch_embedding.bias", "visual.conv1.bias", None),
+            ("vision_model.embeddings.position_embedding.weight", "visual.positional_embedding", None),
+            ("vision_model.post_layernorm.weight", "visual.ln_post.weight", None), ("vision_model.post_layernorm.bias", "visual.ln_post.bias", None),
+            (f"{h}.probe", f"{p}.probe", "flat"),
+            (f"{h}.attention.in_proj_weight", f"{p}.in_proj_weight", None), (f"{h}.attention.in_proj_bias", f"{p}.in_proj_bias", None),
+            (f"{h}.attention.out_proj.weight", f"{p}.out_proj.weight", None), (f"{h}.attention.out_proj.bias", f"{p}.out_proj.bias", None),
+            (f"{h}.layernorm.weight", f"{p}.ln.weight", None), (f"{h}.layernorm.bias", f"{p}.ln.bias", None),
+            (f"{h}.mlp.fc1.weight", f"{p}.mlp.c_fc.weight", None), (f"{h}.mlp.fc1.bias", f"{p}.mlp.c_fc.bias", None),
+            (f"{h}.mlp.fc2.weight", f"{p}.mlp.c_proj.weight", None), (f"{h}.mlp.fc2.bias", f"{p}.mlp.c_proj.bias", None),
+            ("text_model.embeddings.token_embedding.weight", "token_embedding.weight", None),
+            ("text_model.embeddings.position_embedding.weight", "positional_embedding", None),
+            ("text_model.final_layer_norm.weight", "ln_final.weight", None), ("text_model.final_layer_norm.bias", "ln_final.bias", None),
+            ("text_model.head.weight", "text_projection", "t"), ("text_model.head.bias", "text_projection_bias", None),
+            ("logit_scale", "logit_scale", None), ("logit_bias", "logit_bias", None)]
+
+
+_BLOCK_PAIRS = [("layer_norm1.weight", "ln_1.weight"), ("layer_norm1.bias", "ln_1.bias"),
+                ("self_attn.out_proj.weight", "attn.out_proj.weight"), ("self_attn.out_proj.bias", "attn.out_proj.bias"),
+                ("layer_norm2.weight", "ln_2.weight"), ("layer_norm2.bias", "ln_2.bias"),
+                ("mlp.fc1.weight", "mlp.c_fc.weight"), ("mlp.fc1.bias", "mlp.c_fc.bias"),
+                ("mlp.fc2.weight", "mlp.c_proj.weight"), ("mlp.fc2.bias", "mlp.c_proj.bias")]
+
+
+def from_siglip_state_dict(sd: Mapping[str, torch.Tensor], arch: ClipArch) -> Dict[str, torch.Tensor]:
+    """``SiglipModel.state_dict()`` -> the engine's SigLIP names (``SigLIP.load_state_dict`` then loads it strictly): q | k | v
+    concatenated into ``in_proj_*``, ``text_model.head.weight`` transposed into ``text_projection``, ``probe`` flattened.
+    ``position_ids`` buffers are ignored; a missing key and any key left over are errors that name it."""
+    left = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
+    out: Dict[str, torch.Tensor] = {}
+
+    def take(key: str) -> torch.Tensor:
+        if key not in left:
+            raise KeyError(f"HF state dict: missing key '{key}'")
+        return left.pop(key)
+
+    for src, dst, how in _siglip_pairs(arch):
+        t = take(src)
+        out[dst] = t.t().contiguous() if how == "t" else (t.reshape(-1) if how == "flat" else t)
+    for src, dst, layers in (("vision_model", "visual.transformer", arch.v_layers), ("text_model", "transformer", arch.t_layers)):
+        for i in range(layers):
+            s, d = f"{src}.encoder.layers.{i}", f"{dst}.resblocks.{i}"
+            out[f"{d}.attn.in_proj_weight"] = torch.cat([take(f"{s}.self_attn.{p}_proj.weight") for p in "qkv"], dim=0)
+            out[f"{d}.attn.in_proj_bias"] = torch.cat([take(f"{s}.self_attn.{p}_proj.bias") for p in "qkv"], dim=0)
+            for a, b in _BLOCK_PAIRS:
+                out[f"{d}.{b}"] = take(f"{s}.{a}")
+    if left:
+        raise KeyError(f"HF state dict: unexpected key '{sorted(left)[0]}' ({len(left)} left over; not a SiglipModel of this architecture)")
+    return out
+
+
+def to_siglip_state_dict(sd: Mapping[str, torch.Tensor], arch: ClipArch) -> Dict[str, torch.Tensor]:
+    """The way back: the engine's SigLIP names -> ``SiglipModel.state_dict()`` keys (what ``SiglipModel.load_state_dict`` takes)."""
+    out: Dict[str, torch.Tensor] = {}
+    for src, dst, how in _siglip_pairs(arch):
+        t = sd[dst]
+        out[src] = t.t().contiguous() if how == "t" else (t.reshape(1, 1, -1) if how == "flat" else t)
+    for src, dst, layers, w in (("vision_model", "visual.transformer", arch.v_layers, arch.v_width), ("text_model", "transformer", arch.t_layers, arch.t_width)):
+        for i in range(layers):
+            s, d = f"{src}.encoder.layers.{i}", f"{dst}.resblocks.{i}"
+            for j, p in enumerate("qkv"):
+                out[f"{s}.self_attn.{p}_proj.weight"] = sd[f"{d}.attn.in_proj_weight"][j * w:(j + 1) * w].contiguous()
+                out[f"{s}.self_attn.{p}_proj.bias"] = sd[f"{d}.attn.in_proj_bias"][j * w:(j + 1) * w].contiguous()
+            for a, b in _BLOCK_PAIRS:
+                out[f"{s}.{a}"] = sd[f"{d}.{b}"]
+    return out
+
+
 def is_hf_directory(path: str) -> bool:
     return os.path.isdir(path) and os.path.isfile(os.path.join(path, "config.json"))
 
@@ -131,10 +247,15 @@ def read_hf_directory(directory: str) -> Tuple[ClipArch, str, Dict[str, torch.Te
     if weights is None:
         raise FileNotFoundError(f"{directory!r} holds neither of {WEIGHT_FILES} (sharded checkpoints are not read)")
     with open(cfg_path) as f:
-        arch, activation = arch_and_activation_from_hf_config(json.load(f))
+        cfg = json.load(f)
+    siglip = cfg.get("model_type") == "siglip"          # every other model_type (and none) takes the CLIPModel route, refusals included
+    if siglip:
+        arch, activation = arch_from_siglip_config(cfg), SIGLIP_ACT
+    else:
+        arch, activation = arch_and_activation_from_hf_config(cfg)
     if weights.endswith(".safetensors"):
         from safetensors.torch import load_file
         sd = load_file(weights)
     else:
         sd = torch.load(weights, map_location="cpu", weights_only=True)
-    return arch, activation, from_hf_state_dict(sd, arch)
+    return arch, activation, (from_siglip_state_dict if siglip else from_hf_state_dict)(sd, arch)

@@ -50,6 +50,27 @@ class ClipPreprocess:
         return f"ClipPreprocess(n_px={self.n_px}, defer_to_gpu={self.defer_to_gpu})"
 
 
+class SiglipPreprocess:
+    """The SigLIP family's host transform (``transformers.SiglipImageProcessor``): RGB -> bicubic resize straight to ``n_px x n_px``
+    (the aspect ratio is NOT kept, nothing is cropped) -> float in [0, 1] -> mean = std = 0.5, i.e. pixels in [-1, 1].  Host only:
+    ``defer_to_gpu`` is always False (the uint8 kernels of csrc/preprocess.hip implement CLIP's resize-and-crop)."""
+
+    defer_to_gpu = False
+
+    def __init__(self, n_px: int = 224):
+        self.n_px = n_px
+
+    def __call__(self, image) -> torch.Tensor:
+        from PIL import Image
+        image = image.convert("RGB").resize((self.n_px, self.n_px), Image.BICUBIC)
+        arr = np.asarray(image, dtype=np.uint8)
+        x = torch.from_numpy(arr.copy()).permute(2, 0, 1).to(torch.float32).div_(255.0)
+        return (x - 0.5) / 0.5
+
+    def __repr__(self):
+        return f"SiglipPreprocess(n_px={self.n_px})"
+
+
 class ClipPreprocessGPU:
     """The same transform as :class:`ClipPreprocess`, computed by the HIP kernels (csrc/preprocess.hip) and bit-identical
     to it: takes a PIL image (RGB is enforced before the resize here; identical for RGB inputs) or a uint8 ``[H, W, 3]``

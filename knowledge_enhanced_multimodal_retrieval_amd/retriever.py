@@ -107,8 +107,8 @@ class CLIPRetriever:
     def __init__(self, model, store: EmbeddingStore, tokenize_fn=None):
         self.model, self.store = model, store
         if tokenize_fn is None:
-            from .evaluators import default_tokenize
-            tokenize_fn = default_tokenize
+            from .evaluators import model_tokenize
+            tokenize_fn = model_tokenize(model)          # CLIP's BPE, or a SigLIP model's own tokenizer.json (model.tokenizer_dir)
         self.tokenize_fn = tokenize_fn
 
     @classmethod

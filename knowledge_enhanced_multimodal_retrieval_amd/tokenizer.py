@@ -192,3 +192,61 @@ def tokenize(texts: Union[str, Sequence[str]], context_length: int = CONTEXT, tr
             ids[-1] = EOT
         out[i, :len(ids)] = torch.tensor(ids, dtype=torch.int32)
     return out
+
+
+# ---- SigLIP: a callable for the `tokenize_fn=` parameters (evaluators, EmbeddingStore.build, CLIPRetriever) -------------------------
+SIGLIP_CONTEXT = 64
+SIGLIP_EOS = 1          # "</s>"; the pad id as well (SigLIP pads with it, and a pad position is a key like every other)
+
+
+def siglip_canonicalize(text: str) -> str:
+    """``SiglipTokenizer.canonicalize_text``: lower-case, ``string.punctuation`` removed, whitespace collapsed and stripped."""
+    import string
+    text = text.lower().translate(str.maketrans("", "", string.punctuation))
+    return re.sub(r"\s+", " ", text).strip()
+
+
+class SiglipTokenize:
+    """``tokenize_fn`` of a SigLIP checkpoint directory: canonicalise, encode with the ``tokenizers`` package from the directory's
+    ``tokenizer.json``, append the end-of-sequence id 1, cut to ``context_length`` keeping that id, pad with id 1 -> int32
+    ``[B, context_length]``.  Picklable (loader workers): the ``tokenizers`` object is rebuilt from the path on first use.
+    ``sentencepiece`` is not a dependency: a directory that holds only ``spiece.model`` cannot be read."""
+
+    def __init__(self, directory: str, context_length: int = SIGLIP_CONTEXT):
+        path = os.path.join(directory, "tokenizer.json") if os.path.isdir(directory) else directory
+        if not os.path.isfile(path):
+            if os.path.isfile(os.path.join(os.path.dirname(path), "spiece.model")):
+                raise FileNotFoundError(f"{directory!r} holds spiece.model but no tokenizer.json: reading a SentencePiece model needs the "
+                                        "sentencepiece package, which this build does not depend on.  Save the fast tokenizer "
+                                        "(tokenizer.json) next to it, or pass pre-tokenised ids")
+            raise FileNotFoundError(f"{path!r} does not exist (a SigLIP directory's tokenizer.json)")
+        self.path, self.context_length = path, int(context_length)
+        self._tok = None
+
+    def __getstate__(self):
+        return {"path": self.path, "context_length": self.context_length, "_tok": None}
+
+    def _tokenizer(self):
+        if self._tok is None:
+            from tokenizers import Tokenizer
+            tok = Tokenizer.from_file(self.path)
+            tok.no_padding()
+            tok.no_truncation()
+            self._tok = tok
+        return self._tok
+
+    def __call__(self, texts: Union[str, Sequence[str]]) -> torch.Tensor:
+        if isinstance(texts, str):
+            texts = [texts]
+        n = self.context_length
+        out = torch.full((len(texts), n), SIGLIP_EOS, dtype=torch.int32)
+        tok = self._tokenizer()
+        for i, t in enumerate(texts):
+            ids = tok.encode(siglip_canonicalize(t), add_special_tokens=False).ids
+            ids = [j for j in ids if j != SIGLIP_EOS][: n - 1] + [SIGLIP_EOS]
+            out[i, : len(ids)] = torch.tensor(ids, dtype=torch.int32)
+        return out
+
+
+def siglip_tokenizer(directory: str, context_length: int = SIGLIP_CONTEXT) -> SiglipTokenize:
+    return SiglipTokenize(directory, context_length)
