@@ -207,6 +207,11 @@ const char* kemr_model_tensor_name(const kemr_model* m, int i);
  *   ids_dev    : int32 [B,ctx]; pooled at the first position of the row maximum (EOT); family 1: at position ctx - 1
  *   out_dev    : fp32 [B, embed_dim]; L2-normalised when normalize != 0
  *   workspace  : >= kemr_workspace_bytes(m, tower, B) bytes, 256-byte aligned, contents don't matter
+ * Memory contract (tests/test_footprint_towers_gpu.py): exactly kemr_workspace_bytes is enough -- nothing before the workspace's first
+ * or behind its last byte is written or can reach `out`; every workspace byte a result depends on is written by the call first (stale
+ * bytes of an earlier call of another batch size or layout, NaN included, cannot reach `out`); exactly B * embed_dim floats of `out`
+ * are written; nothing outside the B items of pixels / ids can reach them.  A workspace that is too small or not 256-byte aligned is
+ * KEMR_ERR_WORKSPACE BEFORE anything is launched: `out` and the workspace keep their bytes.
  * ------------------------------------------------------------------------------------------- */
 size_t kemr_workspace_bytes(const kemr_model* m, int tower /*kemr_tower*/, int batch);
 int kemr_encode_image(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize,
@@ -223,7 +228,7 @@ int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch, float* ou
  *   lens_dev : int32 [B] on the device, each in 1 .. ctx (clamped on the device)
  *   rows     : HOST integer, the sum of lens (the tokenizer's side knows it; B <= rows <= B * ctx is checked, and the device
  *              clamps the prefix sums into it, so no argument can make a kernel index outside the workspace)
- *   workspace: >= kemr_text_packed_workspace_bytes(m, rows, B) bytes
+ *   workspace: >= kemr_text_packed_workspace_bytes(m, rows, B) bytes (exactly that is enough; the memory contract of the encoders above)
  * A length shorter than argmax_i + 1 pools text i's last computed row (memory-safe, not the reference's embedding). */
 size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows, int batch);
 int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
@@ -270,7 +275,11 @@ int kemr_panel_build(const float* const* parts_dev, const float* part_scale, con
  *   well: thresholds from the block maxima of a strided sample of the gallery (about a tenth of the rows at k = 10), one 256 x 256-tile pass that appends the
  *   candidates above a query's threshold to its lists (the rank count rides along), one selection pass.  Same scores, same
  *   order rule, same outputs bit for bit; lists that overflow re-run the slower kernel on the device (no host round trip).
- *   workspace >= kemr_sim_workspace_bytes(nq, ng, kdim, k), 256-byte aligned */
+ *   workspace >= kemr_sim_workspace_bytes(nq, ng, kdim, k), 256-byte aligned; exactly that is enough and its contents don't matter (every
+ *   byte a result depends on is written by the call first).  Written: top_scores / top_idx [nq, k] wholly, ahead [nq] (accumulated);
+ *   nothing else -- the panels, the ground truth and the CSR arrays are only read, inside their sizes.  The panels' pad rows up to
+ *   ceil256 are read as parts of whole tiles, but their contents cannot reach a listed score, an id or a rank (kemr_sim_topk_deep*,
+ *   kemr_scores_dense likewise) */
 size_t kemr_sim_workspace_bytes(int nq, int ng, int64_t kdim, int k);
 int kemr_sim_topk(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim,
                   int64_t gallery_offset, int k, float* top_scores_dev, int32_t* top_idx_dev,
@@ -290,7 +299,8 @@ int kemr_topk_merge(const float* in_scores_dev, const int32_t* in_idx_dev, int n
                     float* out_scores_dev, int32_t* out_idx_dev, void* stream);
 
 /* Dense score tile (for the learned fusion heads that are not GEMM epilogues and for debugging):
- * out fp32 [nq, ng] row-major = q_panel . g_panel^T.  Reference: fusion_model.py:324-325. */
+ * out fp32 [nq, ng] row-major = q_panel . g_panel^T with a row stride of ld_out >= ng floats (rows need no alignment): columns
+ * ng .. ld_out - 1 are not written.  Reference: fusion_model.py:324-325. */
 int kemr_scores_dense(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim,
                       float* out_dev, int64_t ld_out, void* stream);
 
@@ -331,7 +341,8 @@ int kemr_select_topk(const float* scores_dev, const int32_t* idx_dev, int nq, in
  * against the whole gallery go to the workspace through the dense tile kernel (bit-identical to kemr_scores_dense,
  * kemr_pair_scores and kemr_sim_topk), the selection runs on the block.  The block is what the workspace holds, rounded down to
  * a multiple of 128 query rows of ceil4(ng) floats: kemr_sim_topk_deep_workspace_bytes returns the size for min(ceil128(nq),
- * 1024) rows, any 256-byte aligned workspace of at least 128 rows is accepted, anything smaller is KEMR_ERR_WORKSPACE. */
+ * 1024) rows, any 256-byte aligned workspace of at least 128 rows is accepted, anything smaller is KEMR_ERR_WORKSPACE.  The workspace's
+ * contents don't matter; top_scores / top_idx [nq, k] are written wholly and nothing else is. */
 size_t kemr_sim_topk_deep_workspace_bytes(int nq, int ng, int64_t kdim, int k);
 int kemr_sim_topk_deep(const void* q_panel_dev, int nq, const void* g_panel_dev, int ng, int64_t kdim, int64_t gallery_offset,
                        int k, float* top_scores_dev, int32_t* top_idx_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
@@ -433,7 +444,13 @@ typedef enum kemr_epilogue {
                                       x sigmoid(2 sqrt(2/pi) (x + 0.044715 x^3)) (the SigLIP family's fc1; bf16 operands only) */
 } kemr_epilogue;
 /* A bf16 [m_alloc, k] and C [m_alloc, n] with m_alloc = m rounded up to 256 rows (pad rows of A are read; pad rows of C
- * may be written by the bf16 epilogues), W bf16 [n, k], bias fp32 [n] */
+ * may be written by the bf16 epilogues), W bf16 [n, k], bias fp32 [n].
+ * Memory contract of kemr_op_gemm / kemr_op_gemm_fp8 (tests/test_footprint_ops_gpu.py): rows 0 .. m - 1 of C do not depend on A's pad
+ * rows (they may hold NaN) nor on anything outside A's m_alloc rows, W's n rows and the bias' n floats; nothing in front of C and no
+ * row >= m_alloc of C is written.  C's pad rows m .. m_alloc - 1: scratch for the bf16-store epilogues, for KEMR_EPI_BIAS_RESADD_BF16
+ * and for kemr_op_gemm_fp8 (the 256-row-tile kernels store whole tiles); KEMR_EPI_BIAS_RESID_F32 leaves them as they are wherever a
+ * tile kernel with row masks takes the call, i.e. everywhere but on the persistent kernel (m > 512, n % 256 == 0, k >= 128, from 128
+ * output tiles of 256 x 256 up), where they are scratch. */
 /* ---- image preprocessing on the GPU ------------------------------------------------
  * Replaces the per-sample host transform the reference gets from clip.load (src/clip/datasets/clip_dataset.py:110-125):
  * uint8 HWC RGB [height, width, 3] on the device -> Resize(n_px, bicubic, shorter side; Pillow's antialiased two-pass
@@ -467,12 +484,17 @@ int kemr_op_e4m3_host(const float* in, unsigned char* out, long long n);
 int kemr_op_layernorm_resid(float* x_dev, const void* delta_dev, const float* gamma_dev, const float* beta_dev,
                             void* y_dev, int rows, int width, void* stream);
 /* general form: rows of x_dtype (KEMR_F32|KEMR_BF16); y = LayerNorm(x [+ delta [+ delta2]]) (deltas bf16, may be NULL);
- * writeback != 0 stores the sum back into x (required with delta2); without deltas x is only read, unless y_dev == x_dev */
+ * writeback != 0 stores the sum back into x (required with delta2); without deltas x is only read, unless y_dev == x_dev.
+ * Exactly rows x width elements of x, the deltas and y are touched (no pad rows: a row tile is 4 rows, masked at `rows`); without
+ * writeback x keeps its bits.  Row / output types beyond the two above, for the towers and tests: x_dtype 24 (the 24-bit stream rows,
+ * 3 width bytes each) and out_dtype KEMR_FP8 (e4m3 bytes) or 24 (from KEMR_F32 rows only); a delta needs a bf16 or fp8 output. */
 int kemr_op_layernorm_rows(void* x_dev, int x_dtype, const void* delta_dev, const void* delta2_dev, int writeback,
                            const float* gamma_dev, const float* beta_dev, void* y_dev, int rows, int width, int out_dtype,
                            void* stream);
 /* qkv bf16 [batch*t, 3*width] (heads of 64; q pre-scaled by 1/sqrt(64) = 1/8) -> out bf16 [batch*t, width]; t <= 288, or non-causal
- * t <= KEMR_MAX_VISION_TOKENS (streaming kernel); longer causal sequences are KEMR_ERR_INVALID */
+ * t <= KEMR_MAX_VISION_TOKENS (streaming kernel); longer causal sequences are KEMR_ERR_INVALID.  No pad rows on either side: the
+ * ragged last key block and query tile of an item are masked, so exactly batch * t rows of out are written and nothing before row 0 or
+ * behind row batch * t - 1 of qkv can reach them (kemr_op_attention_hd, both head dims, likewise). */
 int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, int t, int width, int causal, void* stream);
 /* the same with the head dim an argument: 64 = kemr_op_attention; 80 (q pre-scaled by 1/sqrt(80), width % 80 == 0): non-causal, t <= 288.
  * A width that is no multiple of the head dim, another head dim, causal or t > 288 at 80: KEMR_ERR_INVALID, nothing is launched. */
@@ -485,7 +507,9 @@ int kemr_op_layernorm_x3(const float* x_dev, const float* gamma_dev, const float
                          void* stream);
 /* gemm_x3: a_panel [ceil256(m), k3] (A side), w_panel [n, k3] (W side), k3 = 3 k with k % 64 == 0, n % 128 == 0, bias fp32 [n] or NULL.
  *   mode 0: c fp32 [m, n] = acc + bias; 1: c fp32 [m, n] += acc + bias; 2 / 3: c = the A-side triple [ceil256(m), 3 n] bf16 of
- *   quick_gelu(acc + bias) / gelu(acc + bias), the activation in fp32 (rows m .. are not written).  One kernel family: 128 x 128 tiles. */
+ *   quick_gelu(acc + bias) / gelu(acc + bias), the activation in fp32 (rows m .. are not written).  One kernel family: 128 x 128 tiles.
+ *   In modes 0 / 1 c has EXACTLY m rows: the last 128-row tile is masked at m, row m is not the library's.  a_panel's pad rows are read
+ *   and cannot reach a row < m. */
 int kemr_op_gemm_x3(const void* a_panel_dev, const void* w_panel_dev, const float* bias_dev, void* c_dev, int m, int n, int k3,
                     int mode /*0 store f32, 1 add into f32 C, 2 quick_gelu -> triple, 3 gelu -> triple*/, void* stream);
 /* attention_x3: qkv fp32 [rows, 3 width] (q pre-scaled by 1/sqrt(head dim) = 1/8; heads of 64) -> out_panel, the A-side triple [rows, 3 width] bf16 of

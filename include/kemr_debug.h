@@ -65,13 +65,15 @@ int kemr_debug_gemm_stamps(unsigned* host_out, int n_words);
 /* Kernels the product reaches only inside a tower, each a pass-through to its launcher (tests/test_numerics_paths_gpu.py).  Device
  * pointers; row_start_dev: batch + 1 ints, item b = the rows row_start[b] .. row_start[b + 1] - 1 (may be NULL where marked).
  * causal attention over packed items: qkv bf16 [rows, 3 width] (q pre-scaled by 1/8) -> out bf16 [rows, width], every length in
- * 1 .. max_t <= 128 */
+ * 1 .. max_t <= 128.  Exactly the rows row_start[0] .. row_start[batch] - 1 of out are written; an item's keys are its own rows (the
+ * rows before row_start[0] and the next item's cannot reach it); batch + 1 ints of row_start are read */
 int kemr_debug_op_attention_packed(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width,
                                    void* stream);
 /* the attention of one query row per item (the last block of a tower): q bf16 [items, width], k / v from qkv bf16 [rows, 3 width],
  * out bf16 [items, width]; keys of item b: vision (causal 0) the `tokens` rows from row_start[b] (NULL: b * tokens), text (causal 1)
  * the rows from row_start[b] (NULL: b * tokens) up to pool_idx[b], at least 1 and at most the instantiation's.  force_long = 1: the
- * 1088-key instantiation even for tokens <= 320 */
+ * 1088-key instantiation even for tokens <= 320.  Exactly items x width elements of out are written; `items` ints of pool_idx and of
+ * row_start are read; no key row outside an item's can reach its output */
 int kemr_debug_op_attention_pooled(const void* q_dev, const void* qkv_dev, void* out_dev, const int* pool_idx_dev,
                                    const int* row_start_dev, int items, int tokens, int width, int causal, int force_long, void* stream);
 /* the same with the head dim an argument: 64 = the call above; 80 (q pre-scaled by 1/sqrt(80), width a multiple of 80): the vision form
@@ -83,14 +85,17 @@ int kemr_debug_op_attention_pooled_hd(const void* q_dev, const void* qkv_dev, vo
 /* the pooling tail: x rows of x_dtype (KEMR_F32, KEMR_BF16 or 24 = the 24-bit rows of the residual stream, W bf16 upper halves
  * then W third bytes per row) [+ delta [+ delta2]] (bf16, may be NULL) at the pooled row -- b * tokens (ids NULL) or the first
  * arg-max of ids [batch, tokens], inside row_start's rows when given (clamped to the item's last row) -- LayerNorm(gamma, beta)
- * @ proj fp32 [width, d] -> out fp32 [batch, d]; normalize != 0: each row divided by its L2 norm.  d % 4 == 0, batch <= 65535 */
+ * @ proj fp32 [width, d] -> out fp32 [batch, d]; normalize != 0: each row divided by its L2 norm.  d % 4 == 0, batch <= 65535.
+ * Exactly batch x d floats of out are written (a d that is no multiple of the 64-column block is masked); read: the pooled rows of x
+ * and the deltas, batch x tokens ids, batch + 1 ints of row_start, width x d floats of proj */
 int kemr_debug_op_tail(const void* x_dev, int x_dtype, const void* delta_dev, const void* delta2_dev, const int32_t* ids_dev,
                        const int* row_start_dev, int batch, int tokens, int width, const float* gamma_dev, const float* beta_dev,
                        const float* proj_dev, int d, int normalize, float* out_dev, void* stream);
 
 /* The token fronts of the encoders (tests/test_numerics_front_gpu.py): the same argument checks, workspace (kemr_workspace_bytes /
  * kemr_text_packed_workspace_bytes) and launches as kemr_encode_image / kemr_encode_text / kemr_encode_text_packed up to the rows
- * the first LayerNorm reads, then a copy of those rows to out_dev.
+ * the first LayerNorm reads, then a copy of those rows to out_dev.  The encoders' memory contract (include/kemr.h): a workspace of exactly
+ * the stated size is enough, its contents don't matter, a small or misaligned one is refused before anything is launched.
  * image: im2col, the patch-embedding GEMM and the class rows -> fp32 [batch * tokens, v_width] (family 1: no class rows, the conv bias added).
  * text: lens_dev NULL = kemr_encode_text's batch * ctx rows, else kemr_encode_text_packed's `rows` rows and row_start_out_dev gets the
  * batch + 1 row starts; the rows in the residual stream's storage type: fp32, bf16 or 24-bit (3 t_width bytes per row: the bf16
@@ -103,7 +108,8 @@ int kemr_debug_text_tokens(struct kemr_model* m, const int32_t* ids_dev, const i
 /* The pooling head of a family-1 (SigLIP) model alone (tests/test_siglip_ops_gpu.py): h_dev = bf16 [batch * tokens, v_width], the
  * ln_post output of every token row, is copied into the workspace (kemr_workspace_bytes of the vision tower), then the head's launches
  * as kemr_encode_image makes them -- k | v GEMM, the one learned query's attention, out-proj, LayerNorm, fc1 + tanh GELU, fc2, add
- * [, L2 normalise] -> out_dev fp32 [batch, v_width]; attn_out_dev (may be NULL) gets the attention output rows, bf16 [batch, v_width] */
+ * [, L2 normalise] -> out_dev fp32 [batch, v_width]; attn_out_dev (may be NULL) gets the attention output rows, bf16 [batch, v_width].
+ * Workspace: exactly kemr_workspace_bytes is enough, contents don't matter (the pad rows of the copied h included), refusals as above */
 int kemr_debug_map_head(struct kemr_model* m, const void* h_dev, int batch, void* attn_out_dev, float* out_dev, int normalize,
                         void* workspace_dev, size_t workspace_bytes, void* stream);
 

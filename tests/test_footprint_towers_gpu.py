@@ -1,0 +1,202 @@
+"""GPU: the encoders inside their workspace (DESIGN.md "Memory contracts"; helper and assertions: tests/footprint.py).
+
+The product carves about fifteen buffers out of one workspace (csrc/api.hip carve / carve_x3): an overrun of h lands in delta, one of
+the compact qc in ac, and several kernels over-read and mask.  Here every entry point runs twice -- with a roomy zero-filled workspace
+(the plain call) and with a workspace of EXACTLY kemr_workspace_bytes / kemr_text_packed_workspace_bytes, every byte 0xff, inside 0xa5
+margins, the pixels in 0xff margins, ids and lens in 0x7fffffff margins, `out` in 0xa5 margins -- and must give the same bits (A1)
+with every margin intact (A2).  Then the refusals: 256 bytes too few, or a pointer moved by 128 bytes, is KEMR_ERR_WORKSPACE with
+nothing launched (`out` still all sentinel, the workspace still all 0xff).  Engine level: one ClipEngine whose torch.empty workspace
+is reused across batch sizes gives the bits of freshly built engines."""
+import ctypes as C
+
+import pytest
+import torch
+
+import footprint as F
+import siglip_ref as S
+from footprint import In, IntIn, Out, SizeOf, Work
+from knowledge_enhanced_multimodal_retrieval_amd import _lib, debug, engine
+from knowledge_enhanced_multimodal_retrieval_amd.config import ARCHS
+from oracle import clip_ref
+
+pytestmark = pytest.mark.gpu
+
+ERR_WORKSPACE = -4             # include/kemr.h KEMR_ERR_WORKSPACE
+BF16, F32, U8 = torch.bfloat16, torch.float32, torch.uint8
+# tiny-long: 197 vision tokens, context 77, more than 512 token rows at batch 3 (the fused residual adds are live under "bf16-res16");
+# tiny-h / tiny-h-257: heads of 80, patch 14 (im2col has pad columns); tiny-siglip / -576: the pooling head, streaming attention
+NAMES = ["tiny", "tiny-long", "tiny-h", "tiny-h-257", "tiny-siglip", "tiny-siglip-576"]
+
+
+def _precisions(name):
+    """Every name of _lib.PRECISIONS the family serves.  Refused at finalize, so left out: the fp8 precisions with vision heads of 80 and
+    for SigLIP, "fp32x3" for SigLIP (include/kemr.h, options "vision_head_dim" and "family")."""
+    arch = ARCHS[name]
+    names = sorted(_lib.PRECISIONS)
+    if arch.family == "siglip":
+        return [p for p in names if not p.startswith("fp8") and p != "fp32x3"]
+    if arch.v_head_dim == 80:
+        return [p for p in names if not p.startswith("fp8")]
+    return names
+
+
+CASES = [(n, p) for n in NAMES for p in _precisions(n)]
+
+
+def _weights(name):
+    """The seeded state dicts of the neighbouring tower tests (test_encoder_gpu / test_headdim_tower_gpu / test_siglip_tower_gpu)."""
+    arch = ARCHS[name]
+    if arch.family == "siglip":
+        return S.weights(arch)
+    return clip_ref.random_state_dict(arch.cfg_dict(), seed=len(name) if arch.v_head_dim == 80 else 0)
+
+
+def _inputs(name, n):
+    arch = ARCHS[name]
+    px = torch.randn(n, 3, arch.image_size, arch.image_size, generator=torch.Generator().manual_seed(100 + n))
+    ids = S.text_ids(arch, n) if arch.family == "siglip" else clip_ref.synthetic_ids(arch.cfg_dict(), n)
+    return px, ids.to(torch.int32)
+
+
+def _engine(name, device, precision=_lib.DEFAULT_PRECISION):
+    eng = engine.ClipEngine(ARCHS[name], device, precision=precision)
+    eng.load_state_dict(_weights(name))
+    return eng
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _both(device, fn, specs, what):
+    def run(*args):
+        with torch.cuda.device(device):
+            _lib.check(fn(*args, _stream(device)), what)
+    return F.run_both(run, specs, device, what=what)
+
+
+def _refusals(device, fn, calls, i_ws, i_out, what):
+    """The contract call again with 256 bytes too few, then with the pointer moved by 128 bytes: KEMR_ERR_WORKSPACE both times, `out`
+    still all 0xa5 and the workspace still all 0xff -- nothing was launched."""
+    ws, out = calls.win[i_ws], calls.win[i_out]
+    as_ptr = lambda t: C.c_void_p(t.data_ptr())          # noqa: E731
+    for shift, less in ((0, 256), (128, 0)):
+        ws.refill_body(F.POISON)
+        out.refill_body(F.GUARD)
+        args = calls.args(True, as_ptr)
+        args[i_ws] = C.c_void_p(ws.ptr + shift)
+        args[i_ws + 1] = ws.nbytes - less
+        with torch.cuda.device(device):
+            rc = fn(*args, _stream(device))
+        torch.cuda.synchronize(device)
+        assert rc == ERR_WORKSPACE, (what, shift, less, rc, _lib.lib().kemr_last_error())
+        assert F.all_bytes(out.view, F.GUARD) and F.all_bytes(ws.view, F.POISON), (what, shift, less)
+        assert ws.margins_intact() and out.margins_intact()
+
+
+@pytest.mark.parametrize("name,precision", CASES)
+def test_encoders_inside_their_workspace(device, name, precision):
+    arch, L = ARCHS[name], _lib.lib()
+    eng = _engine(name, device, precision)
+    px9, ids9 = _inputs(name, 3)
+    row_bytes = 48 * max(arch.v_width, arch.t_width)          # the widest row any carve has: 46 W bytes (fp32x3), 8 W otherwise
+    for pooled in (True, False):
+        eng.set_last_block_pooled_row(pooled)
+        for batch in (1, 3):
+            normalize = int(batch == 3)
+            what = f"{name} {precision} pooled={int(pooled)} batch={batch}"
+            need = int(L.kemr_workspace_bytes(eng._h, _lib.TOWER_VISION, batch))
+            calls = _both(device, L.kemr_encode_image,
+                          [eng._h, In(px9[:batch]), batch, Out((batch, arch.embed_dim), F32), normalize, Work(need, need + (1 << 20), row_bytes), SizeOf(5)],
+                          f"encode_image {what}")
+            assert bool(torch.isfinite(calls.win[3].view).all())
+            _refusals(device, L.kemr_encode_image, calls, 5, 3, f"encode_image {what}")
+            need = int(L.kemr_workspace_bytes(eng._h, _lib.TOWER_TEXT, batch))
+            calls = _both(device, L.kemr_encode_text,
+                          [eng._h, IntIn(ids9[:batch]), batch, Out((batch, arch.embed_dim), F32), normalize, Work(need, need + (1 << 20), row_bytes), SizeOf(5)],
+                          f"encode_text {what}")
+            assert bool(torch.isfinite(calls.win[3].view).all())
+            _refusals(device, L.kemr_encode_text, calls, 5, 3, f"encode_text {what}")
+            if arch.family == "siglip":          # kemr_encode_text_packed refuses family 1 (a pad position is a key): include/kemr.h
+                continue
+            lens = torch.tensor([1, arch.ctx, 5][:batch], dtype=torch.int32)       # ragged, the shortest 1
+            rows = int(lens.sum())
+            need = int(L.kemr_text_packed_workspace_bytes(eng._h, rows, batch))
+            calls = _both(device, L.kemr_encode_text_packed,
+                          [eng._h, IntIn(ids9[:batch]), IntIn(lens), rows, batch, Out((batch, arch.embed_dim), F32), normalize,
+                           Work(need, need + (1 << 20), row_bytes), SizeOf(7)], f"encode_text_packed {what}")
+            assert bool(torch.isfinite(calls.win[5].view).all())
+            _refusals(device, L.kemr_encode_text_packed, calls, 7, 5, f"encode_text_packed {what}")
+
+
+# ------------------------------------------------------------------------------------------------ the debug entry points
+def _stream_rows(eng, n, width):
+    dt = debug.residual_dtype(eng)
+    return ((n, 3 * width), U8) if dt == _lib.KEMR_F24 else ((n, width), BF16 if dt == _lib.KEMR_BF16 else F32)
+
+
+def test_token_fronts_inside_their_workspace(device):
+    """kemr_debug_image_tokens / kemr_debug_text_tokens (full context and packed) with the exact-size, margined workspace."""
+    name, batch, L = "tiny", 3, _lib.lib()
+    arch, eng = ARCHS[name], _engine(name, device)
+    px, ids = _inputs(name, batch)
+    row_bytes = 8 * arch.v_width
+    need = int(L.kemr_workspace_bytes(eng._h, _lib.TOWER_VISION, batch))
+    calls = _both(device, L.kemr_debug_image_tokens,
+                  [eng._h, In(px), batch, Out((batch * arch.v_tokens, arch.v_width), F32), Work(need, need + (1 << 20), row_bytes), SizeOf(4)],
+                  "debug_image_tokens")
+    _refusals(device, L.kemr_debug_image_tokens, calls, 4, 3, "debug_image_tokens")
+    need = int(L.kemr_workspace_bytes(eng._h, _lib.TOWER_TEXT, batch))
+    shape, dt = _stream_rows(eng, batch * arch.ctx, arch.t_width)
+    calls = _both(device, L.kemr_debug_text_tokens,
+                  [eng._h, IntIn(ids), None, 0, batch, Out(shape, dt), None, Work(need, need + (1 << 20), row_bytes), SizeOf(7)], "debug_text_tokens")
+    _refusals(device, L.kemr_debug_text_tokens, calls, 7, 5, "debug_text_tokens")
+    lens = torch.tensor([1, arch.ctx, 5], dtype=torch.int32)
+    rows = int(lens.sum())
+    need = int(L.kemr_text_packed_workspace_bytes(eng._h, rows, batch))
+    shape, dt = _stream_rows(eng, rows, arch.t_width)
+    calls = _both(device, L.kemr_debug_text_tokens,
+                  [eng._h, IntIn(ids), IntIn(lens), rows, batch, Out(shape, dt), Out((batch + 1,), torch.int32), Work(need, need + (1 << 20), row_bytes),
+                   SizeOf(7)], "debug_text_tokens packed")
+    assert calls.win[6].view.tolist() == [0, 1, 1 + arch.ctx, rows]
+    _refusals(device, L.kemr_debug_text_tokens, calls, 7, 5, "debug_text_tokens packed")
+
+
+def test_map_head_inside_its_workspace(device):
+    name, batch, L = "tiny-siglip", 3, _lib.lib()
+    arch, eng = ARCHS[name], _engine(name, device)
+    h = torch.randn(batch * arch.v_tokens, arch.v_width, generator=torch.Generator().manual_seed(6)).to(BF16)
+    need = int(L.kemr_workspace_bytes(eng._h, _lib.TOWER_VISION, batch))
+    calls = _both(device, L.kemr_debug_map_head,
+                  [eng._h, In(h), batch, Out((batch, arch.v_width), BF16), Out((batch, arch.v_width), F32), 1, Work(need, need + (1 << 20), 8 * arch.v_width),
+                   SizeOf(6)], "debug_map_head")
+    _refusals(device, L.kemr_debug_map_head, calls, 6, 4, "debug_map_head")
+
+
+# ------------------------------------------------------------------------------------------------ what a caller gets
+@pytest.mark.parametrize("name,precision", [("tiny-long", _lib.DEFAULT_PRECISION), ("tiny-long", "bf16-res16"), ("tiny-long", "fp32x3"),
+                                            ("tiny-h-257", _lib.DEFAULT_PRECISION), ("tiny-siglip-576", _lib.DEFAULT_PRECISION)])
+def test_engine_workspace_reuse(device, name, precision):
+    """One ClipEngine, batch 9, then 3, then 9 again, images and texts on both text routes: the reused torch.empty workspace holds
+    another layout's bytes on the second and third call -- and 0xff everywhere on a fourth --, and every result has the bits of a
+    freshly built engine's."""
+    px, ids = _inputs(name, 9)
+    px = px.to(device)
+    routes = (True, False) if ARCHS[name].family != "siglip" else (False,)
+
+    def encode(eng, n):
+        out = [eng.encode_image(px[:n], normalize=True)]
+        for packed in routes:
+            eng.pack_text = packed
+            out.append(eng.encode_text(ids[:n]))
+        return [o.clone() for o in out]
+
+    fresh = {n: encode(_engine(name, device, precision), n) for n in (9, 3)}
+    eng = _engine(name, device, precision)
+    for step, n in enumerate((9, 3, 9, 3)):
+        if step == 3:
+            for ws in eng._ws.values():
+                ws.fill_(F.POISON)
+        for got, want in zip(encode(eng, n), fresh[n]):
+            assert bool(torch.isfinite(got).all())
+            assert F.same_bits(got, want), (name, precision, step, n)
