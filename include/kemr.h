@@ -43,7 +43,10 @@ extern "C" {
  *    caller gets; no entry point was added.  Still 4: option "vision_head_dim" (64, the default every existing caller gets, or 80: the
  *    vision tower of ViT-H-14) and the entry points kemr_op_attention_hd / kemr_op_attention_x3_hd are additions; kemr_cfg did not grow.
  *    Still 4: option "family" (0 = CLIP, the default every existing caller gets; 1 = SigLIP) and the epilogue value
- *    KEMR_EPI_BIAS_TGELU_BF16 (kemr_op_gemm) are additions; no entry point changed, kemr_cfg did not grow. */
+ *    KEMR_EPI_BIAS_TGELU_BF16 (kemr_op_gemm) are additions; no entry point changed, kemr_cfg did not grow.
+ *    Still 4: kemr_transform_workspace_bytes, kemr_transform_u8, kemr_transform_batch_workspace_bytes and kemr_transform_u8_batch (the
+ *    image transform with its kind as an argument: CLIP's or the SigLIP family's) are additions; the four kemr_preprocess_* entry points
+ *    keep their signatures and bits (they are the new ones at KEMR_TRANSFORM_CLIP). */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -191,7 +194,9 @@ int kemr_model_destroy(kemr_model* m);
  *                      mask, pools position ctx - 1 whatever the ids (its last block honours "last_block_pooled_row") and its head adds
  *                      text_projection_bias.  Refused for family 1 with the reason in the message: at finalize embed_dim != v_width,
  *                      the fp8 precisions, KEMR_PREC_FP32X3 and "vision_head_dim" != 64; kemr_encode_text_packed (a pad position is a
- *                      key and the pooled row is the last one, so no row can be left out). */
+ *                      key and the pooled row is the last one, so no row can be left out).  The family's pixels are those of its own
+ *                      image transform (squash to S x S, mean = std = 0.5): KEMR_TRANSFORM_SIGLIP of kemr_transform_u8 /
+ *                      kemr_transform_u8_batch below computes them on the device; the option itself does not touch the input side. */
 int kemr_model_set_option(kemr_model* m, const char* key, int value);
 int kemr_model_get_option(const kemr_model* m, const char* key, int* value);
 /* number of required tensor names; name i via kemr_model_tensor_name (for strict-load diagnostics) */
@@ -469,6 +474,33 @@ size_t kemr_preprocess_batch_workspace_bytes(const int32_t* heights, const int32
 int kemr_preprocess_u8_batch(const unsigned char* packed_dev, const int64_t* offsets, const int32_t* heights,
                              const int32_t* widths, int batch, int n_px, float* out_dev, void* workspace_dev,
                              size_t workspace_bytes, void* stream);
+/* The same four calls with the KIND of transform as an argument (the kemr_preprocess_* entry points are these at KEMR_TRANSFORM_CLIP):
+ *   KEMR_TRANSFORM_CLIP    Resize(n_px, bicubic, shorter side) -> CenterCrop(n_px) -> / 255 -> (x - mean) / std with CLIP's constants;
+ *   KEMR_TRANSFORM_SIGLIP  transformers.SiglipImageProcessor: Image.resize((n_px, n_px), BICUBIC) -- each axis resampled on its own (or
+ *                          copied when its size does not change), the aspect ratio is not kept, nothing is cropped -- -> / 255 ->
+ *                          (x - 0.5) / 0.5.  Bit for bit the host transform (python: preprocess.SiglipPreprocess), same kernels.
+ * Any other kind: the workspace functions return 0, the launch functions KEMR_ERR_INVALID.
+ * Pass order.  The kernels filter horizontally first, then vertically; the intermediate is clipped to 8 bits, so the order is part of
+ * the result.  Pillow (12.2.0, measured) filters VERTICALLY first when height > 100 x width and the output is lower than the input.
+ * KEMR_TRANSFORM_SIGLIP therefore refuses an image with height > 100 * width and height > n_px: the workspace functions return 0, the
+ * launch functions KEMR_ERR_INVALID with a message that names the size (the batch form: and the item; the batch is refused as a
+ * whole); nothing is launched, `out` and the workspace keep their bytes.  The caller computes such an image on the host.
+ * (KEMR_TRANSFORM_CLIP has always filtered horizontally first and accepts such images: beyond 100:1 its bits are not Pillow's.)
+ * Memory contract (tests/test_siglip_transform_gpu.py), all four launch calls, both kinds: exactly kemr_transform_workspace_bytes /
+ * kemr_transform_batch_workspace_bytes is enough -- nothing before the workspace's first or behind its last byte is written or can
+ * reach `out`; every workspace byte a result depends on is written by the call first (stale bytes of an earlier call of another size,
+ * NaN included, cannot reach `out`); exactly 3 * n_px * n_px floats of `out` per image are written (a 0 x 0 item: 0.0f); nothing
+ * outside the heights[b] * widths[b] * 3 bytes of each image -- the bytes in front of, between and behind the images of packed_dev --
+ * can reach them.  A workspace that is too small or not 256-byte aligned is KEMR_ERR_WORKSPACE BEFORE anything is launched: `out` and
+ * the workspace keep their bytes. */
+typedef enum kemr_transform { KEMR_TRANSFORM_CLIP = 0, KEMR_TRANSFORM_SIGLIP = 1 } kemr_transform;
+size_t kemr_transform_workspace_bytes(int transform /*kemr_transform*/, int height, int width, int n_px);
+int kemr_transform_u8(int transform, const unsigned char* img_dev, int height, int width, int n_px, float* out_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t kemr_transform_batch_workspace_bytes(int transform, const int32_t* heights, const int32_t* widths, int batch, int n_px);
+int kemr_transform_u8_batch(int transform, const unsigned char* packed_dev, const int64_t* offsets, const int32_t* heights,
+                            const int32_t* widths, int batch, int n_px, float* out_dev, void* workspace_dev,
+                            size_t workspace_bytes, void* stream);
 
 int kemr_op_gemm(const void* a_dev, const void* w_dev, const float* bias_dev, void* c_dev,
                  int m, int n, int k, int epilogue, void* stream);

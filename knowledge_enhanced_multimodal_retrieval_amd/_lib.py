@@ -37,6 +37,7 @@ PRECISIONS = {"bf16": PREC_BF16, "bf16-res16": PREC_BF16_RES16, "fp8": PREC_FP8,
               # every GEMM / attention operand as a bf16 pair, three products each: the reference's fp32 numbers at a third of the rate
               "fp32x3": PREC_FP32X3}
 TOWER_VISION, TOWER_TEXT = 0, 1
+TRANSFORM_CLIP, TRANSFORM_SIGLIP = 0, 1      # kemr_transform: the kind of kemr_transform_u8 / kemr_transform_u8_batch
 SIDE_QUERY, SIDE_GALLERY = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RESID_F32 = 0, 1, 2
 EPI_BIAS_RESADD_BF16 = 4
@@ -95,6 +96,10 @@ SIGNATURES = {
     "kemr_preprocess_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "kemr_preprocess_batch_workspace_bytes": (_sz, [_vp, _vp, _i, _i]),
     "kemr_preprocess_u8_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "kemr_transform_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "kemr_transform_u8": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "kemr_transform_batch_workspace_bytes": (_sz, [_i, _vp, _vp, _i, _i]),
+    "kemr_transform_u8_batch": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "kemr_op_gemm_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "kemr_op_e4m3_host": (_i, [_vp, _vp, C.c_longlong]),
     "kemr_op_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

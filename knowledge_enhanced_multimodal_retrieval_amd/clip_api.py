@@ -92,7 +92,8 @@ def _load_hf_directory(directory: str, device, activation) -> Tuple[CLIP, ClipPr
         model.weights_source = os.path.abspath(directory)
         # what evaluators.model_tokenize reads when no tokenize_fn is given (encode_dataset, EmbeddingStore.build, CLIPRetriever, the CLIs)
         model.tokenizer_dir = os.path.abspath(directory) if os.path.isfile(os.path.join(directory, "tokenizer.json")) else None
-        return model.to(device).eval(), SiglipPreprocess(arch.image_size)
+        on_gpu = torch.device(device).type == "cuda"
+        return model.to(device).eval(), SiglipPreprocess(arch.image_size, defer_to_gpu=on_gpu and gpu_preprocessing_enabled())
     if activation is not None and check_activation(activation) != act:
         raise ValueError(f"clip.load({directory!r}, activation={activation!r}): its config.json says hidden_act = {act!r}")
     model = CLIP(arch, hf_checkpoint.registered_name(arch), act)
@@ -150,7 +151,7 @@ def load(name: str, device: Union[str, torch.device, None] = None,
         warnings.warn(f"clip.load({name!r}): seeded RANDOM weights (explicitly allowed)", RuntimeWarning, stacklevel=2)
         model.weights_source = "random(seed 0)"
     model = model.to(device).eval()
-    if get_arch(name).family == "siglip":   # squash to S x S, mean = std = 0.5; host transform only (no GPU uint8 kernel for it yet)
-        return model, SiglipPreprocess(get_arch(name).image_size)
     on_gpu = torch.device(device).type == "cuda"
+    if get_arch(name).family == "siglip":   # squash to S x S, mean = std = 0.5; deferred to the device like CLIP's (KEMR_TRANSFORM_SIGLIP)
+        return model, SiglipPreprocess(get_arch(name).image_size, defer_to_gpu=on_gpu and gpu_preprocessing_enabled())
     return model, ClipPreprocess(get_arch(name).image_size, defer_to_gpu=on_gpu and gpu_preprocessing_enabled())

@@ -192,14 +192,11 @@ class CLIP(nn.Module):
         """``image``: float ``[B, 3, S, S]`` normalised pixels as upstream, or the :class:`preprocess.PackedRaw` batch a loader over
         ``CLIPEvalDatasetHF(split, preprocess)`` yields when the transform is deferred to the GPU -- so the reference's own loop
         (``images.to(device)`` -> ``model.encode_image(images)``, evaluator.py:118-121) runs unchanged on either."""
-        from .preprocess import ClipPreprocessGPU, PackedRaw
+        from .preprocess import PackedRaw, gpu_preprocess_for
         dev = self._device()
         if isinstance(image, PackedRaw):
-            if self.arch.family != "clip":
-                raise RuntimeError("encode_image: the GPU uint8 preprocess kernel implements CLIP's transform only; a SigLIP model takes "
-                                   "the pixels of its host transform (preprocess.SiglipPreprocess)")
             if getattr(self, "_gpu_pre", None) is None or self._gpu_pre.device != dev:
-                self._gpu_pre = ClipPreprocessGPU(self.visual.input_resolution, dev)
+                self._gpu_pre = gpu_preprocess_for(self, dev)          # the family's transform: CLIP's resize-and-crop or SigLIP's squash
             image = self._gpu_pre.batch(image)
         return self.engine().encode_image(image.to(dev), normalize=normalize)
 

@@ -1,4 +1,4 @@
-// CLIP image preprocessing on the GPU (the reference applies the callable it gets from
+// Image preprocessing on the GPU: CLIP's transform and the SigLIP family's (kemr_transform in include/kemr.h).  CLIP's (the reference applies the callable it gets from
 // clip.load per sample on the host: /root/reference/src/clip/datasets/clip_dataset.py:110-125):
 //   uint8 HWC RGB -> Resize(n_px, bicubic, shorter side) -> CenterCrop(n_px) -> / 255 -> (x - mean) / std -> fp32 CHW.
 // The resize is Pillow's (Image.resize(..., BICUBIC), the dependency the reference's transform resolves to; libImaging
@@ -7,6 +7,10 @@
 // intermediates.  Integer work, so it is reproduced bit for bit: the host computes the same coefficient tables (double
 // arithmetic in the same order) for the 2 x n_px output rows / columns that survive the crop, the kernels do the int32
 // accumulation.  Only the input rows the vertical pass needs are filtered horizontally.
+// The SigLIP family's (transformers.SiglipImageProcessor; python: preprocess.SiglipPreprocess):
+//   uint8 HWC RGB -> Image.resize((n_px, n_px), BICUBIC) -> / 255 -> (x - 0.5) / 0.5 -> fp32 CHW.
+// Same filter, same kernels: the plan has nw = nh = n_px and no crop offsets, each axis has its own scale (an axis whose size does not
+// change is a copy), the constants are arguments.  Pillow does NOT always filter horizontally first -- see refuses() below.
 #include "common.h"
 
 #include <array>
@@ -80,6 +84,24 @@ void precompute(int in_size, int out_size, int first, int count, Axis& ax) {
     }
 }
 
+// Normalisation constants per kind (CLIP's: SURVEY.md section 8 row a16)
+struct Norm { float m0, m1, m2, d0, d1, d2; };
+constexpr Norm NORMS[2] = {{0.48145466f, 0.4578275f, 0.40821073f, 0.26862954f, 0.26130258f, 0.27577711f},
+                           {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f}};
+
+bool known_kind(int kind) { return kind == KEMR_TRANSFORM_CLIP || kind == KEMR_TRANSFORM_SIGLIP; }
+
+// Pillow's pass order (measured on 12.2.0, tests/test_siglip_transform_host.py pins it): an image with height > 100 x width whose
+// output is lower than its input is filtered VERTICALLY first, every other one horizontally first.  The intermediate is clipped to 8
+// bits, so the two orders give different bytes (up to 2 grey levels at 3000 x 17 -> 64 x 64).  The kernels here are horizontal-first:
+// the squash transform, whose two scales are independent, refuses such an image instead of computing other bits than the host's.
+// (CLIP's geometry has one scale for both axes; its entry points have always been horizontal-first and stay so.)
+bool refuses(int kind, int height, int width, int n) {
+    return kind == KEMR_TRANSFORM_SIGLIP && (long long)height > 100LL * width && height > n;
+}
+#define KEMR_PASS_ORDER_MSG "Pillow filters an image with height > 100 x width vertically first when it lowers it; these kernels filter " \
+                            "horizontally first (compute this image with the host transform)"
+
 struct Plan {
     int nw = 0, nh = 0, left = 0, top = 0;
     Axis hx, vy;
@@ -87,20 +109,26 @@ struct Plan {
     size_t off_hb = 0, off_vk = 0, off_vb = 0, temp_off = 0, bytes = 0;
 };
 
-const Plan& plan_for(int height, int width, int n) {
+const Plan& plan_for(int kind, int height, int width, int n) {
     static std::mutex mu;
-    static std::map<std::tuple<int, int, int>, Plan> cache;      // entries are never modified once inserted
+    static std::map<std::tuple<int, int, int, int>, Plan> cache;      // entries are never modified once inserted
     std::lock_guard<std::mutex> lock(mu);
-    auto key = std::make_tuple(height, width, n);
+    auto key = std::make_tuple(kind, height, width, n);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
     Plan p;
-    // Resize(n): shorter side -> n, the other side int(n * long / short) (torchvision / clip _transform)
-    if (width <= height) { p.nw = n; p.nh = (int)((double)n * height / width); }
-    else { p.nw = (int)((double)n * width / height); p.nh = n; }
-    // CenterCrop(n): int(round((size - n) / 2.0)) with Python's round-half-to-even
-    p.left = (int)nearbyint((p.nw - n) / 2.0);
-    p.top = (int)nearbyint((p.nh - n) / 2.0);
+    if (kind == KEMR_TRANSFORM_SIGLIP) {
+        // Image.resize((n, n)): both sides -> n, nothing is cropped
+        p.nw = p.nh = n;
+        p.left = p.top = 0;
+    } else {
+        // Resize(n): shorter side -> n, the other side int(n * long / short) (torchvision / clip _transform)
+        if (width <= height) { p.nw = n; p.nh = (int)((double)n * height / width); }
+        else { p.nw = (int)((double)n * width / height); p.nh = n; }
+        // CenterCrop(n): int(round((size - n) / 2.0)) with Python's round-half-to-even
+        p.left = (int)nearbyint((p.nw - n) / 2.0);
+        p.top = (int)nearbyint((p.nh - n) / 2.0);
+    }
     precompute(width, p.nw, p.left, n, p.hx);
     precompute(height, p.nh, p.top, n, p.vy);
     p.table = p.hx.kk;
@@ -272,7 +300,7 @@ struct BatchLayout {
     int max_rows = 0;
 };
 
-int layout_batch(const int32_t* heights, const int32_t* widths, const int64_t* offsets, int batch, int n, BatchLayout& L) {
+int layout_batch(int kind, const int32_t* heights, const int32_t* widths, const int64_t* offsets, int batch, int n, BatchLayout& L) {
     std::map<std::pair<int, int>, std::array<int, 4>> seen;       // (h, w) -> table offsets of its plan
     L.desc.resize(batch);
     size_t temp = 0;
@@ -287,7 +315,8 @@ int layout_batch(const int32_t* heights, const int32_t* widths, const int64_t* o
             continue;
         }
         if (h <= 0 || w <= 0 || h > 32768 || w > 32768) KEMR_FAIL(KEMR_ERR_INVALID, "preprocess batch: bad image size %d x %d (image %d)", h, w, b);
-        const Plan& p = plan_for(h, w, n);
+        if (refuses(kind, h, w, n)) KEMR_FAIL(KEMR_ERR_INVALID, "transform batch: image %d is %d x %d -> %d: " KEMR_PASS_ORDER_MSG, b, h, w, n);
+        const Plan& p = plan_for(kind, h, w, n);
         auto it = seen.find({h, w});
         if (it == seen.end()) {
             const int base = (int)L.tables.size();
@@ -316,21 +345,22 @@ int layout_batch(const int32_t* heights, const int32_t* widths, const int64_t* o
 
 using namespace kemr;
 
-extern "C" size_t kemr_preprocess_batch_workspace_bytes(const int32_t* heights, const int32_t* widths, int batch, int n_px) {
-    if (!heights || !widths || batch <= 0 || n_px <= 0 || n_px > 1024) return 0;
+extern "C" size_t kemr_transform_batch_workspace_bytes(int transform, const int32_t* heights, const int32_t* widths, int batch, int n_px) {
+    if (!known_kind(transform) || !heights || !widths || batch <= 0 || n_px <= 0 || n_px > 1024) return 0;
     BatchLayout L;
-    if (layout_batch(heights, widths, nullptr, batch, n_px, L) != KEMR_OK) return 0;
+    if (layout_batch(transform, heights, widths, nullptr, batch, n_px, L) != KEMR_OK) return 0;
     return L.bytes;
 }
 
-extern "C" int kemr_preprocess_u8_batch(const unsigned char* packed_dev, const int64_t* offsets, const int32_t* heights,
-                                        const int32_t* widths, int batch, int n_px, float* out_dev, void* workspace_dev,
-                                        size_t workspace_bytes, void* stream) {
+extern "C" int kemr_transform_u8_batch(int transform, const unsigned char* packed_dev, const int64_t* offsets, const int32_t* heights,
+                                       const int32_t* widths, int batch, int n_px, float* out_dev, void* workspace_dev,
+                                       size_t workspace_bytes, void* stream) {
+    if (!known_kind(transform)) KEMR_FAIL(KEMR_ERR_INVALID, "preprocess batch: unknown transform kind %d", transform);
     if (batch == 0) return KEMR_OK;
     if (!offsets || !heights || !widths || !out_dev || batch < 0) KEMR_FAIL(KEMR_ERR_INVALID, "preprocess batch: null argument");
     if (n_px <= 0 || n_px > 1024) KEMR_FAIL(KEMR_ERR_INVALID, "preprocess batch: bad output size %d", n_px);
     BatchLayout L;
-    KEMR_TRY(layout_batch(heights, widths, offsets, batch, n_px, L));
+    KEMR_TRY(layout_batch(transform, heights, widths, offsets, batch, n_px, L));
     if (!packed_dev && L.max_rows > 0) KEMR_FAIL(KEMR_ERR_INVALID, "preprocess batch: null image buffer");
     if (!workspace_dev || workspace_bytes < L.bytes) KEMR_FAIL(KEMR_ERR_WORKSPACE, "preprocess batch: workspace too small: %zu < %zu bytes", workspace_bytes, L.bytes);
     if ((uintptr_t)workspace_dev % 256) KEMR_FAIL(KEMR_ERR_WORKSPACE, "preprocess batch: workspace must be 256-byte aligned");
@@ -347,6 +377,7 @@ extern "C" int kemr_preprocess_u8_batch(const unsigned char* packed_dev, const i
     KEMR_CHECK_HIP(hipMemcpyAsync(ws, host, blob, hipMemcpyHostToDevice, s));
     KEMR_CHECK_HIP(hipEventRecord(done, s));
     const int n = n_px;
+    const Norm& c = NORMS[transform];
     ProfScope prof(PROF_OTHER, s);
     if (L.max_rows > 0) {                        // 0: every item of the batch is a zero_out item
         hipLaunchKernelGGL(preprocess_h_batch_kernel, dim3((unsigned)(((size_t)L.max_rows * n + 255) / 256), (unsigned)batch), dim3(256), 0, s,
@@ -354,23 +385,26 @@ extern "C" int kemr_preprocess_u8_batch(const unsigned char* packed_dev, const i
         KEMR_CHECK_LAUNCH("preprocess_h_batch_kernel");
     }
     hipLaunchKernelGGL(preprocess_v_batch_kernel, dim3((unsigned)((n * n + 255) / 256), (unsigned)batch), dim3(256), 0, s,
-                       (const PreImg*)ws, (const int32_t*)(ws + L.tab_off), (const uint8_t*)(ws + L.temp_off), n, 0.48145466f, 0.4578275f,
-                       0.40821073f, 0.26862954f, 0.26130258f, 0.27577711f, out_dev);
+                       (const PreImg*)ws, (const int32_t*)(ws + L.tab_off), (const uint8_t*)(ws + L.temp_off), n, c.m0, c.m1, c.m2, c.d0, c.d1,
+                       c.d2, out_dev);
     KEMR_CHECK_LAUNCH("preprocess_v_batch_kernel");
     return KEMR_OK;
 }
 
-extern "C" size_t kemr_preprocess_workspace_bytes(int height, int width, int n_px) {
-    if (height <= 0 || width <= 0 || n_px <= 0 || height > 32768 || width > 32768 || n_px > 1024) return 0;
-    return plan_for(height, width, n_px).bytes;
+extern "C" size_t kemr_transform_workspace_bytes(int transform, int height, int width, int n_px) {
+    if (!known_kind(transform) || height <= 0 || width <= 0 || n_px <= 0 || height > 32768 || width > 32768 || n_px > 1024) return 0;
+    if (refuses(transform, height, width, n_px)) return 0;
+    return plan_for(transform, height, width, n_px).bytes;
 }
 
-extern "C" int kemr_preprocess_u8(const unsigned char* img_dev, int height, int width, int n_px, float* out_dev,
-                                  void* workspace_dev, size_t workspace_bytes, void* stream) {
+extern "C" int kemr_transform_u8(int transform, const unsigned char* img_dev, int height, int width, int n_px, float* out_dev,
+                                 void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!known_kind(transform)) KEMR_FAIL(KEMR_ERR_INVALID, "preprocess: unknown transform kind %d", transform);
     if (!img_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "preprocess: null argument");
     if (height <= 0 || width <= 0 || n_px <= 0 || height > 32768 || width > 32768 || n_px > 1024)
         KEMR_FAIL(KEMR_ERR_INVALID, "preprocess: bad sizes %d x %d -> %d", height, width, n_px);
-    const Plan& p = plan_for(height, width, n_px);
+    if (refuses(transform, height, width, n_px)) KEMR_FAIL(KEMR_ERR_INVALID, "transform: %d x %d -> %d: " KEMR_PASS_ORDER_MSG, height, width, n_px);
+    const Plan& p = plan_for(transform, height, width, n_px);
     if (!workspace_dev || workspace_bytes < p.bytes) KEMR_FAIL(KEMR_ERR_WORKSPACE, "preprocess: workspace too small: %zu < %zu bytes", workspace_bytes, p.bytes);
     if ((uintptr_t)workspace_dev % 256) KEMR_FAIL(KEMR_ERR_WORKSPACE, "preprocess: workspace must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
@@ -379,14 +413,33 @@ extern "C" int kemr_preprocess_u8(const unsigned char* img_dev, int height, int 
     uint8_t* temp = (uint8_t*)workspace_dev + p.temp_off;
     if (!p.table.empty()) KEMR_CHECK_HIP(hipMemcpyAsync(tab, p.table.data(), p.table.size() * 4, hipMemcpyHostToDevice, s));
     const int row_lo = p.vy.in_lo, rows = p.vy.in_hi - p.vy.in_lo;
+    const Norm& c = NORMS[transform];
     ProfScope prof(PROF_OTHER, s);
     hipLaunchKernelGGL(preprocess_h_kernel, dim3((unsigned)(((size_t)rows * n + 255) / 256)), dim3(256), 0, s, img_dev, width, row_lo, rows, n,
                        tab, tab + p.off_hb, p.hx.ksize, p.hx.resample ? 1 : 0, p.left, temp);
     KEMR_CHECK_LAUNCH("preprocess_h_kernel");
-    // CLIP's normalisation constants
     hipLaunchKernelGGL(preprocess_v_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, s, temp, row_lo, n, tab + p.off_vk,
-                       tab + p.off_vb, p.vy.ksize, p.vy.resample ? 1 : 0, p.top, 0.48145466f, 0.4578275f, 0.40821073f, 0.26862954f,
-                       0.26130258f, 0.27577711f, out_dev);
+                       tab + p.off_vb, p.vy.ksize, p.vy.resample ? 1 : 0, p.top, c.m0, c.m1, c.m2, c.d0, c.d1, c.d2, out_dev);
     KEMR_CHECK_LAUNCH("preprocess_v_kernel");
     return KEMR_OK;
+}
+
+// the CLIP entry points: the calls above at KEMR_TRANSFORM_CLIP
+extern "C" size_t kemr_preprocess_batch_workspace_bytes(const int32_t* heights, const int32_t* widths, int batch, int n_px) {
+    return kemr_transform_batch_workspace_bytes(KEMR_TRANSFORM_CLIP, heights, widths, batch, n_px);
+}
+
+extern "C" int kemr_preprocess_u8_batch(const unsigned char* packed_dev, const int64_t* offsets, const int32_t* heights,
+                                        const int32_t* widths, int batch, int n_px, float* out_dev, void* workspace_dev,
+                                        size_t workspace_bytes, void* stream) {
+    return kemr_transform_u8_batch(KEMR_TRANSFORM_CLIP, packed_dev, offsets, heights, widths, batch, n_px, out_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" size_t kemr_preprocess_workspace_bytes(int height, int width, int n_px) {
+    return kemr_transform_workspace_bytes(KEMR_TRANSFORM_CLIP, height, width, n_px);
+}
+
+extern "C" int kemr_preprocess_u8(const unsigned char* img_dev, int height, int width, int n_px, float* out_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return kemr_transform_u8(KEMR_TRANSFORM_CLIP, img_dev, height, width, n_px, out_dev, workspace_dev, workspace_bytes, stream);
 }

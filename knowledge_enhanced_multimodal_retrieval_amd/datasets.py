@@ -25,7 +25,7 @@ class CLIPEvalDatasetHF(Dataset):
     def __init__(self, hf_dataset, preprocessor=None, max_text_length: int = 150, image_size: int = 224):
         self.dataset, self.preprocessor = hf_dataset, preprocessor
         self.max_text_length, self.image_size = max_text_length, image_size
-        # The preprocess object of clip.load / load_clip_model may say "defer to the GPU" (preprocess.ClipPreprocess): the item is
+        # The preprocess object of clip.load / load_clip_model may say "defer to the GPU" (ClipPreprocess / SiglipPreprocess): the item is
         # then the decoded image as uint8 [H, W, 3]; collate_fn_eval packs a batch of them and evaluators.encode_dataset runs the
         # transform on the device, bit-identical to the host one.  The reference's call site stays as it is.
         if getattr(preprocessor, "defer_to_gpu", False):
@@ -55,8 +55,11 @@ class CLIPEvalDatasetHF(Dataset):
                 # EMPTY uint8 [0, 0, 3] item, which pack_raw / kemr_preprocess_u8_batch turn into that same all-zero tensor
                 # (a black uint8 picture would normalise to (-1.79, -1.75, -1.48) and give a different embedding).
                 from .preprocess import RawRGB
+                # (a host transform that states its output size -- ClipPreprocess / SiglipPreprocess at 336, 384, ... -- gets zeros of
+                # that size, so that the item stacks with its batch; any other callable the reference's 224)
+                size = int(getattr(self.preprocessor, "n_px", self.image_size))
                 image = (torch.zeros(0, 0, 3, dtype=torch.uint8) if isinstance(self.preprocessor, RawRGB)
-                         else torch.zeros(3, self.image_size, self.image_size))
+                         else torch.zeros(3, size, size))
             else:
                 from PIL import Image
                 image = Image.new("RGB", (self.image_size, self.image_size))

@@ -27,7 +27,7 @@ from . import engine
 from . import metrics as M
 from . import sparql_fusion as SF
 from .datasets import CLIPEvalDatasetHF, CollateAndTokenize, SyntheticHFSplit, SyntheticRawImageDataset, SyntheticRetrievalDataset, collate_fn_eval
-from .preprocess import ClipPreprocessGPU, PackedRaw
+from .preprocess import ClipPreprocessGPU, PackedRaw, gpu_preprocess_for
 from .logging_utils import save_metrics_to_json, setup_logger
 
 logger = logging.getLogger(__name__)
@@ -173,6 +173,13 @@ def model_name_arg(value: str) -> str:
     raise argparse.ArgumentTypeError(f"{value!r} is neither one of {clip_api.available_models()} nor a directory with a config.json")
 
 
+def image_transform_name(dataset) -> str:
+    """What the results JSON records under ``image_transform``: where the dataset's image transform runs."""
+    return {"RawRGB": "gpu (batched kernels, bit-identical to the host transform)", "ClipPreprocess": "host (PIL, per sample)",
+            "SiglipPreprocess": "host (PIL, per sample)"}.get(type(getattr(dataset, "preprocessor", None)).__name__,
+                                                              "none (pre-normalised tensors)")
+
+
 @torch.no_grad()
 def encode_dataset(model, dataset, batch_size: int = 64, seed: int = 42, num_workers: Optional[int] = 0,
                    tokenize_fn: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, List[str]]:
@@ -251,9 +258,9 @@ def encode_dataset(model, dataset, batch_size: int = 64, seed: int = 42, num_wor
 
     gpu_pre = None
     for images, q_ids, t_ids, ids in loader:
-        if isinstance(images, PackedRaw):      # raw uint8 images (preprocess.RawRGB): resize / crop / normalise on the device,
+        if isinstance(images, PackedRaw):      # raw uint8 images (preprocess.RawRGB): the model family's transform on the device,
             if gpu_pre is None:                # one launch pair per loader batch
-                gpu_pre = ClipPreprocessGPU(int(getattr(getattr(model, "visual", None), "input_resolution", 224)), device)
+                gpu_pre = gpu_preprocess_for(model, device)
             images = gpu_pre.batch(images)
         pend_i.append(images.to(device, non_blocking=True))
         if by_rows:                            # lengths from the host copy, before the upload
@@ -424,8 +431,7 @@ def _run(args, baseline: bool, log_name: str):
                # provenance (not in the reference's file): what the numbers were computed with
                "weights_source": getattr(model, "weights_source", "unknown"), "tokenizer": model_tokenizer_name(model),
                "precision": _lib.env_precision(), "data": "synthetic" if args.synthetic > 0 else args.dataset,
-               "image_transform": {"RawRGB": "gpu (batched kernels, bit-identical to the host transform)", "ClipPreprocess": "host (PIL, per sample)"}.get(
-                   type(getattr(dataset, "preprocessor", None)).__name__, "none (pre-normalised tensors)"),
+               "image_transform": image_transform_name(dataset),
                "loader_workers": workers}
     if not baseline:
         results["tasks"] = list(args.tasks)

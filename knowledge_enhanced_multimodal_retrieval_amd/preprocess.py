@@ -52,13 +52,13 @@ class ClipPreprocess:
 
 class SiglipPreprocess:
     """The SigLIP family's host transform (``transformers.SiglipImageProcessor``): RGB -> bicubic resize straight to ``n_px x n_px``
-    (the aspect ratio is NOT kept, nothing is cropped) -> float in [0, 1] -> mean = std = 0.5, i.e. pixels in [-1, 1].  Host only:
-    ``defer_to_gpu`` is always False (the uint8 kernels of csrc/preprocess.hip implement CLIP's resize-and-crop)."""
+    (the aspect ratio is NOT kept, nothing is cropped) -> float in [0, 1] -> mean = std = 0.5, i.e. pixels in [-1, 1].  Called, it is
+    always this host transform; ``defer_to_gpu`` means what it means on :class:`ClipPreprocess`: the dataset classes may hand the
+    decoded image over raw and ``evaluators.encode_dataset`` runs :class:`SiglipPreprocessGPU` per loader batch (bit-identical)."""
 
-    defer_to_gpu = False
-
-    def __init__(self, n_px: int = 224):
+    def __init__(self, n_px: int = 224, defer_to_gpu: bool = False):
         self.n_px = n_px
+        self.defer_to_gpu = bool(defer_to_gpu)
 
     def __call__(self, image) -> torch.Tensor:
         from PIL import Image
@@ -68,7 +68,7 @@ class SiglipPreprocess:
         return (x - 0.5) / 0.5
 
     def __repr__(self):
-        return f"SiglipPreprocess(n_px={self.n_px})"
+        return f"SiglipPreprocess(n_px={self.n_px}, defer_to_gpu={self.defer_to_gpu})"
 
 
 class ClipPreprocessGPU:
@@ -76,12 +76,21 @@ class ClipPreprocessGPU:
     to it: takes a PIL image (RGB is enforced before the resize here; identical for RGB inputs) or a uint8 ``[H, W, 3]``
     tensor on any device, returns float32 ``[3, n_px, n_px]`` on ``device``.  No CPU fallback."""
 
+    kind = 0                           # _lib.TRANSFORM_CLIP: the kind argument of kemr_transform_u8 / kemr_transform_u8_batch
+
     def __init__(self, n_px: int = 224, device="cuda:0"):
         self.n_px = n_px
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("ClipPreprocessGPU needs a GPU device")
+            raise RuntimeError(f"{type(self).__name__} needs a GPU device")
         self._ws = None
+
+    def _on_host(self, h: int, w: int) -> bool:
+        """True for an image the library refuses and the host transform computes instead (none for CLIP's transform)."""
+        return False
+
+    def _host(self, image: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError
 
     def __call__(self, image) -> torch.Tensor:
         import ctypes as C
@@ -89,26 +98,28 @@ class ClipPreprocessGPU:
         if not torch.is_tensor(image):
             image = torch.from_numpy(np.asarray(image.convert("RGB"), dtype=np.uint8).copy())
         if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
-            raise RuntimeError(f"ClipPreprocessGPU expects uint8 [H, W, 3], got {image.dtype} {tuple(image.shape)}")
+            raise RuntimeError(f"{type(self).__name__} expects uint8 [H, W, 3], got {image.dtype} {tuple(image.shape)}")
+        h, w = int(image.shape[0]), int(image.shape[1])
+        if self._on_host(h, w):
+            return self._host(image).to(self.device)
         img = image.to(self.device).contiguous()
-        h, w = int(img.shape[0]), int(img.shape[1])
         if h == 0 and w == 0:          # an undecodable item (datasets.CLIPEvalDatasetHF): zeros after normalisation, as the reference
             return torch.zeros((3, self.n_px, self.n_px), dtype=torch.float32, device=self.device)
         L = _lib.lib()
-        need = int(L.kemr_preprocess_workspace_bytes(h, w, self.n_px))
+        need = int(L.kemr_transform_workspace_bytes(self.kind, h, w, self.n_px))
         if need == 0:
-            raise RuntimeError(f"ClipPreprocessGPU: unsupported size {h} x {w} -> {self.n_px}")
+            raise RuntimeError(f"{type(self).__name__}: unsupported size {h} x {w} -> {self.n_px}")
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         out = torch.empty((3, self.n_px, self.n_px), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(L.kemr_preprocess_u8(C.c_void_p(img.data_ptr()), h, w, self.n_px, C.c_void_p(out.data_ptr()),
-                                            C.c_void_p(self._ws.data_ptr()), self._ws.numel(),
-                                            C.c_void_p(engine._stream_ptr(self.device))), "preprocess_u8")
+            _lib.check(L.kemr_transform_u8(self.kind, C.c_void_p(img.data_ptr()), h, w, self.n_px, C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(self._ws.data_ptr()), self._ws.numel(),
+                                           C.c_void_p(engine._stream_ptr(self.device))), "transform_u8")
         return out
 
     def batch(self, packed: "PackedRaw") -> torch.Tensor:
-        """A whole loader batch in one launch pair (``kemr_preprocess_u8_batch``): ``packed`` holds the uint8 images back
+        """A whole loader batch in one launch pair (``kemr_transform_u8_batch``): ``packed`` holds the uint8 images back
         to back (:func:`pack_raw`); the bytes cross to the device in ONE copy (asynchronous when the buffer is pinned,
         as the DataLoader's pin thread leaves it).  Returns float32 ``[B, 3, n_px, n_px]``, each image bit-identical to
         ``self(image)`` and to the host transform."""
@@ -120,23 +131,59 @@ class ClipPreprocessGPU:
             return out
         L = _lib.lib()
         hs, ws, offs = packed.heights, packed.widths, packed.offsets          # int32 / int32 / int64 host arrays
-        need = int(L.kemr_preprocess_batch_workspace_bytes(C.c_void_p(hs.ctypes.data), C.c_void_p(ws.ctypes.data), b, self.n_px))
+        # images the library refuses (SiglipPreprocessGPU._on_host): the kernel sees an empty descriptor in their place -- the offsets
+        # are the packed buffer's own, so nothing is repacked and the others still go in ONE call -- and the host transform fills the slot
+        on_host = [i for i in range(b) if self._on_host(int(hs[i]), int(ws[i]))]
+        host_px = []
+        if on_host:
+            hs, ws = hs.copy(), ws.copy()                                     # (the arrays may be views of the batch's own tensors)
+        for i in on_host:
+            h, w, off = int(hs[i]), int(ws[i]), int(offs[i])
+            host_px.append(self._host(packed.data[off:off + h * w * 3].cpu().view(h, w, 3)))
+            hs[i] = ws[i] = 0
+        need = int(L.kemr_transform_batch_workspace_bytes(self.kind, C.c_void_p(hs.ctypes.data), C.c_void_p(ws.ctypes.data), b, self.n_px))
         if need == 0:
-            raise RuntimeError(f"ClipPreprocessGPU.batch: unsupported image size in the batch -> {self.n_px}")
+            raise RuntimeError(f"{type(self).__name__}.batch: unsupported image size in the batch -> {self.n_px}")
         if self._ws is None or self._ws.numel() < need:
             # grow-only, stream-ordered reuse: every user of the old buffer was queued on the same stream before this point
             self._ws = torch.empty(max(need, 2 * (0 if self._ws is None else self._ws.numel())), dtype=torch.uint8, device=self.device)
         data = packed.data if packed.data.device == self.device else packed.data.to(self.device, non_blocking=True)
         with torch.cuda.device(self.device):
-            _lib.check(L.kemr_preprocess_u8_batch(C.c_void_p(data.data_ptr()), C.c_void_p(offs.ctypes.data),
-                                                  C.c_void_p(hs.ctypes.data), C.c_void_p(ws.ctypes.data), b, self.n_px,
-                                                  C.c_void_p(out.data_ptr()), C.c_void_p(self._ws.data_ptr()), self._ws.numel(),
-                                                  C.c_void_p(engine._stream_ptr(self.device))), "preprocess_u8_batch")
+            _lib.check(L.kemr_transform_u8_batch(self.kind, C.c_void_p(data.data_ptr()), C.c_void_p(offs.ctypes.data),
+                                                 C.c_void_p(hs.ctypes.data), C.c_void_p(ws.ctypes.data), b, self.n_px,
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(self._ws.data_ptr()), self._ws.numel(),
+                                                 C.c_void_p(engine._stream_ptr(self.device))), "transform_u8_batch")
         data.record_stream(torch.cuda.current_stream(self.device))
+        for i, px in zip(on_host, host_px):
+            out[i].copy_(px)
         return out
 
     def __repr__(self):
-        return f"ClipPreprocessGPU(n_px={self.n_px})"
+        return f"{type(self).__name__}(n_px={self.n_px})"
+
+
+class SiglipPreprocessGPU(ClipPreprocessGPU):
+    """The same transform as :class:`SiglipPreprocess` -- squash to ``n_px x n_px``, mean = std = 0.5 -- computed by the same HIP
+    kernels (``KEMR_TRANSFORM_SIGLIP``) and bit-identical to it; same calls as :class:`ClipPreprocessGPU`.  Pillow filters an image
+    with ``height > 100 * width`` that it lowers vertically first, the kernels filter horizontally first, and the library refuses
+    such an image (include/kemr.h): it is computed by the host transform here and copied into its slot -- rare, and the same bits by
+    construction; the rest of a batch still goes through the kernels in one call."""
+
+    kind = 1                           # _lib.TRANSFORM_SIGLIP
+
+    def _on_host(self, h: int, w: int) -> bool:
+        return h > 100 * w and h > self.n_px
+
+    def _host(self, image: torch.Tensor) -> torch.Tensor:
+        from PIL import Image
+        return SiglipPreprocess(self.n_px)(Image.fromarray(image.cpu().numpy()))
+
+
+def gpu_preprocess_for(model, device) -> ClipPreprocessGPU:
+    """The device transform of a model's family at its input resolution (what a :class:`PackedRaw` batch for that model goes through)."""
+    n_px = int(getattr(getattr(model, "visual", None), "input_resolution", 224))
+    family = getattr(getattr(model, "arch", None), "family", "clip")
+    return (SiglipPreprocessGPU if family == "siglip" else ClipPreprocessGPU)(n_px, device)
 
 
 class PackedRaw:
@@ -168,7 +215,7 @@ class PackedRaw:
 
     def to(self, device=None, non_blocking: bool = False, **_kw):
         """``images.to(device)`` of the reference's loop (evaluator.py:118): the pixel bytes move, the sizes stay host arrays.
-        ``CLIP.encode_image`` accepts the result (it runs :meth:`ClipPreprocessGPU.batch` first)."""
+        ``CLIP.encode_image`` accepts the result (it runs the ``batch`` of its family's device transform first)."""
         return PackedRaw(self.data.to(device, non_blocking=non_blocking), self._h, self._w)
 
     @property
@@ -189,7 +236,7 @@ def pack_raw(images) -> PackedRaw:
 
 class RawRGB:
     """Dataset-side half of GPU preprocessing: a PIL image -> uint8 ``[H, W, 3]`` tensor, nothing else.  Give it to a
-    dataset as its ``preprocessor`` and ``evaluators.encode_dataset`` runs :class:`ClipPreprocessGPU` on the device: the
+    dataset as its ``preprocessor`` and ``evaluators.encode_dataset`` runs the model family's device transform (:func:`gpu_preprocess_for`): the
     DataLoader workers then only decode, the resize / crop / normalise leaves the host (bit-identical result)."""
 
     def __call__(self, image) -> torch.Tensor:
