@@ -46,7 +46,10 @@ extern "C" {
  *    KEMR_EPI_BIAS_TGELU_BF16 (kemr_op_gemm) are additions; no entry point changed, kemr_cfg did not grow.
  *    Still 4: kemr_transform_workspace_bytes, kemr_transform_u8, kemr_transform_batch_workspace_bytes and kemr_transform_u8_batch (the
  *    image transform with its kind as an argument: CLIP's or the SigLIP family's) are additions; the four kemr_preprocess_* entry points
- *    keep their signatures and bits (they are the new ones at KEMR_TRANSFORM_CLIP). */
+ *    keep their signatures and bits (they are the new ones at KEMR_TRANSFORM_CLIP).
+ *    Still 4: kemr_model_create_family, model family 2 (BERT sentence encoders) behind it, KEMR_MAX_BERT_CTX and option "pooling" are
+ *    additions; kemr_model_create, option "family" (0 / 1) and every existing entry point keep their behaviour and messages -- what
+ *    they refuse for a family-2 model, no existing caller could reach.  kemr_cfg did not grow. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -113,6 +116,9 @@ typedef enum kemr_tower { KEMR_TOWER_VISION = 0, KEMR_TOWER_TEXT = 1 } kemr_towe
  * whole-sequence-in-LDS kernel. */
 #define KEMR_MAX_VISION_TOKENS 1025
 #define KEMR_MAX_TEXT_CTX 288
+/* family 2 (BERT sentence encoders): the longest text, absolute positions 0 .. 511 (non-causal attention over packed items of
+ * different lengths, csrc/attention_varlen.hip) */
+#define KEMR_MAX_BERT_CTX 512
 
 /* Architecture numbers of an OpenAI-CLIP style model (MLP is 4*width; heads are width/64, except a vision tower under option
  * "vision_head_dim" = 80, whose heads are v_width/80: OpenCLIP's ViT-H-14 {1024,224,14,1280,32,1024,24,49408,77}).
@@ -148,6 +154,30 @@ int kemr_abi_version(void);
  *   load_tensor may be called again after finalize (fine-tuned checkpoint): call finalize again.
  * ------------------------------------------------------------------------------------------- */
 int kemr_model_create(const kemr_cfg* cfg, kemr_model** out);
+/* The same with the model family decided AT creation (the configuration checks depend on it): 0 and 1 are kemr_model_create followed by
+ * kemr_model_set_option("family", family), exactly; 2 = a BERT sentence encoder -- transformers.BertModel without its pooler, then mean
+ * or CLS pooling: intfloat/e5-base-v2 {768,0,0,0,0,768,12,30522,512}, thenlper/gte-large {1024,0,0,0,0,1024,24,30522,512} (the
+ * reference's text-to-text baselines, src/clip/eval/evaluator_lm.py, baselines/evaluate_text_models.py).
+ * Family 2 is text-only: image_size, patch, v_width and v_layers must be 0, embed_dim == t_width (no projection), t_width in
+ * {256, 512, 768, 1024, 1280} with heads of 64 and a 4 x MLP, ctx <= KEMR_MAX_BERT_CTX.
+ * Tensors (fp32, strict): token_embedding.weight [vocab, W] (word_embeddings), positional_embedding [ctx, W] (position_embeddings),
+ *   token_type_embedding [2, W], ln_embed.{weight,bias} (embeddings.LayerNorm); per block transformer.resblocks.i.: attn.in_proj_weight
+ *   [3W, W] / attn.in_proj_bias (query | key | value stacked), attn.out_proj.{weight,bias} (attention.output.dense), ln_1.{weight,bias}
+ *   (attention.output.LayerNorm), mlp.c_fc.* (intermediate.dense), mlp.c_proj.* (output.dense), ln_2.{weight,bias} (output.LayerNorm).
+ * Finalize folds 1/8 into the query rows as everywhere and adds token_type_embedding[0] to the positional table in fp32 (every token
+ *   is of type 0).  Refused for family 2 with the reason in the message: the fp8 precisions and KEMR_PREC_FP32X3.
+ * What the encoder computes (kemr_encode_text_packed, the only encode call of this family; kemr_encode_text -- a padding mask is a
+ *   length -- and kemr_encode_image are refused, kemr_workspace_bytes is 0): per packed row x = LayerNorm(tok[id] + pos'[p]); per block
+ *   (post-LN) q | k | v = h W^T + b, non-causal attention among the item's own rows, x = LayerNorm(x + out_proj(a)), x = LayerNorm(x +
+ *   fc2(gelu(fc1(x)))) with the exact GELU; every LayerNorm with eps 1e-12; h, the GEMM operand, is bf16(x); the stream x is stored in
+ *   the precision's type (24-bit / fp32 / bf16).  out[i] = the mean of item i's lens[i] final rows, summed in fp32 (option "pooling" 0,
+ *   the default: sentence-transformers' masked mean pooling) or its first row (option "pooling" 1: CLS, as BGE uses), L2-normalised when
+ *   normalize != 0.  Options "residual_fusion", "last_block_pooled_row", "activation" and "vision_head_dim" are not consulted;
+ *   kemr_model_set_option("family", 2) is refused with a message naming this entry point.  A length that cuts a text short encodes the
+ *   shorter text.  Workspace: kemr_text_packed_workspace_bytes (16, 17 or 18 bytes per allocated row and width element -- bf16, 24-bit or fp32
+ *   stream -- + the row starts; no pooled-row area), the
+ *   memory contract of the encoders below. */
+int kemr_model_create_family(const kemr_cfg* cfg, int family, kemr_model** out);
 int kemr_model_load_tensor(kemr_model* m, const char* name, const void* host_ptr, int dtype /*kemr_dtype, F32 only*/,
                            const int64_t* shape, int rank);
 int kemr_model_finalize(kemr_model* m, int precision /*kemr_precision*/);
@@ -196,7 +226,9 @@ int kemr_model_destroy(kemr_model* m);
  *                      the fp8 precisions, KEMR_PREC_FP32X3 and "vision_head_dim" != 64; kemr_encode_text_packed (a pad position is a
  *                      key and the pooled row is the last one, so no row can be left out).  The family's pixels are those of its own
  *                      image transform (squash to S x S, mean = std = 0.5): KEMR_TRANSFORM_SIGLIP of kemr_transform_u8 /
- *                      kemr_transform_u8_batch below computes them on the device; the option itself does not touch the input side. */
+ *                      kemr_transform_u8_batch below computes them on the device; the option itself does not touch the input side.
+ *                      2 (BERT) is refused here: kemr_model_create_family.
+ *   "pooling"          (family 2 only; any time) 0 = mean over the item's rows (default), 1 = the item's first row (CLS). */
 int kemr_model_set_option(kemr_model* m, const char* key, int value);
 int kemr_model_get_option(const kemr_model* m, const char* key, int* value);
 /* number of required tensor names; name i via kemr_model_tensor_name (for strict-load diagnostics) */

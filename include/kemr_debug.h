@@ -113,6 +113,25 @@ int kemr_debug_text_tokens(struct kemr_model* m, const int32_t* ids_dev, const i
 int kemr_debug_map_head(struct kemr_model* m, const void* h_dev, int batch, void* attn_out_dev, float* out_dev, int normalize,
                         void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The kernels of model family 2 (BERT sentence encoders) alone (tests/test_bert_ops_gpu.py), each a pass-through to its launcher.
+ * attention_varlen: NON-causal attention over packed items, qkv bf16 [rows, 3 width] (heads of 64, q pre-scaled by 1/8) -> out bf16
+ *   [rows, width]; item b = the rows row_start[b] .. row_start[b + 1] - 1, 1 .. max_t <= KEMR_MAX_BERT_CTX of them.  Exactly the rows
+ *   row_start[0] .. row_start[batch] - 1 of out are written; no row outside an item's own can reach its output.
+ * layernorm_post: the post-LN form, o = LayerNorm(x + delta) (delta bf16 [rows, width]); x (x_dtype KEMR_F32, KEMR_BF16 or 24) is
+ *   overwritten with o in its storage type, h bf16 [rows, width] = bf16(o).  Exactly rows x width elements of each are touched.
+ * pool_rows: out fp32 [batch, width] = per item the mean of its rows of x (pooling 0) or its first row (pooling 1), divided by its L2
+ *   norm when normalize != 0.
+ * bert_front: kemr_encode_text_packed's checks, workspace and launches up to the first QKV GEMM of a family-2 model: x_out = the `rows`
+ *   stream rows (the model's storage type), h_out = their bf16 copies, row_start_out = the batch + 1 row starts. */
+int kemr_debug_op_attention_varlen(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width,
+                                   void* stream);
+int kemr_debug_op_layernorm_post(void* x_dev, int x_dtype, const void* delta_dev, const float* gamma_dev, const float* beta_dev,
+                                 void* h_dev, int rows, int width, float eps, void* stream);
+int kemr_debug_op_pool_rows(const void* x_dev, int x_dtype, const int* row_start_dev, int batch, int width, int pooling, int normalize,
+                            float* out_dev, void* stream);
+int kemr_debug_bert_front(struct kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, void* x_out_dev,
+                          void* h_out_dev, int* row_start_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

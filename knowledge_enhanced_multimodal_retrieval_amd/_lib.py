@@ -45,6 +45,8 @@ EPI_BIAS_GELU_BF16 = 5      # exact (erf) GELU; 3 is internal to the library
 EPI_BIAS_TGELU_BF16 = 8     # tanh GELU ("gelu_pytorch_tanh": the SigLIP family's fc1)
 # model option "activation" (include/kemr.h): the MLP's activation, by the name Hugging Face configs give it (`hidden_act`)
 ACTIVATIONS = {"quick_gelu": 0, "gelu": 1}
+FAMILY_BERT = 2             # kemr_model_create_family: a BERT sentence encoder (text-only)
+MAX_BERT_CTX = 512          # KEMR_MAX_BERT_CTX
 MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused / kemr_cross_attention_rerank / kemr_list_fuse
 
 
@@ -60,6 +62,7 @@ SIGNATURES = {
     "kemr_last_error": (C.c_char_p, []),
     "kemr_abi_version": (_i, []),
     "kemr_model_create": (_i, [C.POINTER(KemrCfg), C.POINTER(_vp)]),
+    "kemr_model_create_family": (_i, [C.POINTER(KemrCfg), _i, C.POINTER(_vp)]),
     "kemr_model_load_tensor": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(_i64), _i]),
     "kemr_model_finalize": (_i, [_vp, _i]),
     "kemr_model_destroy": (_i, [_vp]),
@@ -126,6 +129,10 @@ DEBUG_SIGNATURES = {
     "kemr_debug_image_tokens": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "kemr_debug_text_tokens": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "kemr_debug_map_head": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "kemr_debug_op_attention_varlen": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "kemr_debug_op_layernorm_post": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "kemr_debug_op_pool_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "kemr_debug_bert_front": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 ABI_VERSION = 4
 

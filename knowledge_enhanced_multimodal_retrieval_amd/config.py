@@ -95,6 +95,54 @@ class ClipArch:
         return 2.0 * (self.t_layers * per_layer + w * self.embed_dim)
 
 
+@dataclass(frozen=True)
+class BertArch:
+    """A BERT sentence encoder (model family 2 of the library, `kemr_model_create_family`): ``transformers.BertModel`` without its
+    pooler, then mean or CLS pooling.  Text-only: heads of 64, a 4 x MLP, exact GELU, LayerNorm eps 1e-12, absolute positions.
+    intfloat/e5-base-v2 = BertArch(768, 12), thenlper/gte-large = BertArch(1024, 24)."""
+    width: int
+    layers: int
+    vocab: int = 30522
+    ctx: int = 512                # positions the model serves (`max_seq_length` of a sentence-transformers directory, else max_position_embeddings)
+    pooling: str = "mean"         # "mean" (masked mean pooling) or "cls"
+    positions: int = 0            # rows of the checkpoint's positional table when it has more than ctx (0 = ctx)
+    family: str = "bert"
+
+    def __post_init__(self):
+        if self.width not in (256, 512, 768, 1024, 1280):
+            raise ValueError(f"BertArch: width {self.width}; served: 256, 512, 768, 1024, 1280 (heads of 64, multiples of 256)")
+        if not 1 <= self.ctx <= 512:
+            raise ValueError(f"BertArch: ctx {self.ctx} not in 1..512")
+        if self.pooling not in BERT_POOLING:
+            raise ValueError(f"BertArch: pooling {self.pooling!r}; served: {list(BERT_POOLING)}")
+
+    @property
+    def embed_dim(self) -> int:
+        return self.width
+
+    @property
+    def heads(self) -> int:
+        return self.width // 64
+
+    def cfg_dict(self) -> Dict[str, int]:
+        """The nine numbers of kemr_cfg for family 2: the vision fields are 0, embed_dim is the width."""
+        return dict(embed_dim=self.width, image_size=0, patch=0, v_width=0, v_layers=0, t_width=self.width, t_layers=self.layers,
+                    vocab=self.vocab, ctx=self.ctx)
+
+    def text_flops(self, tokens: int) -> float:
+        """Algorithmic FLOPs of one text of `tokens` tokens."""
+        t, w = tokens, self.width
+        return 2.0 * self.layers * (t * w * 3 * w + t * w * w + 2 * t * t * w + 2 * t * w * 4 * w)
+
+
+BERT_POOLING = {"mean": 0, "cls": 1}     # model option "pooling" (include/kemr.h)
+BERT_ARCHS: Dict[str, BertArch] = {
+    "e5-base-v2": BertArch(768, 12),
+    "gte-large": BertArch(1024, 24),
+    "tiny-bert": BertArch(256, 2, vocab=1024),       # the test fixture
+}
+
+
 def _siglip(image_size: int, width: int, layers: int, **kw) -> ClipArch:
     """A SigLIP arch: both towers `width` wide and `layers` deep, patch 16, joint dim = width, vocabulary 32000, 64 positions."""
     kw = {"vocab": 32000, "ctx": 64, **kw}

@@ -80,7 +80,9 @@ struct kemr_model {
     int x3 = 0;                                     // KEMR_PREC_FP32X3: split-bf16 operand triples, fp32 between the kernels (run_blocks_x3)
     int v_head_dim = 64;                            // option "vision_head_dim" (before finalize): 64, or 80 (ViT-H-14: 1280 = 16 heads of 80)
     int stream24 = 1;                               // option "residual_stream_24bit" (before finalize; default on since round 4): the fp32-class stream stored in 3 bytes
-    int family = 0;                                 // option "family" (before the first load_tensor): 0 = CLIP, 1 = SigLIP (no class token / ln_pre, tanh GELU, eps 1e-6, pooling head, unmasked text)
+    int family = 0;                                 // option "family" (before the first load_tensor): 0 = CLIP, 1 = SigLIP (no class token / ln_pre, tanh GELU, eps 1e-6, pooling head, unmasked text);
+                                                    // 2 = BERT sentence encoder (kemr_model_create_family only: text-only, post-LN blocks, eps 1e-12, mean / CLS pooling)
+    int pooling = 0;                                // option "pooling" (family 2): 0 = mean of the item's rows, 1 = its first row (CLS)
     bool any_loaded = false;                        // a tensor was loaded: the name list is fixed from then on
     float eps = 1e-5f;                              // every LayerNorm's epsilon: 1e-6 for family 1
     int vtokens = 0;                                // token rows per image: patches + 1 (class token), patches for family 1
@@ -96,6 +98,7 @@ struct kemr_model {
     // made at finalize, the k | v rows of in_proj (wkv = in_proj_weight + W * W), out_proj, LayerNorm and MLP
     const float* tproj_b = nullptr;
     const bf16_t *mh_q = nullptr, *mh_wkv = nullptr, *mh_wo = nullptr, *mh_w1 = nullptr, *mh_w2 = nullptr;
+    const float *lne_g = nullptr, *lne_b = nullptr;  // family 2: the embedding LayerNorm (ln_embed.*)
     const float *mh_bkv = nullptr, *mh_bo = nullptr, *mh_ln_g = nullptr, *mh_ln_b = nullptr, *mh_b1 = nullptr, *mh_b2 = nullptr;
 };
 
@@ -136,6 +139,19 @@ int check_cfg(const kemr_cfg& c) {
     return KEMR_OK;
 }
 
+// family 2 (BERT sentence encoders): text-only, the vision fields are 0, the embedding is the pooled stream row
+int check_cfg_bert(const kemr_cfg& c) {
+    if (c.image_size || c.patch || c.v_width || c.v_layers)
+        KEMR_FAIL(KEMR_ERR_INVALID, "cfg: family 2 (BERT) is text-only: image_size, patch, v_width and v_layers must be 0 (got %d, %d, %d, %d)", c.image_size, c.patch, c.v_width, c.v_layers);
+    if (c.t_width != 256 && c.t_width != 512 && c.t_width != 768 && c.t_width != 1024 && c.t_width != 1280)
+        KEMR_FAIL(KEMR_ERR_INVALID, "cfg: family 2 (BERT) serves t_width in {256,512,768,1024,1280}, got %d", c.t_width);
+    if (c.embed_dim != c.t_width)
+        KEMR_FAIL(KEMR_ERR_INVALID, "cfg: family 2 (BERT) has no projection: embed_dim %d must equal t_width %d", c.embed_dim, c.t_width);
+    if (c.t_layers <= 0 || c.vocab <= 0 || c.ctx <= 0) KEMR_FAIL(KEMR_ERR_INVALID, "cfg: non-positive field");
+    if (c.ctx > KEMR_MAX_BERT_CTX) KEMR_FAIL(KEMR_ERR_INVALID, "cfg: family 2 (BERT) sequence length %d > %d not supported", c.ctx, KEMR_MAX_BERT_CTX);
+    return KEMR_OK;
+}
+
 // the required tensors of a model family, in load order (kemr_model_create; option "family" rebuilds the list)
 void build_names(kemr_model* m) {
     const kemr_cfg* cfg = &m->cfg;
@@ -143,6 +159,18 @@ void build_names(kemr_model* m) {
     m->tensors.clear();
     auto add = [&](const std::string& n, std::vector<int64_t> shape) { m->names.push_back(n); m->tensors[n].shape = std::move(shape); };
     const int vw = cfg->v_width, tw = cfg->t_width, D = cfg->embed_dim;
+    if (m->family == 2) {
+        // BertModel without its pooler, by OpenAI-style names: ln_1 = attention.output.LayerNorm, ln_2 = output.LayerNorm (post-LN)
+        m->vtokens = 0;
+        m->eps = 1e-12f;
+        add("token_embedding.weight", {cfg->vocab, tw});
+        add("positional_embedding", {cfg->ctx, tw});
+        add("token_type_embedding", {2, tw});
+        add("ln_embed.weight", {tw});
+        add("ln_embed.bias", {tw});
+        add_block_names(m->names, m->tensors, "transformer", tw, cfg->t_layers);
+        return;
+    }
     const bool sig = m->family == 1;
     m->vtokens = sig ? m->patches : m->patches + 1;
     m->eps = sig ? 1e-6f : 1e-5f;
@@ -192,22 +220,29 @@ struct ArenaPlan {
 extern "C" const char* kemr_last_error(void) { return g_err; }
 extern "C" int kemr_abi_version(void) { return KEMR_ABI_VERSION; }
 
-extern "C" int kemr_model_create(const kemr_cfg* cfg, kemr_model** out) {
+static int model_create(const kemr_cfg* cfg, int family, kemr_model** out) {
     if (!cfg || !out) KEMR_FAIL(KEMR_ERR_INVALID, "model_create: null argument");
-    KEMR_TRY(check_cfg(*cfg));
+    if (family < 0 || family > 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_create_family: family 0 (CLIP), 1 (SigLIP) or 2 (BERT), got %d", family);
+    KEMR_TRY(family == 2 ? check_cfg_bert(*cfg) : check_cfg(*cfg));
     kemr_model* m = new (std::nothrow) kemr_model();
     if (!m) KEMR_FAIL(KEMR_ERR_NOMEM, "model_create: out of memory");
     m->cfg = *cfg;
+    m->family = family;
     { const char* v = getenv("KEMR_RESADD"); const int e = (v && *v) ? atoi(v) : 1; m->resadd = e < 0 ? 0 : e > 2 ? 2 : e; }
     { const char* v = getenv("KEMR_LAST_BLOCK_FULL"); m->last_pooled = (v && *v && atoi(v) != 0) ? 0 : 1; }
     { const char* v = getenv("KEMR_STREAM24"); m->stream24 = (v && *v) ? (atoi(v) != 0 ? 1 : 0) : 1; }
-    m->grid = cfg->image_size / cfg->patch;
-    m->patches = m->grid * m->grid;
-    m->kpad = (int)round_up(3 * cfg->patch * cfg->patch, 64);
+    if (family != 2) {
+        m->grid = cfg->image_size / cfg->patch;
+        m->patches = m->grid * m->grid;
+        m->kpad = (int)round_up(3 * cfg->patch * cfg->patch, 64);
+    }
     build_names(m);
     *out = m;
     return KEMR_OK;
 }
+
+extern "C" int kemr_model_create(const kemr_cfg* cfg, kemr_model** out) { return model_create(cfg, 0, out); }
+extern "C" int kemr_model_create_family(const kemr_cfg* cfg, int family, kemr_model** out) { return model_create(cfg, family, out); }
 
 extern "C" int kemr_model_num_tensors(const kemr_model* m) { return m ? (int)m->names.size() : 0; }
 extern "C" const char* kemr_model_tensor_name(const kemr_model* m, int i) {
@@ -247,6 +282,10 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
     if (precision < KEMR_PREC_BF16 || precision > KEMR_PREC_FP32X3)
         KEMR_FAIL(KEMR_ERR_INVALID, "finalize: unsupported precision %d", precision);
     const int fp8 = (precision == KEMR_PREC_FP8 || precision == KEMR_PREC_FP8_RES16) ? 1 : precision == KEMR_PREC_FP8_MLP ? 3 : 0;
+    if (m->family == 2) {
+        if (fp8) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: the fp8 precisions are not served for family 2 (BERT): the e4m3 path is validated on the CLIP towers only");
+        if (precision == KEMR_PREC_FP32X3) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: KEMR_PREC_FP32X3 is not served for family 2 (BERT): the split-bf16 towers have no post-LN blocks");
+    }
     if (fp8 && ((m->cfg.v_width % 128) || (m->cfg.t_width % 128) || m->cfg.v_width < 256 || m->cfg.t_width < 256))
         KEMR_FAIL(KEMR_ERR_INVALID, "finalize: fp8 needs tower widths that are multiples of 128 and >= 256");
     if (m->v_head_dim == 80) {
@@ -354,6 +393,12 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
             float* d = (float*)dst;
             const size_t w = cb.size();
             for (size_t i = 0; i < t.data.size(); ++i) d[i] = t.data[i] + cb[i % w];
+        } else if (m->family == 2 && n == "positional_embedding") {
+            // family 2: every token is of type 0 (a single segment), so token_type_embedding[0] rides in the positional table, added in fp32
+            const std::vector<float>& tt = m->tensors["token_type_embedding"].data;
+            float* d = (float*)dst;
+            const size_t w = (size_t)m->cfg.t_width;
+            for (size_t i = 0; i < t.data.size(); ++i) d[i] = t.data[i] + tt[i % w];
         } else if (n == "visual.attn_pool.probe") {
             // the pooling head's single query, the same for every image: (probe . Wq^T + bq) / 8 in fp32 (double accumulation), rounded to
             // bf16 once -- what the q rows of a block's QKV GEMM are, with the scale folded in before the rounding
@@ -439,13 +484,17 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
             L.w2 = H(b + ".mlp.c_proj.weight"); L.b2 = F(b + ".mlp.c_proj.bias");
         }
     };
-    tower(m->vis, "visual.transformer", m->cfg.v_width, m->cfg.v_layers, m->vtokens, fp8);
     tower(m->txt, "transformer", m->cfg.t_width, m->cfg.t_layers, m->cfg.ctx, 0);
-    m->vis.head_dim = m->v_head_dim;
-    m->conv_w = H("visual.conv1.weight");
-    m->vpos = F("visual.positional_embedding");
-    m->lnpost_g = F("visual.ln_post.weight"); m->lnpost_b = F("visual.ln_post.bias");
-    if (m->family == 1) {
+    if (m->family != 2) {
+        tower(m->vis, "visual.transformer", m->cfg.v_width, m->cfg.v_layers, m->vtokens, fp8);
+        m->vis.head_dim = m->v_head_dim;
+        m->conv_w = H("visual.conv1.weight");
+        m->vpos = F("visual.positional_embedding");
+        m->lnpost_g = F("visual.ln_post.weight"); m->lnpost_b = F("visual.ln_post.bias");
+    }
+    if (m->family == 2) {
+        m->lne_g = F("ln_embed.weight"); m->lne_b = F("ln_embed.bias");
+    } else if (m->family == 1) {
         const std::string h = "visual.attn_pool";
         const size_t vw = (size_t)m->cfg.v_width;
         m->cls = m->lnpre_g = m->lnpre_b = m->vproj = nullptr;
@@ -463,7 +512,7 @@ extern "C" int kemr_model_finalize(kemr_model* m, int precision) {
         m->tproj_b = nullptr;
     }
     m->tok = F("token_embedding.weight"); m->tpos = F("positional_embedding");
-    m->lnf_g = F("ln_final.weight"); m->lnf_b = F("ln_final.bias"); m->tproj = F("text_projection");
+    if (m->family != 2) { m->lnf_g = F("ln_final.weight"); m->lnf_b = F("ln_final.bias"); m->tproj = F("text_projection"); }
 
     for (auto& kv : m->tensors) { std::vector<float>().swap(kv.second.data); kv.second.loaded = false; }
     m->res_dtype = (precision == KEMR_PREC_BF16_RES16 || precision == KEMR_PREC_FP8_RES16) ? KEMR_BF16 : KEMR_F32;
@@ -653,6 +702,7 @@ int image_front(kemr_model* m, const float* pixels_dev, int batch, const void* o
                 hipStream_t s, const char* what, Workspace& w) {
     if (!m || !pixels_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
     if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
+    if (m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 2 (BERT): a text-only model has no vision tower", what);
     if (m->x3) KEMR_FAIL(KEMR_ERR_STATE, "%s: not available for a KEMR_PREC_FP32X3 model", what);
     if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
     if ((int64_t)batch * m->vtokens > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
@@ -696,6 +746,8 @@ int map_head(const kemr_model* m, const Workspace& w, const bf16_t* h, int batch
 int text_front(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, bool packed, const void* out_dev,
                void* workspace_dev, size_t workspace_bytes, hipStream_t s, const char* what, Workspace& w, int** row_start) {
     if (!m || !ids_dev || !out_dev || (packed && !lens_dev)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
+    if (m->family == 2)
+        KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 2 (BERT): a padding mask is a length -- call kemr_encode_text_packed with the lengths (kemr_debug_bert_front for the front alone)", what);
     if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
     if (m->x3) KEMR_FAIL(KEMR_ERR_STATE, "%s: not available for a KEMR_PREC_FP32X3 model", what);
     if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
@@ -811,6 +863,63 @@ int encode_text_x3(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_de
     return launch_tail(w.x, KEMR_F32, nullptr, nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s, row_start);
 }
 
+// ---- family 2: BERT sentence encoders (transformers.BertModel without its pooler + mean / CLS pooling) on packed rows ----
+// Workspace: the token-row buffers of `carve` with no pooled-row area (every row runs through every block and feeds the pooling), then
+// the batch + 1 row starts.  bert_front = the argument checks, the carve, the row starts and the embedding front; every check, the
+// workspace's included, comes before the first launch.
+size_t bert_ws_bytes(const kemr_model* m, int rows, int batch) {
+    return ws_bytes_rows(m->cfg.t_width, rows, m->res_dtype) + (size_t)round_up(((int64_t)batch + 1) * 4, 256);
+}
+
+int bert_front(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, const void* out_dev, void* workspace_dev,
+               size_t workspace_bytes, hipStream_t s, const char* what, Workspace& w, int** row_start) {
+    if (!m || !ids_dev || !lens_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
+    if (m->family != 2) KEMR_FAIL(KEMR_ERR_INVALID, "%s: only family 2 (BERT) has this front", what);
+    if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
+    if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
+    const int W = m->cfg.t_width, T = m->cfg.ctx;
+    if (batch > 65535) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d > 65535", what, batch);
+    if (rows < batch || (int64_t)rows > (int64_t)batch * T) KEMR_FAIL(KEMR_ERR_INVALID, "%s: %d rows for %d texts of 1 .. %d positions", what, rows, batch, T);
+    if (rows > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: %d rows in one call (at most %d)", what, rows, 1 << 24);
+    const size_t base_bytes = ws_bytes_rows(W, rows, m->res_dtype), need = bert_ws_bytes(m, rows, batch);
+    if (!workspace_dev || workspace_bytes < need) KEMR_FAIL(KEMR_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    KEMR_TRY(carve(w, workspace_dev, workspace_bytes, W, rows, 0, m->res_dtype));
+    *row_start = (int*)((char*)workspace_dev + base_bytes);
+    KEMR_TRY(launch_row_starts(lens_dev, batch, T, rows, *row_start, s));
+    return launch_bert_embed(ids_dev, m->tok, m->tpos, m->lne_g, m->lne_b, w.x, w.x_dtype, w.h, batch, T, W, m->cfg.vocab, *row_start, rows, m->eps, s);
+}
+
+// Post-LN blocks: QKV on h, attention over the packed items, out-proj into delta (store-only), x = LN(x + delta) with h = bf16(x), fc1
+// with the exact GELU, fc2 into delta2, x = LN(x + delta2) with h = bf16(x).  Options "residual_fusion", "last_block_pooled_row" and
+// "activation" are not consulted.
+int encode_bert(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev, int normalize,
+                void* workspace_dev, size_t workspace_bytes, hipStream_t s) {
+    Workspace w;
+    int* row_start = nullptr;
+    KEMR_TRY(bert_front(m, ids_dev, lens_dev, rows, batch, out_dev, workspace_dev, workspace_bytes, s, "encode_text_packed", w, &row_start));
+    if (batch == 0) return KEMR_OK;
+    const TowerW& t = m->txt;
+    const int W = t.width, M = rows;
+    for (int l = 0; l < t.layers; ++l) {
+        const LayerW& L = t.layer[l];
+        GemmParams g{};
+        g.M = M;
+        g.c_rows_padded = 1;       // every workspace buffer has ceil256(M) rows
+        g.A = w.h; g.lda = W; g.W = L.wqkv; g.ldw = W; g.bias = L.bqkv; g.C = w.big; g.ldc = 3 * W; g.N = 3 * W; g.K = W;
+        KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
+        KEMR_TRY(launch_attention_varlen(w.big, w.h, row_start, batch, t.tokens, W, s));
+        g.A = w.h; g.W = L.wo; g.bias = L.bo; g.C = w.delta; g.ldc = W; g.N = W;
+        KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
+        KEMR_TRY(launch_layernorm_post(w.x, w.x_dtype, w.delta, L.ln1_g, L.ln1_b, w.h, M, W, s, m->eps));
+        g.A = w.h; g.W = L.w1; g.bias = L.b1; g.C = w.big; g.ldc = 4 * W; g.N = 4 * W;
+        KEMR_TRY(launch_gemm(g, EPI_BIAS_GELU_BF16, s));
+        g.A = w.big; g.lda = 4 * W; g.W = L.w2; g.ldw = 4 * W; g.bias = L.b2; g.C = w.delta2; g.ldc = W; g.N = W; g.K = 4 * W;
+        KEMR_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
+        KEMR_TRY(launch_layernorm_post(w.x, w.x_dtype, w.delta2, L.ln2_g, L.ln2_b, w.h, M, W, s, m->eps));
+    }
+    return launch_pool_rows(w.x, w.x_dtype, row_start, batch, W, m->pooling, normalize, out_dev, s);
+}
+
 // family 1's activation is the family's (tanh GELU); option "activation" is not consulted there
 int fc1_epilogue(const kemr_model* m) { return m->family == 1 ? EPI_BIAS_TGELU_BF16 : m->activation == 1 ? EPI_BIAS_GELU_BF16 : EPI_BIAS_QGELU_BF16; }
 
@@ -818,6 +927,7 @@ int fc1_epilogue(const kemr_model* m) { return m->family == 1 ? EPI_BIAS_TGELU_B
 
 extern "C" size_t kemr_workspace_bytes(const kemr_model* m, int tower, int batch) {
     if (!m || batch <= 0) return 0;
+    if (m->family == 2) return 0;                      // family 2 has the packed call only (kemr_text_packed_workspace_bytes)
     if (m->x3) {
         if (tower == KEMR_TOWER_VISION) return ws_bytes_x3(m->cfg.v_width, (int64_t)batch * (m->patches + 1));
         return tower == KEMR_TOWER_TEXT ? ws_bytes_x3(m->cfg.t_width, (int64_t)batch * m->cfg.ctx) : 0;
@@ -829,6 +939,7 @@ extern "C" size_t kemr_workspace_bytes(const kemr_model* m, int tower, int batch
 
 extern "C" size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows, int batch) {
     if (!m || batch <= 0 || rows < batch) return 0;
+    if (m->family == 2) return bert_ws_bytes(m, rows, batch);                                      // buffers + row_start (no pooled-row area)
     if (m->x3) return ws_bytes_x3(m->cfg.t_width, rows) + (size_t)round_up(((int64_t)batch + 1) * 4, 256);
     return ws_bytes_rows(m->cfg.t_width, rows, m->res_dtype) + compact_bytes(m->cfg.t_width, batch) +
            (size_t)round_up(((int64_t)batch + 1) * 4, 256);                                        // buffers + pooled-row area + row_start
@@ -837,6 +948,7 @@ extern "C" size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows
 extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize,
                                  void* workspace_dev, size_t workspace_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
+    if (m && m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: not available for family 2 (BERT): a text-only model has no vision tower");
     if (m && m->finalized && m->x3) return encode_image_x3(m, pixels_dev, batch, out_dev, normalize, workspace_dev, workspace_bytes, s);
     Workspace w;
     KEMR_TRY(image_front(m, pixels_dev, batch, out_dev, workspace_dev, workspace_bytes, s, "encode_image", w));
@@ -861,6 +973,8 @@ extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int bat
 extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch, float* out_dev, int normalize,
                                 void* workspace_dev, size_t workspace_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
+    if (m && m->family == 2)
+        KEMR_FAIL(KEMR_ERR_INVALID, "encode_text: not available for family 2 (BERT): a padding mask is a length -- call kemr_encode_text_packed with the lengths");
     if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, nullptr, 0, batch, false, out_dev, normalize, workspace_dev, workspace_bytes, s);
     Workspace w;
     int* no_rows = nullptr;
@@ -894,6 +1008,7 @@ extern "C" int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, co
     hipStream_t s = (hipStream_t)stream;
     if (m && m->family == 1)
         KEMR_FAIL(KEMR_ERR_INVALID, "encode_text_packed: not available for family 1 (SigLIP): its text tower is unmasked and pools the last position, so a pad position is a key and no row can be left out");
+    if (m && m->family == 2) return encode_bert(m, ids_dev, lens_dev, rows, batch, out_dev, normalize, workspace_dev, workspace_bytes, s);
     if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, lens_dev, rows, batch, true, out_dev, normalize, workspace_dev, workspace_bytes, s);
     Workspace w;
     int* row_start = nullptr;
@@ -922,6 +1037,8 @@ extern "C" int kemr_model_set_option(kemr_model* m, const char* key, int value) 
         return KEMR_OK;
     }
     if (!strcmp(key, "family")) {
+        if (value == 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): 0 (CLIP) or 1 (SigLIP), got 2 (family 2, BERT, has its own configuration checks and is decided at creation: kemr_model_create_family)");
+        if (m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): a family 2 (BERT) model keeps its family (kemr_model_create_family)");
         if (value < 0 || value > 1) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): 0 (CLIP) or 1 (SigLIP), got %d", value);
         if (m->any_loaded || m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "model_set_option(family): set it before the first kemr_model_load_tensor (it decides the tensor names)");
         if (value == 1 && m->v_head_dim != 64) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): family 1 (SigLIP) serves vision_head_dim 64 only, got %d", m->v_head_dim);
@@ -929,7 +1046,14 @@ extern "C" int kemr_model_set_option(kemr_model* m, const char* key, int value) 
         build_names(m);
         return KEMR_OK;
     }
+    if (!strcmp(key, "pooling")) {
+        if (m->family != 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(pooling): the option exists for family 2 (BERT) only");
+        if (value < 0 || value > 1) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(pooling): 0 (mean) or 1 (first row, CLS), got %d", value);
+        m->pooling = value;
+        return KEMR_OK;
+    }
     if (!strcmp(key, "vision_head_dim")) {
+        if (m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): family 2 (BERT) has no vision tower");
         if (m->family == 1 && value != 64) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): family 1 (SigLIP) serves vision_head_dim 64 only, got %d", value);
         if (value != 64 && value != 80) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): 64 or 80, got %d", value);
         if (m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "model_set_option(vision_head_dim): set it before kemr_model_finalize");
@@ -958,6 +1082,7 @@ extern "C" int kemr_model_get_option(const kemr_model* m, const char* key, int* 
     if (!strcmp(key, "activation")) { *value = m->activation; return KEMR_OK; }
     if (!strcmp(key, "vision_head_dim")) { *value = m->v_head_dim; return KEMR_OK; }
     if (!strcmp(key, "family")) { *value = m->family; return KEMR_OK; }
+    if (!strcmp(key, "pooling")) { *value = m->pooling; return KEMR_OK; }
     if (!strcmp(key, "precision_residual_bf16")) { *value = m->res_dtype == KEMR_BF16; return KEMR_OK; }
     KEMR_FAIL(KEMR_ERR_INVALID, "model_get_option: unknown key '%s'", key);
 }
@@ -1098,6 +1223,40 @@ extern "C" int kemr_debug_map_head(kemr_model* m, const void* h_dev, int batch, 
     KEMR_CHECK_HIP(hipMemcpyAsync(w.h, h_dev, (size_t)batch * T * W * 2, hipMemcpyDeviceToDevice, s));
     KEMR_TRY(map_head(m, w, w.h, batch, normalize, out_dev, s));
     if (attn_out_dev) KEMR_CHECK_HIP(hipMemcpyAsync(attn_out_dev, w.ac, (size_t)batch * W * 2, hipMemcpyDeviceToDevice, s));
+    return KEMR_OK;
+}
+
+// ---- family 2 (BERT): the new kernels alone ----
+extern "C" int kemr_debug_op_attention_varlen(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width,
+                                              void* stream) {
+    if (!qkv_dev || !out_dev || !row_start_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_attention_varlen: null argument");
+    return launch_attention_varlen((const bf16_t*)qkv_dev, (bf16_t*)out_dev, row_start_dev, batch, max_t, width, (hipStream_t)stream);
+}
+
+extern "C" int kemr_debug_op_layernorm_post(void* x_dev, int x_dtype, const void* delta_dev, const float* gamma_dev, const float* beta_dev,
+                                            void* h_dev, int rows, int width, float eps, void* stream) {
+    if (!x_dev || !delta_dev || !gamma_dev || !beta_dev || !h_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_layernorm_post: null argument");
+    return launch_layernorm_post(x_dev, x_dtype, (const bf16_t*)delta_dev, gamma_dev, beta_dev, (bf16_t*)h_dev, rows, width, (hipStream_t)stream, eps);
+}
+
+extern "C" int kemr_debug_op_pool_rows(const void* x_dev, int x_dtype, const int* row_start_dev, int batch, int width, int pooling, int normalize,
+                                       float* out_dev, void* stream) {
+    if (!x_dev || !row_start_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_pool_rows: null argument");
+    return launch_pool_rows(x_dev, x_dtype, row_start_dev, batch, width, pooling, normalize, out_dev, (hipStream_t)stream);
+}
+
+extern "C" int kemr_debug_bert_front(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, void* x_out_dev,
+                                     void* h_out_dev, int* row_start_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h_out_dev || !row_start_out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_bert_front: null output");
+    hipStream_t s = (hipStream_t)stream;
+    Workspace w;
+    int* row_start = nullptr;
+    KEMR_TRY(bert_front(m, ids_dev, lens_dev, rows, batch, x_out_dev, workspace_dev, workspace_bytes, s, "debug_bert_front", w, &row_start));
+    if (batch == 0) return KEMR_OK;
+    const int xb = w.x_dtype == KEMR_BF16 ? 2 : (w.x_dtype == KEMR_F24 ? 3 : 4);
+    KEMR_CHECK_HIP(hipMemcpyAsync(x_out_dev, w.x, (size_t)rows * m->cfg.t_width * xb, hipMemcpyDeviceToDevice, s));
+    KEMR_CHECK_HIP(hipMemcpyAsync(h_out_dev, w.h, (size_t)rows * m->cfg.t_width * 2, hipMemcpyDeviceToDevice, s));
+    KEMR_CHECK_HIP(hipMemcpyAsync(row_start_out_dev, row_start, ((size_t)batch + 1) * 4, hipMemcpyDeviceToDevice, s));
     return KEMR_OK;
 }
 

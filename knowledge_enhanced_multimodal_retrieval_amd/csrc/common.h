@@ -260,6 +260,9 @@ int launch_select_topk(const float* scores, const int32_t* idx, int nq, int n, l
 // eps: 1e-5 (CLIP), 1e-6 for the SigLIP family
 int launch_layernorm(void* x, int x_dtype, const bf16_t* delta, const bf16_t* delta2, int writeback, const float* gamma,
                      const float* beta, void* y, int rows, int width, int out_dtype, hipStream_t stream, float eps = 1e-5f);
+// the post-LN form (BERT family): x = LayerNorm(x + delta) written back in the stream's storage type, h = its bf16 copy
+int launch_layernorm_post(void* x, int x_dtype, const bf16_t* delta, const float* gamma, const float* beta, bf16_t* h, int rows, int width,
+                          hipStream_t stream, float eps);
 // KEMR_PREC_FP32X3: y = LayerNorm(x) of fp32 rows stored as the A-side triple [hi | lo | hi] into [ceil256(rows), 3 width] bf16, pad rows zero
 int launch_layernorm_x3(const float* x, const float* gamma, const float* beta, bf16_t* y_panel, int rows, int width, hipStream_t stream);
 // KEMR_PREC_FP32X3 (fp32x3.hip): fp32 q | k | v rows [*, 3 width] -> the attention output as an A-side triple [*, 3 width] bf16; streaming
@@ -270,6 +273,9 @@ int launch_im2col_x3(const float* pixels, bf16_t* patches, int batch, int image_
 int launch_attention(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, int causal, hipStream_t stream);
 // non-causal, t up to KEMR_MAX_VISION_TOKENS: K / V streamed through LDS with an online softmax (attention_long.hip)
 int launch_attention_long(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, hipStream_t stream);
+// attention_varlen.hip: NON-causal, items of lengths 1 .. max_t <= KEMR_MAX_BERT_CTX packed one behind the other (row_start as below): the
+// BERT family's attention; per item the arithmetic of launch_attention_long at t = its length
+int launch_attention_varlen(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream);
 // causal, items of lengths 1 .. max_t packed one behind the other: item b = rows row_start[b] .. row_start[b + 1] - 1 (device ints)
 int launch_attention_packed(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream);
 // attention80.hip: heads of 80 columns (the vision tower of ViT-H-14), non-causal, t <= 288: the tile kernel, the pooled row of the last
@@ -300,6 +306,12 @@ int launch_row_starts(const int32_t* lens, int batch, int max_len, int rows, int
 // positions, `rows` in total
 int launch_text_embed(const int32_t* ids, const float* tok_emb, const float* pos, void* x, int x_dtype, int batch, int ctx,
                       int width, int vocab, hipStream_t stream, const int* row_start = nullptr, int rows = 0);
+// BERT family (embed.hip): packed rows x = LayerNorm(tok[id] + pos[p]) in the stream's storage type and h = bf16 of the same values;
+// the pooling tail: per item the mean of its rows (pooling 0) or its first row (1), optionally L2-normalised, -> out fp32 [batch, width]
+int launch_bert_embed(const int32_t* ids, const float* tok_emb, const float* pos, const float* gamma, const float* beta, void* x, int x_dtype,
+                      bf16_t* h, int batch, int ctx, int width, int vocab, const int* row_start, int rows, float eps, hipStream_t stream);
+int launch_pool_rows(const void* x, int x_dtype, const int* row_start, int batch, int width, int pooling, int normalize, float* out,
+                     hipStream_t stream);
 // pooled row -> LayerNorm -> @ proj [width, d] (+ proj_bias [d]) -> optional L2 normalise.  ids == nullptr: row = b * tokens + pool_pos (0: CLS)
 // delta, delta2 (optional): the last block's pending residual updates, added to the pooled row
 int launch_tail(const void* x, int x_dtype, const bf16_t* delta, const bf16_t* delta2, const int32_t* ids, int batch, int tokens, int width, const float* gamma,

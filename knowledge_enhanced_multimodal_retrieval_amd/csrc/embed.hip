@@ -438,4 +438,163 @@ int launch_add_rows_out(const bf16_t* a, const bf16_t* b, int rows, int width, i
     return KEMR_OK;
 }
 
+// ---- BERT sentence encoders (model family 2): the embedding front and the pooling tail -----------------------------------------------
+// the stream row in its storage type (4 elements at index i4 of the row), as the kernels above write it
+template <typename XT>
+__device__ __forceinline__ void store_stream4(XT* row, int i4, float4 a, int width) {
+    if constexpr (sizeof(XT) == 4) {
+        ((float4*)row)[i4] = a;
+    } else if constexpr (sizeof(XT) == 3) {            // 24-bit rows: W upper halves, then W third bytes (common.h f24_t)
+        const uint32_t e0 = f32_to_f24_bits(a.x), e1 = f32_to_f24_bits(a.y), e2 = f32_to_f24_bits(a.z), e3 = f32_to_f24_bits(a.w);
+        uint8_t* r = (uint8_t*)row;
+        uint2 h;
+        h.x = (e0 >> 16) | (e1 & 0xffff0000u);
+        h.y = (e2 >> 16) | (e3 & 0xffff0000u);
+        ((uint2*)r)[i4] = h;
+        ((uint32_t*)(r + 2 * (size_t)width))[i4] = ((e0 >> 8) & 0xff) | (e1 & 0xff00) | ((e2 << 8) & 0xff0000) | ((e3 << 16) & 0xff000000u);
+    } else {
+        uint2 pk;
+        pk.x = pack_bf16x2(a.x, a.y);
+        pk.y = pack_bf16x2(a.z, a.w);
+        ((uint2*)row)[i4] = pk;
+    }
+}
+template <typename XT>
+__device__ __forceinline__ float load_stream1(const XT* row, int i, int width) {
+    if constexpr (sizeof(XT) == 4) return row[i];
+    else if constexpr (sizeof(XT) == 3) return f24_to_f32(((const bf16_t*)row)[i], ((const uint8_t*)row)[2 * (size_t)width + i]);
+    else return bf16_to_f32(row[i]);
+}
+
+// BertEmbeddings of packed rows: x = LayerNorm(tok[id] + pos'[p]) with pos' = positional + token_type[0] (folded at finalize), the
+// two-pass fp32 statistics of layernorm.hip, one wave per row.  Written: the stream row (its storage type) and h = bf16 of the same
+// fp32 values (the first QKV GEMM's A operand).  Row r belongs to the last text i with row_start[i] <= r, at position r - row_start[i].
+template <int NV, typename XT>
+__global__ __launch_bounds__(256) void bert_embed_kernel(const int32_t* __restrict__ ids, const float* __restrict__ tok, const float* __restrict__ pos,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta, XT* __restrict__ x,
+                                                         bf16_t* __restrict__ h, int ctx, int vocab, const int* __restrict__ row_start, int batch,
+                                                         int rows, float eps) {
+    constexpr int W = NV * 256;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    int lo = 0, hi = batch - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (row_start[mid] <= row) lo = mid; else hi = mid - 1;
+    }
+    int t = row - row_start[lo];
+    t = t < 0 ? 0 : (t < ctx ? t : ctx - 1);
+    int id = ids[(size_t)lo * ctx + t];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);   // out-of-range ids are clamped (torch would raise)
+    float4 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const float4 a = ((const float4*)(tok + (size_t)id * W))[i * 64 + lane];
+        const float4 p = ((const float4*)(pos + (size_t)t * W))[i * 64 + lane];
+        v[i] = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
+        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    }
+    const float mean = wave_sum(s) * (1.0f / W);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
+        q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / W) + eps);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const float4 g = ((const float4*)gamma)[i * 64 + lane];
+        const float4 b = ((const float4*)beta)[i * 64 + lane];
+        float4 o;
+        o.x = v[i].x * rstd * g.x + b.x;
+        o.y = v[i].y * rstd * g.y + b.y;
+        o.z = v[i].z * rstd * g.z + b.z;
+        o.w = v[i].w * rstd * g.w + b.w;
+        store_stream4(x + (size_t)row * W, i * 64 + lane, o, W);
+        store_stream4(h + (size_t)row * W, i * 64 + lane, o, W);
+    }
+}
+
+template <typename XT>
+static int launch_bert_embed_xt(const int32_t* ids, const float* tok, const float* pos, const float* g, const float* b, XT* x, bf16_t* h,
+                                int batch, int ctx, int width, int vocab, const int* row_start, int rows, float eps, hipStream_t s) {
+    const dim3 grid((rows + 3) / 4), blk(256);
+    switch (width) {
+        case 256:  hipLaunchKernelGGL((bert_embed_kernel<1, XT>), grid, blk, 0, s, ids, tok, pos, g, b, x, h, ctx, vocab, row_start, batch, rows, eps); break;
+        case 512:  hipLaunchKernelGGL((bert_embed_kernel<2, XT>), grid, blk, 0, s, ids, tok, pos, g, b, x, h, ctx, vocab, row_start, batch, rows, eps); break;
+        case 768:  hipLaunchKernelGGL((bert_embed_kernel<3, XT>), grid, blk, 0, s, ids, tok, pos, g, b, x, h, ctx, vocab, row_start, batch, rows, eps); break;
+        case 1024: hipLaunchKernelGGL((bert_embed_kernel<4, XT>), grid, blk, 0, s, ids, tok, pos, g, b, x, h, ctx, vocab, row_start, batch, rows, eps); break;
+        case 1280: hipLaunchKernelGGL((bert_embed_kernel<5, XT>), grid, blk, 0, s, ids, tok, pos, g, b, x, h, ctx, vocab, row_start, batch, rows, eps); break;
+        default: KEMR_FAIL(KEMR_ERR_INVALID, "bert_embed: width %d not in {256,512,768,1024,1280}", width);
+    }
+    KEMR_CHECK_LAUNCH("bert_embed_kernel");
+    return KEMR_OK;
+}
+
+int launch_bert_embed(const int32_t* ids, const float* tok_emb, const float* pos, const float* gamma, const float* beta, void* x, int x_dtype,
+                      bf16_t* h, int batch, int ctx, int width, int vocab, const int* row_start, int rows, float eps, hipStream_t stream) {
+    if (batch <= 0 || rows <= 0) return KEMR_OK;
+    if (!row_start) KEMR_FAIL(KEMR_ERR_INVALID, "bert_embed: null row_start");
+    ProfScope prof(PROF_OTHER, stream);
+    if (x_dtype == KEMR_BF16) return launch_bert_embed_xt(ids, tok_emb, pos, gamma, beta, (bf16_t*)x, h, batch, ctx, width, vocab, row_start, rows, eps, stream);
+    if (x_dtype == KEMR_F24) return launch_bert_embed_xt(ids, tok_emb, pos, gamma, beta, (f24_t*)x, h, batch, ctx, width, vocab, row_start, rows, eps, stream);
+    if (x_dtype == KEMR_F32) return launch_bert_embed_xt(ids, tok_emb, pos, gamma, beta, (float*)x, h, batch, ctx, width, vocab, row_start, rows, eps, stream);
+    KEMR_FAIL(KEMR_ERR_INVALID, "bert_embed: bad row dtype %d", x_dtype);
+}
+
+// The sentence encoders' pooling: out[b] = the mean of item b's stream rows (pooling 0: masked mean pooling -- the mask is the length)
+// or its first row (pooling 1: CLS), optionally divided by its L2 norm.  One workgroup per item; thread j owns the columns j, j + 256,
+// ... and sums them over the item's rows one after the other in fp32 (a fixed order: same bits on every run), then one division by the
+// length.  width <= 1280: at most 5 columns per thread.
+template <typename XT>
+__global__ __launch_bounds__(256) void pool_rows_kernel(const XT* __restrict__ x, const int* __restrict__ row_start, int width, int pooling,
+                                                        int normalize, float* __restrict__ out) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int r0 = row_start[b];
+    int len = row_start[b + 1] - r0;
+    len = len < 1 ? 1 : len;
+    const int n = pooling == 1 ? 1 : len;
+    float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int r = 0; r < n; ++r) {
+        const XT* xr = x + (size_t)(r0 + r) * width;
+#pragma unroll
+        for (int c = 0; c < 5; ++c) {
+            const int j = tid + c * 256;
+            if (j < width) acc[c] += load_stream1(xr, j, width);
+        }
+    }
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+        acc[c] = acc[c] / (float)n;                     // IEEE division (n = 1: exact)
+        ss += acc[c] * acc[c];                          // (columns >= width hold 0)
+    }
+    float scale = 1.0f;
+    if (normalize) scale = 1.0f / sqrtf(block_sum(ss, red));       // uniform branch; no eps, like the reference's x / x.norm()
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+        const int j = tid + c * 256;
+        if (j < width) out[(size_t)b * width + j] = acc[c] * scale;
+    }
+}
+
+int launch_pool_rows(const void* x, int x_dtype, const int* row_start, int batch, int width, int pooling, int normalize, float* out,
+                     hipStream_t stream) {
+    if (batch <= 0) return KEMR_OK;
+    if (!row_start) KEMR_FAIL(KEMR_ERR_INVALID, "pool_rows: null row_start");
+    if (width <= 0 || width > 1280 || width % 4) KEMR_FAIL(KEMR_ERR_INVALID, "pool_rows: width %d not a multiple of 4 in 4..1280", width);
+    if (pooling != 0 && pooling != 1) KEMR_FAIL(KEMR_ERR_INVALID, "pool_rows: pooling %d is neither 0 (mean) nor 1 (first row)", pooling);
+    ProfScope prof(PROF_OTHER, stream);
+    if (x_dtype == KEMR_BF16) hipLaunchKernelGGL(pool_rows_kernel<bf16_t>, dim3(batch), dim3(256), 0, stream, (const bf16_t*)x, row_start, width, pooling, normalize, out);
+    else if (x_dtype == KEMR_F24) hipLaunchKernelGGL(pool_rows_kernel<f24_t>, dim3(batch), dim3(256), 0, stream, (const f24_t*)x, row_start, width, pooling, normalize, out);
+    else if (x_dtype == KEMR_F32) hipLaunchKernelGGL(pool_rows_kernel<float>, dim3(batch), dim3(256), 0, stream, (const float*)x, row_start, width, pooling, normalize, out);
+    else KEMR_FAIL(KEMR_ERR_INVALID, "pool_rows: bad row dtype %d", x_dtype);
+    KEMR_CHECK_LAUNCH("pool_rows_kernel");
+    return KEMR_OK;
+}
+
 }  // namespace kemr

@@ -13,6 +13,9 @@ namespace kemr {
 //                              stays pending and is added for good, together with the MLP delta, by the next ln_1
 // (one x write per block instead of two; the sums are formed in the same order as two separate updates, so an fp32
 // stream holds bit-identical values).
+//   MODE 3 (post-LN blocks, the BERT family): o = LN(x + d1); x = o (the NORMALISED row is the stream), y = bf16(o) -- both stores
+//                              round the same fp32 o, so h is bf16(o) whatever the stream's storage type.  A lane writes the elements
+//                              it read itself, after the last load of the row: in place is safe.
 // (W = the row's width in elements; only the 24-bit rows need it: their third bytes sit behind the W upper halves)
 __device__ __forceinline__ float4 load_row4(const float* r, int i, int) { return ((const float4*)r)[i]; }
 __device__ __forceinline__ float4 load_row4(const f24_t* r, int i, int W) {
@@ -156,6 +159,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(XT* x, const bf16_t* __r
         o.y = v[i].y * rstd * g.y + b.y;
         o.z = v[i].z * rstd * g.z + b.z;
         o.w = v[i].w * rstd * g.w + b.w;
+        if constexpr (MODE == 3) store_row4_nt(xr, i * 64 + lane, o, W);
         store_row4(y + (size_t)row * W, i * 64 + lane, o, W);
     }
 }
@@ -238,6 +242,34 @@ int launch_layernorm_x3(const float* x, const float* gamma, const float* beta, b
         case 1280: return launch_x3_nv<5>(x, gamma, beta, y_panel, rows, stream);
     }
     KEMR_FAIL(KEMR_ERR_INVALID, "layernorm_x3: width %d not in {256,512,768,1024,1280}", width);
+}
+
+// The post-LN form (MODE 3): x = LN(x + delta) in the stream's storage type, h = its bf16 copy.  Its own dispatch: the instantiations
+// behind launch_layernorm are not touched.
+template <typename XT>
+static int launch_post_xt(XT* x, const bf16_t* d, const float* g, const float* b, bf16_t* h, int rows, int width, hipStream_t s, float eps) {
+    const int blocks = (rows + 3) / 4;
+    ProfScope prof(PROF_LAYERNORM, s);
+    switch (width) {
+        case 256:  hipLaunchKernelGGL((layernorm_kernel<1, XT, bf16_t, 3>), dim3(blocks), dim3(256), 0, s, x, d, (const bf16_t*)nullptr, g, b, h, rows, eps); break;
+        case 512:  hipLaunchKernelGGL((layernorm_kernel<2, XT, bf16_t, 3>), dim3(blocks), dim3(256), 0, s, x, d, (const bf16_t*)nullptr, g, b, h, rows, eps); break;
+        case 768:  hipLaunchKernelGGL((layernorm_kernel<3, XT, bf16_t, 3>), dim3(blocks), dim3(256), 0, s, x, d, (const bf16_t*)nullptr, g, b, h, rows, eps); break;
+        case 1024: hipLaunchKernelGGL((layernorm_kernel<4, XT, bf16_t, 3>), dim3(blocks), dim3(256), 0, s, x, d, (const bf16_t*)nullptr, g, b, h, rows, eps); break;
+        case 1280: hipLaunchKernelGGL((layernorm_kernel<5, XT, bf16_t, 3>), dim3(blocks), dim3(256), 0, s, x, d, (const bf16_t*)nullptr, g, b, h, rows, eps); break;
+        default: KEMR_FAIL(KEMR_ERR_INVALID, "layernorm_post: width %d not in {256,512,768,1024,1280}", width);
+    }
+    KEMR_CHECK_LAUNCH("layernorm_kernel (post)");
+    return KEMR_OK;
+}
+
+int launch_layernorm_post(void* x, int x_dtype, const bf16_t* delta, const float* gamma, const float* beta, bf16_t* h, int rows, int width,
+                          hipStream_t stream, float eps) {
+    if (rows <= 0) return KEMR_OK;
+    if (!delta) KEMR_FAIL(KEMR_ERR_INVALID, "layernorm_post: the post-LN form needs the update it adds");
+    if (x_dtype == KEMR_BF16) return launch_post_xt((bf16_t*)x, delta, gamma, beta, h, rows, width, stream, eps);
+    if (x_dtype == KEMR_F24) return launch_post_xt((f24_t*)x, delta, gamma, beta, h, rows, width, stream, eps);
+    if (x_dtype == KEMR_F32) return launch_post_xt((float*)x, delta, gamma, beta, h, rows, width, stream, eps);
+    KEMR_FAIL(KEMR_ERR_INVALID, "layernorm_post: bad row dtype %d", x_dtype);
 }
 
 // x_dtype: KEMR_F32 or KEMR_BF16 rows.  delta != nullptr: LN(x + delta [+ delta2]); with `writeback` the sum replaces x

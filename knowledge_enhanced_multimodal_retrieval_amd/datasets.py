@@ -222,6 +222,21 @@ class CollateAndTokenize:
         return images, self.tokenize_fn(queries), self.tokenize_fn(targets), uuids
 
 
+class TextOnlyDatasetHF(Dataset):
+    """Text-only evaluation dataset over a HuggingFace split (columns query_text / target_text), word-truncated like
+    :class:`CLIPEvalDatasetHF`: a sample is ``(query, target_text)`` (reference: src/clip/datasets/clip_dataset.py:135-167)."""
+
+    def __init__(self, hf_dataset, max_text_length: int = 150):
+        self.dataset, self.max_text_length = hf_dataset, max_text_length
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, idx):
+        sample = self.dataset[idx]
+        return truncate_words(sample["query_text"], self.max_text_length), truncate_words(sample["target_text"], self.max_text_length)
+
+
 def collate_fn_eval_texts(batch):
     queries, targets = zip(*batch)
     return list(queries), list(targets)

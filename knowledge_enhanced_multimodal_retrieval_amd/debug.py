@@ -198,3 +198,60 @@ def text_tokens(eng, ids, lens=None, rows: int = 0, fill: int = 0xff):
         _lib.check(L.kemr_debug_text_tokens(eng._h, _ptr(ids), _ptr(lens_d), rows, batch, _ptr(out), _ptr(rs), _ptr(ws), ws.numel(),
                                             _stream(eng.device)), "debug_text_tokens")
     return out, rs
+
+
+# ---- the kernels of the BERT family alone (tests/test_bert_ops_gpu.py)
+def op_attention_varlen(qkv, row_start, max_t: int, width: int, fill: float = 0.0):
+    """Non-causal attention over packed items: qkv bf16 [rows, 3 width], row_start int32 [batch + 1] (device) -> bf16 [rows, width]
+    (rows no item owns keep `fill`)."""
+    import torch
+    out = torch.full((qkv.shape[0], width), fill, dtype=torch.bfloat16, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.lib().kemr_debug_op_attention_varlen(_ptr(qkv), _ptr(out), _ptr(row_start), row_start.numel() - 1, max_t, width,
+                                                             _stream(qkv.device)), "debug_op_attention_varlen")
+    return out
+
+
+def op_layernorm_post(x, x_dtype: int, delta, gamma, beta, rows: int, width: int, eps: float):
+    """The post-LN form in place on a copy of x (fp32 / bf16 [rows, width], or uint8 [rows, 3 width] 24-bit rows): -> (x', h bf16)."""
+    import torch
+    x = x.clone()
+    h = torch.empty((rows, width), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().kemr_debug_op_layernorm_post(_ptr(x), x_dtype, _ptr(delta), _ptr(gamma), _ptr(beta), _ptr(h), rows, width,
+                                                           float(eps), _stream(x.device)), "debug_op_layernorm_post")
+    return x, h
+
+
+def op_pool_rows(x, x_dtype: int, row_start, width: int, pooling: int, normalize: bool):
+    """The sentence encoders' pooling tail: stream rows x, row_start int32 [batch + 1] -> fp32 [batch, width]."""
+    import torch
+    batch = row_start.numel() - 1
+    out = torch.empty((batch, width), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().kemr_debug_op_pool_rows(_ptr(x), x_dtype, _ptr(row_start), batch, width, pooling, 1 if normalize else 0,
+                                                      _ptr(out), _stream(x.device)), "debug_op_pool_rows")
+    return out
+
+
+def bert_front(eng, ids, lens, rows: int, fill: int = 0xff):
+    """The embedding front of a BertEngine: -> (stream rows: fp32 / bf16 [rows, width] or uint8 [rows, 3 width], h bf16 [rows, width],
+    row_start int32 [batch + 1])."""
+    import torch
+    a = eng.arch
+    batch = ids.shape[0]
+    ids = ids.to(device=eng.device, dtype=torch.int32).contiguous()
+    lens_d = torch.as_tensor(lens).to(device=eng.device, dtype=torch.int32).contiguous()
+    dt = residual_dtype(eng)
+    if dt == _lib.KEMR_F24:
+        x = torch.empty((rows, 3 * a.width), dtype=torch.uint8, device=eng.device)
+    else:
+        x = torch.empty((rows, a.width), dtype=torch.bfloat16 if dt == _lib.KEMR_BF16 else torch.float32, device=eng.device)
+    h = torch.empty((rows, a.width), dtype=torch.bfloat16, device=eng.device)
+    rs = torch.full((batch + 1,), -1, dtype=torch.int32, device=eng.device)
+    L = _lib.lib()
+    ws = _front_workspace(eng, int(L.kemr_text_packed_workspace_bytes(eng._h, rows, batch)), fill)
+    with torch.cuda.device(eng.device):
+        _lib.check(L.kemr_debug_bert_front(eng._h, _ptr(ids), _ptr(lens_d), rows, batch, _ptr(x), _ptr(h), _ptr(rs), _ptr(ws), ws.numel(),
+                                           _stream(eng.device)), "debug_bert_front")
+    return x, h, rs

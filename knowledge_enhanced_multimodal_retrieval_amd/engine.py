@@ -275,6 +275,89 @@ class ClipEngine:
         return out
 
 
+class BertEngine:
+    """One packed BERT sentence encoder (model family 2 of the library) in HBM: ``transformers.BertModel`` without its pooler, then mean
+    or CLS pooling -- E5, GTE, BGE.  ``encode_ids`` is `kemr_encode_text_packed`: the texts of a call are packed one behind the other,
+    each on its own ``lens[i]`` positions (a padding mask is a length), so a call costs sum(lens) token rows, not B x the longest."""
+
+    ROW_BUDGET = 65536           # token rows per packed call: 256 row tiles of the persistent GEMM (TEXT_ROW_BUDGET's reasoning)
+
+    def __init__(self, arch, device: torch.device | str = "cuda:0", precision: str = _lib.DEFAULT_PRECISION):
+        if precision not in ("bf16-x24", "bf16", "bf16-res16"):
+            raise ValueError(f"BertEngine: precision {precision!r}; served: 'bf16-x24' (default), 'bf16', 'bf16-res16' (the fp8 precisions and "
+                             "fp32x3 are not served for this family)")
+        self.precision, self.arch = precision, arch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("BertEngine needs a GPU device; the HIP path has no CPU fallback")
+        self._L = _lib.lib()
+        cfg = _lib.KemrCfg(**arch.cfg_dict())
+        h = C.c_void_p()
+        _lib.check(self._L.kemr_model_create_family(C.byref(cfg), _lib.FAMILY_BERT, C.byref(h)), "model_create_family")
+        self._h = h
+        from .config import BERT_POOLING
+        _lib.check(self._L.kemr_model_set_option(self._h, b"pooling", BERT_POOLING[arch.pooling]), "model_set_option")
+        self._ws: Optional[torch.Tensor] = None
+        self.ready = False
+
+    __del__ = ClipEngine.__del__
+    tensor_names = ClipEngine.tensor_names
+
+    def set_pooling(self, pooling: str) -> None:
+        from .config import BERT_POOLING
+        if pooling not in BERT_POOLING:
+            raise ValueError(f"pooling {pooling!r}; served: {list(BERT_POOLING)}")
+        _lib.check(self._L.kemr_model_set_option(self._h, b"pooling", BERT_POOLING[pooling]), "model_set_option")
+
+    def load_state_dict(self, sd: Mapping[str, torch.Tensor]) -> None:
+        """Strict load of a state dict under the engine's names (hf_checkpoint.from_bert_state_dict) + pack to HBM."""
+        for name, t in sd.items():
+            host = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+            shape = (C.c_int64 * max(host.dim(), 1))(*host.shape)
+            _lib.check(self._L.kemr_model_load_tensor(self._h, name.encode(), C.c_void_p(host.data_ptr()), _lib.KEMR_F32, shape, host.dim()),
+                       f"load_tensor({name})")
+        _lib.check(self._L.kemr_model_set_option(self._h, b"residual_stream_24bit", 1 if self.precision.endswith("-x24") else 0), "model_set_option")
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.kemr_model_finalize(self._h, _lib.PRECISIONS[self.precision]), "model_finalize")
+        self.ready = True
+
+    def encode_ids(self, ids: torch.Tensor, lens, normalize: bool = False) -> torch.Tensor:
+        """ids int [B, ctx] (host or device; positions behind a text's length are never read), lens int [B] on the HOST (what the
+        tokenizer returned) -> fp32 [B, width] on the device, in input order."""
+        a = self.arch
+        if not self.ready:
+            raise RuntimeError("BertEngine: load_state_dict() must be called before encoding")
+        if ids.dim() != 2 or ids.shape[1] != a.ctx:
+            raise RuntimeError(f"encode_ids expects [B,{a.ctx}] token ids, got {tuple(ids.shape)}")
+        n = ids.shape[0]
+        lens = torch.as_tensor(lens, device="cpu").reshape(-1).to(torch.int32).clamp(1, a.ctx).contiguous()
+        if lens.numel() != n:
+            raise RuntimeError(f"encode_ids: {lens.numel()} lengths for {n} texts")
+        ids = ids.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous()
+        out = torch.empty((n, a.width), dtype=torch.float32, device=self.device)
+        if n == 0:
+            return out
+        lens_dev = lens.to(self.device, non_blocking=True)
+        csum = torch.cumsum(lens.to(torch.int64), 0).tolist()
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr(self.device)
+            s0, base = 0, 0
+            while s0 < n:
+                s1 = s0 + 1
+                while s1 < n and csum[s1] - base <= self.ROW_BUDGET and s1 - s0 < 65528:
+                    s1 += 1
+                rows = csum[s1 - 1] - base
+                need = int(self._L.kemr_text_packed_workspace_bytes(self._h, rows, s1 - s0))
+                if self._ws is None or self._ws.numel() < need:
+                    self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                _lib.check(self._L.kemr_encode_text_packed(self._h, C.c_void_p(ids[s0:].data_ptr()), C.c_void_p(lens_dev[s0:].data_ptr()),
+                                                           rows, s1 - s0, C.c_void_p(out[s0:].data_ptr()), 1 if normalize else 0,
+                                                           C.c_void_p(self._ws.data_ptr()), self._ws.numel(), C.c_void_p(stream)),
+                           "encode_text_packed")
+                s0, base = s1, csum[s1 - 1]
+        return out
+
+
 def precision_gap(model_or_engine, pixels: Optional[torch.Tensor], ids: Optional[torch.Tensor], fast: str = _lib.DEFAULT_PRECISION,
                   exact: str = "fp32x3") -> Dict[str, Dict[str, object]]:
     """Is `fast` safe for THIS checkpoint on THIS data?  Packs the same weights twice, at precision `fast` and at `exact` (the

@@ -26,6 +26,7 @@ from . import _lib
 from . import engine
 from . import metrics as M
 from . import sparql_fusion as SF
+from .datasets import TextOnlyDatasetHF, collate_fn_eval_texts
 from .datasets import CLIPEvalDatasetHF, CollateAndTokenize, SyntheticHFSplit, SyntheticRawImageDataset, SyntheticRetrievalDataset, collate_fn_eval
 from .preprocess import ClipPreprocessGPU, PackedRaw, gpu_preprocess_for
 from .logging_utils import save_metrics_to_json, setup_logger
@@ -609,3 +610,219 @@ def main_fusion(argv=None):
     else:
         print(json.dumps(results, indent=2))
     return results
+
+
+# ------------------------------------------------------------------------------------------------ sentence encoders (text-to-text baselines)
+def _text_loader(dataset, batch_size: int, seed: int, collate, shuffle: bool = False, num_workers: int = 0) -> DataLoader:
+    g = torch.Generator()
+    g.manual_seed(seed)
+    return DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers, collate_fn=collate,
+                      worker_init_fn=seed_worker if num_workers else None, generator=g)
+
+
+@torch.no_grad()
+def evaluate_text_model(model, dataset, batch_size: int = 32, device: str = "cuda", seed: int = 42, compute_recall: bool = True,
+                        compute_mrr: bool = True, num_workers: int = 0) -> Dict[str, float]:
+    """Text-to-text retrieval of a sentence encoder, query -> target (reference: src/clip/eval/evaluator_lm.py:40-135; same signature,
+    same ``T2T_*`` keys).  `model`: a ``sentence_model.SentenceEncoder`` (or anything with ``SentenceTransformer.encode``'s contract);
+    `dataset`: samples ``(query, target_text)``.  The embeddings stay on the GPU and go into the fused rank kernel
+    (``metrics.compute_retrieval_metrics``) instead of back to the host and through two ``np.argsort`` passes; `device` is accepted and
+    must be the model's.  `num_workers`: the texts are strings in memory, 0 (the default here; the reference forks 4) loses nothing."""
+    model = model.to(device)
+    model.eval()
+    queries, targets = [], []
+    logger.info(f"Encoding texts for {len(dataset)} samples...")
+    for q, t in _text_loader(dataset, batch_size, seed, collate_fn_eval_texts, num_workers=num_workers):
+        queries.append(model.encode(q, convert_to_tensor=True, device=device, show_progress_bar=False, normalize_embeddings=True))
+        targets.append(model.encode(t, convert_to_tensor=True, device=device, show_progress_bar=False, normalize_embeddings=True))
+    query, target = torch.cat(queries), torch.cat(targets)
+    logger.info(f"Query embeddings: {tuple(query.shape)}")
+    logger.info(f"Target embeddings: {tuple(target.shape)}")
+    return M.compute_retrieval_metrics(query, target, prefix="T2T", compute_recall=compute_recall, compute_mrr=compute_mrr)
+
+
+@torch.no_grad()
+def evaluate_text_model_for_training(model, dataset, batch_size: int = 32, device: str = "cuda", seed: int = 42) -> Dict[str, float]:
+    """MRR / Mean_Rank only (reference: evaluator_lm.py:138-170)."""
+    return evaluate_text_model(model, dataset, batch_size, device, seed, compute_recall=False, compute_mrr=True)
+
+
+def _load_sentence_encoder(model_name: str, device: str):
+    from .sentence_model import SentenceEncoder
+    if not os.path.isdir(model_name):
+        raise RuntimeError(f"--model_name {model_name!r} is not a directory: the sentence encoders are loaded from a local checkpoint "
+                           "directory (config.json, weights, tokenizer.json), e.g. a download of intfloat/e5-base-v2 or thenlper/gte-large; "
+                           "nothing here contacts a model hub")
+    return SentenceEncoder.from_pretrained(model_name, device=device, precision=_lib.env_precision())
+
+
+def text_lm_parser() -> argparse.ArgumentParser:
+    """The arguments of the reference's src/clip/eval/evaluator_lm.py:173-201 (+ --dataset / --synthetic, as the other CLIs have)."""
+    p = argparse.ArgumentParser(description="Evaluate text-only models")
+    p.add_argument("--model_name", type=str, required=True, help="local directory of a BERT sentence encoder (E5, GTE)")
+    p.add_argument("--texts_dir", type=str, required=True, help="accepted for the reference's command lines; not read")
+    p.add_argument("--images_dir", type=str, required=True, help="accepted for the reference's command lines; not read")
+    p.add_argument("--split", type=str, default="test", choices=["train", "val", "test"])
+    p.add_argument("--mrr_only", action="store_true")
+    p.add_argument("--batch_size", type=int, default=32)
+    p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--output_file", type=str, required=True)
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--dataset", type=str, default="xuemduan/reevaluate-image-text-pairs")
+    p.add_argument("--synthetic", type=int, default=0, help="N > 0: N synthetic (query, target) pairs instead of the dataset")
+    return p
+
+
+class _SyntheticTextSplit:
+    def __init__(self, n: int, seed: int):
+        self._raw = SyntheticRawImageDataset(n, seed)
+
+    def __len__(self):
+        return len(self._raw)
+
+    def __getitem__(self, idx):
+        _, query, target, _ = self._raw[idx]
+        return {"query_text": query, "target_text": target}
+
+
+def _seed_all(seed: int) -> None:
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    random.seed(seed)
+
+
+def _save_text_results(log, args, dataset, metrics, extra) -> dict:
+    log.info("EVALUATION RESULTS (T2T Only)")
+    for name, value in sorted(metrics.items()):
+        log.info(f"{name}: {value:.2f}" + ("" if "Mean_Rank" in name else "%"))
+    results = {"model_name": args.model_name, "split": args.split, "num_samples": len(dataset), "seed": args.seed, "metrics": metrics,
+               "precision": _lib.env_precision(), **extra}
+    save_metrics_to_json(results, args.output_file)
+    log.info(f"Results saved to {args.output_file}")
+    return results
+
+
+def main_text_lm(argv=None):
+    args = text_lm_parser().parse_args(argv)
+    _seed_all(args.seed)
+    out_dir = Path(args.output_file).parent
+    out_dir.mkdir(parents=True, exist_ok=True)
+    name = "src.clip.eval.evaluator_lm"
+    setup_logger(name, str(out_dir / "evaluation.log"))
+    log = logging.getLogger(name)
+    log.info(f"Text-Only Model Evaluation (T2T only, MI355X HIP engine)  Model: {args.model_name}  Split: {args.split}  MRR only: {args.mrr_only}  Seed: {args.seed}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("no GPU visible: the encoder and the ranking run only in the HIP kernels (no CPU fallback)")
+    device = args.device if args.device.startswith("cuda") else "cuda"
+    model = _load_sentence_encoder(args.model_name, device)
+    if args.synthetic > 0:
+        dataset = TextOnlyDatasetHF(_SyntheticTextSplit(args.synthetic, args.seed))
+    else:
+        from datasets import load_dataset
+        dataset = TextOnlyDatasetHF(load_dataset(args.dataset)[{"val": "validation"}.get(args.split, args.split)])
+    fn = evaluate_text_model_for_training if args.mrr_only else evaluate_text_model
+    metrics = fn(model, dataset, batch_size=args.batch_size, device=device, seed=args.seed)
+    return _save_text_results(log, args, dataset, metrics, {"data": "synthetic" if args.synthetic > 0 else args.dataset})
+
+
+# ---- the legacy five-variant script (reference: baselines/evaluate_text_models.py)
+class TextVariantsDataset(torch.utils.data.Dataset):
+    """One artifact per sample: the five description variants of ``<text_folder>/<uuid>.json`` (missing ones are "")."""
+    KEYS = {"content": "content_descriptions", "metadata": "metadata_descriptions", "hybrid_o1": "hybrid_descriptions",
+            "hybrid_o2": "hybrid_descriptions"}
+
+    def __init__(self, uuids: Sequence[str], text_folder: str, description_type: str, random_seed: int = 42, num_variants: int = 5):
+        self.uuids, self.text_folder, self.num_variants = list(uuids), Path(text_folder), num_variants
+        self.key = self.KEYS[description_type]
+
+    def __len__(self):
+        return len(self.uuids)
+
+    def __getitem__(self, idx):
+        import json
+        try:
+            with open(self.text_folder / f"{self.uuids[idx]}.json", "r", encoding="utf-8") as f:
+                found = json.load(f).get(self.key, [])
+        except Exception as e:          # noqa: BLE001 - the reference substitutes empty texts as well
+            logger.error(f"Error loading text for {self.uuids[idx]}: {e}")
+            found = []
+        texts = [d if isinstance(d, str) and d.strip() else "" for d in found[: self.num_variants]]
+        return texts + [""] * (self.num_variants - len(texts))
+
+
+def variant_metrics(embeddings_by_variant: Sequence[torch.Tensor], mode: str = "multi", k_values: Sequence[int] = (1, 5, 10, 20)) -> Dict[str, float]:
+    """The single / multi metrics of the legacy script from the per-variant embeddings ([N, D] each, L2-normalised): for a query
+    variant v the candidates are the other variants of every artifact, artifact-major (candidate id = artifact * 4 + slot), and a
+    query's rank is that of the FIRST candidate of its own artifact (``ranking.ranks_of_groups``).  single: variant 0 queries;
+    multi: every variant queries, all 5 N ranks averaged."""
+    if mode not in ("single", "multi"):
+        raise ValueError(f"mode {mode!r}: 'single' or 'multi'")
+    from . import ranking
+    nv = len(embeddings_by_variant)
+    n = embeddings_by_variant[0].shape[0]
+    ranks = []
+    for qv in ([0] if mode == "single" else range(nv)):
+        others = [v for v in range(nv) if v != qv]
+        cand = torch.stack([embeddings_by_variant[v] for v in others], dim=1).reshape(n * len(others), -1)
+        own = torch.arange(n).unsqueeze(1) * len(others) + torch.arange(len(others)).unsqueeze(0)
+        ranks.append(ranking.ranks_of_groups(embeddings_by_variant[qv], cand, own))
+    return {f"T2T_{k}": v for k, v in ranking.metrics_from_ranks(torch.cat(ranks), list(k_values)).items()}
+
+
+@torch.no_grad()
+def evaluate_text_model_variants(model, dataset, batch_size: int = 32, device: str = "cuda", mode: str = "multi", seed: int = 42,
+                                 num_workers: int = 0) -> Dict[str, float]:
+    """``evaluate_text_model`` of the legacy script (reference: baselines/evaluate_text_models.py:96-263; same signature).  The loader
+    shuffles with the seeded generator as there; the metrics do not depend on the order of the artifacts."""
+    model = model.to(device)
+    model.eval()
+    per = [[] for _ in range(5)]
+    for batch in _text_loader(dataset, batch_size, seed, list, shuffle=True, num_workers=num_workers):
+        for v in range(5):
+            per[v].append(model.encode([b[v] for b in batch], convert_to_tensor=True, device=device, show_progress_bar=False,
+                                       normalize_embeddings=True))
+    return variant_metrics([torch.cat(p) for p in per], mode)
+
+
+def text_variants_parser() -> argparse.ArgumentParser:
+    """The arguments of the reference's baselines/evaluate_text_models.py:268-299."""
+    p = argparse.ArgumentParser(description="Evaluate text-only models")
+    p.add_argument("--model_name", type=str, required=True, help="local directory of a BERT sentence encoder (E5, GTE)")
+    p.add_argument("--texts_dir", type=str, required=True)
+    p.add_argument("--description_type", type=str, required=True, choices=["content", "metadata", "hybrid_o1", "hybrid_o2"])
+    p.add_argument("--images_dir", type=str, required=True, help="accepted for the reference's command lines; not read")
+    p.add_argument("--splits_file", type=str, default=None)
+    p.add_argument("--split", type=str, default="test", choices=["train", "val", "test"])
+    p.add_argument("--eval_mode", type=str, default="multi", choices=["single", "multi"])
+    p.add_argument("--batch_size", type=int, default=32)
+    p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--output_file", type=str, required=True)
+    p.add_argument("--seed", type=int, default=42)
+    return p
+
+
+def main_text_variants(argv=None):
+    import json
+    args = text_variants_parser().parse_args(argv)
+    _seed_all(args.seed)
+    out_dir = Path(args.output_file).parent
+    out_dir.mkdir(parents=True, exist_ok=True)
+    name = "baselines.evaluate_text_models"
+    setup_logger(name, str(out_dir / "evaluation.log"))
+    log = logging.getLogger(name)
+    if not args.splits_file or not Path(args.splits_file).exists():
+        # the reference generates splits from `list(set(uuids))`, whose order follows Python's per-process string hashing: its own
+        # runs do not reproduce them.  The file its save_splits_to_json writes is the one stable statement of a split.
+        raise RuntimeError("--splits_file is required here: a JSON with the lists 'train', 'val' and 'test' (what the reference's "
+                           "save_splits_to_json writes); the reference's on-the-fly splits depend on set iteration order")
+    with open(args.splits_file, "r", encoding="utf-8") as f:
+        uuids = json.load(f)[args.split]
+    log.info(f"Text-Only Model Evaluation (T2T only, MI355X HIP engine)  Model: {args.model_name}  Description type: {args.description_type}  "
+             f"Split: {args.split} ({len(uuids)} samples)  Mode: {args.eval_mode}  Seed: {args.seed}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("no GPU visible: the encoder and the ranking run only in the HIP kernels (no CPU fallback)")
+    device = args.device if args.device.startswith("cuda") else "cuda"
+    model = _load_sentence_encoder(args.model_name, device)
+    dataset = TextVariantsDataset(uuids, args.texts_dir, args.description_type, args.seed)
+    metrics = evaluate_text_model_variants(model, dataset, args.batch_size, device, args.eval_mode, args.seed)
+    return _save_text_results(log, args, dataset, metrics, {"description_type": args.description_type, "eval_mode": args.eval_mode})

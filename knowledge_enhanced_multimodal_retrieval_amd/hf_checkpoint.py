@@ -9,6 +9,10 @@ dict onto the OpenAI names the engine loads, and reads ``config.json`` into a :c
 ``transformers.SiglipModel`` directories (``config.json`` with ``model_type: "siglip"``) take the second route of this module:
 :func:`arch_from_siglip_config` and :func:`from_siglip_state_dict` map them onto the names the engine's SigLIP family loads.
 
+``transformers.BertModel`` directories (``model_type: "bert"``: the sentence encoders E5 and GTE of the reference's text-to-text
+baselines) take the third: :func:`arch_from_bert_config` (with the sentence-transformers files ``1_Pooling/config.json`` and
+``sentence_bert_config.json`` where present) and :func:`from_bert_state_dict`.
+
 Local files only: nothing here (or anywhere in the package) contacts a model hub.
 """
 from __future__ import annotations
@@ -19,7 +23,7 @@ from typing import Dict, Mapping, Tuple
 
 import torch
 
-from .config import ARCHS, ClipArch
+from .config import ARCHS, BertArch, ClipArch
 
 # what transformers.CLIPTextConfig / CLIPVisionConfig / CLIPConfig assume for a field that config.json leaves out
 _TEXT_DEFAULTS = dict(hidden_size=512, intermediate_size=2048, num_attention_heads=8, num_hidden_layers=12, vocab_size=49408,
@@ -234,8 +238,142 @@ def to_siglip_state_dict(sd: Mapping[str, torch.Tensor], arch: ClipArch) -> Dict
     return out
 
 
+# ---- BERT sentence encoders (E5, GTE): transformers.BertModel, optionally inside a sentence-transformers directory ---------------------
+_BERT_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_attention_heads=12, num_hidden_layers=12, vocab_size=30522,
+                      max_position_embeddings=512, hidden_act="gelu", layer_norm_eps=1e-12, position_embedding_type="absolute",
+                      type_vocab_size=2)
+
+
+def _read_json(path: str):
+    with open(path) as f:
+        return json.load(f)
+
+
+def sentence_transformers_settings(directory) -> Tuple[str, int]:
+    """(pooling, max_seq_length) a sentence-transformers directory asks for: ``1_Pooling/config.json`` (mean or CLS; anything else is
+    refused) and ``sentence_bert_config.json``; ("mean", 0) where the files are absent (0 = the model's own limit)."""
+    pooling, max_len = "mean", 0
+    if directory:
+        p = os.path.join(directory, "1_Pooling", "config.json")
+        if os.path.isfile(p):
+            pc = _read_json(p)
+            modes = [k for k in ("pooling_mode_cls_token", "pooling_mode_mean_tokens", "pooling_mode_max_tokens", "pooling_mode_mean_sqrt_len_tokens",
+                                 "pooling_mode_weightedmean_tokens", "pooling_mode_lasttoken") if pc.get(k)]
+            if modes == ["pooling_mode_cls_token"]:
+                pooling = "cls"
+            elif modes != ["pooling_mode_mean_tokens"]:
+                raise ValueError(f"1_Pooling/config.json: pooling modes {modes} are not served (mean or CLS, one of them)")
+        p = os.path.join(directory, "sentence_bert_config.json")
+        if os.path.isfile(p):
+            max_len = int(_read_json(p).get("max_seq_length") or 0)
+    return pooling, max_len
+
+
+def arch_from_bert_config(cfg: Mapping, directory: str = "") -> BertArch:
+    """``config.json`` of a ``BertModel`` (as a dict) -> BertArch; `directory` (optional) is searched for the sentence-transformers
+    files.  Everything the kernels do not serve is refused with the reason: MPNet (its attention adds a learned relative position
+    bias), relative position embeddings, widths that are no multiple of 256, heads of another size than 64, an MLP that is not 4 x the
+    width, another activation than the exact GELU."""
+    mt = cfg.get("model_type")
+    if mt == "mpnet":
+        raise ValueError("HF config: model_type 'mpnet' (all-mpnet-base-v2) is not served: its attention adds a learned relative "
+                         "position bias to every score, which the attention kernels do not take")
+    if mt != "bert":
+        raise ValueError(f"HF config: model_type {mt!r} is not a BertModel")
+    c = {**_BERT_DEFAULTS, **{k: v for k, v in cfg.items() if v is not None}}
+    if c["position_embedding_type"] != "absolute":
+        raise ValueError(f"HF config: position_embedding_type = {c['position_embedding_type']!r}; served: 'absolute' (relative positions "
+                         "change every attention score)")
+    w, heads = int(c["hidden_size"]), int(c["num_attention_heads"])
+    if w <= 0 or w % 256:
+        raise ValueError(f"HF config: hidden_size = {w} is not a multiple of 256 (the kernels' tile; e.g. MiniLM's 384 is not served)")
+    if w > 1280:
+        raise ValueError(f"HF config: hidden_size = {w} is beyond the widest served tower (1280)")
+    if heads <= 0 or w != 64 * heads:
+        raise ValueError(f"HF config: num_attention_heads = {heads} at hidden_size {w} is a head dim of {w / max(heads, 1):g}; BERT "
+                         "encoders are served at head dim 64 only")
+    if int(c["intermediate_size"]) != 4 * w:
+        raise ValueError(f"HF config: intermediate_size = {c['intermediate_size']} is not 4 x hidden_size ({4 * w})")
+    if c["hidden_act"] != "gelu":
+        raise ValueError(f"HF config: hidden_act = {c['hidden_act']!r}; BERT encoders are served with the exact 'gelu' only")
+    if float(c["layer_norm_eps"]) != 1e-12:
+        raise ValueError(f"HF config: layer_norm_eps = {c['layer_norm_eps']!r}; BERT encoders are served with 1e-12 only")
+    if int(c["type_vocab_size"]) != 2:
+        raise ValueError(f"HF config: type_vocab_size = {c['type_vocab_size']}; served: 2 (every token is of type 0)")
+    pooling, max_len = sentence_transformers_settings(directory)
+    positions = int(c["max_position_embeddings"])
+    ctx = min(max_len or positions, positions)
+    if ctx > 512:
+        raise ValueError(f"HF config: {ctx} positions; BERT encoders are served up to 512 (set max_seq_length in sentence_bert_config.json)")
+    return BertArch(w, int(c["num_hidden_layers"]), vocab=int(c["vocab_size"]), ctx=ctx, pooling=pooling,
+                    positions=positions if positions != ctx else 0)
+
+
+_BERT_TOP = [("embeddings.word_embeddings.weight", "token_embedding.weight"), ("embeddings.position_embeddings.weight", "positional_embedding"),
+             ("embeddings.token_type_embeddings.weight", "token_type_embedding"),
+             ("embeddings.LayerNorm.weight", "ln_embed.weight"), ("embeddings.LayerNorm.bias", "ln_embed.bias")]
+_BERT_BLOCK = [("attention.output.dense.weight", "attn.out_proj.weight"), ("attention.output.dense.bias", "attn.out_proj.bias"),
+               ("attention.output.LayerNorm.weight", "ln_1.weight"), ("attention.output.LayerNorm.bias", "ln_1.bias"),
+               ("intermediate.dense.weight", "mlp.c_fc.weight"), ("intermediate.dense.bias", "mlp.c_fc.bias"),
+               ("output.dense.weight", "mlp.c_proj.weight"), ("output.dense.bias", "mlp.c_proj.bias"),
+               ("output.LayerNorm.weight", "ln_2.weight"), ("output.LayerNorm.bias", "ln_2.bias")]
+
+
+def from_bert_state_dict(sd: Mapping[str, torch.Tensor], arch: BertArch) -> Dict[str, torch.Tensor]:
+    """``BertModel.state_dict()`` (bare keys, or ``bert.``-prefixed as a task model saves them) -> the engine's names: query | key |
+    value concatenated into ``in_proj_*``, ``ln_1`` = attention.output.LayerNorm, ``ln_2`` = output.LayerNorm, the positional table cut
+    to the ``arch.ctx`` positions served.  ``pooler.*``, ``position_ids`` / ``token_type_ids`` buffers and the heads of a task model
+    (``cls.*``) are ignored; a missing key and any other key left over are errors that name it."""
+    left = {}
+    for k, v in sd.items():
+        k = k[5:] if k.startswith("bert.") else k
+        if k.startswith("pooler.") or k.startswith("cls.") or k.endswith("position_ids") or k.endswith("token_type_ids"):
+            continue
+        left[k] = v
+    out: Dict[str, torch.Tensor] = {}
+
+    def take(key: str) -> torch.Tensor:
+        if key not in left:
+            raise KeyError(f"HF state dict: missing key '{key}'")
+        return left.pop(key)
+
+    for src, dst in _BERT_TOP:
+        out[dst] = take(src)
+    out["positional_embedding"] = out["positional_embedding"][: arch.ctx].contiguous()
+    for i in range(arch.layers):
+        s, d = f"encoder.layer.{i}", f"transformer.resblocks.{i}"
+        out[f"{d}.attn.in_proj_weight"] = torch.cat([take(f"{s}.attention.self.{p}.weight") for p in ("query", "key", "value")], dim=0)
+        out[f"{d}.attn.in_proj_bias"] = torch.cat([take(f"{s}.attention.self.{p}.bias") for p in ("query", "key", "value")], dim=0)
+        for a, b in _BERT_BLOCK:
+            out[f"{d}.{b}"] = take(f"{s}.{a}")
+    if left:
+        raise KeyError(f"HF state dict: unexpected key '{sorted(left)[0]}' ({len(left)} left over; not a BertModel of this architecture)")
+    return out
+
+
+def to_bert_state_dict(sd: Mapping[str, torch.Tensor], arch: BertArch) -> Dict[str, torch.Tensor]:
+    """The way back: the engine's names -> ``BertModel(add_pooling_layer=False).state_dict()`` keys."""
+    out: Dict[str, torch.Tensor] = {src: sd[dst] for src, dst in _BERT_TOP}
+    w = arch.width
+    for i in range(arch.layers):
+        s, d = f"encoder.layer.{i}", f"transformer.resblocks.{i}"
+        for j, p in enumerate(("query", "key", "value")):
+            out[f"{s}.attention.self.{p}.weight"] = sd[f"{d}.attn.in_proj_weight"][j * w:(j + 1) * w].contiguous()
+            out[f"{s}.attention.self.{p}.bias"] = sd[f"{d}.attn.in_proj_bias"][j * w:(j + 1) * w].contiguous()
+        for a, b in _BERT_BLOCK:
+            out[f"{s}.{a}"] = sd[f"{d}.{b}"]
+    return out
+
+
 def is_hf_directory(path: str) -> bool:
     return os.path.isdir(path) and os.path.isfile(os.path.join(path, "config.json"))
+
+
+def _load_weights(weights: str) -> Dict[str, torch.Tensor]:
+    if weights.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        return load_file(weights)
+    return torch.load(weights, map_location="cpu", weights_only=True)
 
 
 def read_hf_directory(directory: str) -> Tuple[ClipArch, str, Dict[str, torch.Tensor]]:
@@ -248,6 +386,9 @@ def read_hf_directory(directory: str) -> Tuple[ClipArch, str, Dict[str, torch.Te
         raise FileNotFoundError(f"{directory!r} holds neither of {WEIGHT_FILES} (sharded checkpoints are not read)")
     with open(cfg_path) as f:
         cfg = json.load(f)
+    if cfg.get("model_type") in ("bert", "mpnet"):      # a sentence encoder: (BertArch, "gelu", state dict under the engine's names)
+        barch = arch_from_bert_config(cfg, directory)
+        return barch, "gelu", from_bert_state_dict(_load_weights(weights), barch)
     siglip = cfg.get("model_type") == "siglip"          # every other model_type (and none) takes the CLIPModel route, refusals included
     if siglip:
         arch, activation = arch_from_siglip_config(cfg), SIGLIP_ACT

@@ -73,6 +73,30 @@ def ranks_and_topk_deep(query_parts: Sequence[ArrayLike], gallery_parts: Sequenc
     return ranks, top_s, top_i
 
 
+def ranks_of_groups(query: ArrayLike, candidates: ArrayLike, own: ArrayLike, precision: str = "fp32x3") -> torch.Tensor:
+    """Rank (1-based) of the FIRST of a query's own candidates: ``own`` int [nq, g] lists the g candidate ids that count as correct for
+    query i (the reference's ``text_to_artifact == i``, baselines/evaluate_text_models.py:183-227: four variants per artifact).  The
+    first own candidate in the ranking is the best-scoring one (lowest id on a tie), so its rank is an ordinary ground-truth rank: g
+    ``pair_scores`` calls pick it, one rank-only ``sim_topk`` pass counts what is ahead of it.  No N x 4N matrix, no argsort."""
+    q = to_device_f32(query)
+    c = to_device_f32(candidates, q.device)
+    own = torch.as_tensor(own).to(device=q.device, dtype=torch.int32)
+    if own.dim() != 2 or own.shape[0] != q.shape[0] or own.shape[1] < 1:
+        raise ValueError(f"ranks_of_groups: own must be [nq, g], got {tuple(own.shape)} for {q.shape[0]} queries")
+    if int(own.min()) < 0 or int(own.max()) >= c.shape[0]:
+        raise ValueError("ranks_of_groups: own candidate ids must lie inside the gallery")
+    terms = PRECISION_TERMS[precision]
+    qp = engine.build_panel([q], _lib.SIDE_QUERY, terms)
+    gp = engine.build_panel([c], _lib.SIDE_GALLERY, terms)
+    rows = torch.arange(q.shape[0], device=q.device, dtype=torch.int32)
+    scores = torch.stack([engine.pair_scores(qp, gp, rows, own[:, j].contiguous()) for j in range(own.shape[1])], dim=1)
+    _require_finite(scores, "own-candidate scores")
+    best = scores.max(dim=1, keepdim=True).values
+    ids = torch.where(scores == best, own, torch.full_like(own, 2 ** 31 - 1)).min(dim=1).values      # best score, then lowest id
+    ranks, _, _ = ranks_and_topk([q], [c], k=0, precision=precision, gt_idx=ids)
+    return ranks
+
+
 def _panels_and_ground_truth(query_parts, gallery_parts, weights, row_gate, precision, gt_idx, bonus, gallery_offset):
     """The operands both routes share: (query panel, gallery panel, gt ids, the ground-truth pairs' fused scores, zeroed ahead)."""
     terms = PRECISION_TERMS[precision]

@@ -250,3 +250,58 @@ class SiglipTokenize:
 
 def siglip_tokenizer(directory: str, context_length: int = SIGLIP_CONTEXT) -> SiglipTokenize:
     return SiglipTokenize(directory, context_length)
+
+
+# ---- BERT sentence encoders (E5, GTE): WordPiece from the directory's tokenizer.json ------------------------------------------------
+class BertTokenize:
+    """Tokenizer of a BERT checkpoint directory: the ``tokenizers`` package on the directory's ``tokenizer.json`` (its normaliser,
+    WordPiece model and ``[CLS] ... [SEP]`` post-processor as saved), truncated to ``max_length`` keeping ``[SEP]`` -> (ids int32
+    ``[B, max_length]`` zero-padded, lengths int32 ``[B]``).  The lengths ARE the padding mask: the engine computes a text on its first
+    ``lens[i]`` positions only.  Picklable: the ``tokenizers`` object is rebuilt from the path on first use."""
+
+    def __init__(self, directory: str, max_length: int = 512):
+        path = os.path.join(directory, "tokenizer.json") if os.path.isdir(directory) else directory
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{path!r} does not exist (a BERT directory's tokenizer.json; vocab.txt alone is not read)")
+        if not 2 <= int(max_length) <= 512:
+            raise ValueError(f"bert_tokenizer: max_length {max_length} not in 2..512")
+        self.path, self.max_length = path, int(max_length)
+        self._tok = None
+
+    def __getstate__(self):
+        return {"path": self.path, "max_length": self.max_length, "_tok": None}
+
+    def _tokenizer(self):
+        if self._tok is None:
+            from tokenizers import Tokenizer
+            tok = Tokenizer.from_file(self.path)
+            tok.no_padding()
+            tok.enable_truncation(max_length=self.max_length)
+            self._tok = tok
+        return self._tok
+
+    def encode_lists(self, texts: Sequence[str]):
+        """The id lists themselves (ragged), for callers that sort by length before they pad."""
+        return [e.ids for e in self._tokenizer().encode_batch([str(t) for t in texts], add_special_tokens=True)]
+
+    def __call__(self, texts: Union[str, Sequence[str]]):
+        if isinstance(texts, str):
+            texts = [texts]
+        return pad_id_lists(self.encode_lists(texts), self.max_length)
+
+
+def pad_id_lists(id_lists, max_length: int):
+    """Ragged id lists -> (int32 [B, max_length] zero-padded, int32 [B] lengths); an empty list counts as one pad token."""
+    out = torch.zeros(len(id_lists), max_length, dtype=torch.int32)
+    lens = torch.ones(len(id_lists), dtype=torch.int32)
+    for i, ids in enumerate(id_lists):
+        if len(ids) > max_length:
+            raise RuntimeError(f"{len(ids)} ids for {max_length} positions")
+        if ids:
+            out[i, : len(ids)] = torch.tensor(ids, dtype=torch.int32)
+            lens[i] = len(ids)
+    return out, lens
+
+
+def bert_tokenizer(directory: str, max_length: int = 512) -> BertTokenize:
+    return BertTokenize(directory, max_length)

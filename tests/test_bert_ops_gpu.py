@@ -1,0 +1,258 @@
+"""GPU: the kernels of the BERT sentence encoders (model family 2) alone, each against its fp64 statement and rounding budget
+(oracle/rounding.py check_budget): the non-causal attention over packed items of different lengths (csrc/attention_varlen.hip), the
+post-LN LayerNorm mode, the embedding front and the pooling tail.
+
+The attention kernel is csrc/attention_long.hip's tile code with the length read per item: per item its arithmetic and order are
+attention_long's at T = the item's length, so ``rounding.attention_long_emulation`` called per item states it, with the bars of
+tests/test_attention_long_gpu.py (budget ratio <= 1, |signed bias| <= 0.02 ulp)."""
+import pytest
+import torch
+
+import bert_ref as B
+from knowledge_enhanced_multimodal_retrieval_amd import _lib, debug, engine
+from oracle import rounding as R
+
+pytestmark = pytest.mark.gpu
+
+MAX_BIAS = 0.02
+LN_F32_FACTOR = 2.0 ** -21  # fp32 LayerNorm outputs within 2^-21 max|y| (tests/test_numerics_gpu.py, tests/test_numerics_paths_gpu.py)
+MAX_T = 512
+
+
+def _note(name, value):
+    print(f"NUMERICS {name} {value}")
+
+
+def _qkv(rows, width, seed, qscale=0.25):
+    g = torch.Generator().manual_seed(seed)
+    qkv = torch.randn(rows, 3 * width, generator=g)
+    qkv[:, :width] *= qscale                    # pre-scaled queries: logits of a few units
+    return qkv.to(torch.bfloat16)
+
+
+def _row_start(lens):
+    return torch.tensor([0] + list(lens)).cumsum(0).int()
+
+
+def _emulation(qkv, row_start, width):
+    """attention_long_emulation per item, on the item's own rows."""
+    ref = torch.zeros(qkv.shape[0], width, dtype=torch.float64)
+    extra = torch.zeros_like(ref)
+    for a, e in zip(row_start[:-1].tolist(), row_start[1:].tolist()):
+        ref[a:e], extra[a:e] = R.attention_long_emulation(qkv[a:e], 1, e - a, width)
+    return ref, extra
+
+
+def _check(got, ref, extra, what, max_bias=MAX_BIAS):
+    top, bias = R.check_budget(got.cpu(), ref, extra, max_bias=max_bias, what=what, bias_rounding_only=True)
+    _note(f"{what}_ratio_bias", (round(top, 4), round(bias, 5)))
+
+
+def _reference(order, width):
+    """(qkv, row_start, ref, extra) of the length set in the given order: computed once per (order, width), shared, never modified."""
+    def make():
+        lens = B.LENGTHS if order == "sorted" else B.SHUFFLED
+        rs = _row_start(lens)
+        qkv = _qkv(int(rs[-1]), width, 300 + width)          # the same rows in both orders: the items differ, so do their neighbours
+        return (qkv, rs) + _emulation(qkv, rs, width)
+    return B.cached(("varlen", order, width), make)
+
+
+# ------------------------------------------------------------------------------------------------ attention over packed items
+@pytest.mark.parametrize("order,width", [("sorted", 256), ("shuffled", 256), ("sorted", 768)])
+def test_varlen_attention_against_per_item_emulation(device, order, width):
+    """Lengths 1 .. 512 at the edges of a 16-query tile, a 64-key chunk and a 128-query block, 2 418 rows in one launch."""
+    qkv, rs, ref, extra = _reference(order, width)
+    assert int(rs[-1]) == 2418
+    got = debug.op_attention_varlen(qkv.to(device), rs.to(device), MAX_T, width, fill=float("nan")).cpu()
+    assert bool(torch.isfinite(got).all())                   # every row of every item was written
+    _check(got, ref, extra, f"attn_varlen_{order}_w{width}")
+    ones = [int(a) for a, e in zip(rs[:-1], rs[1:]) if e - a == 1]
+    assert ones and all(torch.equal(got[a], qkv[a, 2 * width:]) for a in ones)           # one key: the output is its V row, exactly
+    # against the fp32 softmax of the same bf16 inputs, with the bars of tests/test_attention_long_gpu.py
+    worst, mean = 0.0, 0.0
+    for a, e in zip(rs[:-1].tolist(), rs[1:].tolist()):
+        q, k, v = qkv[a:e].float().view(e - a, 3, width // 64, 64).permute(1, 2, 0, 3)
+        o = (torch.softmax(q @ k.transpose(-1, -2), -1) @ v).transpose(0, 1).reshape(e - a, width)
+        err = (got[a:e].float() - o).abs()
+        worst, mean = max(worst, float(err.max())), mean + float(err.sum())
+    assert worst < 3e-2 and mean / got.numel() < 3e-3, (worst, mean / got.numel())
+
+
+@pytest.mark.parametrize("case", ["spike_first_chunk", "spike_last_ragged_chunk", "max_moves_every_chunk", "max_creeps"])
+def test_varlen_online_rescale(device, case):
+    """tests/test_attention_long_gpu.py::test_online_rescale per packed item: a key ~20 logits ahead in the first chunk, or in the
+    last, ragged chunk (the row maximum arrives last: O and l of everything before are rescaled by ~e^-20 at the end), and logits
+    rising along the keys so that every chunk moves the maximum.  Items of 65, 257 and 512 rows: 2, 5 and 8 chunks."""
+    width, lens = 256, [257, 65, 512]
+    rs = _row_start(lens)
+    g = torch.Generator().manual_seed(11)
+    qkv = torch.randn(int(rs[-1]), 3 * width, generator=g) * 0.1
+    qkv[:, :width] *= 0.5
+    for hd in range(width // 64):
+        qkv[:, hd * 64] = 4.0                                      # q . k picks up 4 * k[d0] in every head
+        for a, n in zip(rs[:-1].tolist(), lens):
+            if case == "max_moves_every_chunk":
+                qkv[a:a + n, width + hd * 64] = torch.linspace(-8, 8, n)          # logits -32 .. 32, rising
+            elif case == "max_creeps":
+                qkv[a:a + n, width + hd * 64] = torch.linspace(-2, 2, n)          # logits -8 .. 8, rising
+            else:
+                qkv[a + (5 if case == "spike_first_chunk" else n - 1), width + hd * 64] = 5.0      # logit 20 over ~0
+    qkv = qkv.to(torch.bfloat16)
+    got = debug.op_attention_varlen(qkv.to(device), rs.to(device), MAX_T, width)
+    ref, extra = _emulation(qkv, rs, width)
+    # spikes: most outputs sit just below a bf16 value, so the signed bias is not centred at 0 even for correct rounding -- ratio only
+    _check(got, ref, extra, f"attn_varlen_{case}", max_bias=None if case.startswith("spike") else MAX_BIAS)
+
+
+def test_varlen_items_are_isolated_and_runs_repeat(device):
+    """Overwriting every OTHER item's q | k | v rows with NaN leaves an item's output bit-identical (its keys are its own rows, and no
+    clamped or padded load strays into a neighbour); two runs give the same bits; rows no item owns are not written; max_t beyond 512
+    and a width that is no multiple of 64 are refused."""
+    width = 256
+    qkv, rs, _, _ = _reference("shuffled", width)
+    qd, rd = qkv.to(device), rs.to(device)
+    base = debug.op_attention_varlen(qd, rd, MAX_T, width)
+    assert torch.equal(base, debug.op_attention_varlen(qd, rd, MAX_T, width))
+    for i in (0, 3, 7, len(B.SHUFFLED) - 1):
+        a, e = int(rs[i]), int(rs[i + 1])
+        poisoned = torch.full_like(qd, float("nan"))
+        poisoned[a:e] = qd[a:e]
+        got = debug.op_attention_varlen(poisoned, rd, MAX_T, width)
+        assert torch.equal(got[a:e], base[a:e]), (i, a, e)
+    # a launch over the middle items only: the rows in front of row_start[0] and behind row_start[batch] keep their fill
+    sub = rs[4:9].to(device)
+    got = debug.op_attention_varlen(qd, sub, MAX_T, width, fill=7.0)
+    a, e = int(rs[4]), int(rs[8])
+    assert torch.equal(got[a:e], base[a:e]) and bool((got[:a] == 7.0).all()) and bool((got[e:] == 7.0).all())
+    with pytest.raises(RuntimeError, match="not in 1..512"):
+        debug.op_attention_varlen(qd, rd, 513, width)
+    with pytest.raises(RuntimeError, match="multiple of the head dim 64"):
+        debug.op_attention_varlen(qd, rd, MAX_T, 96)
+
+
+# ------------------------------------------------------------------------------------------------ the post-LN LayerNorm mode
+def _ln64(xs, gamma, beta, eps=B.EPS):
+    """fp64 LayerNorm of the rows the kernel sees + the `extra` of its fp32 two-pass arithmetic (tests/test_numerics_gpu.py _ln64)."""
+    x = xs.double()
+    mean = x.mean(-1, keepdim=True)
+    d = x - mean
+    rstd = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + eps)
+    g, b = gamma.double(), beta.double()
+    y = d * rstd * g + b
+    extra = 2.0 ** -24 * (32 * x.abs().amax(-1, keepdim=True) * rstd * g.abs() + 8 * (d * rstd * g).abs() + 2 * b.abs())
+    return y, extra
+
+
+def _check_f32_rows(got, ref, what, half_ulp=0.0):
+    """fp32-class outputs: within LN_F32_FACTOR max|y| of the row (the bar of the fp32 LayerNorm and tail tests), plus the storage
+    type's own rounding where the rows are 24-bit (half an ulp at 16 significant bits: <= 2^-17 of the binade's top, < 2^-16 |y|)."""
+    err = (got.double() - ref).abs()
+    bar = LN_F32_FACTOR * ref.abs().amax(-1, keepdim=True) + half_ulp * ref.abs()
+    worst = float((err / bar).max())
+    _note(f"{what}_err_over_bar", round(worst, 4))
+    assert worst <= 1.0, (what, worst)
+
+
+def _stored(kind, x32):
+    """The stored rows (device form) and the values the kernel reads from them, exactly (tests/test_numerics_paths_gpu.py _rows)."""
+    if kind == "f32":
+        return x32, x32, _lib.KEMR_F32
+    x24 = engine.pack_f24_rows(x32)
+    return x24, engine.unpack_f24_rows(x24, x32.shape[1]), _lib.KEMR_F24
+
+
+@pytest.mark.parametrize("kind", ["f32", "f24"])
+@pytest.mark.parametrize("width", [256, 768, 1024])
+def test_layernorm_post_mode_against_fp64(device, kind, width):
+    """o = LN(x + delta) at eps 1e-12: h = bf16(o) within the rounding budget, the stream row = o in its storage type; rows 133 (not a
+    multiple of the 4-row block), with the rows where LayerNorms go wrong (a common offset of 1000, one outlier channel)."""
+    rows = 133
+    g = torch.Generator().manual_seed(width + len(kind))
+    x = torch.randn(rows, width, generator=g) * 3 + 0.7
+    x[0] = 1000.0 + torch.randn(width, generator=g)
+    x[1] = torch.randn(width, generator=g)
+    x[1, width // 3] = 1e4
+    delta = (torch.randn(rows, width, generator=g) * 0.5).to(torch.bfloat16)
+    gamma, beta = 1 + 0.1 * torch.randn(width, generator=g), 0.1 * torch.randn(width, generator=g)
+    xdev, xread, dt = _stored(kind, x)
+    guard = torch.full((4, xdev.shape[1]), 0, dtype=xdev.dtype)
+    xs = xread + delta.float()                                     # one fp32 add, as the kernel's
+    ref, extra = _ln64(xs, gamma, beta)
+    x2, h = debug.op_layernorm_post(torch.cat([xdev, guard]).to(device), dt, delta.to(device), gamma.to(device), beta.to(device), rows, width, B.EPS)
+    assert not bool(x2[rows:].any())                               # the rows behind `rows` are not touched
+    top, bias = R.check_budget(h.cpu(), ref, extra, max_bias=MAX_BIAS, what=f"ln_post_{kind}_w{width}")
+    _note(f"ln_post_{kind}_w{width}_ratio_bias", (round(top, 4), round(bias, 5)))
+    if kind == "f32":
+        o = x2[:rows].cpu()
+        _check_f32_rows(o[1:], ref[1:], f"ln_post_stream_f32_w{width}")          # (row 0: the offset row's fp32 mean, held by `extra` above)
+        assert torch.equal(o.to(torch.bfloat16), h.cpu())            # h IS bf16 of the stream row
+    else:
+        o = engine.unpack_f24_rows(x2[:rows].cpu(), width)
+        _check_f32_rows(o[1:], ref[1:], f"ln_post_stream_f24_w{width}", half_ulp=2.0 ** -16)
+
+
+# ------------------------------------------------------------------------------------------------ front and pooling tail on an engine
+def _engine(device, precision, pooling="mean"):
+    eng = engine.BertEngine(B.BertArch(256, 2, vocab=1024, ctx=512, pooling=pooling), device, precision)
+    eng.load_state_dict(B.cached("sd0", lambda: B.random_state_dict(B.ARCH, 0)))
+    return eng
+
+
+@pytest.mark.parametrize("precision", ["bf16", "bf16-x24"])
+def test_embedding_front_against_fp64(device, precision):
+    """x = LayerNorm(tok[id] + (pos + token_type[0])[p]) per packed row: the row starts are rounding.text_row_starts', h within the
+    bf16 budget of the fp64 LayerNorm of the exactly summed rows, the stream rows within the fp32-class bar."""
+    sd = B.cached("sd0", lambda: B.random_state_dict(B.ARCH, 0))
+    ids, lens = B.random_ids(B.SHUFFLED, seed=2)
+    rows = int(lens.sum())
+    eng = _engine(device, precision)
+    x, h, rs = debug.bert_front(eng, ids, lens, rows)
+    want_rs = R.text_row_starts(lens, rows, 512)
+    assert torch.equal(rs.cpu(), want_rs)
+    pos = sd["positional_embedding"] + sd["token_type_embedding"][0]          # fp32, as finalize folds it
+    xs, _ = R.text_tokens_statement(ids, lens, rows, sd["token_embedding.weight"], pos, 1024, 512)
+    ref, extra = _ln64(xs, sd["ln_embed.weight"], sd["ln_embed.bias"])
+    top, bias = R.check_budget(h.cpu(), ref, extra, max_bias=MAX_BIAS, what=f"bert_front_h_{precision}")
+    _note(f"bert_front_h_{precision}_ratio_bias", (round(top, 4), round(bias, 5)))
+    if precision == "bf16":
+        assert x.dtype == torch.float32
+        _check_f32_rows(x.cpu(), ref, "bert_front_stream_f32")
+        assert torch.equal(x.cpu().to(torch.bfloat16), h.cpu())
+    else:
+        _check_f32_rows(engine.unpack_f24_rows(x.cpu(), 256), ref, "bert_front_stream_f24", half_ulp=2.0 ** -16)
+
+
+@pytest.mark.parametrize("kind", ["f32", "f24"])
+@pytest.mark.parametrize("pooling", [0, 1])
+def test_pooling_tail_against_fp64(device, kind, pooling):
+    """Mean of an item's rows (fp32 sum in row order, one division) or its first row, then the L2 step: lengths 1 .. 512 in one launch,
+    a length-1 item first and last.  Budget of the mean: a sequential fp32 sum of n terms is within (n - 1) u sum|x| of the exact sum
+    (u = 2^-24; the standard bound), so the mean within (n - 1) u mean|x|; the division rounds once (the half ulp of the budget ratio).
+    The L2 step against rounding.l2norm_emulation of the kernel's own unnormalised output, the bound the existing tail test uses (its
+    sum of squares is no longer than the one that bound assumes: ceil(W / 256) terms per thread, 6 + 3 adds across the workgroup)."""
+    width = 768
+    lens = [1] + B.SHUFFLED + [1]
+    rs = _row_start(lens)
+    g = torch.Generator().manual_seed(40 + pooling)
+    x32 = torch.randn(int(rs[-1]), width, generator=g) + 0.25
+    xdev, xread, dt = _stored(kind, x32)
+    got = debug.op_pool_rows(xdev.to(device), dt, rs.to(device), width, pooling, False).cpu()
+    ref = torch.zeros(len(lens), width, dtype=torch.float64)
+    extra = torch.zeros_like(ref)
+    for i, (a, e) in enumerate(zip(rs[:-1].tolist(), rs[1:].tolist())):
+        rows = xread[a:e].double() if pooling == 0 else xread[a:a + 1].double()
+        ref[i] = rows.mean(0)
+        extra[i] = (rows.shape[0] - 1) * 2.0 ** -24 * rows.abs().mean(0)
+    top, _ = R.check_budget(got, ref, extra, fmt="fp32", what=f"pool_rows_{kind}_p{pooling}")
+    _note(f"pool_rows_{kind}_p{pooling}_ratio", round(top, 4))
+    for i in (0, len(lens) - 1):                                    # a length-1 item: its row, exactly
+        assert torch.equal(got[i], xread[int(rs[i])])
+    if pooling == 1:
+        assert torch.equal(got, xread[rs[:-1].long()])              # CLS: the first rows themselves
+    gotn = debug.op_pool_rows(xdev.to(device), dt, rs.to(device), width, pooling, True).cpu()
+    refn, extran = R.l2norm_emulation(got)
+    topn, _ = R.check_budget(gotn, refn, extran, fmt="fp32", what=f"pool_rows_l2_{kind}_p{pooling}")
+    _note(f"pool_rows_l2_{kind}_p{pooling}_ratio", round(topn, 4))
+    with pytest.raises(RuntimeError, match="neither 0"):
+        debug.op_pool_rows(xdev.to(device), dt, rs.to(device), width, 2, False)
