@@ -459,6 +459,47 @@ int kemr_list_fuse(const float* list_scores_dev, const int32_t* list_idx_dev, in
                    const int32_t* gt_idx_dev, int32_t* ahead_dev, int32_t* found_dev, float* gt_score_dev,      /* all four or none  */
                    float* out_scores_dev, void* stream);
 
+/* The pooled tower rows, for training the projection heads on frozen towers: kemr_encode_image / kemr_encode_text /
+ * kemr_encode_text_packed with the same arguments minus `normalize`, but out_dev is fp32 [batch, tower width] (v_width / t_width) and
+ * holds the pooled row of the residual stream with the last block's pending updates applied -- exactly the values the tail feeds its
+ * LayerNorm (ln_post / ln_final), BEFORE that LayerNorm and the projection.  LayerNorm + projection (+ x / ||x||) of these rows in fp32 is
+ * the embedding of the counterpart call, up to the tail's own rounding.  The same workspace sizes and checks; the tail runs in a
+ * store-the-row mode and leaves no state behind (the counterpart calls produce the same bits before and after).  Family 0 (CLIP) at every
+ * precision; KEMR_ERR_INVALID for family 1 (SigLIP: its head is the attention pool over every row) and family 2 (BERT: no head). */
+int kemr_encode_image_pooled(kemr_model* m, const float* pixels_dev, int batch, float* out_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+int kemr_encode_text_pooled(kemr_model* m, const int32_t* ids_dev, int batch, float* out_dev,
+                            void* workspace_dev, size_t workspace_bytes, void* stream);
+int kemr_encode_text_packed_pooled(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
+                                   void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Fused InfoNCE (the symmetric contrastive loss of the fine-tuning recipe), forward and backward; the n x n logits are never stored.
+ * For fp32 features a, b [n, d] (row-major, any norm) and z = a b^T * inv_temperature:
+ *   loss_a2b = mean_i (lse_j z_ij - z_ii),  loss_b2a = mean_j (lse_i z_ij - z_jj),  loss = (loss_a2b + loss_b2a) / 2
+ *   dL/dz = (softmax_rows(z) + softmax_cols(z)) / (2 n) - I / n,  grad_a = dL/dz b * inv_temperature,  grad_b = dL/dz^T a * inv_temperature
+ * forward writes loss_dev fp32 [3] = loss, loss_a2b, loss_b2a and lse_dev fp32 [2 n] = the n row lse values, then the n column lse values
+ * (natural logarithm); backward takes that lse_dev and OVERWRITES grad_a_dev / grad_b_dev fp32 [n, d] with the gradient of `loss` (the
+ * caller scales by the upstream gradient).  Products at fp32 grade: every operand and the dL/dz tile are bf16 pairs (hi = rne(v), lo =
+ * rne(v - hi), the split of kemr_panel_build's terms == 3) contracted as hi.hi + lo.hi + hi.lo with fp32 accumulation; the log-sum-exp is
+ * online and max-subtracted in fp32.  No atomics, fixed reduction orders: the same inputs give the same bits on every call, and the two
+ * passes of forward see the same bits of every logit.
+ * 1 <= n <= 65536; d a multiple of 4, 4 <= d <= 1280; inv_temperature positive and finite; no pointer NULL.
+ * Workspace (the same size for both calls; backward does not need forward's contents, only lse_dev), with n256 = ceil256(n),
+ * dpad = ceil64(d), dpadT = ceil128(d), each term rounded up to 256 bytes:
+ *   2 * (n256 * 2 dpad * 2)      pair panels [hi | lo] of a and b
+ * + 2 * (2 dpadT * n256 * 2)     their transposes (backward's second contraction)
+ * + 2 n * 16 * 2 * 4             per (row, column chunk) running maximum and sum, both passes
+ * + 2 n * 4 + 2 n * 4            diagonal logits and per-row loss terms, both passes
+ * 256-byte aligned; exactly that is enough and its contents don't matter (every byte that is read is written first; pad rows and pad
+ * columns are zero-filled by the call and masked in the log-sum-exp).  Anything outside these ranges, a NULL pointer (KEMR_ERR_INVALID)
+ * and a short or misaligned workspace (KEMR_ERR_WORKSPACE) are refused BEFORE anything is launched: the outputs and the workspace keep
+ * their bytes.  kemr_infonce_workspace_bytes returns 0 for an n or d out of range. */
+size_t kemr_infonce_workspace_bytes(int n, int d);
+int kemr_infonce_forward(const float* a_dev, const float* b_dev, int n, int d, float inv_temperature,
+                         float* loss_dev, float* lse_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int kemr_infonce_backward(const float* a_dev, const float* b_dev, const float* lse_dev, int n, int d, float inv_temperature,
+                          float* grad_a_dev, float* grad_b_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Optional per-kernel-class timing with hipEvents recorded on the launch stream (bench.py's roofline line).
  * Classes: 0 GEMM, 1 LayerNorm, 2 attention, 3 embed/tail, 4 similarity tile kernel.  Not thread-safe;
  * profile_end synchronises the device.  Off by default: no events are recorded on the normal path. */

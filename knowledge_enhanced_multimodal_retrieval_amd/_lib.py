@@ -75,6 +75,9 @@ SIGNATURES = {
     "kemr_encode_text": (_i, [_vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "kemr_text_packed_workspace_bytes": (_sz, [_vp, _i, _i]),
     "kemr_encode_text_packed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp]),
+    "kemr_encode_image_pooled": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "kemr_encode_text_pooled": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "kemr_encode_text_packed_pooled": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "kemr_panel_kdim": (_i64, [_i, _i, _i]),
     "kemr_panel_build": (_i, [C.POINTER(_vp), C.POINTER(_f), C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp]),
     "kemr_sim_workspace_bytes": (_sz, [_i, _i, _i64, _i]),
@@ -92,6 +95,9 @@ SIGNATURES = {
     "kemr_cross_attention_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp]),
     "kemr_cross_attention_rerank": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp]),
     "kemr_list_fuse": (_i, [_vp, _vp, _i, _i, _i64, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kemr_infonce_workspace_bytes": (_sz, [_i, _i]),
+    "kemr_infonce_forward": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "kemr_infonce_backward": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "kemr_profile_begin": (_i, [_i]),
     "kemr_profile_end": (_i, [C.POINTER(C.c_double), C.POINTER(_i64), _i]),
     "kemr_op_gemm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -8,7 +8,10 @@ torch tensors, ``.load_state_dict(sd, strict=True)`` / ``.state_dict()`` with Op
 This class holds real ``nn.Parameter``s under exactly those names (fp32 master copy, what checkpoints are saved
 from) and packs them into the HIP engine lazily; the forward arithmetic never runs in PyTorch.
 
-Inference only: ``encode_*`` run without autograd.  After changing parameters in place call ``refresh()``.
+``encode_*`` run without autograd: there is no backward pass through the towers.  What can be trained are the projection heads on
+frozen towers -- ``encode_image_pooled`` / ``encode_text_pooled`` return the rows the final LayerNorms read, ``finetune.ProjectionHeads``
+trains ``visual.ln_post`` / ``visual.proj`` / ``ln_final`` / ``text_projection`` (this module's own parameters) on them, and the engine
+re-packs itself after an optimizer step (``_fingerprint``).  After a write through ``p.data`` call ``refresh()``.
 """
 from __future__ import annotations
 
@@ -208,6 +211,23 @@ class CLIP(nn.Module):
         host before the upload (engine.ClipEngine.encode_text); ids already on the GPU cost one small device-to-host copy unless the
         caller passes ``lens`` (``engine.text_lengths(host_tokens)``)."""
         return self.engine().encode_text(text, normalize=normalize, lens=lens)
+
+    # ------------------------------------------------------------------ pooled tower rows (finetune.py: heads on frozen towers)
+    @torch.no_grad()
+    def encode_image_pooled(self, image: torch.Tensor) -> torch.Tensor:
+        """fp32 ``[B, vision width]``: the class-token row before ``visual.ln_post`` and ``visual.proj``.  Inputs as ``encode_image``."""
+        from .preprocess import PackedRaw, gpu_preprocess_for
+        dev = self._device()
+        if isinstance(image, PackedRaw):
+            if getattr(self, "_gpu_pre", None) is None or self._gpu_pre.device != dev:
+                self._gpu_pre = gpu_preprocess_for(self, dev)
+            image = self._gpu_pre.batch(image)
+        return self.engine().encode_image_pooled(image.to(dev))
+
+    @torch.no_grad()
+    def encode_text_pooled(self, text: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp32 ``[B, text width]``: the end-of-text row before ``ln_final`` and ``text_projection``.  Inputs as ``encode_text``."""
+        return self.engine().encode_text_pooled(text, lens=lens)
 
     # ------------------------------------------------------------------ the calls made on a transformers.CLIPModel
     @classmethod

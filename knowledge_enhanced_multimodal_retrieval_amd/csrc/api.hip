@@ -819,7 +819,7 @@ int run_blocks_x3(const TowerW& t, const WorkspaceX3& w, int M, int batch, int c
 }
 
 int encode_image_x3(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize, void* workspace_dev,
-                    size_t workspace_bytes, hipStream_t s) {
+                    size_t workspace_bytes, hipStream_t s, bool pooled = false) {
     if (!pixels_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: null argument");
     if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("encode_image: negative batch"), KEMR_ERR_INVALID);
     if ((int64_t)batch * (m->patches + 1) > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: batch %d too large", batch);
@@ -834,11 +834,11 @@ int encode_image_x3(kemr_model* m, const float* pixels_dev, int batch, float* ou
     KEMR_TRY(launch_cls_rows(w.x, m->cls, m->vpos, batch, T, W, s));
     KEMR_TRY(launch_layernorm(w.x, KEMR_F32, nullptr, nullptr, 0, m->lnpre_g, m->lnpre_b, w.x, M, W, KEMR_F32, s));
     KEMR_TRY(run_blocks_x3(m->vis, w, M, batch, 0, nullptr, m->activation, s));
-    return launch_tail(w.x, KEMR_F32, nullptr, nullptr, nullptr, batch, T, W, m->lnpost_g, m->lnpost_b, m->vproj, m->cfg.embed_dim, normalize, out_dev, s);
+    return launch_tail(w.x, KEMR_F32, nullptr, nullptr, nullptr, batch, T, W, m->lnpost_g, m->lnpost_b, pooled ? nullptr : m->vproj, m->cfg.embed_dim, normalize, out_dev, s);
 }
 
 int encode_text_x3(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, bool packed, float* out_dev,
-                   int normalize, void* workspace_dev, size_t workspace_bytes, hipStream_t s) {
+                   int normalize, void* workspace_dev, size_t workspace_bytes, hipStream_t s, bool pooled = false) {
     const char* what = packed ? "encode_text_packed" : "encode_text";
     if (!ids_dev || !out_dev || (packed && !lens_dev)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
     if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
@@ -860,7 +860,7 @@ int encode_text_x3(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_de
         KEMR_TRY(launch_text_embed(ids_dev, m->tok, m->tpos, w.x, KEMR_F32, batch, T, W, m->cfg.vocab, s));
     }
     KEMR_TRY(run_blocks_x3(m->txt, w, M, batch, 1, row_start, m->activation, s));
-    return launch_tail(w.x, KEMR_F32, nullptr, nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s, row_start);
+    return launch_tail(w.x, KEMR_F32, nullptr, nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, pooled ? nullptr : m->tproj, m->cfg.embed_dim, normalize, out_dev, s, row_start);
 }
 
 // ---- family 2: BERT sentence encoders (transformers.BertModel without its pooler + mean / CLS pooling) on packed rows ----
@@ -945,11 +945,21 @@ extern "C" size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows
            (size_t)round_up(((int64_t)batch + 1) * 4, 256);                                        // buffers + pooled-row area + row_start
 }
 
-extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize,
-                                 void* workspace_dev, size_t workspace_bytes, void* stream) {
+// pooled: the tail stores the pooled row of the residual stream (pending updates applied) instead of normalising and projecting it --
+// kemr_encode_*_pooled; family 0 only (SigLIP's head is the attention pool over every row, BERT has no head)
+static int pooled_family_check(const kemr_model* m, bool pooled, const char* what) {
+    if (pooled && m && m->family == 1) KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 1 (SigLIP): its head is the attention pool over every row, not LayerNorm + projection of one pooled row", what);
+    if (pooled && m && m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 2 (BERT): a sentence encoder has no projection head", what);
+    return KEMR_OK;
+}
+
+static int encode_image_any(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize,
+                            void* workspace_dev, size_t workspace_bytes, void* stream, bool pooled) {
     hipStream_t s = (hipStream_t)stream;
+    KEMR_TRY(pooled_family_check(m, pooled, "encode_image_pooled"));
+    const float* vproj = (pooled || !m) ? nullptr : m->vproj;
     if (m && m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: not available for family 2 (BERT): a text-only model has no vision tower");
-    if (m && m->finalized && m->x3) return encode_image_x3(m, pixels_dev, batch, out_dev, normalize, workspace_dev, workspace_bytes, s);
+    if (m && m->finalized && m->x3) return encode_image_x3(m, pixels_dev, batch, out_dev, normalize, workspace_dev, workspace_bytes, s, pooled);
     Workspace w;
     KEMR_TRY(image_front(m, pixels_dev, batch, out_dev, workspace_dev, workspace_bytes, s, "encode_image", w));
     if (batch == 0) return KEMR_OK;
@@ -965,17 +975,19 @@ extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int bat
     }
     KEMR_TRY(launch_layernorm(w.x32, KEMR_F32, nullptr, nullptr, 0, m->lnpre_g, m->lnpre_b, w.x, batch * T, W, w.x_dtype, s));
     KEMR_TRY(run_blocks(m->vis, w, batch, 0, m->fp8, m->resadd, fc1_epilogue(m), s, &vb, nullptr, 0, m->last_pooled, nullptr, &vc));
-    if (vc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnpost_g, m->lnpost_b, m->vproj, m->cfg.embed_dim, normalize, out_dev, s));
-    else KEMR_TRY(launch_tail(w.x, w.x_dtype, vb ? w.delta : nullptr, vb ? w.delta2 : nullptr, nullptr, batch, T, W, m->lnpost_g, m->lnpost_b, m->vproj, m->cfg.embed_dim, normalize, out_dev, s));
+    if (vc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnpost_g, m->lnpost_b, vproj, m->cfg.embed_dim, normalize, out_dev, s));
+    else KEMR_TRY(launch_tail(w.x, w.x_dtype, vb ? w.delta : nullptr, vb ? w.delta2 : nullptr, nullptr, batch, T, W, m->lnpost_g, m->lnpost_b, vproj, m->cfg.embed_dim, normalize, out_dev, s));
     return KEMR_OK;
 }
 
-extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch, float* out_dev, int normalize,
-                                void* workspace_dev, size_t workspace_bytes, void* stream) {
+static int encode_text_any(kemr_model* m, const int32_t* ids_dev, int batch, float* out_dev, int normalize,
+                           void* workspace_dev, size_t workspace_bytes, void* stream, bool pooled) {
     hipStream_t s = (hipStream_t)stream;
+    KEMR_TRY(pooled_family_check(m, pooled, "encode_text_pooled"));
+    const float* tproj = (pooled || !m) ? nullptr : m->tproj;
     if (m && m->family == 2)
         KEMR_FAIL(KEMR_ERR_INVALID, "encode_text: not available for family 2 (BERT): a padding mask is a length -- call kemr_encode_text_packed with the lengths");
-    if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, nullptr, 0, batch, false, out_dev, normalize, workspace_dev, workspace_bytes, s);
+    if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, nullptr, 0, batch, false, out_dev, normalize, workspace_dev, workspace_bytes, s, pooled);
     Workspace w;
     int* no_rows = nullptr;
     KEMR_TRY(text_front(m, ids_dev, nullptr, 0, batch, false, out_dev, workspace_dev, workspace_bytes, s, "encode_text", w, &no_rows));
@@ -989,8 +1001,8 @@ extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch
         return launch_tail(w.x, w.x_dtype, tb ? w.delta : nullptr, tb ? w.delta2 : nullptr, nullptr, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s, nullptr, m->eps, T - 1, m->tproj_b);
     }
     KEMR_TRY(run_blocks(m->txt, w, batch, 1, 0, m->resadd, fc1_epilogue(m), s, &tb, nullptr, 0, m->last_pooled, ids_dev, &tc));
-    if (tc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
-    else KEMR_TRY(launch_tail(w.x, w.x_dtype, tb ? w.delta : nullptr, tb ? w.delta2 : nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
+    if (tc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, tproj, m->cfg.embed_dim, normalize, out_dev, s));
+    else KEMR_TRY(launch_tail(w.x, w.x_dtype, tb ? w.delta : nullptr, tb ? w.delta2 : nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, tproj, m->cfg.embed_dim, normalize, out_dev, s));
     return KEMR_OK;
 }
 
@@ -1003,13 +1015,15 @@ extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch
 // shorter length pools the last computed row instead (memory-safe, wrong).  `rows` is a HOST integer: the tokenizer's side knows the lengths without
 // asking the device (the python wrapper derives lens and rows from the same host tokens); lengths and prefix sums are clamped on the
 // device (row_starts_kernel) so that no argument can index outside the workspace.
-extern "C" int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
-                                       int normalize, void* workspace_dev, size_t workspace_bytes, void* stream) {
+static int encode_text_packed_any(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
+                                  int normalize, void* workspace_dev, size_t workspace_bytes, void* stream, bool pooled) {
     hipStream_t s = (hipStream_t)stream;
+    KEMR_TRY(pooled_family_check(m, pooled, "encode_text_packed_pooled"));
+    const float* tproj = (pooled || !m) ? nullptr : m->tproj;
     if (m && m->family == 1)
         KEMR_FAIL(KEMR_ERR_INVALID, "encode_text_packed: not available for family 1 (SigLIP): its text tower is unmasked and pools the last position, so a pad position is a key and no row can be left out");
     if (m && m->family == 2) return encode_bert(m, ids_dev, lens_dev, rows, batch, out_dev, normalize, workspace_dev, workspace_bytes, s);
-    if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, lens_dev, rows, batch, true, out_dev, normalize, workspace_dev, workspace_bytes, s);
+    if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, lens_dev, rows, batch, true, out_dev, normalize, workspace_dev, workspace_bytes, s, pooled);
     Workspace w;
     int* row_start = nullptr;
     KEMR_TRY(text_front(m, ids_dev, lens_dev, rows, batch, true, out_dev, workspace_dev, workspace_bytes, s, "encode_text_packed", w, &row_start));
@@ -1017,9 +1031,34 @@ extern "C" int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, co
     const int W = m->cfg.t_width, T = m->cfg.ctx;
     bool tb = false, tc = false;
     KEMR_TRY(run_blocks(m->txt, w, batch, 1, 0, m->resadd, fc1_epilogue(m), s, &tb, row_start, rows, m->last_pooled, ids_dev, &tc));
-    if (tc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s));
-    else KEMR_TRY(launch_tail(w.x, w.x_dtype, tb ? w.delta : nullptr, tb ? w.delta2 : nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, m->tproj, m->cfg.embed_dim, normalize, out_dev, s, row_start));
+    if (tc) KEMR_TRY(launch_tail(w.xc, w.x_dtype, w.d1c, w.d2c, nullptr, batch, 1, W, m->lnf_g, m->lnf_b, tproj, m->cfg.embed_dim, normalize, out_dev, s));
+    else KEMR_TRY(launch_tail(w.x, w.x_dtype, tb ? w.delta : nullptr, tb ? w.delta2 : nullptr, ids_dev, batch, T, W, m->lnf_g, m->lnf_b, tproj, m->cfg.embed_dim, normalize, out_dev, s, row_start));
     return KEMR_OK;
+}
+
+extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize,
+                                 void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return encode_image_any(m, pixels_dev, batch, out_dev, normalize, workspace_dev, workspace_bytes, stream, false);
+}
+extern "C" int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch, float* out_dev, int normalize,
+                                void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return encode_text_any(m, ids_dev, batch, out_dev, normalize, workspace_dev, workspace_bytes, stream, false);
+}
+extern "C" int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
+                                       int normalize, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return encode_text_packed_any(m, ids_dev, lens_dev, rows, batch, out_dev, normalize, workspace_dev, workspace_bytes, stream, false);
+}
+extern "C" int kemr_encode_image_pooled(kemr_model* m, const float* pixels_dev, int batch, float* out_dev,
+                                        void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return encode_image_any(m, pixels_dev, batch, out_dev, 0, workspace_dev, workspace_bytes, stream, true);
+}
+extern "C" int kemr_encode_text_pooled(kemr_model* m, const int32_t* ids_dev, int batch, float* out_dev,
+                                       void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return encode_text_any(m, ids_dev, batch, out_dev, 0, workspace_dev, workspace_bytes, stream, true);
+}
+extern "C" int kemr_encode_text_packed_pooled(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
+                                              void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return encode_text_packed_any(m, ids_dev, lens_dev, rows, batch, out_dev, 0, workspace_dev, workspace_bytes, stream, true);
 }
 
 // ------------------------------------------------------------------------------------------------ per-model options

@@ -293,7 +293,9 @@ __global__ __launch_bounds__(256) void tail_proj_kernel(const XT* __restrict__ x
         if (dr2) v += bf16_to_f32(dr2[i]);
         y[i] = v;
         s += v;
+        if (!proj) out[(size_t)b * width + i] = v;     // pooled-row mode: the values the LayerNorm below would read
     }
+    if (!proj) return;                                 // uniform
     const float mean = block_sum(s, red) / width;
     float q = 0.f;
     for (int i = tid; i < width; i += 256) { const float c = y[i] - mean; q += c * c; }
@@ -347,7 +349,9 @@ int launch_tail(const void* x, int x_dtype, const bf16_t* delta, const bf16_t* d
     if (batch > 65535) KEMR_FAIL(KEMR_ERR_INVALID, "tail: batch %d > 65535", batch);
     const size_t smem = (size_t)width * 4 + 32;
     ProfScope prof(PROF_OTHER, stream);
-    const dim3 grid((d + 63) / 64, batch);
+    // proj == nullptr (kemr_encode_*_pooled): out fp32 [batch, width] = the pooled rows themselves, one workgroup per item
+    const dim3 grid(proj ? (d + 63) / 64 : 1, batch);
+    if (!proj) normalize = 0;
     if (x_dtype == KEMR_BF16)
         hipLaunchKernelGGL(tail_proj_kernel<bf16_t>, grid, dim3(256), smem, stream, (const bf16_t*)x, delta, delta2, ids, tokens, width, gamma, beta, proj, d, out, row_start, eps, pool_pos, proj_bias);
     else if (x_dtype == KEMR_F24)

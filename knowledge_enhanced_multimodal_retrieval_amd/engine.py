@@ -184,11 +184,12 @@ class ClipEngine:
             self._ws[tower] = ws
         return ws
 
-    def _encode(self, fn, tower: int, x: torch.Tensor, max_batch: int, normalize: bool) -> torch.Tensor:
+    def _encode(self, fn, tower: int, x: torch.Tensor, max_batch: int, normalize: bool, pooled_width: Optional[int] = None) -> torch.Tensor:
+        """pooled_width: `fn` is the kemr_encode_*_pooled form (no `normalize` argument, rows of the tower's width)."""
         if not self.ready:
             raise RuntimeError("ClipEngine: load_state_dict() must be called before encoding")
         n = x.shape[0]
-        out = torch.empty((n, self.arch.embed_dim), dtype=torch.float32, device=self.device)
+        out = torch.empty((n, pooled_width or self.arch.embed_dim), dtype=torch.float32, device=self.device)
         if n == 0:
             return out
         with torch.cuda.device(self.device):
@@ -196,9 +197,9 @@ class ClipEngine:
             ws = self._workspace(tower, min(n, max_batch))
             for s in range(0, n, max_batch):
                 xb = x[s:s + max_batch]
-                _lib.check(fn(self._h, C.c_void_p(xb.data_ptr()), xb.shape[0], C.c_void_p(out[s:].data_ptr()),
-                              1 if normalize else 0, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)),
-                           "encode")
+                tail = (C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream))
+                head = (self._h, C.c_void_p(xb.data_ptr()), xb.shape[0], C.c_void_p(out[s:].data_ptr()))
+                _lib.check(fn(*head, *tail) if pooled_width else fn(*head, 1 if normalize else 0, *tail), "encode")
         return out
 
     def encode_image(self, pixels: torch.Tensor, normalize: bool = False) -> torch.Tensor:
@@ -209,7 +210,29 @@ class ClipEngine:
         pixels = pixels.to(dtype=torch.float32).contiguous()
         return self._encode(self._L.kemr_encode_image, _lib.TOWER_VISION, pixels, self.image_batch, normalize)
 
-    def encode_text(self, ids: torch.Tensor, normalize: bool = False, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _refuse_pooled(self, what: str) -> None:
+        if self.arch.family != "clip":
+            raise RuntimeError(f"{what}: pooled tower rows are served for the CLIP family only (SigLIP's head is the attention pool "
+                               f"over every row, BERT has no head); this model's family is {self.arch.family!r}")
+
+    def encode_image_pooled(self, pixels: torch.Tensor) -> torch.Tensor:
+        """fp32 [B, v_width]: the class-token row of the residual stream BEFORE ln_post and the projection (kemr_encode_image_pooled);
+        ``(ln_post(rows) @ visual.proj)`` is ``encode_image(pixels)``.  What a head trained on frozen towers takes as its input."""
+        a = self.arch
+        self._refuse_pooled("encode_image_pooled")
+        _require_cuda(pixels, "pixels")
+        if pixels.dim() != 4 or tuple(pixels.shape[1:]) != (3, a.image_size, a.image_size):
+            raise RuntimeError(f"encode_image_pooled expects [B,3,{a.image_size},{a.image_size}], got {tuple(pixels.shape)}")
+        pixels = pixels.to(dtype=torch.float32).contiguous()
+        return self._encode(self._L.kemr_encode_image_pooled, _lib.TOWER_VISION, pixels, self.image_batch, False, pooled_width=a.v_width)
+
+    def encode_text_pooled(self, ids: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp32 [B, t_width]: the end-of-text row BEFORE ln_final and the projection (kemr_encode_text_pooled / _packed_pooled, chosen
+        like encode_text chooses between the dense and the packed call)."""
+        self._refuse_pooled("encode_text_pooled")
+        return self.encode_text(ids, lens=lens, _pooled=True)
+
+    def encode_text(self, ids: torch.Tensor, normalize: bool = False, lens: Optional[torch.Tensor] = None, _pooled: bool = False) -> torch.Tensor:
         """``model.encode_text(tokens)`` (+ the optional L2 normalisation).  The rows behind a text's end-of-text token cannot reach
         its embedding (causal mask, pooled at ``tokens.argmax(-1)``), so by default only the first ``lens[i] = argmax_i + 1``
         positions of every text are computed, packed one text behind the other (kemr_encode_text_packed: the same embeddings --
@@ -244,12 +267,14 @@ class ClipEngine:
         if pack and lens is None and os.environ.get("KEMR_TEXT_PACK_SYNC", "1") != "0":
             lens = text_lengths(ids).cpu()                    # the one synchronising copy of this path
         if not pack or lens is None:
+            if _pooled:
+                return self._encode(self._L.kemr_encode_text_pooled, _lib.TOWER_TEXT, ids, MAX_TEXT_BATCH, False, pooled_width=a.t_width)
             return self._encode(self._L.kemr_encode_text, _lib.TOWER_TEXT, ids, MAX_TEXT_BATCH, normalize)
         n = ids.shape[0]
         lens = torch.as_tensor(lens, dtype=torch.int32, device="cpu").reshape(-1).clamp(1, a.ctx).contiguous()
         if lens.numel() != n:
             raise RuntimeError(f"encode_text: {lens.numel()} lengths for {n} texts")
-        out = torch.empty((n, a.embed_dim), dtype=torch.float32, device=self.device)
+        out = torch.empty((n, a.t_width if _pooled else a.embed_dim), dtype=torch.float32, device=self.device)
         if n == 0:
             return out
         lens_dev = lens.to(self.device, non_blocking=True)
@@ -268,9 +293,12 @@ class ClipEngine:
                 if ws is None or ws.numel() < need:
                     ws = self._ws["text_packed"] = torch.empty(max(need, int(self._L.kemr_text_packed_workspace_bytes(
                         self._h, min(TEXT_ROW_BUDGET, n * a.ctx), min(n, 65528)))), dtype=torch.uint8, device=self.device)
-                _lib.check(self._L.kemr_encode_text_packed(self._h, C.c_void_p(ids[s0:].data_ptr()), C.c_void_p(lens_dev[s0:].data_ptr()),
-                                                           rows, s1 - s0, C.c_void_p(out[s0:].data_ptr()), 1 if normalize else 0,
-                                                           C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)), "encode_text_packed")
+                head = (self._h, C.c_void_p(ids[s0:].data_ptr()), C.c_void_p(lens_dev[s0:].data_ptr()), rows, s1 - s0, C.c_void_p(out[s0:].data_ptr()))
+                tail = (C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream))
+                if _pooled:
+                    _lib.check(self._L.kemr_encode_text_packed_pooled(*head, *tail), "encode_text_packed_pooled")
+                else:
+                    _lib.check(self._L.kemr_encode_text_packed(*head, 1 if normalize else 0, *tail), "encode_text_packed")
                 s0, base = s1, csum[s1 - 1]
         return out
 
@@ -999,3 +1027,50 @@ def op_attention_x3(qkv: torch.Tensor, batch: int, t: int, width: int, causal: b
             _lib.check(L.kemr_op_attention_x3_hd(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), _opt_ptr(row_start), batch, t, width,
                                                  int(head_dim), 1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))), "op_attention_x3_hd")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ fused InfoNCE (csrc/infonce.hip)
+def _infonce_args(a: torch.Tensor, b: torch.Tensor, what: str) -> Tuple[int, int]:
+    _require_cuda(a, f"{what}: features_a")
+    _require_cuda(b, f"{what}: features_b")
+    if a.dim() != 2 or a.shape != b.shape or a.device != b.device:
+        raise RuntimeError(f"{what}: features must be two [n, d] tensors on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or not a.is_contiguous() or not b.is_contiguous():
+        raise RuntimeError(f"{what}: features must be contiguous fp32")
+    return int(a.shape[0]), int(a.shape[1])
+
+
+def infonce_workspace_bytes(n: int, d: int) -> int:
+    need = int(_lib.lib().kemr_infonce_workspace_bytes(n, d))
+    if need == 0:
+        raise RuntimeError(f"infonce: n={n} must be in 1..65536 and d={d} a multiple of 4 in 4..1280")
+    return need
+
+
+def infonce_forward(a: torch.Tensor, b: torch.Tensor, temperature: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(losses fp32 [3] = loss, loss_a2b, loss_b2a; lse fp32 [2 n] = row lse, column lse) of z = a b^T / temperature; z is never stored."""
+    n, d = _infonce_args(a, b, "infonce_forward")
+    ws = torch.empty(infonce_workspace_bytes(n, d), dtype=torch.uint8, device=a.device)
+    loss = torch.empty(3, dtype=torch.float32, device=a.device)
+    lse = torch.empty(2 * n, dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.lib().kemr_infonce_forward(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, d, 1.0 / float(temperature),
+                                                   C.c_void_p(loss.data_ptr()), C.c_void_p(lse.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                                   ws.numel(), C.c_void_p(_stream_ptr(a.device))), "infonce_forward")
+    return loss, lse
+
+
+def infonce_backward(a: torch.Tensor, b: torch.Tensor, lse: torch.Tensor, temperature: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d loss / d a, d loss / d b), fp32 [n, d] each, from the lse values infonce_forward saved."""
+    n, d = _infonce_args(a, b, "infonce_backward")
+    _require_cuda(lse, "infonce_backward: lse")
+    if lse.dtype != torch.float32 or lse.numel() != 2 * n or not lse.is_contiguous():
+        raise RuntimeError("infonce_backward: lse must be the contiguous fp32 [2 n] tensor of infonce_forward")
+    ws = torch.empty(infonce_workspace_bytes(n, d), dtype=torch.uint8, device=a.device)
+    ga, gb = torch.empty_like(a), torch.empty_like(b)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.lib().kemr_infonce_backward(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(lse.data_ptr()), n, d,
+                                                    1.0 / float(temperature), C.c_void_p(ga.data_ptr()), C.c_void_p(gb.data_ptr()),
+                                                    C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(_stream_ptr(a.device))),
+                   "infonce_backward")
+    return ga, gb
