@@ -132,6 +132,13 @@ int kemr_debug_op_pool_rows(const void* x_dev, int x_dtype, const int* row_start
 int kemr_debug_bert_front(struct kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, void* x_out_dev,
                           void* h_out_dev, int* row_start_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The pack step of kemr_model_finalize alone (tests/test_pack_host.py), on the host: the bytes finalize would upload as the device arena
+ * for `precision` -- every required tensor in kemr_model_tensor_name order, each entry on a multiple of 256 bytes; the per-row scales of an
+ * e4m3 matrix in front of it, the pooling head's query behind the probe.  *bytes = the arena's size; host_out == NULL returns the size
+ * only, else `capacity` must reach it.  The same refusals as kemr_model_finalize (codes and messages), no GPU call, and the loaded
+ * tensors stay loaded: it runs on a machine without a device and kemr_model_finalize may follow. */
+int kemr_debug_pack_weights(const struct kemr_model* m, int precision, void* host_out, size_t capacity, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

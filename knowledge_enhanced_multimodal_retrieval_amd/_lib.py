@@ -139,6 +139,7 @@ DEBUG_SIGNATURES = {
     "kemr_debug_op_layernorm_post": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "kemr_debug_op_pool_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "kemr_debug_bert_front": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kemr_debug_pack_weights": (_i, [_vp, _i, _vp, _sz, C.POINTER(_sz)]),
 }
 ABI_VERSION = 4
 

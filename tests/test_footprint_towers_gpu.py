@@ -1,6 +1,6 @@
 """GPU: the encoders inside their workspace (DESIGN.md "Memory contracts"; helper and assertions: tests/footprint.py).
 
-The product carves about fifteen buffers out of one workspace (csrc/api.hip carve / carve_x3): an overrun of h lands in delta, one of
+The product carves about fifteen buffers out of one workspace (csrc/encode.hip ws_layout / ws_layout_x3, carve / carve_x3): an overrun of h lands in delta, one of
 the compact qc in ac, and several kernels over-read and mask.  Here every entry point runs twice -- with a roomy zero-filled workspace
 (the plain call) and with a workspace of EXACTLY kemr_workspace_bytes / kemr_text_packed_workspace_bytes, every byte 0xff, inside 0xa5
 margins, the pixels in 0xff margins, ids and lens in 0x7fffffff margins, `out` in 0xa5 margins -- and must give the same bits (A1)

@@ -63,7 +63,7 @@ def test_the_environment_and_the_engine_accept_the_name(monkeypatch):
 
 
 def x3_workspace_bytes(width, rows):
-    """include/kemr.h / csrc/api.hip: per row of the ceil256(rows) allocated, x fp32 [W], h bf16 [3W], qkv fp32 [3W], hidden bf16 [12W]."""
+    """include/kemr.h / csrc/encode.hip ws_layout_x3: per row of the ceil256(rows) allocated, x fp32 [W], h bf16 [3W], qkv fp32 [3W], hidden bf16 [12W]."""
     mp = (rows + 255) // 256 * 256
     return mp * width * (4 + 3 * 2 + 3 * 4 + 12 * 2)
 
