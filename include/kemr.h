@@ -500,6 +500,40 @@ int kemr_infonce_forward(const float* a_dev, const float* b_dev, int n, int d, f
 int kemr_infonce_backward(const float* a_dev, const float* b_dev, const float* lse_dev, int n, int d, float inv_temperature,
                           float* grad_a_dev, float* grad_b_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Fused pair-score contrastive loss: the symmetric InfoNCE of kemr_infonce_forward over the scores of a learned fusion head,
+ * S = head(q, img, tgt), forward and backward -- what trains the heads over frozen encoders; the n x n scores are never stored.
+ * For fp32 q, img, tgt [n, d] (row-major), t2i = q img^T, t2t = q tgt^T and z = S * inv_temperature:
+ *   KEMR_PAIRHEAD_GATED   s_ij = g_i t2i_ij + (1 - g_i) t2t_ij, gate_dev fp32 [n] (the head's gate per query, computed by the caller);
+ *                         w0_dev .. b1_dev and hidden are ignored
+ *   KEMR_PAIRHEAD_LINEAR  s_ij = b1 + sum_k w1_k max(0, w0_k0 t2i_ij + w0_k1 t2t_ij + b0_k), the arithmetic of kemr_linear_head fma for fma;
+ *                         w0_dev fp32 [hidden, 2], b0_dev [hidden], w1_dev [hidden], b1_dev [1], 1 <= hidden <= 256; gate_dev is ignored
+ *   loss, loss_q2g (rows), loss_g2q (columns) and lse_dev [2 n] as kemr_infonce_forward defines them
+ *   G = dL/ds = ((softmax_rows(z) + softmax_cols(z)) / (2 n) - I / n) * inv_temperature
+ * backward takes forward's lse_dev and OVERWRITES grad_dev with the gradient of `loss`:
+ *   GATED   fp32 [n]: dL/dg_i = sum_j G_ij (t2i_ij - t2t_ij)
+ *   LINEAR  fp32 [4 hidden + 1] = dL/dw0 [hidden, 2] | dL/db0 [hidden] | dL/dw1 [hidden] | dL/db1; a unit counts where its pre-activation > 0
+ * No gradient goes to q, img, tgt (frozen encoders).  t2i and t2t are computed as kemr_infonce_forward computes its logits, bit for bit, and
+ * both passes of forward and the backward see the same bits of every score; with g = 1 (g = 0) forward returns the bits of
+ * kemr_infonce_forward(q, img) (of (q, tgt)).  No atomics, fixed reduction orders: the same inputs give the same bits on every call.
+ * 1 <= n <= 65536; d a multiple of 4, 4 <= d <= 1280; inv_temperature positive and finite; no pointer that the mode reads NULL.
+ * Workspace (one size for both calls; backward needs only lse_dev of forward), n256 = ceil256(n), dpad = ceil64(d),
+ * tiles = ceil(n / 128), per = ceil(tiles / min(tiles, 16)), chunks = ceil(tiles / per), each term rounded up to 256 bytes:
+ *   3 * (n256 * 2 dpad * 2)               pair panels [hi | lo] of q, img, tgt
+ * + 2 n * 16 * 2 * 4 + 2 n * 4 + 2 n * 4  forward's chunk statistics, diagonal scores and loss terms, both passes
+ * + GATED: n * 16 * 4; LINEAR: tiles * chunks * (4 hidden + 1) * 4    backward's partial sums
+ * 256-byte aligned; exactly that is enough, its contents don't matter.  Anything out of range, an unknown mode, a NULL pointer
+ * (KEMR_ERR_INVALID) and a short or misaligned workspace (KEMR_ERR_WORKSPACE) are refused BEFORE anything is launched: the outputs and
+ * the workspace keep their bytes.  kemr_pairhead_workspace_bytes returns 0 for arguments out of range. */
+#define KEMR_PAIRHEAD_GATED 0
+#define KEMR_PAIRHEAD_LINEAR 1
+size_t kemr_pairhead_workspace_bytes(int mode, int n, int d, int hidden);
+int kemr_pairhead_forward(int mode, const float* q_dev, const float* img_dev, const float* tgt_dev, int n, int d, float inv_temperature,
+                          const float* gate_dev, const float* w0_dev, const float* b0_dev, const float* w1_dev, const float* b1_dev,
+                          int hidden, float* loss_dev, float* lse_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int kemr_pairhead_backward(int mode, const float* q_dev, const float* img_dev, const float* tgt_dev, const float* lse_dev, int n, int d,
+                           float inv_temperature, const float* gate_dev, const float* w0_dev, const float* b0_dev, const float* w1_dev,
+                           const float* b1_dev, int hidden, float* grad_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Optional per-kernel-class timing with hipEvents recorded on the launch stream (bench.py's roofline line).
  * Classes: 0 GEMM, 1 LayerNorm, 2 attention, 3 embed/tail, 4 similarity tile kernel.  Not thread-safe;
  * profile_end synchronises the device.  Off by default: no events are recorded on the normal path. */

@@ -47,6 +47,7 @@ EPI_BIAS_TGELU_BF16 = 8     # tanh GELU ("gelu_pytorch_tanh": the SigLIP family'
 ACTIVATIONS = {"quick_gelu": 0, "gelu": 1}
 FAMILY_BERT = 2             # kemr_model_create_family: a BERT sentence encoder (text-only)
 MAX_BERT_CTX = 512          # KEMR_MAX_BERT_CTX
+PAIRHEAD_GATED, PAIRHEAD_LINEAR = 0, 1      # KEMR_PAIRHEAD_*: the mode of kemr_pairhead_forward / _backward
 MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused / kemr_cross_attention_rerank / kemr_list_fuse
 
 
@@ -98,6 +99,9 @@ SIGNATURES = {
     "kemr_infonce_workspace_bytes": (_sz, [_i, _i]),
     "kemr_infonce_forward": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "kemr_infonce_backward": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "kemr_pairhead_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "kemr_pairhead_forward": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "kemr_pairhead_backward": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "kemr_profile_begin": (_i, [_i]),
     "kemr_profile_end": (_i, [C.POINTER(C.c_double), C.POINTER(_i64), _i]),
     "kemr_op_gemm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -7,6 +7,8 @@
 // and the K loop walks three virtual segments hi.hi + lo.hi + hi.lo over them, so one panel per operand serves both roles (sim.hip's
 // panels store the third segment; here it would double the workspace).  The K loop itself is sim_kernel's: LDS-DMA staging, chunk-XOR
 // swizzle, v_mfma_f32_16x16x32_bf16, a 128 x 128 fp32 tile per 256-thread workgroup.
+// The logit tile, its dump, the per-row scan and the chunk merge live in nce_tile.h: pairhead.hip (the same loss over a fusion head's scores)
+// shares them, and launches this file's panel, merge and loss kernels through nce_launch_*.
 //
 // Forward, infonce_stats_kernel: a workgroup owns 128 rows of X and walks a chunk of Y's 128-row tiles; two scanner threads per row
 // keep an online (max, sum) pair over their 64 logits of every tile (pad columns masked) and the row's diagonal logit.  Per (row, chunk)
@@ -19,29 +21,13 @@
 // panel [2 dpadT, ceil256(n)], k = the tile's 128 items contiguous) in three products again.  The fp32 accumulators of 128 rows x 768
 // columns would be 384 VGPRs a lane; NS <= 2 keeps them at 128 and splits wider outputs over workgroups, each recomputing the logits.
 // dL/db is the same kernel on swapped operands.  Every output element has one owner and one summation order: no atomics.
-#include "common.h"
-#include <cmath>
+#include "nce_tile.h"
 
 // z = fl(s / tau) is ONE rounded value everywhere it is used: contracted into z - max or z - lse as an fma, the forward's maximum, its
 // sum and the backward's recomputation would each see a different z (one item: lse != z, a loss and a gradient that are not 0).
 #pragma clang fp contract(off)
 
 namespace kemr {
-
-constexpr int NBK = 64;
-constexpr int NT = 128;           // tile edge
-constexpr int NLD = 132;          // LDS row stride of the logit tile in floats (sim.hip SLD)
-constexpr int NCE_TILE_BYTES = NT * NBK * 2;                  // 16 KiB: one operand tile of one K step
-constexpr int NCE_A_BYTES = NT * NLD * 4;                     // 67 584: logit tile, aliases the two operand stages (65 536)
-constexpr int NCE_P_BYTES = 4 * NCE_TILE_BYTES;               // dL/dz tile as [hi k0 | hi k1 | lo k0 | lo k1]
-constexpr int NCE_MAX_CHUNKS = 16;
-constexpr int NCE_MAX_NS = 2;         // 3 (192 accumulator VGPRs) spills 36 registers next to the logit tile's 64
-constexpr float NCE_LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ void nce_glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------------------ panels
 // [n256, 2 dpad]: hi | lo; columns d .. dpad and rows n .. n256 are +0
@@ -84,77 +70,6 @@ __global__ __launch_bounds__(256) void infonce_panel_t_kernel(const float* __res
     *(uint32_t*)(out + (size_t)(dpadT + c) * n256 + j) = lo;
 }
 
-// ------------------------------------------------------------------------------------------------ logit tile
-// acc[ci][qi][r] = S[x row wq*64 + qi*16 + lrow][y row wcn*64 + ci*16 + lq*4 + r] over hi.hi + (lo.hi, hi.lo | swap: hi.lo, lo.hi).
-// Ends behind a workgroup barrier: every wave is done with the stages, the caller may overwrite them.
-__device__ __forceinline__ void nce_logit_tile(const bf16_t* __restrict__ gX, const bf16_t* __restrict__ gY, int dpad, int swap, char* smem,
-                                               f32x4 (&acc)[4][4], int wid, int lane) {
-    constexpr int STAGE_BYTES = 2 * NCE_TILE_BYTES;
-    const int ld = 2 * dpad;
-    const int srow = lane >> 3, schunk = lane & 7;
-    const int lrow = lane & 15, lq = lane >> 4;
-    const int swz = lrow >> 1;
-    const int wq = wid >> 1, wcn = wid & 1;
-    const int per = dpad / NBK, nt = 3 * per;
-    auto stage = [&](int buf, int kt) {
-        char* sA = smem + buf * STAGE_BYTES;         // Y tile
-        char* sB = sA + NCE_TILE_BYTES;              // X tile
-        const int term = kt / per, k0 = (kt - term * per) * NBK;
-        const int xseg = swap ? (term == 2) : (term == 1);
-        const int yseg = swap ? (term == 1) : (term == 2);
-        const int xo = xseg * dpad + k0, yo = yseg * dpad + k0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int piece = wid * 4 + j;
-            const int r = piece * 8 + srow;
-            const int c = schunk ^ ((r >> 1) & 7);
-            nce_glds16(gY + (size_t)r * ld + yo + c * 8, sA + piece * 1024);
-            nce_glds16(gX + (size_t)r * ld + xo + c * 8, sB + piece * 1024);
-        }
-    };
-#pragma unroll
-    for (int ci = 0; ci < 4; ++ci)
-#pragma unroll
-        for (int qi = 0; qi < 4; ++qi) acc[ci][qi] = f32x4{0.f, 0.f, 0.f, 0.f};
-    stage(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = 0; kt < nt; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < nt) stage(cur ^ 1, kt + 1);
-        const char* sA = smem + cur * STAGE_BYTES + (wcn * 64 + lrow) * 128;
-        const char* sB = smem + cur * STAGE_BYTES + NCE_TILE_BYTES + (wq * 64 + lrow) * 128;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int coff = ((kk * 4 + lq) ^ swz) << 4;
-            bf16x8 yf[4], xf[4];
-#pragma unroll
-            for (int ci = 0; ci < 4; ++ci) yf[ci] = *(const bf16x8*)(sA + ci * 16 * 128 + coff);
-#pragma unroll
-            for (int qi = 0; qi < 4; ++qi) xf[qi] = *(const bf16x8*)(sB + qi * 16 * 128 + coff);
-#pragma unroll
-            for (int ci = 0; ci < 4; ++ci)
-#pragma unroll
-                for (int qi = 0; qi < 4; ++qi)
-                    acc[ci][qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(yf[ci], xf[qi], acc[ci][qi], 0, 0, 0);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-}
-
-__device__ __forceinline__ void nce_dump_tile(const f32x4 (&acc)[4][4], float* sS, int wid, int lane) {
-    const int lrow = lane & 15, lq = lane >> 4;
-    const int wq = wid >> 1, wcn = wid & 1;
-#pragma unroll
-    for (int ci = 0; ci < 4; ++ci)
-#pragma unroll
-        for (int qi = 0; qi < 4; ++qi) {
-            const f32x4 v = acc[ci][qi];
-            *(float4*)(sS + (wq * 64 + qi * 16 + lrow) * NLD + wcn * 64 + ci * 16 + lq * 4) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-}
-
 // ------------------------------------------------------------------------------------------------ forward
 struct NceStats {
     const bf16_t* X;
@@ -185,52 +100,10 @@ __global__ __launch_bounds__(256) void infonce_stats_kernel(const NceStats p) {
         nce_logit_tile(gX, p.Y + (size_t)gtile * NT * (2 * p.dpad), p.dpad, p.swap, smem, acc, wid, lane);
         nce_dump_tile(acc, sS, wid, lane);
         __syncthreads();
-        const int c0 = gtile * NT + half * 64;
-        const int nvalid = min(64, p.n - c0);              // pad columns (logit 0) are not data
-        if (q_valid && nvalid > 0) {
-            const float* rowp = sS + q_local * NLD + half * 64;
-            float tm = -INFINITY;
-#pragma unroll 4
-            for (int j4 = 0; j4 < 16; ++j4) {
-                const float4 v4 = *(const float4*)(rowp + j4 * 4);
-                const float ve[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (j4 * 4 + e < nvalid) tm = fmaxf(tm, ve[e] * p.inv_t);
-            }
-            if (tm > m) {                                  // exp2(-inf) = 0 on the first tile
-                s *= __builtin_amdgcn_exp2f((m - tm) * NCE_LOG2E);
-                m = tm;
-            }
-            float ts = 0.f;
-#pragma unroll 4
-            for (int j4 = 0; j4 < 16; ++j4) {
-                const float4 v4 = *(const float4*)(rowp + j4 * 4);
-                const float ve[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (j4 * 4 + e < nvalid) ts += __builtin_amdgcn_exp2f((ve[e] * p.inv_t - m) * NCE_LOG2E);
-            }
-            s += ts;
-            const int dj = qrow - c0;
-            if (dj >= 0 && dj < 64) p.diag[qrow] = rowp[dj] * p.inv_t;        // one owner per row
-        }
+        nce_scan_tile(sS, q_local, half, qrow, q_valid, gtile, p.n, p.inv_t, m, s, p.diag);
         __syncthreads();          // the scan is done with sS before the next tile's operands are staged over it
     }
-    float* xs = sS;               // [128][2][2]
-    xs[(q_local * 2 + half) * 2] = m;
-    xs[(q_local * 2 + half) * 2 + 1] = s;
-    __syncthreads();
-    if (q_valid && half == 0) {
-        const float m0 = xs[q_local * 4], s0 = xs[q_local * 4 + 1], m1 = xs[q_local * 4 + 2], s1 = xs[q_local * 4 + 3];
-        const float mm = fmaxf(m0, m1);
-        float ss = 0.f;
-        if (m0 > -INFINITY) ss += s0 * __builtin_amdgcn_exp2f((m0 - mm) * NCE_LOG2E);
-        if (m1 > -INFINITY) ss += s1 * __builtin_amdgcn_exp2f((m1 - mm) * NCE_LOG2E);
-        float* dst = p.part + ((size_t)qrow * p.nchunks + chunk) * 2;
-        dst[0] = mm;
-        dst[1] = ss;
-    }
+    nce_store_part(sS, q_local, half, qrow, q_valid, m, s, p.nchunks, chunk, p.part);
 }
 
 // lse[row] = log sum over the chunks in chunk order; term[row] = lse - z_ii
@@ -454,29 +327,34 @@ static int nce_check(const char* fn, const void* a, const void* b, int n, int d,
     return KEMR_OK;
 }
 
-static int nce_build_panels(const float* a, const float* b, int n, int d, const NceLayout& L, char* ws, bool transposed, hipStream_t s) {
-    const long long total = (long long)L.n256 * (L.dpad / 2);
-    const unsigned grid = (unsigned)((total + 255) / 256);
-    hipLaunchKernelGGL(infonce_panel_kernel, dim3(grid), dim3(256), 0, s, a, n, d, L.dpad, (bf16_t*)(ws + L.off_pa), total);
-    hipLaunchKernelGGL(infonce_panel_kernel, dim3(grid), dim3(256), 0, s, b, n, d, L.dpad, (bf16_t*)(ws + L.off_pb), total);
+int nce_launch_panel(const float* src, int n, int d, int dpad, int n256, bf16_t* out, hipStream_t s) {
+    const long long total = (long long)n256 * (dpad / 2);
+    hipLaunchKernelGGL(infonce_panel_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, n, d, dpad, out, total);
     KEMR_CHECK_LAUNCH("infonce_panel_kernel");
+    return KEMR_OK;
+}
+
+int nce_launch_merge(const float* part, const float* diag, int n, int nchunks, float* lse, float* term, hipStream_t s) {
+    hipLaunchKernelGGL(infonce_merge_kernel, dim3((n + 255) / 256), dim3(256), 0, s, part, diag, n, nchunks, lse, term);
+    KEMR_CHECK_LAUNCH("infonce_merge_kernel");
+    return KEMR_OK;
+}
+
+int nce_launch_loss(const float* term, int n, float* loss, hipStream_t s) {
+    hipLaunchKernelGGL(infonce_loss_kernel, dim3(1), dim3(256), 0, s, term, n, loss);
+    KEMR_CHECK_LAUNCH("infonce_loss_kernel");
+    return KEMR_OK;
+}
+
+static int nce_build_panels(const float* a, const float* b, int n, int d, const NceLayout& L, char* ws, bool transposed, hipStream_t s) {
+    KEMR_TRY(nce_launch_panel(a, n, d, L.dpad, L.n256, (bf16_t*)(ws + L.off_pa), s));
+    KEMR_TRY(nce_launch_panel(b, n, d, L.dpad, L.n256, (bf16_t*)(ws + L.off_pb), s));
     if (transposed) {
         const long long tt = (long long)L.dpadT * (L.n256 / 2);
         const unsigned gt = (unsigned)((tt + 255) / 256);
         hipLaunchKernelGGL(infonce_panel_t_kernel, dim3(gt), dim3(256), 0, s, a, n, d, L.dpadT, L.n256, (bf16_t*)(ws + L.off_ta), tt);
         hipLaunchKernelGGL(infonce_panel_t_kernel, dim3(gt), dim3(256), 0, s, b, n, d, L.dpadT, L.n256, (bf16_t*)(ws + L.off_tb), tt);
         KEMR_CHECK_LAUNCH("infonce_panel_t_kernel");
-    }
-    return KEMR_OK;
-}
-
-template <typename K>
-static int nce_lds_attr(K kern, int bytes, int* attr_dev) {
-    int dev = 0;
-    KEMR_CHECK_HIP(hipGetDevice(&dev));
-    if (*attr_dev != dev) {
-        KEMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        *attr_dev = dev;
     }
     return KEMR_OK;
 }
@@ -524,12 +402,9 @@ extern "C" int kemr_infonce_forward(const float* a_dev, const float* b_dev, int 
         p.nchunks = L.nchunks; p.tiles_per_chunk = L.tpc; p.g_tiles = L.g_tiles;
         hipLaunchKernelGGL(infonce_stats_kernel, dim3(L.g_tiles * L.nchunks), dim3(256), NCE_A_BYTES, s, p);
         KEMR_CHECK_LAUNCH("infonce_stats_kernel");
-        hipLaunchKernelGGL(infonce_merge_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float*)p.part, (const float*)p.diag, n, L.nchunks,
-                           lse_dev + (size_t)pass * n, term + (size_t)pass * n);
-        KEMR_CHECK_LAUNCH("infonce_merge_kernel");
+        KEMR_TRY(nce_launch_merge(p.part, p.diag, n, L.nchunks, lse_dev + (size_t)pass * n, term + (size_t)pass * n, s));
     }
-    hipLaunchKernelGGL(infonce_loss_kernel, dim3(1), dim3(256), 0, s, (const float*)term, n, loss_dev);
-    KEMR_CHECK_LAUNCH("infonce_loss_kernel");
+    KEMR_TRY(nce_launch_loss(term, n, loss_dev, s));
     return KEMR_OK;
 }
 

@@ -1074,3 +1074,77 @@ def infonce_backward(a: torch.Tensor, b: torch.Tensor, lse: torch.Tensor, temper
                                                     C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(_stream_ptr(a.device))),
                    "infonce_backward")
     return ga, gb
+
+
+# ------------------------------------------------------------------------------------------------ fused pair-score contrastive loss (csrc/pairhead.hip)
+def _pairhead_args(mode: int, q: torch.Tensor, img: torch.Tensor, tgt: torch.Tensor, gate, linear, what: str):
+    """Checks of both pairhead calls; returns (n, d, hidden, the five head pointers as c_void_p)."""
+    for t, name in ((q, "q"), (img, "img"), (tgt, "tgt")):
+        _require_cuda(t, f"{what}: {name}")
+    if q.dim() != 2 or q.shape != img.shape or q.shape != tgt.shape or q.device != img.device or q.device != tgt.device:
+        raise RuntimeError(f"{what}: q, img, tgt must be three [n, d] tensors on one device, got {tuple(q.shape)}, {tuple(img.shape)}, "
+                           f"{tuple(tgt.shape)}")
+    heads = []
+    if mode == _lib.PAIRHEAD_GATED:
+        if gate is None or linear is not None:
+            raise RuntimeError(f"{what}: the gated mode takes gate= (fp32 [n]) and no linear=")
+        heads, shapes, hidden = [gate], [(q.shape[0],)], 0
+    elif mode == _lib.PAIRHEAD_LINEAR:
+        if linear is None or gate is not None or len(linear) != 4:
+            raise RuntimeError(f"{what}: the linear mode takes linear=(w0 [hidden, 2], b0 [hidden], w1 [hidden], b1 [1]) and no gate=")
+        heads, hidden = list(linear), int(linear[1].numel())
+        shapes = [(hidden, 2), (hidden,), (hidden,), (1,)]
+    else:
+        raise RuntimeError(f"{what}: mode={mode} is neither PAIRHEAD_GATED nor PAIRHEAD_LINEAR")
+    for t in [q, img, tgt] + heads:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"{what}: every tensor must be contiguous fp32")
+    for t, shape in zip(heads, shapes):
+        _require_cuda(t, f"{what}: head parameters")
+        if tuple(t.shape) != shape or t.device != q.device:
+            raise RuntimeError(f"{what}: a head tensor has shape {tuple(t.shape)}, expected {shape} on {q.device}")
+    ptr = [C.c_void_p(t.data_ptr()) for t in heads]
+    ptrs = ptr + [None] * 4 if mode == _lib.PAIRHEAD_GATED else [None] + ptr
+    return int(q.shape[0]), int(q.shape[1]), hidden, ptrs
+
+
+def pairhead_workspace_bytes(mode: int, n: int, d: int, hidden: int = 0) -> int:
+    need = int(_lib.lib().kemr_pairhead_workspace_bytes(mode, n, d, hidden))
+    if need == 0:
+        raise RuntimeError(f"pairhead: mode={mode} must be 0 (gated) or 1 (linear), n={n} in 1..65536, d={d} a multiple of 4 in 4..1280 "
+                           f"and, for the linear head, hidden={hidden} in 1..256")
+    return need
+
+
+def pairhead_forward(mode: int, q: torch.Tensor, img: torch.Tensor, tgt: torch.Tensor, temperature: float, gate=None, linear=None
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(losses fp32 [3] = loss, loss_q2g, loss_g2q; lse fp32 [2 n]) of the symmetric InfoNCE over S = head(q, img, tgt) / temperature
+    (``kemr_pairhead_forward``); S is never stored.  ``gate`` fp32 [n] (PAIRHEAD_GATED) or ``linear`` = (w0, b0, w1, b1) (PAIRHEAD_LINEAR)."""
+    n, d, hidden, hp = _pairhead_args(mode, q, img, tgt, gate, linear, "pairhead_forward")
+    ws = torch.empty(pairhead_workspace_bytes(mode, n, d, hidden), dtype=torch.uint8, device=q.device)
+    loss = torch.empty(3, dtype=torch.float32, device=q.device)
+    lse = torch.empty(2 * n, dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        _lib.check(_lib.lib().kemr_pairhead_forward(mode, C.c_void_p(q.data_ptr()), C.c_void_p(img.data_ptr()), C.c_void_p(tgt.data_ptr()), n, d,
+                                                    1.0 / float(temperature), *hp, hidden, C.c_void_p(loss.data_ptr()),
+                                                    C.c_void_p(lse.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                    C.c_void_p(_stream_ptr(q.device))), "pairhead_forward")
+    return loss, lse
+
+
+def pairhead_backward(mode: int, q: torch.Tensor, img: torch.Tensor, tgt: torch.Tensor, lse: torch.Tensor, temperature: float, gate=None,
+                      linear=None) -> torch.Tensor:
+    """The gradient of pairhead_forward's `loss` from the lse values it saved: fp32 [n] = dL/dgate (PAIRHEAD_GATED) or fp32
+    [4 hidden + 1] = dL/dw0 | dL/db0 | dL/dw1 | dL/db1 (PAIRHEAD_LINEAR)."""
+    n, d, hidden, hp = _pairhead_args(mode, q, img, tgt, gate, linear, "pairhead_backward")
+    _require_cuda(lse, "pairhead_backward: lse")
+    if lse.dtype != torch.float32 or lse.numel() != 2 * n or not lse.is_contiguous():
+        raise RuntimeError("pairhead_backward: lse must be the contiguous fp32 [2 n] tensor of pairhead_forward")
+    ws = torch.empty(pairhead_workspace_bytes(mode, n, d, hidden), dtype=torch.uint8, device=q.device)
+    grad = torch.empty(n if mode == _lib.PAIRHEAD_GATED else 4 * hidden + 1, dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        _lib.check(_lib.lib().kemr_pairhead_backward(mode, C.c_void_p(q.data_ptr()), C.c_void_p(img.data_ptr()), C.c_void_p(tgt.data_ptr()),
+                                                     C.c_void_p(lse.data_ptr()), n, d, 1.0 / float(temperature), *hp, hidden,
+                                                     C.c_void_p(grad.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                     C.c_void_p(_stream_ptr(q.device))), "pairhead_backward")
+    return grad
