@@ -16,7 +16,28 @@
  *    the hot path.  Scratch comes from the caller through a workspace sized by *_workspace_bytes().
  *    The library owns only the model handle and its packed weights (allocated in finalize).
  *  - all launches are asynchronous on the hipStream_t passed as `void* stream` (0 = default stream);
- *    no entry point synchronises the device except kemr_model_finalize().
+ *    no entry point waits for the device except the calls listed below under "calls that synchronise the host".
+ *    Stream contract (tests/stream_order.py, tests/test_stream_*_gpu.py):
+ *      - every kernel, memset and copy of a call is queued on the stream passed, in order, and on no other stream; the library
+ *        creates no stream of its own.  A call may therefore be queued before its inputs exist (behind the work that produces them
+ *        on that stream), and its arguments may be overwritten by work queued behind it.  Host arrays (the sizes and offsets of the
+ *        batch transforms, the pointer arrays of kemr_panel_build) are read before the call returns.
+ *      - the call returns without waiting for the device.  What a call copies host to device (the descriptor blob of the batch
+ *        transforms, the tap table of the single-image transforms) leaves from pinned staging slots of the library's own; a call
+ *        waits for a slot only with 64 such copies in flight.  A slot is chosen, filled and sent under one lock, so two
+ *        host threads are never handed the same slot.
+ *      - a finalized model handle is read-only during the encode calls: one handle may serve several streams at once when every
+ *        call in flight has a workspace of its own.  Two calls that share a workspace must be ordered by the caller (the Python
+ *        engines do this for their own workspace: engine.CallOrder).  kemr_model_set_option and the kemr_debug_set switches are
+ *        host state read when a call is made: change them between calls, not beside them.
+ *      - calls that synchronise the host, because their contract needs a host value or a quiet device: kemr_model_finalize
+ *        (waits for the device, then uploads the packed weights with a blocking copy), kemr_model_destroy (frees the weights: the
+ *        free waits for the device; no call that reads the handle may be pending anyway), kemr_profile_end (returns the measured
+ *        times), kemr_debug_sim_lists and kemr_debug_gemm_stamps (kemr_debug.h: return what finished calls left behind); one level
+ *        up, ClipEngine.encode_text with token ids on the device and no `lens` (one copy of B lengths to the host sizes the packed
+ *        launches).  No other entry point waits for the device.  The event profiler (kemr_profile_begin / _end) keeps one
+ *        process-wide record: profile one stream at a time.
+ *      - capturing calls into a HIP graph is not part of this contract and is not tested.
  *  - no HIP call happens at library load time (fork-safe for DataLoader workers,
  *    reference: src/clip/eval/evaluator_baseline.py:83-92).
  */

@@ -50,7 +50,9 @@ extern "C" {
  *                   kernel); [A/B] 0 = plain (rounds 1-3), 1 = deltas only, 2 = deltas + row loads
  *   "attn_waves"    also: [A/B] 7 = the vision attention kernel with plain K / V loads (rounds 1-3), 5 = Q rows non-temporal as well,
  *                   8 (with attn_v 0) = TIMING ONLY, wrong results: the ragged 17th query tile (one valid row) is not computed
- *   "ab_variants"   read-only: 1 = the library holds the [A/B] kernels */
+ *   "ab_variants"   read-only: 1 = the library holds the [A/B] kernels
+ *   "staging_slots" read-only: pinned staging slots the transforms' host-to-device copies leave from (8 to begin with, 64 at most)
+ *   "staging_grown" read-only: how often such a slot took a larger buffer and kept the one it had outgrown */
 int kemr_debug_set(const char* key, int value);
 int kemr_debug_get(const char* key, int* value);
 

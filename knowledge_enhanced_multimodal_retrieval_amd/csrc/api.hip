@@ -73,6 +73,8 @@ const DebugKnob* debug_knobs(int* n) {
         {"ln_nt", &g_ln_nt, 0, 3, 1u << 3},           // LayerNorm cache hints: 3 = deltas, residual rows and the x write-back non-temporal (the product kernel); 0 / 1 / 2 = earlier levels: A/B builds
         {"sim_lists", sim_lists_knob(), 0, 3, ~0u},   // 0 = never the candidate-list route, 1 = where it pays, 2 = wherever it fits + the fallback forced, 3 = wherever it fits
         {"ab_variants", &g_ab_variants, -1, -2, 0},   // read-only: 1 = this library was built with the A/B experiment kernels
+        {"staging_slots", &g_staging_slots, -1, -2, 0},   // read-only: pinned staging slots in the ring (preprocess.hip: 8 to begin with, 64 at most)
+        {"staging_grown", &g_staging_grown, -1, -2, 0},   // read-only: times a staging slot took a larger buffer and kept the outgrown one
     };
     *n = (int)(sizeof(knobs) / sizeof(knobs[0]));
     return knobs;

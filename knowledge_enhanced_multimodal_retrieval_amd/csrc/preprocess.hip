@@ -25,6 +25,8 @@
 
 namespace kemr {
 
+int g_staging_slots = 8, g_staging_grown = 0;     // kemr_debug_get "staging_slots" / "staging_grown" (staged_copy below)
+
 namespace {
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;
@@ -268,27 +270,59 @@ __global__ __launch_bounds__(256) void preprocess_v_batch_kernel(const PreImg* _
     out[2 * plane + gid] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)v2, 255.0f), m2), d2);
 }
 
-// Pinned staging for the per-batch descriptor blob: a ring of slots, each guarded by an event recorded after its copy; a slot
-// is reused only after that copy has finished (with 8 slots the wait only triggers when the host is 8 batches ahead).
-int staging_slot(size_t bytes, char** host, hipEvent_t* done) {
+// Pinned staging for what a call copies host to device (the batch calls' descriptor blob, the single-image calls' tap table): slots,
+// each guarded by an event recorded after its copy; a slot is reused only after that copy has finished.  The host never waits for
+// the device here while the ring may grow: the slot whose turn it is, else any slot whose copy has finished, else a new slot (the
+// caller is many calls ahead of the device, or its streams are held back); only with MAX_SLOTS slots in flight does it wait.
+// The slot is chosen, filled, sent and its event recorded under ONE lock: a second host thread can never be handed a slot whose
+// event does not guard its latest copy yet.
+// (tests/test_stream_order_gpu.py, tests/test_stream_concurrent_gpu.py: calls enqueued while their stream is held back.)
+struct StagedPiece { const void* src; size_t off, bytes; };          // `bytes` from src to offset `off` of the staged block
+
+int staged_copy(void* dst_dev, size_t bytes, const StagedPiece* pieces, int n_pieces, hipStream_t s) {
     struct Slot { char* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
+    constexpr size_t MAX_SLOTS = 64;
     static std::mutex mu;
-    static Slot ring[8];
-    static unsigned next = 0;
+    static std::vector<Slot> ring(8);
+    static size_t next = 0;
     std::lock_guard<std::mutex> lock(mu);
-    Slot& sl = ring[next++ % 8];
+    size_t pick = ring.size();
+    for (size_t i = 0; i < ring.size() && pick == ring.size(); ++i) {
+        const size_t j = (next + i) % ring.size();
+        if (ring[j].used) {
+            const hipError_t q = hipEventQuery(ring[j].ev);
+            if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }      // (not an error: nothing may stay behind for KEMR_CHECK_LAUNCH)
+            KEMR_CHECK_HIP(q);
+        }
+        pick = j;
+    }
+    if (pick == ring.size()) {
+        if (ring.size() < MAX_SLOTS) {
+            ring.emplace_back();
+        } else {
+            pick = next % ring.size();
+            KEMR_CHECK_HIP(hipEventSynchronize(ring[pick].ev));
+        }
+    }
+    next = pick + 1;
+    g_staging_slots = (int)ring.size();
+    Slot& sl = ring[pick];
     if (!sl.ev) KEMR_CHECK_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    if (sl.used) KEMR_CHECK_HIP(hipEventSynchronize(sl.ev));
     if (sl.cap < bytes) {
-        if (sl.host) KEMR_CHECK_HIP(hipHostFree(sl.host));
+        // hipHostFree waits for the device: never on this path.  An outgrown buffer is kept for the life of the process; a slot's
+        // capacity more than doubles whenever it grows, so what is kept stays below the slot's final size.
+        static std::vector<char*> outgrown;
+        if (sl.host) { outgrown.push_back(sl.host); ++g_staging_grown; }
         sl.host = nullptr; sl.cap = 0;
         const size_t cap = (size_t)round_up((int64_t)bytes * 2, 65536);
         KEMR_CHECK_HIP(hipHostMalloc((void**)&sl.host, cap, hipHostMallocDefault));
         sl.cap = cap;
     }
-    sl.used = true;
-    *host = sl.host;
-    *done = sl.ev;
+    for (int i = 0; i < n_pieces; ++i)
+        if (pieces[i].bytes) memcpy(sl.host + pieces[i].off, pieces[i].src, pieces[i].bytes);
+    KEMR_CHECK_HIP(hipMemcpyAsync(dst_dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+    sl.used = true;                              // from here on the buffer is the device's until sl.ev says otherwise
+    KEMR_CHECK_HIP(hipEventRecord(sl.ev, s));
     return KEMR_OK;
 }
 
@@ -369,13 +403,8 @@ extern "C" int kemr_transform_u8_batch(int transform, const unsigned char* packe
     // descriptors + tables cross in ONE copy out of a pinned slot: a pageable source would make the "async" copy wait for
     // the stream, i.e. for the encoders queued before it, and stall the loader thread behind the GPU
     const size_t blob = L.tab_off + L.tables.size() * 4;
-    char* host = nullptr;
-    hipEvent_t done = nullptr;
-    KEMR_TRY(staging_slot(blob, &host, &done));
-    memcpy(host, L.desc.data(), L.desc.size() * sizeof(PreImg));
-    if (!L.tables.empty()) memcpy(host + L.tab_off, L.tables.data(), L.tables.size() * 4);
-    KEMR_CHECK_HIP(hipMemcpyAsync(ws, host, blob, hipMemcpyHostToDevice, s));
-    KEMR_CHECK_HIP(hipEventRecord(done, s));
+    const StagedPiece pieces[2] = {{L.desc.data(), 0, L.desc.size() * sizeof(PreImg)}, {L.tables.data(), L.tab_off, L.tables.size() * 4}};
+    KEMR_TRY(staged_copy(ws, blob, pieces, 2, s));
     const int n = n_px;
     const Norm& c = NORMS[transform];
     ProfScope prof(PROF_OTHER, s);
@@ -411,7 +440,10 @@ extern "C" int kemr_transform_u8(int transform, const unsigned char* img_dev, in
     const int n = n_px;
     int32_t* tab = (int32_t*)workspace_dev;
     uint8_t* temp = (uint8_t*)workspace_dev + p.temp_off;
-    if (!p.table.empty()) KEMR_CHECK_HIP(hipMemcpyAsync(tab, p.table.data(), p.table.size() * 4, hipMemcpyHostToDevice, s));
+    if (!p.table.empty()) {                      // out of a pinned slot, as the batch call's blob: whether a copy from pageable memory waits for the stream is the runtime's choice
+        const StagedPiece piece = {p.table.data(), 0, p.table.size() * 4};
+        KEMR_TRY(staged_copy(tab, piece.bytes, &piece, 1, s));
+    }
     const int row_lo = p.vy.in_lo, rows = p.vy.in_hi - p.vy.in_lo;
     const Norm& c = NORMS[transform];
     ProfScope prof(PROF_OTHER, s);

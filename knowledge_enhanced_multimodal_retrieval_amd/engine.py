@@ -5,6 +5,7 @@ PyTorch is plumbing here (device memory, streams): every tensor that crosses int
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Dict, Mapping, Optional, Sequence, Tuple
@@ -61,6 +62,63 @@ def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+class CallOrder:
+    """Orders the calls of ONE object that keeps a workspace across calls (ClipEngine, BertEngine, the GPU preprocessors).  The library
+    orders a call on the stream it is given and nowhere else (include/kemr.h "Stream contract"), so two calls of one object made under
+    two ``torch.cuda.stream(...)`` contexts would share the scratch buffer with nothing between them.  ``begin`` makes the current
+    stream wait for the object's previous call when that call was queued on another stream (one event wait on the device, only then);
+    ``end`` records the event the next call may have to wait for.  ``retire`` keeps a workspace that a larger one replaced referenced
+    until the call that replaced it has finished: freed earlier, the caching allocator could hand the block out while a call queued on
+    another stream than the block's own is still pending.  Nothing here synchronises the host.  A call made while its stream is being
+    captured into a graph takes no part (an event recorded inside a capture cannot be waited for outside it; capture is not part of
+    the stream contract)."""
+
+    def __init__(self):
+        self._event: Optional[torch.cuda.Event] = None
+        self._stream = None
+        self._capturing = False
+        self._old: list = []             # workspaces replaced during the current call
+        self._retired: list = []         # (event recorded behind the call that replaced them, those workspaces)
+
+    def begin(self, device: torch.device):
+        cur = torch.cuda.current_stream(device)
+        self._capturing = torch.cuda.is_current_stream_capturing()
+        if self._capturing:
+            return cur
+        if self._event is not None and cur != self._stream:
+            cur.wait_event(self._event)
+        if self._retired:
+            self._retired = [r for r in self._retired if not r[0].query()]
+        return cur
+
+    def retire(self, ws: Optional[torch.Tensor]) -> None:
+        if ws is not None:
+            self._old.append(ws)
+
+    def end(self, cur) -> None:
+        if self._capturing:
+            return
+        if self._event is None:
+            self._event = torch.cuda.Event()
+        self._event.record(cur)
+        self._stream = cur
+        if self._old:
+            done = torch.cuda.Event()
+            done.record(cur)
+            self._retired.append((done, self._old))
+            self._old = []
+
+    @contextlib.contextmanager
+    def call(self, device: torch.device):
+        """``with order.call(device) as stream:`` -- begin, the launches, end.  ``end`` runs as well when a launch raises in the
+        middle of a call: what is queued by then is ordered for the next call, and workspaces retired by then wait for it."""
+        cur = self.begin(device)
+        try:
+            yield cur
+        finally:
+            self.end(cur)
+
+
 def _require_cuda(t: torch.Tensor, what: str) -> None:
     if not t.is_cuda:
         raise RuntimeError(f"{what} must live on the GPU (got device {t.device}); this path has no CPU fallback")
@@ -103,6 +161,7 @@ class ClipEngine:
         if activation != self.activation:                # (family "siglip": its tanh GELU is the family's, the option is not consulted)
             self.set_activation(activation)
         self._ws: Dict[object, torch.Tensor] = {}
+        self._order = CallOrder()                        # the workspaces are reused: calls made under different streams are ordered
         self._state: Optional[Mapping[str, torch.Tensor]] = None
         self.ready = False
         self.pack_text = os.environ.get("KEMR_TEXT_PACKED", "1") != "0"     # encode_text: only the positions up to the end-of-text token
@@ -180,6 +239,7 @@ class ClipEngine:
         need = int(self._L.kemr_workspace_bytes(self._h, tower, batch))
         ws = self._ws.get(tower)
         if ws is None or ws.numel() < need:
+            self._order.retire(ws)
             ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._ws[tower] = ws
         return ws
@@ -192,8 +252,8 @@ class ClipEngine:
         out = torch.empty((n, pooled_width or self.arch.embed_dim), dtype=torch.float32, device=self.device)
         if n == 0:
             return out
-        with torch.cuda.device(self.device):
-            stream = _stream_ptr(self.device)
+        with torch.cuda.device(self.device), self._order.call(self.device) as cur:
+            stream = cur.cuda_stream
             ws = self._workspace(tower, min(n, max_batch))
             for s in range(0, n, max_batch):
                 xb = x[s:s + max_batch]
@@ -280,8 +340,8 @@ class ClipEngine:
         lens_dev = lens.to(self.device, non_blocking=True)
         # calls of at most TEXT_ROW_BUDGET token rows (256 row tiles of the persistent GEMM: whole rounds, engine.tile_friendly_batch)
         csum = torch.cumsum(lens.to(torch.int64), 0).tolist()
-        with torch.cuda.device(self.device):
-            stream = _stream_ptr(self.device)
+        with torch.cuda.device(self.device), self._order.call(self.device) as cur:
+            stream = cur.cuda_stream
             s0, base = 0, 0
             while s0 < n:
                 s1 = s0 + 1
@@ -291,6 +351,7 @@ class ClipEngine:
                 need = int(self._L.kemr_text_packed_workspace_bytes(self._h, rows, s1 - s0))
                 ws = self._ws.get("text_packed")
                 if ws is None or ws.numel() < need:
+                    self._order.retire(ws)
                     ws = self._ws["text_packed"] = torch.empty(max(need, int(self._L.kemr_text_packed_workspace_bytes(
                         self._h, min(TEXT_ROW_BUDGET, n * a.ctx), min(n, 65528)))), dtype=torch.uint8, device=self.device)
                 head = (self._h, C.c_void_p(ids[s0:].data_ptr()), C.c_void_p(lens_dev[s0:].data_ptr()), rows, s1 - s0, C.c_void_p(out[s0:].data_ptr()))
@@ -326,6 +387,7 @@ class BertEngine:
         from .config import BERT_POOLING
         _lib.check(self._L.kemr_model_set_option(self._h, b"pooling", BERT_POOLING[arch.pooling]), "model_set_option")
         self._ws: Optional[torch.Tensor] = None
+        self._order = CallOrder()
         self.ready = False
 
     __del__ = ClipEngine.__del__
@@ -367,8 +429,8 @@ class BertEngine:
             return out
         lens_dev = lens.to(self.device, non_blocking=True)
         csum = torch.cumsum(lens.to(torch.int64), 0).tolist()
-        with torch.cuda.device(self.device):
-            stream = _stream_ptr(self.device)
+        with torch.cuda.device(self.device), self._order.call(self.device) as cur:
+            stream = cur.cuda_stream
             s0, base = 0, 0
             while s0 < n:
                 s1 = s0 + 1
@@ -377,6 +439,7 @@ class BertEngine:
                 rows = csum[s1 - 1] - base
                 need = int(self._L.kemr_text_packed_workspace_bytes(self._h, rows, s1 - s0))
                 if self._ws is None or self._ws.numel() < need:
+                    self._order.retire(self._ws)
                     self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
                 _lib.check(self._L.kemr_encode_text_packed(self._h, C.c_void_p(ids[s0:].data_ptr()), C.c_void_p(lens_dev[s0:].data_ptr()),
                                                            rows, s1 - s0, C.c_void_p(out[s0:].data_ptr()), 1 if normalize else 0,

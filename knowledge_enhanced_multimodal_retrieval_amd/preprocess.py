@@ -84,6 +84,7 @@ class ClipPreprocessGPU:
         if self.device.type != "cuda":
             raise RuntimeError(f"{type(self).__name__} needs a GPU device")
         self._ws = None
+        self._order = None                 # engine.CallOrder: the workspace is reused, calls under different streams are ordered
 
     def _on_host(self, h: int, w: int) -> bool:
         """True for an image the library refuses and the host transform computes instead (none for CLIP's transform)."""
@@ -94,7 +95,7 @@ class ClipPreprocessGPU:
 
     def __call__(self, image) -> torch.Tensor:
         import ctypes as C
-        from . import _lib, engine
+        from . import _lib
         if not torch.is_tensor(image):
             image = torch.from_numpy(np.asarray(image.convert("RGB"), dtype=np.uint8).copy())
         if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
@@ -109,14 +110,22 @@ class ClipPreprocessGPU:
         need = int(L.kemr_transform_workspace_bytes(self.kind, h, w, self.n_px))
         if need == 0:
             raise RuntimeError(f"{type(self).__name__}: unsupported size {h} x {w} -> {self.n_px}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         out = torch.empty((3, self.n_px, self.n_px), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device), self._call() as cur:
+            if self._ws is None or self._ws.numel() < need:
+                self._order.retire(self._ws)
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             _lib.check(L.kemr_transform_u8(self.kind, C.c_void_p(img.data_ptr()), h, w, self.n_px, C.c_void_p(out.data_ptr()),
-                                           C.c_void_p(self._ws.data_ptr()), self._ws.numel(),
-                                           C.c_void_p(engine._stream_ptr(self.device))), "transform_u8")
+                                           C.c_void_p(self._ws.data_ptr()), self._ws.numel(), C.c_void_p(cur.cuda_stream)), "transform_u8")
         return out
+
+    def _call(self):
+        """``with self._call() as stream``: the current stream, made to wait for this object's previous call if that ran on another
+        stream, and the call recorded for the next one even when it raises (engine.CallOrder.call)."""
+        from . import engine
+        if self._order is None:
+            self._order = engine.CallOrder()
+        return self._order.call(self.device)
 
     def batch(self, packed: "PackedRaw") -> torch.Tensor:
         """A whole loader batch in one launch pair (``kemr_transform_u8_batch``): ``packed`` holds the uint8 images back
@@ -124,7 +133,7 @@ class ClipPreprocessGPU:
         as the DataLoader's pin thread leaves it).  Returns float32 ``[B, 3, n_px, n_px]``, each image bit-identical to
         ``self(image)`` and to the host transform."""
         import ctypes as C
-        from . import _lib, engine
+        from . import _lib
         b = len(packed)
         out = torch.empty((b, 3, self.n_px, self.n_px), dtype=torch.float32, device=self.device)
         if b == 0:
@@ -144,15 +153,16 @@ class ClipPreprocessGPU:
         need = int(L.kemr_transform_batch_workspace_bytes(self.kind, C.c_void_p(hs.ctypes.data), C.c_void_p(ws.ctypes.data), b, self.n_px))
         if need == 0:
             raise RuntimeError(f"{type(self).__name__}.batch: unsupported image size in the batch -> {self.n_px}")
-        if self._ws is None or self._ws.numel() < need:
-            # grow-only, stream-ordered reuse: every user of the old buffer was queued on the same stream before this point
-            self._ws = torch.empty(max(need, 2 * (0 if self._ws is None else self._ws.numel())), dtype=torch.uint8, device=self.device)
         data = packed.data if packed.data.device == self.device else packed.data.to(self.device, non_blocking=True)
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device), self._call() as cur:
+            if self._ws is None or self._ws.numel() < need:
+                # grow-only reuse: the old buffer stays referenced until this call, which is ordered behind every user of it, has finished
+                self._order.retire(self._ws)
+                self._ws = torch.empty(max(need, 2 * (0 if self._ws is None else self._ws.numel())), dtype=torch.uint8, device=self.device)
             _lib.check(L.kemr_transform_u8_batch(self.kind, C.c_void_p(data.data_ptr()), C.c_void_p(offs.ctypes.data),
                                                  C.c_void_p(hs.ctypes.data), C.c_void_p(ws.ctypes.data), b, self.n_px,
                                                  C.c_void_p(out.data_ptr()), C.c_void_p(self._ws.data_ptr()), self._ws.numel(),
-                                                 C.c_void_p(engine._stream_ptr(self.device))), "transform_u8_batch")
+                                                 C.c_void_p(cur.cuda_stream)), "transform_u8_batch")
         data.record_stream(torch.cuda.current_stream(self.device))
         for i, px in zip(on_host, host_px):
             out[i].copy_(px)

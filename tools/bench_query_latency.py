@@ -38,8 +38,9 @@ for terms, label in ((1, "bf16"), (3, "fp32x3")):
         te += e0.elapsed_time(e1); ts += e1.elapsed_time(e2)
     print(label, "wall per query %.3f ms; gpu: text tower %.3f ms, panel+sim+top10 %.3f ms" % (wall, te / 50, ts / 50), flush=True)
 
-# ---- the same query path captured once into a HIP graph (torch.cuda.CUDAGraph) and replayed: the path is capture-safe
-# (no allocation, no synchronisation inside the library), but at B = 1 the ~90 kernels are GPU-bound, so nothing is gained
+# ---- the same query path captured once into a HIP graph (torch.cuda.CUDAGraph) and replayed -- an experiment: the library allocates
+# nothing and synchronises nothing on this path, but graph capture is not part of its stream contract and no test covers it
+# (DESIGN.md "Stream contract").  At B = 1 the ~90 kernels are GPU-bound, so nothing is gained
 terms = 1
 panel = engine.build_panel([img, tgt], _lib.SIDE_GALLERY, terms)
 static_ids = clip_ref.synthetic_ids(clip_ref.ARCHS["ViT-L/14"], 1).to(dev)
