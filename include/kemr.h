@@ -70,7 +70,10 @@ extern "C" {
  *    keep their signatures and bits (they are the new ones at KEMR_TRANSFORM_CLIP).
  *    Still 4: kemr_model_create_family, model family 2 (BERT sentence encoders) behind it, KEMR_MAX_BERT_CTX and option "pooling" are
  *    additions; kemr_model_create, option "family" (0 / 1) and every existing entry point keep their behaviour and messages -- what
- *    they refuse for a family-2 model, no existing caller could reach.  kemr_cfg did not grow. */
+ *    they refuse for a family-2 model, no existing caller could reach.  kemr_cfg did not grow.
+ *    Still 4: model family 3 (MPNet sentence encoders: a family-2 model under option "family" = 3, with a relative position bias in
+ *    every attention score) and option "layer_norm_eps" (family 3 only) are additions; kemr_model_create_family keeps refusing 3; families 0 - 2 keep their tensors, arithmetic and
+ *    messages, and no entry point changed. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -137,8 +140,8 @@ typedef enum kemr_tower { KEMR_TOWER_VISION = 0, KEMR_TOWER_TEXT = 1 } kemr_towe
  * whole-sequence-in-LDS kernel. */
 #define KEMR_MAX_VISION_TOKENS 1025
 #define KEMR_MAX_TEXT_CTX 288
-/* family 2 (BERT sentence encoders): the longest text, absolute positions 0 .. 511 (non-causal attention over packed items of
- * different lengths, csrc/attention_varlen.hip) */
+/* families 2 and 3 (BERT and MPNet sentence encoders): the longest text, absolute positions 0 .. 511 (non-causal attention over packed
+ * items of different lengths, csrc/attention_varlen.hip; family 3's relative position bias spans the distances -511 .. 511) */
 #define KEMR_MAX_BERT_CTX 512
 
 /* Architecture numbers of an OpenAI-CLIP style model (MLP is 4*width; heads are width/64, except a vision tower under option
@@ -197,7 +200,26 @@ int kemr_model_create(const kemr_cfg* cfg, kemr_model** out);
  *   kemr_model_set_option("family", 2) is refused with a message naming this entry point.  A length that cuts a text short encodes the
  *   shorter text.  Workspace: kemr_text_packed_workspace_bytes (16, 17 or 18 bytes per allocated row and width element -- bf16, 24-bit or fp32
  *   stream -- + the row starts; no pooled-row area), the
- *   memory contract of the encoders below. */
+ *   memory contract of the encoders below.
+ * Family 3 = an MPNet sentence encoder, reached from a family-2 model: kemr_model_create_family(cfg, 2, &m), then
+ * kemr_model_set_option(m, "family", 3) before the first kemr_model_load_tensor (2 <-> 3 share the configuration checks and differ in the
+ * tensor list, as 0 <-> 1 do behind kemr_model_create; passing 3 to kemr_model_create_family itself is refused, as it always was, with a
+ * message naming the option) -- transformers.MPNetModel without its pooler, then mean or CLS pooling:
+ * sentence-transformers/all-mpnet-base-v2 {768,0,0,0,0,768,12,30527,512} (the third sentence encoder of the reference's text-to-text
+ * baselines).  Everything said of family 2 holds -- the configuration checks, the packed call as the only encode call, the post-LN
+ * blocks with the exact GELU, pooling, workspace, and every refusal with family 2's wording (the fp8 precisions, KEMR_PREC_FP32X3,
+ * kemr_encode_text, kemr_encode_image, options "family" and "vision_head_dim") -- with these differences:
+ *   Tensors: no token_type_embedding (MPNet has no token types; positional_embedding [ctx, W] is taken verbatim -- position j of a text
+ *   reads row j, so the caller passes rows 2 .. 2 + ctx - 1 of MPNet's position_embeddings, whose position ids start at padding_idx + 1
+ *   = 2); in addition relative_attention_bias [32, W / 64] (encoder.relative_attention_bias.weight: ONE table for all layers); the
+ *   blocks' names are family 2's (attn.q | k | v stacked into in_proj, attn.o = out_proj, attention.LayerNorm = ln_1).
+ *   Scores: q . k^T / 8 + bias[h][bucket(key - query)] before the softmax, in every layer.  bucket = MPNetEncoder's
+ *   relative_position_bucket at 32 buckets and max distance 128, by integer thresholds: with n = query - key, 16 is added when n < 0;
+ *   |n| < 8 is bucket |n|; buckets 8 .. 15 begin at |n| = 8, 12, 16, 23, 32, 46, 64, 91.  Finalize expands the 32 buckets once into a
+ *   device table by distance, fp32 [heads, 1023], that the attention kernel stages per head into LDS and reads as the start value of its
+ *   score accumulators (fp32, unscaled, no rounding of the bias; csrc/attention_varlen.hip).
+ *   LayerNorm eps: option "layer_norm_eps" below, 1e-5 by default.
+ *   A text's token j sits at position j: what MPNetModel computes whenever no <pad> id occurs inside a text's length. */
 int kemr_model_create_family(const kemr_cfg* cfg, int family, kemr_model** out);
 int kemr_model_load_tensor(kemr_model* m, const char* name, const void* host_ptr, int dtype /*kemr_dtype, F32 only*/,
                            const int64_t* shape, int rank);
@@ -248,8 +270,13 @@ int kemr_model_destroy(kemr_model* m);
  *                      key and the pooled row is the last one, so no row can be left out).  The family's pixels are those of its own
  *                      image transform (squash to S x S, mean = std = 0.5): KEMR_TRANSFORM_SIGLIP of kemr_transform_u8 /
  *                      kemr_transform_u8_batch below computes them on the device; the option itself does not touch the input side.
- *                      2 (BERT) is refused here: kemr_model_create_family.
- *   "pooling"          (family 2 only; any time) 0 = mean over the item's rows (default), 1 = the item's first row (CLS). */
+ *                      For a kemr_model_create model 2 (BERT) and 3 (MPNet) are refused here: kemr_model_create_family.  For a model
+ *                      created as family 2: 2 (BERT) or 3 (MPNet: see kemr_model_create_family), likewise before the first load; 0 and 1
+ *                      are refused.
+ *   "pooling"          (families 2 and 3 only; any time) 0 = mean over the item's rows (default), 1 = the item's first row (CLS).
+ *   "layer_norm_eps"   (family 3 only; set BEFORE kemr_model_finalize) the epsilon of every LayerNorm as its negative decimal exponent:
+ *                      5 = 1e-5 (default: what the published all-mpnet-base-v2 config holds), 12 = 1e-12 (MPNetConfig's own default).
+ *                      Any other value is refused, and so is the key for families 0 - 2 (set and get). */
 int kemr_model_set_option(kemr_model* m, const char* key, int value);
 int kemr_model_get_option(const kemr_model* m, const char* key, int* value);
 /* number of required tensor names; name i via kemr_model_tensor_name (for strict-load diagnostics) */

@@ -127,6 +127,11 @@ int kemr_debug_map_head(struct kemr_model* m, const void* h_dev, int batch, void
  *   stream rows (the model's storage type), h_out = their bf16 copies, row_start_out = the batch + 1 row starts. */
 int kemr_debug_op_attention_varlen(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width,
                                    void* stream);
+/* attention_varlen_bias (model family 3, MPNet; tests/test_mpnet_ops_gpu.py): the same launch with a learned relative position bias,
+ *   scores = q . k^T + bias_by_distance[h][(key - query) + 511]; bias_by_distance_dev fp32 [width / 64, 1023], read-only.  The same
+ *   rows are written and the same refusals hold; a null table is refused here (kemr_debug_op_attention_varlen is the launch without). */
+int kemr_debug_op_attention_varlen_bias(const void* qkv_dev, void* out_dev, const int* row_start_dev, const float* bias_by_distance_dev,
+                                        int batch, int max_t, int width, void* stream);
 int kemr_debug_op_layernorm_post(void* x_dev, int x_dtype, const void* delta_dev, const float* gamma_dev, const float* beta_dev,
                                  void* h_dev, int rows, int width, float eps, void* stream);
 int kemr_debug_op_pool_rows(const void* x_dev, int x_dtype, const int* row_start_dev, int batch, int width, int pooling, int normalize,

@@ -46,6 +46,8 @@ EPI_BIAS_TGELU_BF16 = 8     # tanh GELU ("gelu_pytorch_tanh": the SigLIP family'
 # model option "activation" (include/kemr.h): the MLP's activation, by the name Hugging Face configs give it (`hidden_act`)
 ACTIVATIONS = {"quick_gelu": 0, "gelu": 1}
 FAMILY_BERT = 2             # kemr_model_create_family: a BERT sentence encoder (text-only)
+FAMILY_MPNET = 3            # option "family" of a FAMILY_BERT model: MPNet's relative position bias in every attention score, no token types
+MPNET_DISTANCES = 2 * 512 - 1   # columns of the bias table by distance: key - query in -511 .. 511
 MAX_BERT_CTX = 512          # KEMR_MAX_BERT_CTX
 PAIRHEAD_GATED, PAIRHEAD_LINEAR = 0, 1      # KEMR_PAIRHEAD_*: the mode of kemr_pairhead_forward / _backward
 MAX_DEEP_K = 1024           # KEMR_MAX_DEEP_K: longest list of kemr_select_topk / kemr_sim_topk_deep / kemr_sim_topk_deep_fused / kemr_cross_attention_rerank / kemr_list_fuse
@@ -140,6 +142,7 @@ DEBUG_SIGNATURES = {
     "kemr_debug_text_tokens": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "kemr_debug_map_head": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "kemr_debug_op_attention_varlen": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "kemr_debug_op_attention_varlen_bias": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "kemr_debug_op_layernorm_post": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "kemr_debug_op_pool_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "kemr_debug_bert_front": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

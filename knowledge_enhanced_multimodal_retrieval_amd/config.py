@@ -99,7 +99,12 @@ class ClipArch:
 class BertArch:
     """A BERT sentence encoder (model family 2 of the library, `kemr_model_create_family`): ``transformers.BertModel`` without its
     pooler, then mean or CLS pooling.  Text-only: heads of 64, a 4 x MLP, exact GELU, LayerNorm eps 1e-12, absolute positions.
-    intfloat/e5-base-v2 = BertArch(768, 12), thenlper/gte-large = BertArch(1024, 24)."""
+    intfloat/e5-base-v2 = BertArch(768, 12), thenlper/gte-large = BertArch(1024, 24).
+
+    ``relative_bias=True`` says "MPNet" (model family 3, ``transformers.MPNetModel``): the same blocks with a learned relative position
+    bias added to every attention score (one [32, heads] table for all layers), no token types, and ``layer_norm_eps`` 1e-5 (the
+    published all-mpnet-base-v2) or 1e-12 (MPNetConfig's default).  sentence-transformers/all-mpnet-base-v2 =
+    BertArch(768, 12, vocab=30527, relative_bias=True, layer_norm_eps=1e-5)."""
     width: int
     layers: int
     vocab: int = 30522
@@ -107,8 +112,14 @@ class BertArch:
     pooling: str = "mean"         # "mean" (masked mean pooling) or "cls"
     positions: int = 0            # rows of the checkpoint's positional table when it has more than ctx (0 = ctx)
     family: str = "bert"
+    relative_bias: bool = False   # MPNet's relative position bias in every attention score (model family 3)
+    layer_norm_eps: float = 1e-12
 
     def __post_init__(self):
+        if not self.relative_bias and self.layer_norm_eps != 1e-12:
+            raise ValueError(f"BertArch: layer_norm_eps {self.layer_norm_eps!r}; BERT encoders are served with 1e-12 only")
+        if self.relative_bias and self.layer_norm_eps not in MPNET_EPS:
+            raise ValueError(f"BertArch: layer_norm_eps {self.layer_norm_eps!r}; MPNet encoders are served with {sorted(MPNET_EPS)} only")
         if self.width not in (256, 512, 768, 1024, 1280):
             raise ValueError(f"BertArch: width {self.width}; served: 256, 512, 768, 1024, 1280 (heads of 64, multiples of 256)")
         if not 1 <= self.ctx <= 512:
@@ -124,8 +135,13 @@ class BertArch:
     def heads(self) -> int:
         return self.width // 64
 
+    @property
+    def library_family(self) -> int:
+        """The library's family number: 2 (BERT, `kemr_model_create_family`) or 3 (MPNet: a family-2 model with option "family" = 3)."""
+        return 3 if self.relative_bias else 2
+
     def cfg_dict(self) -> Dict[str, int]:
-        """The nine numbers of kemr_cfg for family 2: the vision fields are 0, embed_dim is the width."""
+        """The nine numbers of kemr_cfg for families 2 and 3: the vision fields are 0, embed_dim is the width."""
         return dict(embed_dim=self.width, image_size=0, patch=0, v_width=0, v_layers=0, t_width=self.width, t_layers=self.layers,
                     vocab=self.vocab, ctx=self.ctx)
 
@@ -136,9 +152,11 @@ class BertArch:
 
 
 BERT_POOLING = {"mean": 0, "cls": 1}     # model option "pooling" (include/kemr.h)
+MPNET_EPS = {1e-5: 5, 1e-12: 12}         # model option "layer_norm_eps" (family 3): the exponent
 BERT_ARCHS: Dict[str, BertArch] = {
     "e5-base-v2": BertArch(768, 12),
     "gte-large": BertArch(1024, 24),
+    "all-mpnet-base-v2": BertArch(768, 12, vocab=30527, relative_bias=True, layer_norm_eps=1e-5),
     "tiny-bert": BertArch(256, 2, vocab=1024),       # the test fixture
 }
 

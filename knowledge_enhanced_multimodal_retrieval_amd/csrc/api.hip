@@ -163,6 +163,13 @@ extern "C" int kemr_debug_op_attention_varlen(const void* qkv_dev, void* out_dev
     return launch_attention_varlen((const bf16_t*)qkv_dev, (bf16_t*)out_dev, row_start_dev, batch, max_t, width, (hipStream_t)stream);
 }
 
+// family 3 (MPNet): the same launch with the [width / 64, 1023] table of biases by distance
+extern "C" int kemr_debug_op_attention_varlen_bias(const void* qkv_dev, void* out_dev, const int* row_start_dev, const float* bias_by_distance_dev,
+                                                   int batch, int max_t, int width, void* stream) {
+    if (!qkv_dev || !out_dev || !row_start_dev || !bias_by_distance_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_attention_varlen_bias: null argument");
+    return launch_attention_varlen((const bf16_t*)qkv_dev, (bf16_t*)out_dev, row_start_dev, batch, max_t, width, (hipStream_t)stream, bias_by_distance_dev);
+}
+
 extern "C" int kemr_debug_op_layernorm_post(void* x_dev, int x_dtype, const void* delta_dev, const float* gamma_dev, const float* beta_dev,
                                             void* h_dev, int rows, int width, float eps, void* stream) {
     if (!x_dev || !delta_dev || !gamma_dev || !beta_dev || !h_dev) KEMR_FAIL(KEMR_ERR_INVALID, "debug_op_layernorm_post: null argument");

@@ -19,6 +19,16 @@
 // item b (not as a key, not as a query); pad keys of the last chunk are zero-filled in LDS and masked to -inf; exactly the item's rows
 // of `out` are written.  Lengths beyond max_t are clamped to it (the rows behind are then left unwritten; the encoder's row_start comes
 // from row_starts_kernel, which clamps the lengths to ctx itself).
+//
+// BIAS (model family 3, MPNet): scores = q . k^T + bias[h][key - query], a learned relative position bias.  The instantiation takes a
+// device table bias_by_distance fp32 [heads, VA_ND = 1023], entry [h][d + 511] for d = key - query in -511 .. 511 (model.hip expands
+// the checkpoint's 32 buckets once at finalize).  The head's 4 KB row is staged into LDS behind the two chunk images before the first
+// barrier; lane (lrow, lq) of S^T tile (i, t) holds the keys k0 + 16 t + 4 lq + r, r = 0..3, of ONE query, so its four biases are four
+// consecutive entries, read as the START VALUE of the tile's first MFMA accumulator instead of zero (no add instruction; q carries the
+// 1/8, the bias enters unscaled).  Clamped query rows index with their clamped position and pad keys reach at most key 511, so every
+// index stays in 0 .. 1022; the pad-key mask to -inf comes after, as before.  The table is read-only and per head: the fixed order of
+// every sum, the isolation of an item and the memory contract above hold unchanged.  The instantiation without BIAS is the kernel as it
+// was: every bias statement is under `if constexpr`.
 #include "common.h"
 
 namespace kemr {
@@ -42,6 +52,9 @@ constexpr int VA_NT16 = VA_KC / 16;       // 16-key S^T tiles per chunk
 constexpr int VA_NU = VA_KC / 32;         // 32-key PV blocks per chunk
 constexpr int VA_STAGE = VA_KC * 128 * 2; // bytes of one K + V chunk image
 constexpr int VA_NCH = VA_KC * 8 / (VA_NW * 64);   // 16-byte pieces of K (and of V) per thread and chunk
+constexpr int VA_ND = 2 * KEMR_MAX_BERT_CTX - 1;   // distances key - query of the bias table: -511 .. 511
+constexpr int VA_NDP = 2 * KEMR_MAX_BERT_CTX;      // floats of its LDS image
+static_assert(VA_NDP <= VA_NW * 64 * 4, "the bias row is staged in one pass of four floats per thread");
 
 __device__ __forceinline__ bf16x4 lds_read_tr16_v(const char* p) {
     typedef __attribute__((ext_vector_type(4))) short s4;
@@ -53,10 +66,12 @@ __device__ __forceinline__ bf16x4 lds_read_tr16_v(const char* p) {
 // Work items (query block fastest, then head, then item) are numbered so that the workgroups dealt to one XCD (the dispatcher
 // deals linear ids round-robin over the eight XCDs) take a contiguous range: the query blocks of one (item, head) read the same
 // K / V rows through the same L2.  Only a locality heuristic; every work item is computed exactly once whatever the placement.
+template <bool BIAS>
 __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_varlen_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                                       const int* __restrict__ row_start, int max_t, int width, int nqb, int items) {
+                                                                       const int* __restrict__ row_start, int max_t, int width, int nqb, int items,
+                                                                       const float* __restrict__ bias_by_distance) {
     constexpr float LOG2E = 1.4426950408889634f;
-    __shared__ __attribute__((aligned(16))) char smem[2 * VA_STAGE];
+    __shared__ __attribute__((aligned(16))) char smem[2 * VA_STAGE + (BIAS ? VA_NDP * 4 : 0)];
 
     const int heads = width >> 6;
     const int per_xcd = (int)(gridDim.x >> 3);
@@ -80,11 +95,13 @@ __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_va
     // query fragments of the wave's two tiles (B operand of S^T = K . Q^T): rows clamped to the last valid one
     bf16x8 qf[VA_QT][2];
     bool live[VA_QT];                                  // wave-uniform: the tile holds at least one query of the item
+    int boff[VA_QT];                                   // BIAS: the table index of the lane's query against key 4 lq
 #pragma unroll
     for (int i = 0; i < VA_QT; ++i) {
         live[i] = qb * VA_QB + i * (VA_NW * 16) + wid * 16 < T;
         const int q = qb * VA_QB + i * (VA_NW * 16) + wid * 16 + lrow;
         const int qc = q < T ? q : T - 1;
+        boff[i] = (KEMR_MAX_BERT_CTX - 1) - qc + lq * 4;            // 0 <= qc <= 511: with a key in 0 .. 508 + r the index is in 0 .. 1022
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) qf[i][kk] = *(const bf16x8*)(base + (size_t)qc * ld + kk * 32 + lq * 8);
     }
@@ -120,6 +137,16 @@ __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_va
     };
 
     load_chunk(0);
+    const float* sB = (const float*)(smem + 2 * VA_STAGE);
+    if constexpr (BIAS) {                              // the head's row of the table: visible behind the first barrier, read-only from then on
+        const float* src = bias_by_distance + (size_t)h * VA_ND;
+        float* dstb = (float*)(smem + 2 * VA_STAGE);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = tid * 4 + j;
+            if (e < VA_NDP) dstb[e] = e < VA_ND ? src[e] : 0.f;
+        }
+    }
     store_chunk(0, smem);
     __syncthreads();
 
@@ -155,6 +182,10 @@ __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_va
             for (int i = 0; i < VA_QT; ++i) {
                 s[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (live[i] && (!tail || k0 + t * 16 < T)) {
+                    if constexpr (BIAS) {              // the accumulator starts at bias[key - query]: keys k0 + 16 t + 4 lq + r
+                        const float* bp = sB + boff[i] + k0 + t * 16;
+                        s[i][t] = f32x4{bp[0], bp[1], bp[2], bp[3]};
+                    }
                     s[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t][0], qf[i][0], s[i][t], 0, 0, 0);
                     s[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t][1], qf[i][1], s[i][t], 0, 0, 0);
                 }
@@ -256,7 +287,8 @@ __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_va
     }
 }
 
-int launch_attention_varlen(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream) {
+int launch_attention_varlen(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream,
+                            const float* bias_by_distance) {
     if (batch <= 0) return KEMR_OK;
     if (!row_start) KEMR_FAIL(KEMR_ERR_INVALID, "attention_varlen: null row_start");
     if (width <= 0 || width % 64 != 0) KEMR_FAIL(KEMR_ERR_INVALID, "attention_varlen: width %d is not a multiple of the head dim 64", width);
@@ -267,7 +299,10 @@ int launch_attention_varlen(const bf16_t* qkv, bf16_t* out, const int* row_start
     if (items > 0x7ffffff0LL) KEMR_FAIL(KEMR_ERR_INVALID, "attention_varlen: batch %d too large", batch);
     const long long blocks = (items + 7) / 8 * 8;
     ProfScope prof(PROF_ATTENTION, stream);
-    hipLaunchKernelGGL(attention_varlen_kernel, dim3((unsigned)blocks), dim3(VA_NW * 64), 0, stream, qkv, out, row_start, max_t, width, nqb, (int)items);
+    if (bias_by_distance)
+        hipLaunchKernelGGL(attention_varlen_kernel<true>, dim3((unsigned)blocks), dim3(VA_NW * 64), 0, stream, qkv, out, row_start, max_t, width, nqb, (int)items, bias_by_distance);
+    else
+        hipLaunchKernelGGL(attention_varlen_kernel<false>, dim3((unsigned)blocks), dim3(VA_NW * 64), 0, stream, qkv, out, row_start, max_t, width, nqb, (int)items, bias_by_distance);
     KEMR_CHECK_LAUNCH("attention_varlen_kernel");
     return KEMR_OK;
 }

@@ -276,7 +276,10 @@ int launch_attention(const bf16_t* qkv, bf16_t* out, int batch, int t, int width
 int launch_attention_long(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, hipStream_t stream);
 // attention_varlen.hip: NON-causal, items of lengths 1 .. max_t <= KEMR_MAX_BERT_CTX packed one behind the other (row_start as below): the
 // BERT family's attention; per item the arithmetic of launch_attention_long at t = its length
-int launch_attention_varlen(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream);
+// bias_by_distance (family 3, MPNet; nullptr = no bias, the kernel as it was): fp32 [width / 64, 1023] on the device, entry [h][d + 511]
+// is added to the score of every (query, key) pair of head h with key - query = d
+int launch_attention_varlen(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream,
+                            const float* bias_by_distance = nullptr);
 // causal, items of lengths 1 .. max_t packed one behind the other: item b = rows row_start[b] .. row_start[b + 1] - 1 (device ints)
 int launch_attention_packed(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream);
 // attention80.hip: heads of 80 columns (the vision tower of ViT-H-14), non-causal, t <= 288: the tile kernel, the pooled row of the last

@@ -212,7 +212,7 @@ int run_blocks(const TowerW& t, const Workspace& w, int batch, const BlockOpts& 
 int check_image_args(const kemr_model* m, const void* pixels_dev, int batch, const void* out_dev, const char* what, bool x3_served) {
     if (!m || !pixels_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
     if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
-    if (m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 2 (BERT): a text-only model has no vision tower", what);
+    if (is_sentence_family(m->family)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 2 (BERT): a text-only model has no vision tower", what);
     if (m->x3 && !x3_served) KEMR_FAIL(KEMR_ERR_STATE, "%s: not available for a KEMR_PREC_FP32X3 model", what);
     if (batch < 0) KEMR_FAIL(KEMR_ERR_INVALID, "%s: negative batch", what);
     if (batch > 0 && (int64_t)batch * m->vtokens > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
@@ -223,7 +223,7 @@ int check_image_args(const kemr_model* m, const void* pixels_dev, int batch, con
 int check_text_args(const kemr_model* m, const void* ids_dev, const void* lens_dev, int rows, int batch, bool packed, const void* out_dev,
                     const char* what, bool x3_served) {
     if (!m || !ids_dev || !out_dev || (packed && !lens_dev)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
-    if (m->family == 2)
+    if (is_sentence_family(m->family))
         KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 2 (BERT): a padding mask is a length -- call kemr_encode_text_packed with the lengths (kemr_debug_bert_front for the front alone)", what);
     if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
     if (m->x3 && !x3_served) KEMR_FAIL(KEMR_ERR_STATE, "%s: not available for a KEMR_PREC_FP32X3 model", what);
@@ -340,7 +340,7 @@ int encode_text_x3(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_de
 int bert_front(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, const void* out_dev, void* workspace_dev,
                size_t workspace_bytes, hipStream_t s, const char* what, Workspace& w) {
     if (!m || !ids_dev || !lens_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "%s: null argument", what);
-    if (m->family != 2) KEMR_FAIL(KEMR_ERR_INVALID, "%s: only family 2 (BERT) has this front", what);
+    if (!is_sentence_family(m->family)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: only family 2 (BERT) has this front", what);
     if (!m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "%s: model not finalized", what);
     if (batch <= 0) return batch == 0 ? KEMR_OK : (set_error("%s: negative batch", what), KEMR_ERR_INVALID);
     const int W = m->cfg.t_width, T = m->cfg.ctx;
@@ -354,7 +354,7 @@ int bert_front(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, i
 
 // Post-LN blocks: QKV on h, attention over the packed items, out-proj into delta (store-only), x = LN(x + delta) with h = bf16(x), fc1
 // with the exact GELU, fc2 into delta2, x = LN(x + delta2) with h = bf16(x).  Options "residual_fusion", "last_block_pooled_row" and
-// "activation" are not consulted.
+// "activation" are not consulted.  Family 3 (MPNet) runs the same sequence; its attention launch carries the model's bias table.
 int encode_bert(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev, int normalize,
                 void* workspace_dev, size_t workspace_bytes, hipStream_t s) {
     Workspace w;
@@ -365,7 +365,7 @@ int encode_bert(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, 
     for (int l = 0; l < t.layers; ++l) {
         const LayerW& L = t.layer[l];
         KEMR_TRY(launch_gemm(linear(w.h, L.wqkv, L.bqkv, w.big, 3 * W, M, 3 * W, W), EPI_BIAS_BF16, s));
-        KEMR_TRY(launch_attention_varlen(w.big, w.h, w.row_start, batch, t.tokens, W, s));
+        KEMR_TRY(launch_attention_varlen(w.big, w.h, w.row_start, batch, t.tokens, W, s, m->family == 3 ? m->rel_bias : nullptr));
         KEMR_TRY(launch_gemm(linear(w.h, L.wo, L.bo, w.delta, W, M, W, W), EPI_BIAS_BF16, s));
         KEMR_TRY(launch_layernorm_post(w.x, w.x_dtype, w.delta, L.ln1_g, L.ln1_b, w.h, M, W, s, m->eps));
         KEMR_TRY(launch_gemm(linear(w.h, L.w1, L.b1, w.big, 4 * W, M, 4 * W, W), EPI_BIAS_GELU_BF16, s));
@@ -382,7 +382,7 @@ int fc1_epilogue(const kemr_model* m) { return m->family == 1 ? EPI_BIAS_TGELU_B
 // kemr_encode_*_pooled; family 0 only (SigLIP's head is the attention pool over every row, BERT has no head)
 int pooled_family_check(const kemr_model* m, bool pooled, const char* what) {
     if (pooled && m && m->family == 1) KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 1 (SigLIP): its head is the attention pool over every row, not LayerNorm + projection of one pooled row", what);
-    if (pooled && m && m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 2 (BERT): a sentence encoder has no projection head", what);
+    if (pooled && m && is_sentence_family(m->family)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: not available for family 2 (BERT): a sentence encoder has no projection head", what);
     return KEMR_OK;
 }
 
@@ -390,7 +390,7 @@ int encode_image_any(kemr_model* m, const float* pixels_dev, int batch, float* o
                      void* workspace_dev, size_t workspace_bytes, void* stream, bool pooled) {
     hipStream_t s = (hipStream_t)stream;
     KEMR_TRY(pooled_family_check(m, pooled, "encode_image_pooled"));
-    if (m && m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: not available for family 2 (BERT): a text-only model has no vision tower");
+    if (m && is_sentence_family(m->family)) KEMR_FAIL(KEMR_ERR_INVALID, "encode_image: not available for family 2 (BERT): a text-only model has no vision tower");
     if (m && m->finalized && m->x3) return encode_image_x3(m, pixels_dev, batch, out_dev, normalize, workspace_dev, workspace_bytes, s, pooled);
     Workspace w;
     KEMR_TRY(image_front(m, pixels_dev, batch, out_dev, workspace_dev, workspace_bytes, s, "encode_image", w));
@@ -429,11 +429,11 @@ int encode_text_any(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_d
                     int normalize, void* workspace_dev, size_t workspace_bytes, void* stream, bool pooled) {
     hipStream_t s = (hipStream_t)stream;
     KEMR_TRY(pooled_family_check(m, pooled, packed ? "encode_text_packed_pooled" : "encode_text_pooled"));
-    if (!packed && m && m->family == 2)
+    if (!packed && m && is_sentence_family(m->family))
         KEMR_FAIL(KEMR_ERR_INVALID, "encode_text: not available for family 2 (BERT): a padding mask is a length -- call kemr_encode_text_packed with the lengths");
     if (packed && m && m->family == 1)
         KEMR_FAIL(KEMR_ERR_INVALID, "encode_text_packed: not available for family 1 (SigLIP): its text tower is unmasked and pools the last position, so a pad position is a key and no row can be left out");
-    if (packed && m && m->family == 2) return encode_bert(m, ids_dev, lens_dev, rows, batch, out_dev, normalize, workspace_dev, workspace_bytes, s);
+    if (packed && m && is_sentence_family(m->family)) return encode_bert(m, ids_dev, lens_dev, rows, batch, out_dev, normalize, workspace_dev, workspace_bytes, s);
     if (m && m->finalized && m->x3) return encode_text_x3(m, ids_dev, lens_dev, rows, batch, packed, out_dev, normalize, workspace_dev, workspace_bytes, s, pooled);
     Workspace w;
     KEMR_TRY(text_front(m, ids_dev, lens_dev, rows, batch, packed, out_dev, workspace_dev, workspace_bytes, s, packed ? "encode_text_packed" : "encode_text", w));
@@ -460,7 +460,7 @@ int encode_text_any(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_d
 
 extern "C" size_t kemr_workspace_bytes(const kemr_model* m, int tower, int batch) {
     if (!m || batch <= 0) return 0;
-    if (m->family == 2) return 0;                      // family 2 has the packed call only (kemr_text_packed_workspace_bytes)
+    if (is_sentence_family(m->family)) return 0;                      // family 2 has the packed call only (kemr_text_packed_workspace_bytes)
     if (tower != KEMR_TOWER_VISION && tower != KEMR_TOWER_TEXT) return 0;
     const bool vision = tower == KEMR_TOWER_VISION;
     const int W = vision ? m->cfg.v_width : m->cfg.t_width;
@@ -472,7 +472,7 @@ extern "C" size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows
     if (!m || batch <= 0 || rows < batch) return 0;
     if (m->x3) return ws_layout_x3(m->cfg.t_width, rows, batch + 1).total;
     // buffers + pooled-row area (none for family 2) + row_start
-    return ws_layout(m->cfg.t_width, rows, m->family == 2 ? 0 : batch, m->res_dtype, batch + 1).total;
+    return ws_layout(m->cfg.t_width, rows, is_sentence_family(m->family) ? 0 : batch, m->res_dtype, batch + 1).total;
 }
 
 extern "C" int kemr_encode_image(kemr_model* m, const float* pixels_dev, int batch, float* out_dev, int normalize,

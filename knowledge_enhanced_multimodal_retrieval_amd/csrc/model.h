@@ -30,6 +30,7 @@ enum TensorKind : int {
     KIND_VPOS_SIGLIP,    // family 1's vision positional table: + visual.conv1.bias per row
     KIND_TPOS_BERT,      // family 2's positional table: + token_type_embedding[0] per row
     KIND_PROBE,          // family 1's pooling probe: verbatim, and behind it the head's one query (probe . Wq^T + bq) / 8 as bf16
+    KIND_REL_BIAS,       // family 3's relative_attention_bias [32, heads]: packed as the table by distance fp32 [heads, 1023] (expand_relative_bias)
 };
 struct TensorSpec {
     std::string name;
@@ -61,6 +62,14 @@ struct TowerW {
     std::vector<LayerW> layer;
 };
 
+// families 2 (BERT) and 3 (MPNet) are the sentence encoders: text-only, post-LN blocks, the packed encode call only.  What is checked or
+// refused for family 2 holds for family 3 alike, with the same messages.
+inline bool is_sentence_family(int family) { return family == 2 || family == 3; }
+// MPNet's bucket of a distance d = key - query (transformers MPNetEncoder.relative_position_bucket at 32 buckets, max distance 128),
+// by integer thresholds; and the table by distance out[h * 1023 + d + 511] = weight[bucket(d) * heads + h], d in -511 .. 511
+int relative_position_bucket(int d);
+void expand_relative_bias(const float* weight, int heads, float* out);
+
 // model.hip: the refusals of kemr_model_finalize (null model, precision, family, head dim, missing keys) and the pure host packing step
 int fp8_bits(int precision);
 int check_finalize(const kemr_model* m, int precision);
@@ -86,7 +95,10 @@ struct kemr_model {
     int stream24 = 1;                               // option "residual_stream_24bit" (before finalize; default on since round 4): the fp32-class stream stored in 3 bytes
     int family = 0;                                 // option "family" (before the first load_tensor): 0 = CLIP, 1 = SigLIP (no class token / ln_pre, tanh GELU, eps 1e-6, pooling head, unmasked text);
                                                     // 2 = BERT sentence encoder (kemr_model_create_family only: text-only, post-LN blocks, eps 1e-12, mean / CLS pooling)
-    int pooling = 0;                                // option "pooling" (family 2): 0 = mean of the item's rows, 1 = its first row (CLS)
+                                                    // 3 = MPNet sentence encoder (option "family" = 3 on a model created as family 2: family 2 without token types, with a relative position bias in every
+                                                    // attention score, eps 1e-5 or 1e-12 by option "layer_norm_eps")
+    int pooling = 0;                                // option "pooling" (families 2, 3): 0 = mean of the item's rows, 1 = its first row (CLS)
+    int ln_eps_exp = 5;                             // option "layer_norm_eps" (family 3, before finalize): 5 = 1e-5 (the published all-mpnet-base-v2), 12 = 1e-12 (MPNetConfig's default)
     bool any_loaded = false;                        // a tensor was loaded: the name list is fixed from then on
     float eps = 1e-5f;                              // every LayerNorm's epsilon: 1e-6 for family 1
     int vtokens = 0;                                // token rows per image: patches + 1 (class token), patches for family 1
@@ -102,6 +114,7 @@ struct kemr_model {
     // made by pack_weights, the k | v rows of in_proj (wkv = in_proj_weight + W * W), out_proj, LayerNorm and MLP
     const float* tproj_b = nullptr;
     const kemr::bf16_t *mh_q = nullptr, *mh_wkv = nullptr, *mh_wo = nullptr, *mh_w1 = nullptr, *mh_w2 = nullptr;
-    const float *lne_g = nullptr, *lne_b = nullptr;  // family 2: the embedding LayerNorm (ln_embed.*)
+    const float *lne_g = nullptr, *lne_b = nullptr;  // families 2, 3: the embedding LayerNorm (ln_embed.*)
+    const float* rel_bias = nullptr;                 // family 3: the attention bias by distance, fp32 [heads, 1023], one table for all layers
     const float *mh_bkv = nullptr, *mh_bo = nullptr, *mh_ln_g = nullptr, *mh_ln_b = nullptr, *mh_b1 = nullptr, *mh_b2 = nullptr;
 };

@@ -12,6 +12,8 @@ using namespace kemr;
 
 namespace {
 
+constexpr int REL_DISTANCES = 2 * KEMR_MAX_BERT_CTX - 1;    // key - query in -511 .. 511
+
 int check_cfg(const kemr_cfg& c) {
     if (c.embed_dim <= 0 || c.embed_dim > 1024) KEMR_FAIL(KEMR_ERR_INVALID, "cfg: embed_dim %d not in 1..1024", c.embed_dim);
     if (c.patch <= 0 || c.image_size <= 0 || c.image_size % c.patch) KEMR_FAIL(KEMR_ERR_INVALID, "cfg: image_size %% patch != 0");
@@ -73,13 +75,17 @@ void build_names(kemr_model* m) {
     };
     const int64_t vw = cfg->v_width, tw = cfg->t_width, D = cfg->embed_dim;
     const TensorTower V = TOWER_VISION, T = TOWER_TEXT, H = TOWER_HEAD;
-    if (m->family == 2) {
-        // BertModel without its pooler, by OpenAI-style names: ln_1 = attention.output.LayerNorm, ln_2 = output.LayerNorm (post-LN)
+    if (is_sentence_family(m->family)) {
+        // BertModel without its pooler, by OpenAI-style names: ln_1 = attention.output.LayerNorm, ln_2 = output.LayerNorm (post-LN).
+        // Family 3 (MPNetModel): no token types (the positional table is taken verbatim: the caller passes position_embeddings[2 : 2 + ctx]),
+        // and the encoder's one relative_attention_bias for all layers
+        const bool mpnet = m->family == 3;
         m->vtokens = 0;
-        m->eps = 1e-12f;
+        m->eps = mpnet ? (m->ln_eps_exp == 12 ? 1e-12f : 1e-5f) : 1e-12f;
         add("token_embedding.weight", {cfg->vocab, tw}, T, KIND_F32, &m->tok);
-        add("positional_embedding", {cfg->ctx, tw}, T, KIND_TPOS_BERT, &m->tpos);
-        add("token_type_embedding", {2, tw}, T, KIND_F32, nullptr);
+        add("positional_embedding", {cfg->ctx, tw}, T, mpnet ? KIND_F32 : KIND_TPOS_BERT, &m->tpos);
+        if (mpnet) add("relative_attention_bias", {32, tw / 64}, T, KIND_REL_BIAS, &m->rel_bias);
+        else add("token_type_embedding", {2, tw}, T, KIND_F32, nullptr);
         add("ln_embed.weight", {tw}, T, KIND_F32, &m->lne_g);
         add("ln_embed.bias", {tw}, T, KIND_F32, &m->lne_b);
         blocks("transformer", T, m->txt, tw, cfg->t_layers, cfg->ctx);
@@ -128,8 +134,9 @@ void build_names(kemr_model* m) {
 
 int model_create(const kemr_cfg* cfg, int family, kemr_model** out) {
     if (!cfg || !out) KEMR_FAIL(KEMR_ERR_INVALID, "model_create: null argument");
+    if (family == 3) KEMR_FAIL(KEMR_ERR_INVALID, "model_create_family: family 0 (CLIP), 1 (SigLIP) or 2 (BERT), got 3 (family 3, MPNet, is a family 2 model switched by kemr_model_set_option(m, \"family\", 3) before its first tensor is loaded)");
     if (family < 0 || family > 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_create_family: family 0 (CLIP), 1 (SigLIP) or 2 (BERT), got %d", family);
-    KEMR_TRY(family == 2 ? check_cfg_bert(*cfg) : check_cfg(*cfg));
+    KEMR_TRY(is_sentence_family(family) ? check_cfg_bert(*cfg) : check_cfg(*cfg));
     kemr_model* m = new (std::nothrow) kemr_model();
     if (!m) KEMR_FAIL(KEMR_ERR_NOMEM, "model_create: out of memory");
     m->cfg = *cfg;
@@ -137,7 +144,7 @@ int model_create(const kemr_cfg* cfg, int family, kemr_model** out) {
     { const char* v = getenv("KEMR_RESADD"); const int e = (v && *v) ? atoi(v) : 1; m->resadd = e < 0 ? 0 : e > 2 ? 2 : e; }
     { const char* v = getenv("KEMR_LAST_BLOCK_FULL"); m->last_pooled = (v && *v && atoi(v) != 0) ? 0 : 1; }
     { const char* v = getenv("KEMR_STREAM24"); m->stream24 = (v && *v) ? (atoi(v) != 0 ? 1 : 0) : 1; }
-    if (family != 2) {
+    if (!is_sentence_family(family)) {
         m->grid = cfg->image_size / cfg->patch;
         m->patches = m->grid * m->grid;
         m->kpad = (int)round_up(3 * cfg->patch * cfg->patch, 64);
@@ -216,6 +223,25 @@ void bind_weights(kemr_model* m, int fp8, const std::vector<Placement>& at) {
 
 namespace kemr {
 
+int relative_position_bucket(int d) {
+    // n = query - key; keys behind the query (n < 0) take the upper 16 buckets; |n| < 8 is its own bucket, beyond that the eight
+    // logarithmic buckets 8 .. 15 begin at the distances below (the integer form of 8 + floor(log(|n| / 8) / log(128 / 8) * 8), clamped to 15)
+    static const int first[8] = {8, 12, 16, 23, 32, 46, 64, 91};
+    const int n = -d, a = n < 0 ? -n : n;
+    int b = a;
+    if (a >= 8) {
+        b = 8;
+        while (b < 15 && a >= first[b - 8 + 1]) ++b;
+    }
+    return b + (n < 0 ? 16 : 0);
+}
+
+void expand_relative_bias(const float* weight, int heads, float* out) {
+    for (int h = 0; h < heads; ++h)
+        for (int d = -(KEMR_MAX_BERT_CTX - 1); d < KEMR_MAX_BERT_CTX; ++d)
+            out[(size_t)h * REL_DISTANCES + d + KEMR_MAX_BERT_CTX - 1] = weight[(size_t)relative_position_bucket(d) * heads + h];
+}
+
 int fp8_bits(int precision) {
     return (precision == KEMR_PREC_FP8 || precision == KEMR_PREC_FP8_RES16) ? 1 : precision == KEMR_PREC_FP8_MLP ? 3 : 0;
 }
@@ -225,7 +251,7 @@ int check_finalize(const kemr_model* m, int precision) {
     if (precision < KEMR_PREC_BF16 || precision > KEMR_PREC_FP32X3)
         KEMR_FAIL(KEMR_ERR_INVALID, "finalize: unsupported precision %d", precision);
     const int fp8 = fp8_bits(precision);
-    if (m->family == 2) {
+    if (is_sentence_family(m->family)) {
         if (fp8) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: the fp8 precisions are not served for family 2 (BERT): the e4m3 path is validated on the CLIP towers only");
         if (precision == KEMR_PREC_FP32X3) KEMR_FAIL(KEMR_ERR_INVALID, "finalize: KEMR_PREC_FP32X3 is not served for family 2 (BERT): the split-bf16 towers have no post-LN blocks");
     }
@@ -269,6 +295,7 @@ void pack_weights(const kemr_model& m, int precision, bool fill, PackedWeights& 
             if (is_e4m3(s, fp8)) { bytes = numel; out.at[i].aux = take((size_t)s.t.shape[0] * 4); }
             else bytes = numel * mat_bytes;
             break;
+        case KIND_REL_BIAS: bytes = (size_t)s.t.shape[1] * REL_DISTANCES * 4; break;
         default: bytes = numel * 4;
         }
         out.at[i].off = take(bytes);
@@ -324,6 +351,9 @@ void pack_weights(const kemr_model& m, int precision, bool fill, PackedWeights& 
             break;
         case KIND_TPOS_BERT:         // every token is of type 0 (a single segment), so token_type_embedding[0] rides in the positional table
             add_row(t.data, host_data(m, "token_type_embedding"), (size_t)m.cfg.t_width, (float*)dst);
+            break;
+        case KIND_REL_BIAS:          // [32, heads] by bucket -> [heads, 1023] by distance: the attention kernel indexes key - query + 511
+            expand_relative_bias(t.data.data(), (int)t.shape[1], (float*)dst);
             break;
         case KIND_PROBE: {
             // the pooling head's single query, the same for every image: (probe . Wq^T + bq) / 8 in fp32 (double accumulation), rounded to
@@ -461,8 +491,20 @@ extern "C" int kemr_model_set_option(kemr_model* m, const char* key, int value) 
         return KEMR_OK;
     }
     if (!strcmp(key, "family")) {
+        if (is_sentence_family(m->family)) {
+            // a sentence encoder created by kemr_model_create_family(cfg, 2): 2 (BERT) <-> 3 (MPNet) share the configuration checks and
+            // differ in the tensor list, so the switch works like 0 <-> 1 does for a kemr_model_create model; nothing else is reachable
+            if (value != 2 && value != 3) {
+                if (m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): a family 2 (BERT) model keeps its family (kemr_model_create_family)");
+                KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): a family 3 (MPNet) model becomes 2 (BERT) or stays 3, got %d (families 0 and 1: kemr_model_create_family)", value);
+            }
+            if (m->any_loaded || m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "model_set_option(family): set it before the first kemr_model_load_tensor (it decides the tensor names)");
+            m->family = value;
+            build_names(m);
+            return KEMR_OK;
+        }
         if (value == 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): 0 (CLIP) or 1 (SigLIP), got 2 (family 2, BERT, has its own configuration checks and is decided at creation: kemr_model_create_family)");
-        if (m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): a family 2 (BERT) model keeps its family (kemr_model_create_family)");
+        if (value == 3) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): 0 (CLIP) or 1 (SigLIP), got 3 (family 3, MPNet, is a family-2 model -- kemr_model_create_family(cfg, 2) -- switched by this option)");
         if (value < 0 || value > 1) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): 0 (CLIP) or 1 (SigLIP), got %d", value);
         if (m->any_loaded || m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "model_set_option(family): set it before the first kemr_model_load_tensor (it decides the tensor names)");
         if (value == 1 && m->v_head_dim != 64) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(family): family 1 (SigLIP) serves vision_head_dim 64 only, got %d", m->v_head_dim);
@@ -471,18 +513,26 @@ extern "C" int kemr_model_set_option(kemr_model* m, const char* key, int value) 
         return KEMR_OK;
     }
     if (!strcmp(key, "pooling")) {
-        if (m->family != 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(pooling): the option exists for family 2 (BERT) only");
+        if (!is_sentence_family(m->family)) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(pooling): the option exists for family 2 (BERT) only");
         if (value < 0 || value > 1) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(pooling): 0 (mean) or 1 (first row, CLS), got %d", value);
         m->pooling = value;
         return KEMR_OK;
     }
     if (!strcmp(key, "vision_head_dim")) {
-        if (m->family == 2) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): family 2 (BERT) has no vision tower");
+        if (is_sentence_family(m->family)) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): family 2 (BERT) has no vision tower");
         if (m->family == 1 && value != 64) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): family 1 (SigLIP) serves vision_head_dim 64 only, got %d", value);
         if (value != 64 && value != 80) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): 64 or 80, got %d", value);
         if (m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "model_set_option(vision_head_dim): set it before kemr_model_finalize");
         if (m->cfg.v_width % value) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(vision_head_dim): the vision width %d is not a multiple of %d", m->cfg.v_width, value);
         m->v_head_dim = value;
+        return KEMR_OK;
+    }
+    if (!strcmp(key, "layer_norm_eps")) {
+        if (m->family != 3) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(layer_norm_eps): the option exists for family 3 (MPNet) only");
+        if (value != 5 && value != 12) KEMR_FAIL(KEMR_ERR_INVALID, "model_set_option(layer_norm_eps): 5 (1e-5) or 12 (1e-12), got %d", value);
+        if (m->finalized) KEMR_FAIL(KEMR_ERR_STATE, "model_set_option(layer_norm_eps): set it before kemr_model_finalize");
+        m->ln_eps_exp = value;
+        m->eps = value == 12 ? 1e-12f : 1e-5f;
         return KEMR_OK;
     }
     if (!strcmp(key, "last_block_pooled_row")) {
@@ -507,6 +557,11 @@ extern "C" int kemr_model_get_option(const kemr_model* m, const char* key, int* 
     if (!strcmp(key, "vision_head_dim")) { *value = m->v_head_dim; return KEMR_OK; }
     if (!strcmp(key, "family")) { *value = m->family; return KEMR_OK; }
     if (!strcmp(key, "pooling")) { *value = m->pooling; return KEMR_OK; }
+    if (!strcmp(key, "layer_norm_eps")) {
+        if (m->family != 3) KEMR_FAIL(KEMR_ERR_INVALID, "model_get_option(layer_norm_eps): the option exists for family 3 (MPNet) only");
+        *value = m->ln_eps_exp;
+        return KEMR_OK;
+    }
     if (!strcmp(key, "precision_residual_bf16")) { *value = m->res_dtype == KEMR_BF16; return KEMR_OK; }
     KEMR_FAIL(KEMR_ERR_INVALID, "model_get_option: unknown key '%s'", key);
 }

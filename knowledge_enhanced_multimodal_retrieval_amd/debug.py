@@ -212,6 +212,19 @@ def op_attention_varlen(qkv, row_start, max_t: int, width: int, fill: float = 0.
     return out
 
 
+def op_attention_varlen_bias(qkv, row_start, bias_by_distance, max_t: int, width: int, fill: float = 0.0):
+    """op_attention_varlen with MPNet's relative position bias: bias_by_distance fp32 [width / 64, 1023] (device), entry [h][d + 511]
+    added to the scores of head h at key - query = d."""
+    import torch
+    if bias_by_distance.dtype != torch.float32 or tuple(bias_by_distance.shape) != (width // 64, _lib.MPNET_DISTANCES) or not bias_by_distance.is_contiguous():
+        raise ValueError(f"bias_by_distance must be contiguous fp32 [{width // 64}, {_lib.MPNET_DISTANCES}], got {bias_by_distance.dtype} {tuple(bias_by_distance.shape)}")
+    out = torch.full((qkv.shape[0], width), fill, dtype=torch.bfloat16, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.lib().kemr_debug_op_attention_varlen_bias(_ptr(qkv), _ptr(out), _ptr(row_start), _ptr(bias_by_distance), row_start.numel() - 1,
+                                                                  max_t, width, _stream(qkv.device)), "debug_op_attention_varlen_bias")
+    return out
+
+
 def op_layernorm_post(x, x_dtype: int, delta, gamma, beta, rows: int, width: int, eps: float):
     """The post-LN form in place on a copy of x (fp32 / bf16 [rows, width], or uint8 [rows, 3 width] 24-bit rows): -> (x', h bf16)."""
     import torch

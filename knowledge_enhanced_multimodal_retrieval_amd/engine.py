@@ -366,7 +366,8 @@ class ClipEngine:
 
 class BertEngine:
     """One packed BERT sentence encoder (model family 2 of the library) in HBM: ``transformers.BertModel`` without its pooler, then mean
-    or CLS pooling -- E5, GTE, BGE.  ``encode_ids`` is `kemr_encode_text_packed`: the texts of a call are packed one behind the other,
+    or CLS pooling -- E5, GTE, BGE; or, for an arch with ``relative_bias``, an MPNet one (family 3: all-mpnet-base-v2, whose attention
+    scores carry a learned relative position bias; state dict by hf_checkpoint.from_mpnet_state_dict).  ``encode_ids`` is `kemr_encode_text_packed`: the texts of a call are packed one behind the other,
     each on its own ``lens[i]`` positions (a padding mask is a length), so a call costs sum(lens) token rows, not B x the longest."""
 
     ROW_BUDGET = 65536           # token rows per packed call: 256 row tiles of the persistent GEMM (TEXT_ROW_BUDGET's reasoning)
@@ -382,9 +383,13 @@ class BertEngine:
         self._L = _lib.lib()
         cfg = _lib.KemrCfg(**arch.cfg_dict())
         h = C.c_void_p()
+        mpnet = bool(getattr(arch, "relative_bias", False))
         _lib.check(self._L.kemr_model_create_family(C.byref(cfg), _lib.FAMILY_BERT, C.byref(h)), "model_create_family")
         self._h = h
-        from .config import BERT_POOLING
+        from .config import BERT_POOLING, MPNET_EPS
+        if mpnet:                                      # family 3 is a family-2 model switched before its first tensor is loaded
+            _lib.check(self._L.kemr_model_set_option(self._h, b"family", _lib.FAMILY_MPNET), "model_set_option")
+            _lib.check(self._L.kemr_model_set_option(self._h, b"layer_norm_eps", MPNET_EPS[arch.layer_norm_eps]), "model_set_option")
         _lib.check(self._L.kemr_model_set_option(self._h, b"pooling", BERT_POOLING[arch.pooling]), "model_set_option")
         self._ws: Optional[torch.Tensor] = None
         self._order = CallOrder()

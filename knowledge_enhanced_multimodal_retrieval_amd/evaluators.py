@@ -651,7 +651,8 @@ def _load_sentence_encoder(model_name: str, device: str):
     from .sentence_model import SentenceEncoder
     if not os.path.isdir(model_name):
         raise RuntimeError(f"--model_name {model_name!r} is not a directory: the sentence encoders are loaded from a local checkpoint "
-                           "directory (config.json, weights, tokenizer.json), e.g. a download of intfloat/e5-base-v2 or thenlper/gte-large; "
+                           "directory (config.json, weights, tokenizer.json), e.g. a download of sentence-transformers/all-mpnet-base-v2, "
+                           "intfloat/e5-base-v2 or thenlper/gte-large; "
                            "nothing here contacts a model hub")
     return SentenceEncoder.from_pretrained(model_name, device=device, precision=_lib.env_precision())
 
@@ -659,7 +660,7 @@ def _load_sentence_encoder(model_name: str, device: str):
 def text_lm_parser() -> argparse.ArgumentParser:
     """The arguments of the reference's src/clip/eval/evaluator_lm.py:173-201 (+ --dataset / --synthetic, as the other CLIs have)."""
     p = argparse.ArgumentParser(description="Evaluate text-only models")
-    p.add_argument("--model_name", type=str, required=True, help="local directory of a BERT sentence encoder (E5, GTE)")
+    p.add_argument("--model_name", type=str, required=True, help="local directory of a sentence encoder (all-mpnet-base-v2, E5, GTE)")
     p.add_argument("--texts_dir", type=str, required=True, help="accepted for the reference's command lines; not read")
     p.add_argument("--images_dir", type=str, required=True, help="accepted for the reference's command lines; not read")
     p.add_argument("--split", type=str, default="test", choices=["train", "val", "test"])
@@ -787,7 +788,7 @@ def evaluate_text_model_variants(model, dataset, batch_size: int = 32, device: s
 def text_variants_parser() -> argparse.ArgumentParser:
     """The arguments of the reference's baselines/evaluate_text_models.py:268-299."""
     p = argparse.ArgumentParser(description="Evaluate text-only models")
-    p.add_argument("--model_name", type=str, required=True, help="local directory of a BERT sentence encoder (E5, GTE)")
+    p.add_argument("--model_name", type=str, required=True, help="local directory of a sentence encoder (all-mpnet-base-v2, E5, GTE)")
     p.add_argument("--texts_dir", type=str, required=True)
     p.add_argument("--description_type", type=str, required=True, choices=["content", "metadata", "hybrid_o1", "hybrid_o2"])
     p.add_argument("--images_dir", type=str, required=True, help="accepted for the reference's command lines; not read")

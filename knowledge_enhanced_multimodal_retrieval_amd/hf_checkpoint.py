@@ -13,6 +13,11 @@ dict onto the OpenAI names the engine loads, and reads ``config.json`` into a :c
 baselines) take the third: :func:`arch_from_bert_config` (with the sentence-transformers files ``1_Pooling/config.json`` and
 ``sentence_bert_config.json`` where present) and :func:`from_bert_state_dict`.
 
+``transformers.MPNetModel`` directories (``model_type: "mpnet"``: all-mpnet-base-v2, the baselines' third sentence encoder) are read
+by :func:`read_sentence_directory` alone, the route of ``SentenceEncoder.from_pretrained``: :func:`arch_from_mpnet_config`,
+:func:`from_mpnet_state_dict`, and the bucket rule of MPNet's relative position bias (:func:`relative_position_bucket`,
+:func:`bias_by_distance`) as the library applies it.  :func:`read_hf_directory` (``clip.load``) keeps refusing them.
+
 Local files only: nothing here (or anywhere in the package) contacts a model hub.
 """
 from __future__ import annotations
@@ -23,7 +28,7 @@ from typing import Dict, Mapping, Tuple
 
 import torch
 
-from .config import ARCHS, BertArch, ClipArch
+from .config import ARCHS, MPNET_EPS, BertArch, ClipArch
 
 # what transformers.CLIPTextConfig / CLIPVisionConfig / CLIPConfig assume for a field that config.json leaves out
 _TEXT_DEFAULTS = dict(hidden_size=512, intermediate_size=2048, num_attention_heads=8, num_hidden_layers=12, vocab_size=49408,
@@ -277,7 +282,8 @@ def arch_from_bert_config(cfg: Mapping, directory: str = "") -> BertArch:
     mt = cfg.get("model_type")
     if mt == "mpnet":
         raise ValueError("HF config: model_type 'mpnet' (all-mpnet-base-v2) is not served: its attention adds a learned relative "
-                         "position bias to every score, which the attention kernels do not take")
+                         "position bias to every score, which this route's attention launch does not take (sentence encoders load through "
+                         "hf_checkpoint.read_sentence_directory / SentenceEncoder.from_pretrained, which serves it)")
     if mt != "bert":
         raise ValueError(f"HF config: model_type {mt!r} is not a BertModel")
     c = {**_BERT_DEFAULTS, **{k: v for k, v in cfg.items() if v is not None}}
@@ -365,6 +371,138 @@ def to_bert_state_dict(sd: Mapping[str, torch.Tensor], arch: BertArch) -> Dict[s
     return out
 
 
+# ---- MPNet sentence encoders (all-mpnet-base-v2): transformers.MPNetModel ------------------------------------------------------------
+_MPNET_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_attention_heads=12, num_hidden_layers=12, vocab_size=30527,
+                       max_position_embeddings=512, hidden_act="gelu", layer_norm_eps=1e-12, relative_attention_num_buckets=32, pad_token_id=1)
+MPNET_BUCKETS = 32            # what MPNetEncoder.compute_position_bias passes, whatever the config says
+MPNET_MAX_DISTANCE = 511      # |key - query| at 512 positions
+# buckets 8 .. 15 of |query - key| begin at these distances (the integer form of 8 + floor(8 log(n / 8) / log(16)), capped at 15)
+_MPNET_LOG_BUCKET_STARTS = (8, 12, 16, 23, 32, 46, 64, 91)
+
+
+def relative_position_bucket(distance: int) -> int:
+    """MPNet's bucket of ``distance = key - query`` (``MPNetEncoder.relative_position_bucket`` at 32 buckets, max distance 128), by
+    integer thresholds: keys behind the query take buckets 16 .. 31; |distance| < 8 is its own bucket; then eight logarithmic ones."""
+    n = -int(distance)
+    a = abs(n)
+    b = a if a < 8 else 7 + sum(1 for t in _MPNET_LOG_BUCKET_STARTS if a >= t)
+    return b + (16 if n < 0 else 0)
+
+
+def bias_by_distance(weight: torch.Tensor) -> torch.Tensor:
+    """``encoder.relative_attention_bias.weight`` [32, heads] -> fp32 [heads, 1023]: entry [h][d + 511] is the bias head h adds to a
+    score at ``key - query = d`` -- the table the library builds at finalize and the attention kernel indexes."""
+    if weight.dim() != 2 or weight.shape[0] != MPNET_BUCKETS:
+        raise ValueError(f"relative_attention_bias: shape {tuple(weight.shape)}; expected [{MPNET_BUCKETS}, heads]")
+    idx = torch.tensor([relative_position_bucket(d) for d in range(-MPNET_MAX_DISTANCE, MPNET_MAX_DISTANCE + 1)])
+    return weight.detach().float()[idx].T.contiguous()
+
+
+def arch_from_mpnet_config(cfg: Mapping, directory: str = "") -> BertArch:
+    """``config.json`` of an ``MPNetModel`` (as a dict) -> BertArch with ``relative_bias``; `directory` (optional) is searched for the
+    sentence-transformers files.  Position ids start at padding_idx + 1 = 2, so ``max_position_embeddings`` = 514 means 512 usable
+    positions.  Refused with the reason: another bucket count than 32, a LayerNorm eps other than 1e-5 / 1e-12, and what the BERT route
+    refuses (width, head dim, MLP ratio, activation, more than 512 usable positions)."""
+    mt = cfg.get("model_type")
+    if mt != "mpnet":
+        raise ValueError(f"HF config: model_type {mt!r} is not an MPNetModel")
+    c = {**_MPNET_DEFAULTS, **{k: v for k, v in cfg.items() if v is not None}}
+    if int(c["relative_attention_num_buckets"]) != MPNET_BUCKETS:
+        raise ValueError(f"HF config: relative_attention_num_buckets = {c['relative_attention_num_buckets']}; served: 32 (MPNetEncoder computes "
+                         "its bias with 32 buckets whatever the config says, so another table size cannot be a working checkpoint)")
+    w, heads = int(c["hidden_size"]), int(c["num_attention_heads"])
+    if w <= 0 or w % 256:
+        raise ValueError(f"HF config: hidden_size = {w} is not a multiple of 256 (the kernels' tile; e.g. MiniLM's 384 is not served)")
+    if w > 1280:
+        raise ValueError(f"HF config: hidden_size = {w} is beyond the widest served tower (1280)")
+    if heads <= 0 or w != 64 * heads:
+        raise ValueError(f"HF config: num_attention_heads = {heads} at hidden_size {w} is a head dim of {w / max(heads, 1):g}; MPNet "
+                         "encoders are served at head dim 64 only")
+    if int(c["intermediate_size"]) != 4 * w:
+        raise ValueError(f"HF config: intermediate_size = {c['intermediate_size']} is not 4 x hidden_size ({4 * w})")
+    if c["hidden_act"] != "gelu":
+        raise ValueError(f"HF config: hidden_act = {c['hidden_act']!r}; MPNet encoders are served with the exact 'gelu' only")
+    eps = float(c["layer_norm_eps"])
+    if eps not in MPNET_EPS:
+        raise ValueError(f"HF config: layer_norm_eps = {c['layer_norm_eps']!r}; MPNet encoders are served with 1e-05 (all-mpnet-base-v2) "
+                         "and 1e-12 (MPNetConfig's default) only")
+    if int(c["pad_token_id"]) != 1:
+        raise ValueError(f"HF config: pad_token_id = {c['pad_token_id']}; served: 1 (position ids start at pad_token_id + 1 = 2)")
+    pooling, max_len = sentence_transformers_settings(directory)
+    positions = int(c["max_position_embeddings"]) - 2
+    if positions > 512:
+        raise ValueError(f"HF config: max_position_embeddings = {positions + 2} is {positions} usable positions; MPNet encoders are served up "
+                         "to 514 (512 usable: the bias table spans distances of -511 .. 511)")
+    if positions < 1:
+        raise ValueError(f"HF config: max_position_embeddings = {positions + 2} leaves no usable position (ids start at 2)")
+    ctx = min(max_len or positions, positions)
+    return BertArch(w, int(c["num_hidden_layers"]), vocab=int(c["vocab_size"]), ctx=ctx, pooling=pooling,
+                    positions=positions if positions != ctx else 0, relative_bias=True, layer_norm_eps=eps)
+
+
+_MPNET_TOP = [("embeddings.word_embeddings.weight", "token_embedding.weight"), ("embeddings.position_embeddings.weight", "positional_embedding"),
+              ("embeddings.LayerNorm.weight", "ln_embed.weight"), ("embeddings.LayerNorm.bias", "ln_embed.bias"),
+              ("encoder.relative_attention_bias.weight", "relative_attention_bias")]
+_MPNET_BLOCK = [("attention.attn.o.weight", "attn.out_proj.weight"), ("attention.attn.o.bias", "attn.out_proj.bias"),
+                ("attention.LayerNorm.weight", "ln_1.weight"), ("attention.LayerNorm.bias", "ln_1.bias")] + _BERT_BLOCK[4:]
+MPNET_POSITION_OFFSET = 2     # padding_idx + 1: the row of position_embeddings that position 0 reads
+
+
+def from_mpnet_state_dict(sd: Mapping[str, torch.Tensor], arch: BertArch) -> Dict[str, torch.Tensor]:
+    """``MPNetModel.state_dict()`` (bare keys, or ``mpnet.``-prefixed as a task model saves them) -> the engine's names for family 3:
+    q | k | v concatenated into ``in_proj_*``, ``attn.o`` = out_proj, ``ln_1`` = attention.LayerNorm, ``ln_2`` = output.LayerNorm,
+    ``positional_embedding`` = rows 2 .. 2 + ctx - 1 of the positional table (position j of a text reads row j + 2), the encoder's one
+    ``relative_attention_bias`` [32, heads].  ``pooler.*``, ``position_ids`` buffers and the heads of a task model (``lm_head.*``) are
+    ignored; a missing key and any other key left over are errors that name it."""
+    left = {}
+    for k, v in sd.items():
+        k = k[6:] if k.startswith("mpnet.") else k
+        if k.startswith("pooler.") or k.startswith("lm_head.") or k.endswith("position_ids"):
+            continue
+        left[k] = v
+    out: Dict[str, torch.Tensor] = {}
+
+    def take(key: str) -> torch.Tensor:
+        if key not in left:
+            raise KeyError(f"HF state dict: missing key '{key}'")
+        return left.pop(key)
+
+    for src, dst in _MPNET_TOP:
+        out[dst] = take(src)
+    pos = out["positional_embedding"]
+    if pos.shape[0] < MPNET_POSITION_OFFSET + arch.ctx:
+        raise KeyError(f"HF state dict: position_embeddings has {pos.shape[0]} rows, {MPNET_POSITION_OFFSET + arch.ctx} needed for {arch.ctx} positions")
+    out["positional_embedding"] = pos[MPNET_POSITION_OFFSET:MPNET_POSITION_OFFSET + arch.ctx].contiguous()
+    for i in range(arch.layers):
+        s, d = f"encoder.layer.{i}", f"transformer.resblocks.{i}"
+        out[f"{d}.attn.in_proj_weight"] = torch.cat([take(f"{s}.attention.attn.{p}.weight") for p in ("q", "k", "v")], dim=0)
+        out[f"{d}.attn.in_proj_bias"] = torch.cat([take(f"{s}.attention.attn.{p}.bias") for p in ("q", "k", "v")], dim=0)
+        for a, b in _MPNET_BLOCK:
+            out[f"{d}.{b}"] = take(f"{s}.{a}")
+    if left:
+        raise KeyError(f"HF state dict: unexpected key '{sorted(left)[0]}' ({len(left)} left over; not an MPNetModel of this architecture)")
+    return out
+
+
+def to_mpnet_state_dict(sd: Mapping[str, torch.Tensor], arch: BertArch, positions: int = 0) -> Dict[str, torch.Tensor]:
+    """The way back (tests): the engine's names -> ``MPNetModel(add_pooling_layer=False).state_dict()`` keys.  The positional table gets
+    its two leading rows back (zeros: row 1 is the padding row, row 0 is never read) and is zero-filled up to `positions` usable rows."""
+    out: Dict[str, torch.Tensor] = {src: sd[dst] for src, dst in _MPNET_TOP}
+    pos = sd["positional_embedding"]
+    table = torch.zeros(MPNET_POSITION_OFFSET + max(positions, pos.shape[0]), pos.shape[1], dtype=pos.dtype)
+    table[MPNET_POSITION_OFFSET:MPNET_POSITION_OFFSET + pos.shape[0]] = pos
+    out["embeddings.position_embeddings.weight"] = table
+    w = arch.width
+    for i in range(arch.layers):
+        s, d = f"encoder.layer.{i}", f"transformer.resblocks.{i}"
+        for j, p in enumerate(("q", "k", "v")):
+            out[f"{s}.attention.attn.{p}.weight"] = sd[f"{d}.attn.in_proj_weight"][j * w:(j + 1) * w].contiguous()
+            out[f"{s}.attention.attn.{p}.bias"] = sd[f"{d}.attn.in_proj_bias"][j * w:(j + 1) * w].contiguous()
+        for a, b in _MPNET_BLOCK:
+            out[f"{s}.{a}"] = sd[f"{d}.{b}"]
+    return out
+
+
 def is_hf_directory(path: str) -> bool:
     return os.path.isdir(path) and os.path.isfile(os.path.join(path, "config.json"))
 
@@ -400,3 +538,24 @@ def read_hf_directory(directory: str) -> Tuple[ClipArch, str, Dict[str, torch.Te
     else:
         sd = torch.load(weights, map_location="cpu", weights_only=True)
     return arch, activation, (from_siglip_state_dict if siglip else from_hf_state_dict)(sd, arch)
+
+
+def read_sentence_directory(directory: str) -> Tuple[BertArch, Dict[str, torch.Tensor]]:
+    """(BertArch, state dict under the engine's names) of a sentence encoder's ``save_pretrained`` directory on the local disk, with the
+    sentence-transformers files honoured where present: ``model_type: "bert"`` exactly as :func:`read_hf_directory` reads it, and
+    ``model_type: "mpnet"`` (``transformers.MPNetModel``, model family 3).  Any other model type is refused."""
+    cfg_path = os.path.join(directory, "config.json")
+    if not os.path.isfile(cfg_path):
+        raise FileNotFoundError(f"{directory!r} holds no config.json (not a save_pretrained directory)")
+    cfg = _read_json(cfg_path)
+    mt = cfg.get("model_type")
+    if mt == "bert":
+        arch, _, sd = read_hf_directory(directory)
+        return arch, sd
+    if mt != "mpnet":
+        raise ValueError(f"{directory!r} is not a sentence encoder (config.json model_type is {mt!r}; served: 'bert', 'mpnet')")
+    weights = next((os.path.join(directory, f) for f in WEIGHT_FILES if os.path.isfile(os.path.join(directory, f))), None)
+    if weights is None:
+        raise FileNotFoundError(f"{directory!r} holds neither of {WEIGHT_FILES} (sharded checkpoints are not read)")
+    arch = arch_from_mpnet_config(cfg, directory)
+    return arch, from_mpnet_state_dict(_load_weights(weights), arch)

@@ -6,7 +6,12 @@ The reference loads ``intfloat/e5-base-v2`` and ``thenlper/gte-large`` through `
 calls: a local checkpoint directory in (``transformers`` or sentence-transformers layout), embeddings out, computed by
 ``BertEngine`` -- every text on its own length, packed (no padded positions are computed).
 
-Local files only.  MPNet (``all-mpnet-base-v2``) is refused: its relative attention bias is not served.
+The reference's third sentence encoder, ``sentence-transformers/all-mpnet-base-v2`` (``transformers.MPNetModel``), loads the same way:
+its learned relative position bias rides in the packed attention kernel's score accumulators (model family 3 of the library).  The
+engine places token j of a text at position j, which is what MPNet's position ids (built from the non-pad ids) give whenever no
+``<pad>`` id occurs inside a text's length -- tokenizers never emit one there; a text that held one would differ from Hugging Face.
+
+Local files only.
 """
 from __future__ import annotations
 
@@ -18,7 +23,7 @@ import torch
 from . import _lib
 from .config import BertArch
 from .engine import BertEngine
-from .hf_checkpoint import read_hf_directory
+from .hf_checkpoint import read_sentence_directory
 from .tokenizer import bert_tokenizer, pad_id_lists
 
 
@@ -28,7 +33,7 @@ def length_sorted_order(lengths: Sequence[int]) -> List[int]:
 
 
 class SentenceEncoder:
-    """A BERT sentence encoder on the GPU with ``SentenceTransformer.encode``'s contract."""
+    """A BERT or MPNet sentence encoder on the GPU with ``SentenceTransformer.encode``'s contract."""
 
     def __init__(self, arch: BertArch, state_dict, tokenize, device=None, precision: str = _lib.DEFAULT_PRECISION):
         """`tokenize`: a ``tokenizer.BertTokenize`` (or any object with ``encode_lists(texts) -> list of id lists``, each at most
@@ -41,11 +46,9 @@ class SentenceEncoder:
 
     @classmethod
     def from_pretrained(cls, directory: str, device=None, precision: str = _lib.DEFAULT_PRECISION) -> "SentenceEncoder":
-        """A ``save_pretrained`` directory of a ``BertModel`` (``config.json``, weights, ``tokenizer.json``), optionally with the
-        sentence-transformers files ``1_Pooling/config.json`` and ``sentence_bert_config.json``."""
-        arch, _, sd = read_hf_directory(directory)
-        if not isinstance(arch, BertArch):
-            raise ValueError(f"{directory!r} is not a BERT sentence encoder (config.json model_type is not 'bert')")
+        """A ``save_pretrained`` directory of a ``BertModel`` or an ``MPNetModel`` (``config.json``, weights, ``tokenizer.json``),
+        optionally with the sentence-transformers files ``1_Pooling/config.json`` and ``sentence_bert_config.json``."""
+        arch, sd = read_sentence_directory(directory)
         return cls(arch, sd, bert_tokenizer(directory, arch.ctx), device, precision)
 
     # SentenceTransformer is an nn.Module: the reference calls .to(device) and .eval() on it

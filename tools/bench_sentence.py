@@ -12,6 +12,14 @@ shapes; `--profile` adds the engine's per-kernel-class split from device events,
 model goes to stdout and, with `--out`, to that file.
 
     python tools/bench_sentence.py --texts 2048 --batch 32 --out profiles/sentence_bench.json
+
+`--mpnet` measures the all-mpnet-base-v2 shape instead (model family 3: the relative position bias in the packed attention kernel):
+the same texts -- E5's length distribution, sorted batches -- at max_seq_length 512 and 384 (sentence-transformers' setting for this
+model: longer texts are cut to 384 tokens), and per setting three figures: the engine's texts/s, its ratio to the E5-base-v2 shape
+measured in the same run on the same lengths (same width and depth: the cost of the bias), and its ratio to transformers.MPNetModel in
+bf16 on the same device and batches.  One JSON line per setting.
+
+    python tools/bench_sentence.py --mpnet --texts 2048 --batch 32 --out profiles/mpnet_bench.json
 """
 import argparse
 import ctypes as C
@@ -56,17 +64,76 @@ def hf_pass(model, ids, lens, host_lens, batch):
         torch.nn.functional.normalize((h * m).sum(1) / m.sum(1), dim=-1)
 
 
+def engine_texts_per_s(arch, sd, ids, lens, passes, dev):
+    eng = engine.BertEngine(arch, dev)
+    eng.load_state_dict(sd)
+    ids_d = ids.to(dev)
+    t = timed(lambda: eng.encode_ids(ids_d, lens, normalize=True), passes)
+    L = _lib.lib()                                          # the per-kernel-class split from device events, in a pass of its own
+    _lib.check(L.kemr_profile_begin(1 << 16), "profile_begin")
+    eng.encode_ids(ids_d, lens, normalize=True)
+    ms, n = (C.c_double * 5)(), (C.c_int64 * 5)()
+    _lib.check(L.kemr_profile_end(ms, n, 5), "profile_end")
+    prof = {c: round(ms[i], 3) for i, c in enumerate(CLASSES) if n[i]}
+    del eng
+    return ids.shape[0] / t, prof
+
+
+def mpnet_bench(args, dev):
+    """all-mpnet-base-v2 next to E5-base-v2 on the same lengths, and next to transformers.MPNetModel (bf16, fp32 for reference)."""
+    import dataclasses
+
+    import bert_ref as B
+    import mpnet_ref as M
+    from transformers import MPNetModel
+    lines = []
+    drawn = draw_lengths(args.texts, 512)
+    for max_len in (512, 384):
+        lens = drawn.clamp(max=max_len)                     # the same texts, cut at max_seq_length (still sorted longest first)
+        rows = int(lens.sum())
+        mp = dataclasses.replace(BERT_ARCHS["all-mpnet-base-v2"], ctx=max_len, positions=0 if max_len == 512 else 512)
+        e5 = dataclasses.replace(BERT_ARCHS["e5-base-v2"], ctx=max_len, positions=0 if max_len == 512 else 512)
+        ids_mp, _ = M.random_ids(lens.tolist(), mp, seed=3)
+        ids_e5, _ = B.random_ids(lens.tolist(), e5, seed=3)
+        mp_tps, mp_prof = engine_texts_per_s(mp, M.random_state_dict(mp, seed=0), ids_mp, lens, args.passes, dev)
+        e5_tps, e5_prof = engine_texts_per_s(e5, B.random_state_dict(e5, seed=0), ids_e5, lens, args.passes, dev)
+        res = {"model": "all-mpnet-base-v2", "max_seq_length": max_len, "texts": args.texts, "token_rows": rows, "mean_length": rows / args.texts,
+               "batch": args.batch, "precision": _lib.DEFAULT_PRECISION, "engine_texts_per_s": mp_tps, "e5_base_engine_texts_per_s": e5_tps,
+               "engine_over_e5_base": mp_tps / e5_tps, "engine_ms_per_class": mp_prof, "e5_base_engine_ms_per_class": e5_prof,
+               "device": torch.cuda.get_device_name(0)}
+        ids_d, lens_d = ids_mp.to(dev), lens.to(dev)
+        for dt, tag in ((torch.bfloat16, "bf16"), (torch.float32, "fp32")):
+            cfg = M.mpnet_config(mp, positions=512)
+            cfg._attn_implementation = "eager"              # the only attention MPNetModel has
+            model = MPNetModel(cfg, add_pooling_layer=False).eval().to(device=dev, dtype=dt)
+            with torch.no_grad():
+                t = timed(lambda: hf_pass(model, ids_d, lens_d, lens.tolist(), args.batch), args.passes)
+            res[f"torch_eager_{tag}_texts_per_s"] = args.texts / t
+            del model
+        res["engine_over_torch_bf16"] = res["engine_texts_per_s"] / res["torch_eager_bf16_texts_per_s"]
+        lines.append(json.dumps(res))
+        print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--models", nargs="+", default=["gte-large", "e5-base-v2"], choices=sorted(BERT_ARCHS))
+    ap.add_argument("--models", nargs="+", default=["gte-large", "e5-base-v2"], choices=sorted(k for k, a in BERT_ARCHS.items() if not a.relative_bias))
     ap.add_argument("--texts", type=int, default=2048)
     ap.add_argument("--batch", type=int, default=32, help="texts per BertModel call (SentenceTransformer.encode's batch_size)")
     ap.add_argument("--passes", type=int, default=2)
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--mpnet", action="store_true", help="the all-mpnet-base-v2 shape at max_seq_length 512 and 384, next to E5-base and MPNetModel")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("no GPU visible: nothing is measured without one")
+    if args.mpnet:
+        lines = mpnet_bench(args, torch.device("cuda:0"))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     import bert_ref as B
     from transformers import BertModel
     dev = torch.device("cuda:0")
