@@ -135,9 +135,10 @@ typedef enum kemr_precision { KEMR_PREC_BF16 = 1, KEMR_PREC_BF16_RES16 = 2, KEMR
 typedef enum kemr_tower { KEMR_TOWER_VISION = 0, KEMR_TOWER_TEXT = 1 } kemr_tower;
 
 /* Longest sequences the encoders take: vision (image_size / patch)^2 + 1 tokens up to KEMR_MAX_VISION_TOKENS (a 32 x 32 patch
- * grid: ViT-L/14 at 448 px; ViT-L/14@336px has 577), the text context up to KEMR_MAX_TEXT_CTX (causal attention, 77 in CLIP).
+ * grid: ViT-L/14 at 448 px; ViT-L/14@336px has 577), the text context up to KEMR_MAX_TEXT_CTX (causal attention, 77 in CLIP, 248 in Long-CLIP).
  * Non-causal sequences of more than 288 tokens run on the streaming (flash-form) attention kernel, shorter ones on the
- * whole-sequence-in-LDS kernel. */
+ * whole-sequence-in-LDS kernel; packed causal texts (kemr_encode_text_packed) of more than 128 positions on the streaming kernel's
+ * causal form. */
 #define KEMR_MAX_VISION_TOKENS 1025
 #define KEMR_MAX_TEXT_CTX 288
 /* families 2 and 3 (BERT and MPNet sentence encoders): the longest text, absolute positions 0 .. 511 (non-causal attention over packed
@@ -314,7 +315,11 @@ int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch, float* ou
  *   rows     : HOST integer, the sum of lens (the tokenizer's side knows it; B <= rows <= B * ctx is checked, and the device
  *              clamps the prefix sums into it, so no argument can make a kernel index outside the workspace)
  *   workspace: >= kemr_text_packed_workspace_bytes(m, rows, B) bytes (exactly that is enough; the memory contract of the encoders above)
- * A length shorter than argmax_i + 1 pools text i's last computed row (memory-safe, not the reference's embedding). */
+ * A length shorter than argmax_i + 1 pools text i's last computed row (memory-safe, not the reference's embedding).
+ * Served for family 0 at every ctx <= KEMR_MAX_TEXT_CTX (Long-CLIP's 248 positions included) in the bf16-operand and the fp8 precisions
+ * (whose text tower is bf16): texts of up to 128 positions run the tile attention kernels, longer contexts the causal streaming
+ * kernel (csrc/attention_varlen.hip), both one launch over all packed texts.  A KEMR_PREC_FP32X3 model is served packed up to ctx =
+ * 128 only: above, this call and kemr_encode_text_packed_pooled return KEMR_ERR_INVALID and kemr_encode_text is the call to make. */
 size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows, int batch);
 int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,
                             int normalize, void* workspace_dev, size_t workspace_bytes, void* stream);

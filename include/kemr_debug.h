@@ -67,7 +67,7 @@ int kemr_debug_gemm_stamps(unsigned* host_out, int n_words);
 /* Kernels the product reaches only inside a tower, each a pass-through to its launcher (tests/test_numerics_paths_gpu.py).  Device
  * pointers; row_start_dev: batch + 1 ints, item b = the rows row_start[b] .. row_start[b + 1] - 1 (may be NULL where marked).
  * causal attention over packed items: qkv bf16 [rows, 3 width] (q pre-scaled by 1/8) -> out bf16 [rows, width], every length in
- * 1 .. max_t <= 128.  Exactly the rows row_start[0] .. row_start[batch] - 1 of out are written; an item's keys are its own rows (the
+ * 1 .. max_t <= KEMR_MAX_TEXT_CTX (up to 128: the tile kernels; above: the causal streaming kernel).  Exactly the rows row_start[0] .. row_start[batch] - 1 of out are written; an item's keys are its own rows (the
  * rows before row_start[0] and the next item's cannot reach it); batch + 1 ints of row_start are read */
 int kemr_debug_op_attention_packed(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width,
                                    void* stream);

@@ -8,6 +8,9 @@ Weights: upstream ``clip.load(name)`` downloads a checkpoint, which is impossibl
 * ``name`` may be a path to a state-dict file (``.pt`` with ``model_state_dict`` / ``state_dict`` / bare dict,
   loaded with ``weights_only=True``; or ``.safetensors``), optionally ``"ViT-L/14@/path/file"``; a registered model name is
   matched first, so ``"ViT-L/14@336px"`` is that model and ``"ViT-L/14@336px@/path/file"`` its checkpoint;
+* ``"LongCLIP-B@/path/longclip-B.pt"`` / ``"LongCLIP-L@/path/longclip-L.pt"``: Long-CLIP's released state dicts (OpenAI names, 248
+  text positions); their second positional table ``positional_embedding_res`` is folded into the first at load
+  (``hf_checkpoint.fold_longclip_positions``), an already folded file loads as it is;
 * or a known model name: ``$KEMR_CLIP_WEIGHTS/<name with / and @ -> ->.pt|.safetensors`` is used when present (upstream's
   file names: ``ViT-L-14.pt``, ``ViT-L-14-336px.pt``);
 * or a Hugging Face ``save_pretrained`` DIRECTORY on the local disk (``config.json`` + ``model.safetensors`` |
@@ -37,7 +40,8 @@ from .preprocess import ClipPreprocess, SiglipPreprocess, gpu_preprocessing_enab
 from .tokenizer import tokenize  # noqa: F401  (re-exported)
 
 _PUBLIC = ("ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px", "ViT-H-14",
-           "ViT-B-16-SigLIP", "ViT-B-16-SigLIP-256", "ViT-B-16-SigLIP-384", "ViT-B-16-SigLIP-512", "ViT-L-16-SigLIP-256", "ViT-L-16-SigLIP-384")
+           "ViT-B-16-SigLIP", "ViT-B-16-SigLIP-256", "ViT-B-16-SigLIP-384", "ViT-B-16-SigLIP-512", "ViT-L-16-SigLIP-256", "ViT-L-16-SigLIP-384",
+           "LongCLIP-B", "LongCLIP-L")
 _allow_random = False
 
 

@@ -118,6 +118,9 @@ class CLIP(nn.Module):
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         # the scalars OpenAI's files carry, and the causal-mask buffer of OpenCLIP files (not persistent in newer releases)
         sd = {k: v for k, v in state_dict.items() if k not in ("input_resolution", "context_length", "vocab_size", "attn_mask")}
+        if "positional_embedding_res" in sd:   # a Long-CLIP file as released: its two positional tables become the one the model adds
+            from .hf_checkpoint import fold_longclip_positions
+            sd = fold_longclip_positions(sd, ctx=self.arch.ctx)
         res = super().load_state_dict(sd, strict=strict, assign=assign)
         self._dirty = True
         return res

@@ -175,8 +175,13 @@ ARCHS: Dict[str, ClipArch] = {
     # OpenCLIP / LAION ViT-H/14 under OpenCLIP's own name ("ViT-H/14" stays unknown): vision 1280 wide = 16 heads of 80, 32 layers, 257
     # tokens; text 1024 wide = 16 heads of 64, 24 layers; joint dim 1024; trained with the exact GELU (activation="gelu")
     "ViT-H-14": ClipArch(1024, 224, 14, 1280, 32, 1024, 24, v_head_dim=80),
+    # Long-CLIP: the towers of ViT-B/16 and ViT-L/14 with a text tower of 248 positions (same state-dict names; its second positional
+    # table is folded at load, hf_checkpoint.fold_longclip_positions)
+    "LongCLIP-B": ClipArch(512, 224, 16, 768, 12, 512, 12, ctx=248),
+    "LongCLIP-L": ClipArch(768, 224, 14, 1024, 24, 768, 12, ctx=248),
     # small shapes for tests (same structure, head dim 64)
     "tiny": ClipArch(128, 32, 8, 256, 2, 256, 2, vocab=512, ctx=16),
+    "tiny-ctx248": ClipArch(128, 32, 8, 256, 2, 256, 2, vocab=512, ctx=248),      # "tiny" with Long-CLIP's 248 text positions
     "tiny-long": ClipArch(256, 112, 8, 256, 3, 512, 3, vocab=1024, ctx=77),
     # the structure of ViT-H-14 (vision heads of 80 at width 1280, the only width that is a multiple of 256 and of 80): 5 and 257 tokens
     "tiny-h": ClipArch(128, 28, 14, 1280, 2, 256, 2, vocab=512, ctx=16, v_head_dim=80),

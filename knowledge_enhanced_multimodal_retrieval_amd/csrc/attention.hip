@@ -492,7 +492,8 @@ int launch_attention_pooled(const bf16_t* q, const bf16_t* qkv, bf16_t* out, con
 }
 
 // Causal attention over items of different lengths packed one behind the other: item b = rows row_start[b] .. row_start[b + 1] - 1
-// (device array of batch + 1 ints), every length in 1 .. max_t.
+// (device array of batch + 1 ints), every length in 1 .. max_t.  max_t <= 128: the tile kernels above, one workgroup per item and
+// head; 129 .. KEMR_MAX_TEXT_CTX: the causal instantiation of the streaming kernel (attention_varlen.hip).
 int launch_attention_packed(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream) {
     if (batch <= 0) return KEMR_OK;
     if (!row_start) KEMR_FAIL(KEMR_ERR_INVALID, "attention: packed rows need row_start");
@@ -504,7 +505,7 @@ int launch_attention_packed(const bf16_t* qkv, bf16_t* out, const int* row_start
         case 3: return launch_nt<3>(qkv, out, batch, max_t, width, 1, stream, row_start);
         case 4: return launch_nt<4>(qkv, out, batch, max_t, width, 1, stream, row_start);
     }
-    KEMR_FAIL(KEMR_ERR_INVALID, "attention: packed rows support lengths up to 128, got %d", max_t);
+    return launch_attention_varlen_causal(qkv, out, row_start, batch, max_t, width, stream);       // 129 .. KEMR_MAX_TEXT_CTX, refused above
 }
 
 }  // namespace kemr

@@ -29,6 +29,22 @@
 // index stays in 0 .. 1022; the pad-key mask to -inf comes after, as before.  The table is read-only and per head: the fixed order of
 // every sum, the isolation of an item and the memory contract above hold unchanged.  The instantiation without BIAS is the kernel as it
 // was: every bias statement is under `if constexpr`.
+//
+// CAUSAL (model family 0, the CLIP text towers of 129 .. KEMR_MAX_TEXT_CTX positions, Long-CLIP's 248 among them; packed items of up to
+// 128 rows keep attention.hip's tile kernels): query q of an item sees its keys 0 .. q.  The instantiation changes three things, each
+// under `if constexpr`, so the non-causal instantiations are the kernels they were:
+//   * a workgroup's chunk loop ends at the last chunk that holds a key <= its block's last valid query instead of at the item's last;
+//   * a wave skips the MFMAs, the softmax and the update of a chunk that lies wholly behind one of its 16-query tiles (chunk start >
+//     the tile's last query) -- wave-uniform, and never a barrier or a staging load, exactly as for a dead tile; inside a processed
+//     chunk the 16-key score tiles and 32-key PV blocks wholly behind the tile are skipped too (their P is 0);
+//   * in a chunk that reaches behind the tile's first query, the keys behind the lane's query go to -inf where the pad keys do.
+// No row ever meets a processed chunk without a valid key: tiles start at multiples of 16 and chunks at multiples of 64, so "chunk
+// start 64 c <= the tile's last query q0 + 15" is "64 c <= q0", and every row q0 + j of the tile has key 64 c <= its own position;
+// 64 c <= the block's last valid query < T, so that key is no pad key either.  The running maximum of a row is therefore finite
+// from its first processed chunk on (always chunk 0) and exp2(-inf - (-inf)) cannot occur.  Rows of a live tile behind the item's last
+// row compute on the clamped query against the keys 0 .. T - 1 and are not stored.  The order of every sum is the non-causal one with
+// the skipped terms left out: an item's bits depend on its own rows alone, run to run.  oracle/rounding.py _attention_chunked with the
+// lower-triangular key mask states the arithmetic.
 #include "common.h"
 
 namespace kemr {
@@ -66,7 +82,7 @@ __device__ __forceinline__ bf16x4 lds_read_tr16_v(const char* p) {
 // Work items (query block fastest, then head, then item) are numbered so that the workgroups dealt to one XCD (the dispatcher
 // deals linear ids round-robin over the eight XCDs) take a contiguous range: the query blocks of one (item, head) read the same
 // K / V rows through the same L2.  Only a locality heuristic; every work item is computed exactly once whatever the placement.
-template <bool BIAS>
+template <bool BIAS, bool CAUSAL>
 __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_varlen_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                                        const int* __restrict__ row_start, int max_t, int width, int nqb, int items,
                                                                        const float* __restrict__ bias_by_distance) {
@@ -90,15 +106,18 @@ __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_va
     const int ld = 3 * width;
     const bf16_t* base = qkv + (size_t)r0 * ld + h * 64;
     const int lrow = lane & 15, lq = lane >> 4;
-    const int nch = (T + VA_KC - 1) / VA_KC;
+    // CAUSAL: up to the chunk of the block's last valid query (< T: no more chunks than the item has)
+    const int nch = CAUSAL ? ((qb + 1) * VA_QB <= T ? (qb + 1) * VA_QB - 1 : T - 1) / VA_KC + 1 : (T + VA_KC - 1) / VA_KC;
 
     // query fragments of the wave's two tiles (B operand of S^T = K . Q^T): rows clamped to the last valid one
     bf16x8 qf[VA_QT][2];
     bool live[VA_QT];                                  // wave-uniform: the tile holds at least one query of the item
     int boff[VA_QT];                                   // BIAS: the table index of the lane's query against key 4 lq
+    int tq0[VA_QT];                                    // CAUSAL: the tile's first query (wave-uniform, a multiple of 16)
 #pragma unroll
     for (int i = 0; i < VA_QT; ++i) {
         live[i] = qb * VA_QB + i * (VA_NW * 16) + wid * 16 < T;
+        if constexpr (CAUSAL) tq0[i] = qb * VA_QB + i * (VA_NW * 16) + wid * 16;
         const int q = qb * VA_QB + i * (VA_NW * 16) + wid * 16 + lrow;
         const int qc = q < T ? q : T - 1;
         boff[i] = (KEMR_MAX_BERT_CTX - 1) - qc + lq * 4;            // 0 <= qc <= 511: with a key in 0 .. 508 + r the index is in 0 .. 1022
@@ -167,6 +186,9 @@ __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_va
         const char* sV = sK + VA_KC * 128;
         const int k0 = c * VA_KC;
         const bool tail = k0 + VA_KC > T;              // the ragged last chunk: masks, dead tiles skipped (uniform)
+        // wave-uniform: the tile takes part in this chunk (CAUSAL: the chunk is not wholly behind the tile); keys from `key` on are in reach
+        auto act = [&](int i) { if constexpr (CAUSAL) return live[i] && k0 <= tq0[i] + 15; else return live[i]; };
+        auto reach = [&](int i, int key) { if constexpr (CAUSAL) return key <= tq0[i] + 15; else return true; };
 
         // S^T tiles: s[i][t][r] = S[query of tile i, lrow][key k0 + 16 t + 4 lq + r]
         f32x4 s[VA_QT][VA_NT16];
@@ -181,7 +203,7 @@ __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_va
 #pragma unroll
             for (int i = 0; i < VA_QT; ++i) {
                 s[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (live[i] && (!tail || k0 + t * 16 < T)) {
+                if (act(i) && (!tail || k0 + t * 16 < T) && reach(i, k0 + t * 16)) {       // (a score tile out of reach is masked below)
                     if constexpr (BIAS) {              // the accumulator starts at bias[key - query]: keys k0 + 16 t + 4 lq + r
                         const float* bp = sB + boff[i] + k0 + t * 16;
                         s[i][t] = f32x4{bp[0], bp[1], bp[2], bp[3]};
@@ -210,13 +232,23 @@ __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_va
         // online softmax per query tile
 #pragma unroll
         for (int i = 0; i < VA_QT; ++i) {
-            if (!live[i]) continue;
+            if (!act(i)) continue;
             if (tail) {
 #pragma unroll
                 for (int t = 0; t < VA_NT16; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         s[i][t][r] = k0 + t * 16 + lq * 4 + r < T ? s[i][t][r] : -INFINITY;
+            }
+            if constexpr (CAUSAL) {
+                if (k0 + VA_KC - 1 > tq0[i]) {         // the chunk reaches behind the tile's first query: keys behind the lane's query
+                    const int q = tq0[i] + lrow;
+#pragma unroll
+                    for (int t = 0; t < VA_NT16; ++t)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            s[i][t][r] = k0 + t * 16 + lq * 4 + r <= q ? s[i][t][r] : -INFINITY;
+                }
             }
             float mx = -INFINITY;
 #pragma unroll
@@ -250,7 +282,7 @@ __global__ __launch_bounds__(VA_NW * 64, KEMR_ATTN_VARLEN_OCC) void attention_va
             if (tail && k0 + u * 32 >= T) continue;
 #pragma unroll
             for (int i = 0; i < VA_QT; ++i) {
-                if (!live[i]) continue;
+                if (!act(i) || !reach(i, k0 + u * 32)) continue;   // (out of reach: every key of the block is behind the tile, P = 0)
                 union { bf16x8 v; uint32_t w[4]; } pf;
                 pf.w[0] = pack_bf16x2(s[i][2 * u][0], s[i][2 * u][1]);
                 pf.w[1] = pack_bf16x2(s[i][2 * u][2], s[i][2 * u][3]);
@@ -300,10 +332,24 @@ int launch_attention_varlen(const bf16_t* qkv, bf16_t* out, const int* row_start
     const long long blocks = (items + 7) / 8 * 8;
     ProfScope prof(PROF_ATTENTION, stream);
     if (bias_by_distance)
-        hipLaunchKernelGGL(attention_varlen_kernel<true>, dim3((unsigned)blocks), dim3(VA_NW * 64), 0, stream, qkv, out, row_start, max_t, width, nqb, (int)items, bias_by_distance);
+        hipLaunchKernelGGL((attention_varlen_kernel<true, false>), dim3((unsigned)blocks), dim3(VA_NW * 64), 0, stream, qkv, out, row_start, max_t, width, nqb, (int)items, bias_by_distance);
     else
-        hipLaunchKernelGGL(attention_varlen_kernel<false>, dim3((unsigned)blocks), dim3(VA_NW * 64), 0, stream, qkv, out, row_start, max_t, width, nqb, (int)items, bias_by_distance);
+        hipLaunchKernelGGL((attention_varlen_kernel<false, false>), dim3((unsigned)blocks), dim3(VA_NW * 64), 0, stream, qkv, out, row_start, max_t, width, nqb, (int)items, bias_by_distance);
     KEMR_CHECK_LAUNCH("attention_varlen_kernel");
+    return KEMR_OK;
+}
+
+// The causal instantiation: launch_attention_packed's route for items of 129 .. KEMR_MAX_TEXT_CTX rows (it has checked batch, row_start
+// and the width).
+int launch_attention_varlen_causal(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream) {
+    if (max_t <= 0 || max_t > KEMR_MAX_TEXT_CTX)
+        KEMR_FAIL(KEMR_ERR_INVALID, "attention: packed rows support lengths up to %d, got %d", KEMR_MAX_TEXT_CTX, max_t);
+    const int nqb = (max_t + VA_QB - 1) / VA_QB;
+    const long long items = (long long)batch * (width / 64) * nqb;
+    const long long blocks = (items + 7) / 8 * 8;
+    ProfScope prof(PROF_ATTENTION, stream);
+    hipLaunchKernelGGL((attention_varlen_kernel<false, true>), dim3((unsigned)blocks), dim3(VA_NW * 64), 0, stream, qkv, out, row_start, max_t, width, nqb, (int)items, nullptr);
+    KEMR_CHECK_LAUNCH("attention_varlen_kernel (causal)");
     return KEMR_OK;
 }
 

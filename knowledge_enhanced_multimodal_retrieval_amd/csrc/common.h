@@ -280,7 +280,10 @@ int launch_attention_long(const bf16_t* qkv, bf16_t* out, int batch, int t, int 
 // is added to the score of every (query, key) pair of head h with key - query = d
 int launch_attention_varlen(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream,
                             const float* bias_by_distance = nullptr);
-// causal, items of lengths 1 .. max_t packed one behind the other: item b = rows row_start[b] .. row_start[b + 1] - 1 (device ints)
+// attention_varlen.hip's CAUSAL instantiation (no bias): max_t <= KEMR_MAX_TEXT_CTX; launch_attention_packed's route above 128 rows
+int launch_attention_varlen_causal(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream);
+// causal, items of lengths 1 .. max_t <= KEMR_MAX_TEXT_CTX packed one behind the other: item b = rows row_start[b] .. row_start[b + 1] - 1
+// (device ints); max_t <= 128: the tile kernels of attention.hip, above: the streaming kernel
 int launch_attention_packed(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream);
 // attention80.hip: heads of 80 columns (the vision tower of ViT-H-14), non-causal, t <= 288: the tile kernel, the pooled row of the last
 // block (q [items, width] compact, k / v from the call's qkv buffer, item b = rows b * tokens ..) and the KEMR_PREC_FP32X3 form

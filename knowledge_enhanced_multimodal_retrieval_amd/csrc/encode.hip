@@ -231,7 +231,10 @@ int check_text_args(const kemr_model* m, const void* ids_dev, const void* lens_d
     if (batch == 0) return KEMR_OK;
     const int T = m->cfg.ctx;
     if ((int64_t)batch * T > (1 << 24)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch %d too large", what, batch);
-    if (packed && T > 128) KEMR_FAIL(KEMR_ERR_INVALID, "%s: context length %d > 128", what, T);
+    // cfg.ctx <= KEMR_MAX_TEXT_CTX (kemr_model_create), which is what the packed attention serves; the fp32x3 attention takes packed items
+    // of up to 128 rows only
+    if (packed && m->x3 && T > 128)
+        KEMR_FAIL(KEMR_ERR_INVALID, "%s: context length %d > 128 is not served packed for a KEMR_PREC_FP32X3 model (call kemr_encode_text)", what, T);
     if (packed && (rows < batch || (int64_t)rows > (int64_t)batch * T)) KEMR_FAIL(KEMR_ERR_INVALID, "%s: %d rows for %d texts of 1 .. %d positions", what, rows, batch, T);
     return KEMR_OK;
 }

@@ -310,7 +310,9 @@ class ClipEngine:
             raise RuntimeError(f"encode_text expects [B,{a.ctx}] token ids, got {tuple(ids.shape)}")
         if not self.ready:
             raise RuntimeError("ClipEngine: load_state_dict() must be called before encoding")
-        pack = self.pack_text and a.ctx <= 128 and a.family != "siglip"     # never the packed entry point for SigLIP (the library refuses it)
+        # never the packed entry point for SigLIP (the library refuses it); an fp32x3 model is served packed up to 128 positions only
+        # (include/kemr.h), every other precision at every context the library takes (Long-CLIP's 248 among them)
+        pack = self.pack_text and a.family != "siglip" and (a.ctx <= 128 or self.precision != "fp32x3")
         if pack and not ids.is_cuda:
             # host ids: the lengths are free to compute; caller-supplied ones may only LENGTHEN a text (a length short of the
             # end-of-text token would pool the wrong row: ADVICE r3)

@@ -63,9 +63,15 @@ def model_tokenize(model) -> Callable:
     """The tokenize callable that goes with `model` when the caller names none: CLIP's BPE (`default_tokenize`), or, for a SigLIP
     model, `tokenizer.siglip_tokenizer` on the directory its `tokenizer_dir` attribute names (`clip.load(<dir>)` sets it to the
     checkpoint directory; `--tokenizer_dir` / an assignment set it otherwise).  A SigLIP model without one cannot be tokenised for --
-    CLIP's ids are [B, 77] of another vocabulary -- so that is an error here, before any data is read."""
+    CLIP's ids are [B, 77] of another vocabulary -- so that is an error here, before any data is read.
+    A CLIP-family model with a longer text tower than CLIP's 77 positions (Long-CLIP: 248) gets CLIP's BPE cut at ITS context length,
+    `tokenizer.ClipTokenize(arch.ctx)` -> [B, arch.ctx] ids, picklable for the loader workers; at 77 -- and for the shorter test
+    shapes, as before -- it is `default_tokenize` itself (`model_tokenizer_name` compares by identity)."""
     arch = getattr(model, "arch", None)
     if arch is None or getattr(arch, "family", "clip") != "siglip":
+        if arch is not None and getattr(arch, "family", "clip") == "clip" and int(getattr(arch, "ctx", 77)) > 77:
+            from .tokenizer import ClipTokenize
+            return ClipTokenize(arch.ctx)
         return default_tokenize
     directory = getattr(model, "tokenizer_dir", None)
     if not directory:
@@ -80,7 +86,11 @@ def model_tokenizer_name(model) -> str:
     """What the results JSON records under "tokenizer"."""
     from . import tokenizer
     fn = model_tokenize(model)
-    return tokenizer.tokenizer_name() if fn is default_tokenize else f"siglip tokenizers ({fn.path})"
+    if fn is default_tokenize:
+        return tokenizer.tokenizer_name()
+    if isinstance(fn, tokenizer.ClipTokenize):
+        return f"{tokenizer.tokenizer_name()} context_length={fn.context_length}"
+    return f"siglip tokenizers ({fn.path})"
 
 
 ENCODE_ITEMS = 255          # items per encoder call in encode_dataset (see there)
@@ -214,7 +224,8 @@ def encode_dataset(model, dataset, batch_size: int = 64, seed: int = 42, num_wor
     # kernels of the other tower fit beside it, and a gain of that size does not pay for two-stream bookkeeping in every caller.)
     # Packed text calls (engine.ClipEngine.encode_text: a text is computed up to its end-of-text token only): the tokenizer-side
     # lengths travel with the ids, and a call takes as many (query, target) pairs as fill engine.TEXT_ROW_BUDGET token rows.
-    by_rows = bool(getattr(model, "accepts_text_lengths", False)) and arch is not None and arch.ctx <= 128 and \
+    # (every context the library takes, Long-CLIP's 248 included; an fp32x3 engine above 128 positions ignores the lengths and runs dense)
+    by_rows = bool(getattr(model, "accepts_text_lengths", False)) and arch is not None and \
         os.environ.get("KEMR_TEXT_PACKED", "1") != "0"
 
     def flush_images(final: bool):

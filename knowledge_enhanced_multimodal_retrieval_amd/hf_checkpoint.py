@@ -84,6 +84,38 @@ def arch_and_activation_from_hf_config(cfg: Mapping) -> Tuple[ClipArch, str]:
     return arch, t["hidden_act"]
 
 
+LONGCLIP_KEEP = 20        # positions of CLIP's own table that Long-CLIP keeps as they are
+
+
+def fold_longclip_positions(sd: Mapping[str, torch.Tensor], keep: int = LONGCLIP_KEEP, ctx: int = 0) -> Dict[str, torch.Tensor]:
+    """Long-CLIP's released files are OpenAI-named state dicts with TWO positional tables of the same shape ``[248, W]``:
+    ``positional_embedding`` and ``positional_embedding_res``.  The published model adds ``positional_embedding * mask1 +
+    positional_embedding_res * mask2`` to the token embeddings, ``mask1`` 1 on the positions 0 .. keep - 1 and ``mask2`` 1 on the
+    positions keep .. 247 (keep = 20: the positions of CLIP's table the interpolation left untouched).  The table the model adds is
+    therefore ``cat(positional_embedding[:keep], positional_embedding_res[keep:])``, and that is what this function returns under
+    ``positional_embedding``, with ``positional_embedding_res`` removed: a dict ``CLIP.load_state_dict`` loads strictly.
+
+    A dict without ``positional_embedding_res`` (any CLIP dict; a Long-CLIP one folded earlier) is returned as it is.  Two tables of
+    different shapes, or -- with ``ctx`` given (the architecture's) -- tables of another length, are a ``ValueError`` that names both
+    shapes; ``positional_embedding_res`` without ``positional_embedding`` is a ``KeyError``.  The rule is the published model code's as
+    far as it is known here; it was not checked against a released file, hence ``keep`` is a parameter."""
+    if "positional_embedding_res" not in sd:
+        return dict(sd)
+    if "positional_embedding" not in sd:
+        raise KeyError("state dict: 'positional_embedding_res' without 'positional_embedding'")
+    pos, res = sd["positional_embedding"], sd["positional_embedding_res"]
+    if pos.dim() != 2 or tuple(pos.shape) != tuple(res.shape):
+        raise ValueError(f"state dict: positional_embedding {tuple(pos.shape)} and positional_embedding_res {tuple(res.shape)} differ in shape")
+    if ctx and pos.shape[0] != ctx:
+        raise ValueError(f"state dict: positional_embedding {tuple(pos.shape)} and positional_embedding_res {tuple(res.shape)} do not "
+                         f"hold the architecture's {ctx} positions")
+    if not 0 <= keep <= pos.shape[0]:
+        raise ValueError(f"fold_longclip_positions: keep = {keep} outside 0 .. {pos.shape[0]}")
+    out = {k: v for k, v in sd.items() if k != "positional_embedding_res"}
+    out["positional_embedding"] = torch.cat([pos[:keep], res[keep:].to(pos.dtype)], dim=0).contiguous()
+    return out
+
+
 def registered_name(arch: ClipArch) -> str:
     """The name ``arch`` is registered under in config.ARCHS, or "" for a shape of its own."""
     return next((n for n, a in ARCHS.items() if a == arch), "")

@@ -194,6 +194,24 @@ def tokenize(texts: Union[str, Sequence[str]], context_length: int = CONTEXT, tr
     return out
 
 
+class ClipTokenize:
+    """``tokenize_fn`` of a CLIP-family model whose text tower is not 77 positions long (Long-CLIP: 248): CLIP's BPE with
+    ``context_length`` positions, over-long texts cut and ended in EOT -> int32 ``[B, context_length]``.  A module-level class with one
+    integer of state: picklable, so it survives the loader workers' start method."""
+
+    def __init__(self, context_length: int):
+        self.context_length = int(context_length)
+
+    def __call__(self, texts: Union[str, Sequence[str]]) -> torch.Tensor:
+        return tokenize([texts] if isinstance(texts, str) else list(texts), context_length=self.context_length, truncate=True)
+
+    def __eq__(self, other):
+        return isinstance(other, ClipTokenize) and other.context_length == self.context_length
+
+    def __hash__(self):
+        return hash(("ClipTokenize", self.context_length))
+
+
 # ---- SigLIP: a callable for the `tokenize_fn=` parameters (evaluators, EmbeddingStore.build, CLIPRetriever) -------------------------
 SIGLIP_CONTEXT = 64
 SIGLIP_EOS = 1          # "</s>"; the pad id as well (SigLIP pads with it, and a pad position is a key like every other)
