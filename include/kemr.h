@@ -413,6 +413,20 @@ int kemr_scores_dense(const void* q_panel_dev, int nq, const void* g_panel_dev, 
 int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t ld, const int32_t* gt_idx_dev,
                     int32_t* ahead_dev, int k, float* top_scores_dev, int32_t* top_idx_dev, void* stream);
 
+/* kemr_rank_dense for ONE SHARD's columns of a score matrix whose ground truth may live on another shard (additive in ABI 4; the
+ * dense learned heads over a gallery sharded across GPUs).  Candidate id of column j = id_offset + j (GLOBAL).  gt_idx holds GLOBAL
+ * ids and gt_score the ground-truth pair's score, wherever it was computed.  ahead[q] (WRITTEN, not accumulated) = number of columns
+ * j with id_j != gt_idx[q] that rank before (gt_score[q], gt_idx[q]) under the order rule (score descending, then lower id);
+ * gt_idx[q] < 0 writes 0.  The top-k lists carry global ids.  -inf / NaN behave as on kemr_rank_dense's k <= 32 route.
+ * With id_offset = 0 and gt_score[q] = S[q, gt_idx[q]] the outputs have kemr_rank_dense's bits; over any split of a matrix's columns
+ * into contiguous pieces the per-piece `ahead` values sum to kemr_rank_dense's and kemr_topk_merge of the per-piece lists is its
+ * list.  One workgroup per row, one pass, no atomics: a pure function of the input.  ld >= ng, rows need no alignment.
+ * Refused before any launch: id_offset < 0 or id_offset + ng > INT32_MAX; ld < ng; k outside 1..32 when lists are asked for;
+ * gt_idx / gt_score / ahead not all-or-none; top_scores / top_idx not both-or-none.  nq == 0 is a no-op. */
+int kemr_rank_dense_shard(const float* scores_dev, int nq, int ng, int64_t ld, int64_t id_offset,
+                          const int32_t* gt_idx_dev /* GLOBAL ids */, const float* gt_score_dev,
+                          int32_t* ahead_dev, int k, float* top_scores_dev, int32_t* top_idx_dev, void* stream);
+
 /* Deep ranked lists: up to KEMR_MAX_DEEP_K candidates per query, exact, by selection and a sort of the survivors instead of the
  * register-resident lists behind kemr_sim_topk / kemr_rank_dense (k <= 32).  What the online engine needs to let a SPARQL hit
  * that CLIP ranks 57th receive its bonus (reference src/retrieval.py:79-95 fuses over CLIP's own list), the shortlist that

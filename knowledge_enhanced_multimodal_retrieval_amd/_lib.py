@@ -89,6 +89,7 @@ SIGNATURES = {
     "kemr_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "kemr_scores_dense": (_i, [_vp, _i, _vp, _i, _i64, _vp, _i64, _vp]),
     "kemr_rank_dense": (_i, [_vp, _i, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp]),
+    "kemr_rank_dense_shard": (_i, [_vp, _i, _i, _i64, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "kemr_select_topk": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp, _vp]),
     "kemr_sim_topk_deep_workspace_bytes": (_sz, [_i, _i, _i64, _i]),
     "kemr_sim_topk_deep": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp, _sz, _vp]),

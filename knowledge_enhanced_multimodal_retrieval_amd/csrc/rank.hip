@@ -4,7 +4,8 @@
 // (metrics.py:165-185), evaluate_retrieval (eval/fusion.py:6-20) and the learned-fusion evaluator
 // (eval/evaluator_fusion.py:126).  One 256-thread workgroup per query row: 16-byte loads where the row is
 // aligned, per-thread `ahead` count + sorted top-KMAX list in registers, then a k-round selection over the
-// 256 lists through LDS.  Algorithmic bytes: 4 * N per row.
+// 256 lists through LDS.  Algorithmic bytes: 4 * N per row.  rank_dense_shard_kernel is the same pass over ONE SHARD's columns
+// (global ids, the ground truth's score handed in): what dist.sharded_ranks_dense runs on every rank of a sharded evaluation.
 #include "common.h"
 
 namespace kemr {
@@ -23,6 +24,39 @@ __device__ __forceinline__ void list_insert(float (&s)[KMAX], int (&id)[KMAX], f
         id[i] = shift ? id[i - 1] : (here ? idx : id[i]);
     }
     if (v > s[0]) { s[0] = v; id[0] = idx; }
+}
+
+// The k best of the 256 per-thread lists in LDS (ids < 0 = padding), by the first wave: k rounds of "best entry after the previous
+// pick", so the output is a pure function of the SET of listed entries -- how the columns were dealt to the threads does not matter.
+template <int KMAX>
+__device__ __forceinline__ void select_from_lists(const float* xs, const int* xi, int lane, int q, int k, float* __restrict__ top_s,
+                                                  int32_t* __restrict__ top_i) {
+    float ps = INFINITY;
+    int pi = -1;
+    bool done = false;
+    for (int o = 0; o < k; ++o) {
+        float bs = -INFINITY;
+        int bi = -1;
+        if (!done) {
+            for (int e = lane; e < 256 * KMAX; e += 64) {
+                const int ei = xi[e];
+                if (ei < 0) continue;
+                const float es = xs[e];
+                const bool after_prev = (o == 0) || rank_before(ps, pi, es, ei);
+                if (after_prev && (bi < 0 || rank_before(es, ei, bs, bi))) { bs = es; bi = ei; }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const float os = __shfl_xor(bs, off);
+                const int oi = __shfl_xor(bi, off);
+                if (oi >= 0 && (bi < 0 || rank_before(os, oi, bs, bi))) { bs = os; bi = oi; }
+            }
+            if (bi < 0) done = true;
+        }
+        if (lane == 0) { top_s[(size_t)q * k + o] = bi >= 0 ? bs : -INFINITY; top_i[(size_t)q * k + o] = bi; }
+        ps = bs;
+        pi = bi;
+    }
 }
 
 template <int KMAX>
@@ -60,34 +94,66 @@ __global__ __launch_bounds__(256) void rank_dense_kernel(const float* __restrict
     }
     __syncthreads();
     if (ahead && tid == 0) ahead[q] = has_gt ? (red[0] + red[1]) + (red[2] + red[3]) : 0;
-    if (top_s && tid < 64) {
-        float ps = INFINITY;
-        int pi = -1;
-        bool done = false;
-        for (int o = 0; o < k; ++o) {
-            float bs = -INFINITY;
-            int bi = -1;
-            if (!done) {
-                for (int e = lane; e < 256 * KMAX; e += 64) {
-                    const int ei = xi[e];
-                    if (ei < 0) continue;
-                    const float es = xs[e];
-                    const bool after_prev = (o == 0) || rank_before(ps, pi, es, ei);
-                    if (after_prev && (bi < 0 || rank_before(es, ei, bs, bi))) { bs = es; bi = ei; }
-                }
+    if (top_s && tid < 64) select_from_lists<KMAX>(xs, xi, lane, q, k, top_s, top_i);
+}
+
+// rank_dense_kernel for ONE SHARD's columns of a matrix whose ground truth may live on another shard (dist.sharded_ranks_dense): the
+// candidate id of column j is id0 + j, the ground truth comes as (gt_score, GLOBAL gt id) instead of being read from the row, and every
+// column whose id is not the ground truth's is counted when it ranks before that pair -- so the per-shard counts add up to the count
+// over the whole matrix.  Same single pass, lists and selection; the row is read with 16-byte loads from its first aligned element
+// (rows need no alignment: up to 3 leading and 3 trailing columns go one by one).  A thread's ids still only increase: head columns
+// (< first float4), then its float4s in order, then tail columns.
+template <int KMAX>
+__global__ __launch_bounds__(256) void rank_dense_shard_kernel(const float* __restrict__ S, long long ld, int nq, int ng, int id0,
+                                                               const int32_t* __restrict__ gt_idx, const float* __restrict__ gt_score,
+                                                               int32_t* __restrict__ ahead, int k, float* __restrict__ top_s,
+                                                               int32_t* __restrict__ top_i) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* xs = (float*)smem;                 // [256][KMAX]
+    int* xi = (int*)(xs + 256 * KMAX);        // [256][KMAX]
+    int* red = xi + 256 * KMAX;               // [4]
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const float* row = S + (size_t)q * ld;
+    const int gt = gt_idx ? gt_idx[q] : -1;
+    const bool has_gt = gt >= 0;
+    const float sgt = has_gt ? gt_score[q] : 0.f;
+    float ls[KMAX];
+    int li[KMAX];
 #pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const float os = __shfl_xor(bs, off);
-                    const int oi = __shfl_xor(bi, off);
-                    if (oi >= 0 && (bi < 0 || rank_before(os, oi, bs, bi))) { bs = os; bi = oi; }
-                }
-                if (bi < 0) done = true;
-            }
-            if (lane == 0) { top_s[(size_t)q * k + o] = bi >= 0 ? bs : -INFINITY; top_i[(size_t)q * k + o] = bi; }
-            ps = bs;
-            pi = bi;
-        }
+    for (int i = 0; i < KMAX; ++i) { ls[i] = -INFINITY; li[i] = -1; }
+    int cnt = 0;
+    auto take = [&](float v, int j) {
+        const int id = id0 + j;               // id0 + ng <= INT32_MAX (checked on the host)
+        if (has_gt && id != gt) cnt += rank_before(v, id, sgt, gt) ? 1 : 0;
+        if (top_s && v > ls[KMAX - 1]) list_insert<KMAX>(ls, li, v, id);
+    };
+    const int mis = (int)(((uintptr_t)row >> 2) & 3);            // fp32 elements past a 16-byte boundary
+    const int head = min(ng, (4 - mis) & 3);
+    const int nvec = (ng - head) >> 2;
+    if (tid < head) take(row[tid], tid);
+    const float4* row4 = (const float4*)(row + head);
+    for (int v4 = tid; v4 < nvec; v4 += 256) {
+        const float4 v = row4[v4];
+        const int j = head + 4 * v4;
+        take(v.x, j);
+        take(v.y, j + 1);
+        take(v.z, j + 2);
+        take(v.w, j + 3);
     }
+    const int tail = head + 4 * nvec;
+    if (tail + tid < ng) take(row[tail + tid], tail + tid);      // at most 3 columns
+    if (ahead && has_gt) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+        if (lane == 0) red[tid >> 6] = cnt;
+    }
+    if (top_s) {
+#pragma unroll
+        for (int i = 0; i < KMAX; ++i) { xs[tid * KMAX + i] = ls[i]; xi[tid * KMAX + i] = li[i]; }
+    }
+    __syncthreads();
+    if (ahead && tid == 0) ahead[q] = has_gt ? (red[0] + red[1]) + (red[2] + red[3]) : 0;
+    if (top_s && tid < 64) select_from_lists<KMAX>(xs, xi, lane, q, k, top_s, top_i);
 }
 
 // Learned "linear" fusion head (reference fusion_model.py:25-48, eval mode): out = w1 . relu(W0 . [t2i, t2t] + b0) + b1
@@ -258,5 +324,36 @@ extern "C" int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t 
                            top_scores_dev, top_idx_dev);
     }
     KEMR_CHECK_LAUNCH("rank_dense_kernel");
+    return KEMR_OK;
+}
+
+extern "C" int kemr_rank_dense_shard(const float* scores_dev, int nq, int ng, int64_t ld, int64_t id_offset,
+                                     const int32_t* gt_idx_dev, const float* gt_score_dev, int32_t* ahead_dev, int k,
+                                     float* top_scores_dev, int32_t* top_idx_dev, void* stream) {
+    if (nq == 0) return KEMR_OK;
+    if (!scores_dev || nq < 0 || ng <= 0) KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense_shard: bad argument");
+    if (ld < ng) KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense_shard: ld=%lld < ng=%d", (long long)ld, ng);
+    if (id_offset < 0 || id_offset + ng > (int64_t)INT32_MAX)
+        KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense_shard: id_offset=%lld with ng=%d leaves the int32 id range", (long long)id_offset, ng);
+    if ((top_scores_dev != nullptr) != (top_idx_dev != nullptr))
+        KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense_shard: top_scores/top_idx together");
+    if (top_scores_dev && (k < 1 || k > 32)) KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense_shard: k=%d not in 1..32", k);
+    if ((gt_idx_dev != nullptr) != (ahead_dev != nullptr) || (gt_idx_dev != nullptr) != (gt_score_dev != nullptr))
+        KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense_shard: gt_idx, gt_score and ahead together");
+    hipStream_t s = (hipStream_t)stream;
+    if (!top_scores_dev || k <= 10) {
+        constexpr int KM = 10;
+        const size_t smem = 256 * KM * 8 + 16;
+        hipLaunchKernelGGL(rank_dense_shard_kernel<KM>, dim3(nq), dim3(256), smem, s, scores_dev, (long long)ld, nq, ng, (int)id_offset,
+                           gt_idx_dev, gt_score_dev, ahead_dev, k, top_scores_dev, top_idx_dev);
+    } else {
+        constexpr int KM = 32;
+        const size_t smem = 256 * KM * 8 + 16;
+        auto kern = rank_dense_shard_kernel<KM>;
+        KEMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        hipLaunchKernelGGL(kern, dim3(nq), dim3(256), smem, s, scores_dev, (long long)ld, nq, ng, (int)id_offset, gt_idx_dev,
+                           gt_score_dev, ahead_dev, k, top_scores_dev, top_idx_dev);
+    }
+    KEMR_CHECK_LAUNCH("rank_dense_shard_kernel");
     return KEMR_OK;
 }

@@ -19,6 +19,10 @@ is checked with one 2-element all-reduce per call and refused with a ValueError 
 
 The compute calls are taken from an ``ops`` namespace (default: the HIP-backed ``engine`` module) so that the
 collective plumbing can be exercised with gloo on CPU-only machines in tests; the product path always uses ``engine``.
+
+The drop-in evaluators reach all this under ``torchrun`` through the last section of the module: ``init_from_env`` / ``finish``
+(what a CLI calls first and last), ``active_shard`` (do the evaluators shard?), ``EvenRows`` (equal query rows when ``n`` does not
+divide by the world) and ``sharded_ranks_dense`` (the dense learned heads: ``kemr_rank_dense_shard`` per shard + two reductions).
 """
 from __future__ import annotations
 
@@ -141,6 +145,17 @@ class PendingSearch:
         return self._out
 
 
+def _exchange(s, i, k, world, group, ops) -> PendingSearch:
+    """Per-shard candidate lists ([Q, k] scores + GLOBAL ids) of all shards -> every rank, not waited for; ``result()`` merges them
+    (``kemr_topk_merge``)."""
+    if _skip(world):
+        return PendingSearch(lambda a, b: (a, b), [], (s, i))
+    ss, w1 = all_gather_rows_async(s.unsqueeze(0), group)          # [world, Q, k]
+    ii, w2 = all_gather_rows_async(i.unsqueeze(0), group)
+    merge = lambda a, b: ops.topk_merge(a.permute(1, 0, 2).contiguous(), b.permute(1, 0, 2).contiguous(), k)
+    return PendingSearch(merge, [w1, w2], (ss, ii))
+
+
 class ShardedGallery:
     """This rank's shard of the gallery, packed for the fused similarity kernel."""
 
@@ -177,12 +192,7 @@ class ShardedGallery:
 
     def _exchange(self, s, i, k) -> PendingSearch:
         """Candidates of all shards -> every rank, not waited for."""
-        if _skip(self.world):
-            return PendingSearch(lambda a, b: (a, b), [], (s, i))
-        ss, w1 = all_gather_rows_async(s.unsqueeze(0), self.group)          # [world, Q, k]
-        ii, w2 = all_gather_rows_async(i.unsqueeze(0), self.group)
-        merge = lambda a, b: self.ops.topk_merge(a.permute(1, 0, 2).contiguous(), b.permute(1, 0, 2).contiguous(), k)
-        return PendingSearch(merge, [w1, w2], (ss, ii))
+        return _exchange(s, i, k, self.world, self.group, self.ops)
 
     def search_async(self, local_query_parts: Sequence[torch.Tensor], weights: Optional[Sequence[float]] = None, k: int = 10,
                      row_gate=None, bonus=None) -> PendingSearch:
@@ -319,3 +329,162 @@ class ShardedGallery:
         ranking._require_finite(gt_score[present], "fused scores at the ground truth")
         ranks = torch.where(present, ahead.long() + 1, torch.full_like(ahead, depth + 1, dtype=torch.int64))
         return ranks, top_s, top_i, fused, gi
+
+
+# ------------------------------------------------------------------------------------------------ the drop-in evaluators under torchrun
+def _torchrun_env() -> Optional[Tuple[int, int, int]]:
+    """(world, rank, local_rank) of a torchrun environment with more than one rank, else None: neither RANK nor WORLD_SIZE set, or
+    WORLD_SIZE=1, is "no process group" -- the evaluators then run exactly as they do without this module."""
+    if "RANK" not in os.environ or "WORLD_SIZE" not in os.environ:
+        return None
+    world = int(os.environ["WORLD_SIZE"])
+    if world <= 1:
+        return None
+    return world, int(os.environ["RANK"]), int(os.environ.get("LOCAL_RANK", "0"))
+
+
+def eval_sharded_enabled() -> bool:
+    """KEMR_EVAL_SHARDED=0 is the opt-out: under torchrun every rank then encodes and ranks everything alone, as before."""
+    return os.environ.get("KEMR_EVAL_SHARDED", "1") != "0"
+
+
+_OWN_GROUP = False
+
+# The compute namespace of the sharded evaluators (evaluators._ShardedEmbeddings): always the HIP-backed engine in the product; the
+# gloo tests on CPU-only machines put a numpy stand-in here, as they pass ``ops=`` to ShardedGallery.
+eval_ops = engine
+
+
+def init_from_env() -> Tuple[int, int, torch.device]:
+    """What an evaluator CLI calls first: (world, rank, device) of this process.  Under torchrun (RANK / WORLD_SIZE / LOCAL_RANK)
+    it picks ``cuda:{KEMR_LOCAL_DEVICE or LOCAL_RANK}`` and initialises "nccl" (RCCL) with ``device_id=`` BEFORE anything else
+    touches the GPU; KEMR_DIST_BACKEND=gloo initialises gloo instead (several ranks on ONE GPU with KEMR_LOCAL_DEVICE=0: the
+    rehearsal of the N > 1 path; RCCL refuses two ranks on a device).  Without a torchrun environment, or with
+    KEMR_EVAL_SHARDED=0, it does nothing and returns (1, 0, ``cuda`` or ``cpu``)."""
+    global _OWN_GROUP
+    env = _torchrun_env()
+    if env is None or not eval_sharded_enabled():
+        return 1, 0, torch.device("cuda" if torch.cuda.is_available() else "cpu")      # (no index: the GPU is not touched here)
+    world, rank, local_rank = env
+    dev = torch.device("cpu")
+    if torch.cuda.is_available():
+        dev = torch.device("cuda", int(os.environ.get("KEMR_LOCAL_DEVICE", local_rank)))
+        torch.cuda.set_device(dev)
+    if not dist.is_initialized():
+        backend = os.environ.get("KEMR_DIST_BACKEND", "nccl")
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=dev)
+        else:
+            dist.init_process_group(backend)
+        _OWN_GROUP = True
+    return dist.get_world_size(), dist.get_rank(), dev
+
+
+def finish() -> None:
+    """The counterpart of :func:`init_from_env`: a barrier and the end of the process group it created (nothing otherwise)."""
+    global _OWN_GROUP
+    if _OWN_GROUP and dist.is_available() and dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+    _OWN_GROUP = False
+
+
+def active_shard(group=None) -> Optional[Tuple[int, int]]:
+    """(rank, world) when the evaluators shard their work: a process group is initialised, it has more than one rank (or the
+    collectives are forced, see :func:`force_collectives`) and KEMR_EVAL_SHARDED is not 0.  None: the single-process code runs."""
+    if not (dist.is_available() and dist.is_initialized()) or not eval_sharded_enabled():
+        return None
+    world, rank = _world(group)
+    return None if _skip(world) else (rank, world)
+
+
+def is_writer(group=None) -> bool:
+    """True on the one rank that creates output directories, log files and result files (rank 0; every rank without a group)."""
+    return _world(group)[1] == 0
+
+
+def all_gather_list(items: list, group=None) -> list:
+    """The ranks' python lists concatenated in rank order (``all_gather_object``; used ONCE per evaluation, for the uuids)."""
+    world, _ = _world(group)
+    if _skip(world):
+        return list(items)
+    parts: List[Optional[list]] = [None] * world
+    dist.all_gather_object(parts, list(items), group=group)
+    return [x for part in parts for x in part]
+
+
+class EvenRows:
+    """Equal-rows padding of a contiguous split.  ``ShardedGallery`` refuses unequal query rows and ``n`` need not divide by the
+    world, so every rank brings ``per = ceil(n / world)`` query rows: its own ``hi - lo`` and zero vectors with ground truth 0 behind
+    them.  ``shard_bounds`` fills the ranks front to back, so the gathered row r * per + j IS the global item r * per + j and the
+    pad rows are exactly the gathered rows >= n: ``real()`` drops them before any metric sees them."""
+
+    def __init__(self, n: int, group=None):
+        self.n, self.group = int(n), group
+        self.world, self.rank = _world(group)
+        self.per = (self.n + self.world - 1) // self.world
+        self.lo, self.hi = shard_bounds(self.n, self.world, self.rank)
+        self.rows = self.per * self.world
+
+    def pad(self, x: torch.Tensor) -> torch.Tensor:
+        """[hi - lo, ...] -> [per, ...], zeros behind the own rows."""
+        if x.shape[0] != self.hi - self.lo:
+            raise ValueError(f"rank {self.rank} owns items [{self.lo}, {self.hi}) but got {x.shape[0]} rows")
+        if x.shape[0] == self.per:
+            return x
+        return torch.cat([x, torch.zeros((self.per - x.shape[0],) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)])
+
+    def local_gt(self, device) -> torch.Tensor:
+        """The padded rows' GLOBAL ground-truth ids (query lo + j <-> candidate lo + j; pad rows: 0), int32 [per]."""
+        return self.pad(torch.arange(self.lo, self.hi, dtype=torch.int32, device=device))
+
+    def all_gt(self, device) -> torch.Tensor:
+        """``local_gt`` of every rank, as the gathered rows carry it: int32 [world * per]."""
+        g = torch.arange(self.rows, dtype=torch.int32, device=device)
+        return torch.where(g < self.n, g, torch.zeros_like(g))
+
+    def pad_bonus(self, bonus):
+        """A CSR over the n real queries -> one over all gathered rows (the pad rows hold no entry)."""
+        import numpy as np
+        ptr = np.asarray(bonus[0])
+        if len(ptr) != self.n + 1:
+            raise ValueError(f"the bonus row pointer must have {self.n + 1} entries, got {len(ptr)}")
+        return np.concatenate([ptr, np.full(self.rows - self.n, ptr[-1], ptr.dtype)]), bonus[1], bonus[2]
+
+    def real(self, gathered: torch.Tensor) -> torch.Tensor:
+        if gathered.shape[0] != self.rows:
+            raise ValueError(f"expected {self.rows} gathered rows, got {gathered.shape[0]}")
+        return gathered[: self.n]
+
+
+def sharded_ranks_dense(local_scores: torch.Tensor, lo: int, gt_global: torch.Tensor, k: int = 0, group=None, ops=engine
+                        ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Ranks (and top-k) of a dense score matrix whose COLUMNS are sharded: ``local_scores`` fp32 [Q_all, n_local] holds every query's
+    scores against this rank's candidates, GLOBAL ids ``lo .. lo + n_local - 1`` (the dense learned heads: ``forward(all_q, local_img,
+    local_tgt)``); ``gt_global`` [Q_all] GLOBAL ground-truth ids, the same on every rank.
+
+    1. the owner reads the ground-truth score ``S[q, gt - lo]`` (masked and clamped: no data-dependent shape, no host read; zeros on
+       the other ranks) and ONE ``all_reduce_sum`` hands it to everybody -- 4 * Q_all bytes;
+    2. a non-finite ground-truth score is refused (``ranking._require_finite``);
+    3. ``ops.rank_dense_shard`` counts this shard's columns ahead of it and lists its k best with GLOBAL ids;
+    4. ``all_reduce_sum(ahead)`` -- 4 * Q_all bytes -- and, for k > 0, the candidate exchange + merge of ``ShardedGallery.search``.
+    Returns (ranks int64 [Q_all] 1-based, top scores, top ids), the same on every rank."""
+    world, _ = _world(group)
+    dev = local_scores.device
+    nq, nl = local_scores.shape
+    gt = gt_global.to(device=dev, dtype=torch.int32).reshape(-1)
+    if gt.numel() != nq:
+        raise ValueError(f"sharded_ranks_dense: {nq} score rows but {gt.numel()} ground-truth ids")
+    sgt = torch.zeros(nq, dtype=torch.float32, device=dev)
+    if nl > 0:
+        mine = (gt >= lo) & (gt < lo + nl)
+        local = (gt.long() - lo).clamp(0, nl - 1)
+        sgt = torch.where(mine, local_scores.gather(1, local.view(-1, 1)).reshape(-1).float(), sgt)
+    all_reduce_sum(sgt, group)                                     # exactly one rank contributed a non-zero per query
+    ranking._require_finite(sgt, "ground-truth scores")
+    ahead, s, i = ops.rank_dense_shard(local_scores, lo, gt, sgt, k)
+    pending = _exchange(s, i, k, world, group, ops) if k > 0 else None
+    all_reduce_sum(ahead, group)
+    if pending is not None:
+        s, i = pending.result()
+    return ahead.long() + 1, s, i

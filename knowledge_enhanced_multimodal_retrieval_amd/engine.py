@@ -875,6 +875,44 @@ def rank_dense(scores: torch.Tensor, gt_idx: Optional[torch.Tensor] = None, k: i
     return ahead, top_s, top_i
 
 
+def rank_dense_shard(scores: torch.Tensor, id_offset: int = 0, gt_idx: Optional[torch.Tensor] = None,
+                     gt_score: Optional[torch.Tensor] = None, k: int = 0
+                     ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """``rank_dense`` for ONE SHARD's columns of a score matrix (``kemr_rank_dense_shard``): column j is the candidate with the GLOBAL
+    id ``id_offset + j``; ``gt_idx`` holds GLOBAL ids (on this shard or not, < 0 = none) and ``gt_score`` the ground-truth pairs'
+    scores.  Returns (ahead int32 [nq] or None: this shard's columns ranked before the ground truth, top scores, top GLOBAL ids);
+    the per-shard ``ahead`` values sum to ``rank_dense``'s and ``topk_merge`` of the per-shard lists is its list.  An empty shard
+    (no columns) gives ahead = 0 and padding."""
+    L = _lib.lib()
+    _require_cuda(scores, "score matrix")
+    scores = scores.to(torch.float32)
+    if scores.stride(-1) != 1 or (scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]):
+        scores = scores.contiguous()
+    nq, ng = scores.shape
+    dev = scores.device
+    ld = scores.stride(0) if nq > 1 else max(ng, 1)
+    if (gt_idx is None) != (gt_score is None):
+        raise RuntimeError("rank_dense_shard: gt_idx and gt_score together")
+    ahead = gt = sgt = top_s = top_i = None
+    if gt_idx is not None:
+        gt = gt_idx.to(device=dev, dtype=torch.int32).contiguous()
+        sgt = gt_score.to(device=dev, dtype=torch.float32).contiguous()
+        if gt.numel() != nq or sgt.numel() != nq:
+            raise RuntimeError("rank_dense_shard: gt_idx and gt_score must have one entry per query")
+        ahead = torch.zeros(nq, dtype=torch.int32, device=dev)
+    if k > 0:
+        top_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev) if ng == 0 else \
+            torch.empty((nq, k), dtype=torch.float32, device=dev)
+        top_i = torch.full((nq, k), -1, dtype=torch.int32, device=dev) if ng == 0 else \
+            torch.empty((nq, k), dtype=torch.int32, device=dev)
+    if nq and ng:
+        with torch.cuda.device(dev):
+            _lib.check(L.kemr_rank_dense_shard(C.c_void_p(scores.data_ptr()), nq, ng, ld, int(id_offset), _opt_ptr(gt), _opt_ptr(sgt),
+                                               _opt_ptr(ahead), k, _opt_ptr(top_s), _opt_ptr(top_i), C.c_void_p(_stream_ptr(dev))),
+                       "rank_dense_shard")
+    return ahead, top_s, top_i
+
+
 def gate_rows(x: torch.Tensor, pre: Optional[torch.Tensor], w: torch.Tensor, bias: float, relu: bool,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``kemr_gate_rows``: sigmoid(sum_c act(x[r, c] + pre[c]) w[c] + bias) per row of the contiguous fp32 x [rows, cols] -> fp32

@@ -23,6 +23,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import _lib
+from . import dist as KD
 from . import engine
 from . import metrics as M
 from . import sparql_fusion as SF
@@ -193,13 +194,23 @@ def image_transform_name(dataset) -> str:
 
 @torch.no_grad()
 def encode_dataset(model, dataset, batch_size: int = 64, seed: int = 42, num_workers: Optional[int] = 0,
-                   tokenize_fn: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, List[str]]:
+                   tokenize_fn: Optional[Callable] = None, shard: Optional[Tuple[int, int]] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, List[str]]:
     """Hot loop A: (image, query, target) -> three L2-normalised embedding sets that stay on the GPU.
-    num_workers None = default_loader_workers()."""
+    num_workers None = default_loader_workers().
+    ``shard=(rank, world)``: only the items ``dist.shard_bounds(len(dataset), world, rank)`` are read and encoded (a ``Subset``); the
+    embeddings and uuids returned are that contiguous part's.  A rank whose part is empty encodes nothing and returns [0, D] tensors
+    whose width comes from the model.  None: the whole dataset, as before."""
     if num_workers is None:
         num_workers = default_loader_workers()
     model.eval()
     device = next(model.parameters()).device
+    if shard is not None:
+        lo, hi = KD.shard_bounds(len(dataset), int(shard[1]), int(shard[0]))
+        if hi == lo:
+            empty = torch.zeros((0, model_embed_dim(model)), dtype=torch.float32, device=device)
+            return empty, empty.clone(), empty.clone(), []
+        dataset = torch.utils.data.Subset(dataset, range(lo, hi))
     tokenize_fn = tokenize_fn or model_tokenize(model)
     loader = eval_loader(dataset, batch_size, seed, num_workers, tokenize_fn, pin=device.type == "cuda")
     img, qry, tgt, uuids = [], [], [], []
@@ -294,6 +305,68 @@ def encode_dataset(model, dataset, batch_size: int = 64, seed: int = 42, num_wor
     return torch.cat(img), torch.cat(qry), torch.cat(tgt), uuids
 
 
+def model_embed_dim(model) -> int:
+    """The width of a model's embeddings from the model itself (what a rank with an empty shard has instead of a tensor)."""
+    arch = getattr(model, "arch", None)
+    if arch is not None and hasattr(arch, "embed_dim"):
+        return int(arch.embed_dim)
+    if hasattr(model, "get_sentence_embedding_dimension"):
+        return int(model.get_sentence_embedding_dimension())
+    if hasattr(model, "embed_dim"):
+        return int(model.embed_dim)
+    raise RuntimeError(f"{type(model).__name__} states no embedding width (arch.embed_dim / get_sentence_embedding_dimension / embed_dim)")
+
+
+class _ShardedEmbeddings:
+    """One evaluation's embeddings sharded over the ranks of the process group (``dist.active_shard``): this rank's contiguous part,
+    padded to equal query rows (``dist.EvenRows``), and the ``ShardedGallery`` of each candidate set, built on first use.  Every
+    ``ranks`` / ``metrics`` call is collective and returns the same values on every rank; pad rows never reach a metric."""
+
+    def __init__(self, n: int, image: Optional[torch.Tensor], query: torch.Tensor, target: torch.Tensor, ops=None):
+        self.ops = ops if ops is not None else KD.eval_ops
+        self.even = KD.EvenRows(n)
+        self.device = query.device
+        self.local = {"image": image, "query": query, "target": target}
+        self.padded = {name: None if x is None else self.even.pad(x.float()) for name, x in self.local.items()}
+        self._galleries: Dict[Tuple[str, ...], KD.ShardedGallery] = {}
+
+    def gallery(self, *names: str, precision: str = "fp32x3") -> "KD.ShardedGallery":
+        key = names + (precision,)
+        if key not in self._galleries:
+            self._galleries[key] = KD.ShardedGallery([self.local[n].float() for n in names], self.even.n, precision=precision, ops=self.ops)
+        return self._galleries[key]
+
+    def ranks(self, query_names: Sequence[str], gallery_names: Sequence[str], weights=None, row_gate=None, bonus=None,
+              precision: str = "fp32x3") -> torch.Tensor:
+        if bonus is not None:
+            bonus = None if len(bonus[1]) == 0 else self.even.pad_bonus(bonus)
+        r = self.gallery(*gallery_names, precision=precision).ranks(
+            [self.padded[n] for n in query_names], self.even.local_gt(self.device), weights=weights, k=0, row_gate=row_gate, bonus=bonus)[0]
+        return self.even.real(r)
+
+    def metrics(self, query_names, gallery_names, prefix: str = "", k_values=M.DEFAULT_K, compute_recall: bool = True,
+                compute_mrr: bool = True, **kw) -> Dict[str, float]:
+        return M._metrics_of_ranks(self.ranks(query_names, gallery_names, **kw), prefix, k_values, compute_recall, compute_mrr)
+
+
+def _encode_sharded(model, dataset, batch_size, seed, num_workers, tokenize_fn, shard) -> Tuple[_ShardedEmbeddings, List[str]]:
+    image, query, target, uuids = encode_dataset(model, dataset, batch_size, seed, num_workers, tokenize_fn, shard=shard)
+    logger.info(f"rank {shard[0]} of {shard[1]}: {len(uuids)} of {len(dataset)} items encoded")
+    return _ShardedEmbeddings(len(dataset), image, query, target), uuids
+
+
+def _sparql_sweep_sharded(emb: _ShardedEmbeddings, uuids, text2sparql_results, t2i_weight, t2t_weight) -> Dict[str, Dict[str, float]]:
+    """``sparql_sweep`` over sharded embeddings: ``uuids`` are those of ALL items (gathered once by the caller), so the bonus CSR covers
+    every gathered query with GLOBAL columns and is the same on every rank; each shard adds the entries of its own id range."""
+    fused = (["query", "query"], ["image", "target"])
+    out = {"T2I": emb.metrics(["query"], ["image"]), "T2T": emb.metrics(["query"], ["target"]),
+           "Fused": emb.metrics(*fused, weights=[t2i_weight, t2t_weight])}
+    for alpha in ALPHAS:
+        scale, bonus = SF.sparql_bonus(text2sparql_results, uuids, uuids, "weighted", {"alpha": alpha, "sparql_weight": 1 - alpha})
+        out[f"weighted_alpha={alpha}"] = emb.metrics(*fused, weights=[scale * t2i_weight, scale * t2t_weight], bonus=bonus)
+    return out
+
+
 def sparql_sweep(query, target, image, uuids, text2sparql_results, t2i_weight, t2t_weight) -> Dict[str, Dict[str, float]]:
     """T2I / T2T / fused metrics + the 9-alpha weighted SPARQL fusion of evaluator.py:164-218, every variant one fused
     kernel pass (no N x N matrix, no dense 0/1 hit matrix)."""
@@ -314,7 +387,27 @@ def evaluate_clip_model(model, dataset, batch_size: int = 64, device: str = "cud
                         ) -> Dict[str, float]:
     """evaluator.py semantics: per-task metrics are returned; the fused / SPARQL-sweep analysis is logged and kept in
     ``evaluate_clip_model.last_analysis``.  ``num_workers`` defaults to the reference's 0 (evaluator.py:101); the CLIs opt into
-    ``default_loader_workers()``, a library caller passes a number (None = that default)."""
+    ``default_loader_workers()``, a library caller passes a number (None = that default).
+    With a process group of more than one rank (``dist.active_shard``) every rank encodes its contiguous part of the dataset, ranks
+    against its own shard and receives the same dict (``dist.ShardedGallery``)."""
+    shard = KD.active_shard()
+    if shard is not None:
+        emb, uuids = _encode_sharded(model, dataset, batch_size, seed, num_workers, tokenize_fn, shard)
+        pairs = {"T2I": ("query", "image"), "I2T": ("image", "target"), "T2T": ("query", "target")}
+        result = {}
+        for task in ("T2I", "I2T", "T2T"):
+            if task in tasks:
+                result.update(emb.metrics([pairs[task][0]], [pairs[task][1]], task, compute_recall=compute_recall, compute_mrr=compute_mrr))
+        evaluate_clip_model.last_analysis = {}
+        if analysis and compute_recall:
+            results = load_text2sparql_results() if text2sparql_results is None else text2sparql_results
+            all_uuids = KD.all_gather_list(uuids)                 # the one object exchange of an evaluation
+            for wi, wt in ((0.5, 0.5), (0.1, 0.9)):
+                sweep = _sparql_sweep_sharded(emb, all_uuids, results, wi, wt)
+                evaluate_clip_model.last_analysis[f"{wi}_{wt}"] = sweep
+                for name, m in sweep.items():
+                    logger.info(f"[t2i={wi} t2t={wt}] {name}: " + ", ".join(f"{k}={v:.2f}" for k, v in m.items()))
+        return result
     image, query, target, uuids = encode_dataset(model, dataset, batch_size, seed, num_workers, tokenize_fn)
     logger.info(f"Image embeddings: {tuple(image.shape)}")
     logger.info(f"Query embeddings: {tuple(query.shape)}")
@@ -347,7 +440,12 @@ def evaluate_clip_model_baseline(model, dataset, batch_size: int = 64, device: s
                                  compute_mrr: bool = True, t2i_weight: float = 0.5, t2t_weight: float = 0.5,
                                  tokenize_fn: Optional[Callable] = None, num_workers: Optional[int] = 4) -> Dict[str, float]:
     """evaluator_baseline.py semantics: metrics of the fused score w_i * T2I + w_t * T2T (un-prefixed keys); 4 loader workers
-    as there (evaluator_baseline.py:87)."""
+    as there (evaluator_baseline.py:87).  Sharded over the ranks of a process group like ``evaluate_clip_model``."""
+    shard = KD.active_shard()
+    if shard is not None:
+        emb, _ = _encode_sharded(model, dataset, batch_size, seed, num_workers, tokenize_fn, shard)
+        return emb.metrics(["query", "query"], ["image", "target"], compute_recall=compute_recall, compute_mrr=compute_mrr,
+                           weights=[t2i_weight, t2t_weight])
     image, query, target, _ = encode_dataset(model, dataset, batch_size, seed, num_workers, tokenize_fn)
     return M.compute_retrieval_metrics_final(query, target, image, compute_recall=compute_recall, compute_mrr=compute_mrr,
                                              t2i_weight=t2i_weight, t2t_weight=t2t_weight)
@@ -395,21 +493,67 @@ def _bind_tokenizer(model, args) -> None:
     model_tokenize(model)
 
 
+def _open_outputs(output_file: str, log_name: str) -> logging.Logger:
+    """The output directory and ``evaluation.log`` beside the results file: created by the writer rank only (``dist.is_writer``:
+    rank 0 of a process group, or the only process); the other ranks log to stderr."""
+    out_dir = Path(output_file).parent
+    if KD.is_writer():
+        out_dir.mkdir(parents=True, exist_ok=True)
+        setup_logger(log_name, str(out_dir / "evaluation.log"))
+    else:
+        setup_logger(log_name)
+    return logging.getLogger(log_name)
+
+
+def _sharding_record(n: int) -> Dict[str, object]:
+    """``world_size`` / ``items_per_rank`` of the results JSON (a sharded run only)."""
+    shard = KD.active_shard()
+    if shard is None:
+        return {}
+    return {"world_size": shard[1], "items_per_rank": [hi - lo for lo, hi in (KD.shard_bounds(n, shard[1], r) for r in range(shard[1]))]}
+
+
+def _save_results(results: dict, output_file: str) -> None:
+    """The results JSON, written by the writer rank only (every rank holds the same dict)."""
+    if KD.is_writer():
+        save_metrics_to_json(results, output_file)
+
+
+def _in_process_group(fn: Callable) -> Callable:
+    """A CLI body between ``dist.init_from_env()`` (first: RCCL is initialised before anything else touches the GPU) and
+    ``dist.finish()`` (last).  Under torchrun ``--device cuda`` means this rank's own device.  A rank that fails does not wait in
+    ``finish()``'s barrier for ranks that wait for it in a collective: the exception leaves the process and the launcher ends the rest."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapped(argv=None):
+        KD.init_from_env()
+        out = fn(argv)
+        KD.finish()
+        return out
+    return wrapped
+
+
+def _device_of(args) -> str:
+    """``--device``: under a process group a bare ``cuda`` is this rank's current device (set by ``dist.init_from_env``)."""
+    device = args.device if args.device.startswith("cuda") else "cuda"
+    if device == "cuda" and KD.active_shard() is not None and torch.cuda.is_available():
+        device = f"cuda:{torch.cuda.current_device()}"
+    return device
+
+
 def _run(args, baseline: bool, log_name: str):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     random.seed(args.seed)
-    out_dir = Path(args.output_file).parent
-    out_dir.mkdir(parents=True, exist_ok=True)
-    setup_logger(log_name, str(out_dir / "evaluation.log"))
-    log = logging.getLogger(log_name)
+    log = _open_outputs(args.output_file, log_name)
     log.info("=" * 80)
     log.info("CLIP Model Evaluation (MI355X HIP engine)")
     log.info(f"Model: {args.model_name}  Checkpoint: {args.checkpoint}  Split: {args.split}  Tasks: {args.tasks}  "
              f"MRR only: {args.mrr_only}  Seed: {args.seed}")
     if not torch.cuda.is_available():
         raise RuntimeError("no GPU visible: the encoders and the ranking run only in the HIP kernels (no CPU fallback)")
-    device = args.device if args.device.startswith("cuda") else "cuda"
+    device = _device_of(args)
     from . import clip_api, tokenizer
     from .clip_model import load_clip_model
     if args.synthetic > 0:           # synthetic data: seeded random weights / hash token ids are acceptable, and recorded below
@@ -444,20 +588,22 @@ def _run(args, baseline: bool, log_name: str):
                "weights_source": getattr(model, "weights_source", "unknown"), "tokenizer": model_tokenizer_name(model),
                "precision": _lib.env_precision(), "data": "synthetic" if args.synthetic > 0 else args.dataset,
                "image_transform": image_transform_name(dataset),
-               "loader_workers": workers}
+               "loader_workers": workers, **_sharding_record(len(dataset))}
     if not baseline:
         results["tasks"] = list(args.tasks)
-    save_metrics_to_json(results, args.output_file)
+    _save_results(results, args.output_file)
     log.info(f"Results saved to {args.output_file}")
     return results
 
 
+@_in_process_group
 def main_evaluator(argv=None):
     parser = argparse.ArgumentParser(description="Evaluate CLIP model")
     _common_args(parser, baseline=False)
     return _run(parser.parse_args(argv), baseline=False, log_name="src.clip.eval.evaluator")
 
 
+@_in_process_group
 def main_baseline(argv=None):
     parser = argparse.ArgumentParser(description="Evaluate CLIP model (fused T2I + T2T score)")
     _common_args(parser, baseline=True)
@@ -507,8 +653,13 @@ def evaluate_fusion_model(fusion_model, dataset, batch_size: int = 64, device: s
     if rerank_depth is not None:
         _check_rerank_depth(fusion_model.fusion_type, int(rerank_depth))
     fusion_model.eval()
-    image, query, target, uuids = encode_dataset(fusion_model.clip_model, dataset, batch_size, seed, num_workers, tokenize_fn)
     from . import ranking
+    shard = KD.active_shard()
+    if shard is not None:
+        result = _evaluate_fusion_sharded(fusion_model, dataset, batch_size, seed, tokenize_fn, num_workers, rerank_depth,
+                                          text2sparql_results, fusion_strategy, fusion_params, shard)
+        return _log_fusion_result(result)
+    image, query, target, uuids = encode_dataset(fusion_model.clip_model, dataset, batch_size, seed, num_workers, tokenize_fn)
     if rerank_depth is None:
         ranks, _, _ = fusion_model.rank(query, image, target, k=0)
         result = ranking.metrics_from_ranks(ranks, [1, 5, 10, 20])
@@ -526,10 +677,56 @@ def evaluate_fusion_model(fusion_model, dataset, batch_size: int = 64, device: s
         if fused:
             result["Head_Weight"] = float(fused["head_weight"])
             result["SPARQL_Strategy"] = fusion_strategy
+    return _log_fusion_result(result)
+
+
+def _log_fusion_result(result):
     logger.info("Fusion Model Evaluation Results")
     for k, v in result.items():
         logger.info(f"{k}: {v}" if isinstance(v, str) else f"{k}: {v:.2f}" + ("%" if ("R@" in k or "MRR" in k or "Recall" in k) else ""))
     return result
+
+
+def _evaluate_fusion_sharded(fusion_model, dataset, batch_size, seed, tokenize_fn, num_workers, rerank_depth, text2sparql_results,
+                             fusion_strategy, fusion_params, shard) -> Dict[str, float]:
+    """``evaluate_fusion_model`` over a process group, one route per head family:
+    gated family and bilinear: the head folds into the fused contraction (``FusionModel._parts`` of the padded local queries; a gate is a
+        function of its own query row) -> ``ShardedGallery.ranks(row_gate=...)``;
+    ``rerank_depth``: ``ShardedGallery.rerank`` against this rank's ``HeadGallery``, with or without the SPARQL bonus;
+    dense linear / cross_attention: all-gather the query embeddings (4 * D bytes per item), the head on (all queries) x (local
+        candidates), then ``dist.sharded_ranks_dense``."""
+    from . import ranking
+    emb, uuids = _encode_sharded(fusion_model.clip_model, dataset, batch_size, seed, num_workers, tokenize_fn, shard)
+    even, image, target, q_pad = emb.even, emb.local["image"], emb.local["target"], emb.padded["query"]
+    if rerank_depth is not None:
+        depth = int(rerank_depth)
+        fused = {}
+        if text2sparql_results is not None:
+            all_uuids = KD.all_gather_list(uuids)
+            head_weight, bonus = SF.sparql_bonus(text2sparql_results, all_uuids, all_uuids, fusion_strategy, fusion_params)
+            fused = {"bonus": even.pad_bonus(bonus), "head_weight": head_weight}
+        head_gallery = fusion_model.prepare_gallery(image, target) if even.hi > even.lo else None
+        ranks = emb.gallery("image", "target").rerank(fusion_model, head_gallery, q_pad, depth=depth, k=1,
+                                                      local_gt=even.local_gt(emb.device), **fused)[0]
+        ranks = even.real(ranks)
+        result = ranking.metrics_from_ranks(ranks, [1, 5, 10, 20])
+        result["Shortlist_Recall"] = float((ranks <= depth).double().mean().item() * 100.0)
+        result["Rerank_Depth"] = depth
+        if fused:
+            result["Head_Weight"] = float(fused["head_weight"])
+            result["SPARQL_Strategy"] = fusion_strategy
+        return result
+    if fusion_model.fusion_type in ("linear", "cross_attention"):
+        all_q = KD.all_gather_rows(q_pad)
+        if even.hi > even.lo:
+            scores = fusion_model.forward(all_q, image, target)
+        else:
+            scores = torch.zeros((all_q.shape[0], 0), dtype=torch.float32, device=emb.device)
+        ranks = KD.sharded_ranks_dense(scores, even.lo, even.all_gt(emb.device), k=0, ops=emb.ops)[0]
+        return ranking.metrics_from_ranks(even.real(ranks), [1, 5, 10, 20])
+    qs, _, weights, gates = fusion_model._parts(q_pad, image, target)     # the query side: (transformed) rows, weights, per-row gates
+    ranks = emb.gallery("image", "target").ranks(qs, even.local_gt(emb.device), weights=weights, k=0, row_gate=gates)[0]
+    return ranking.metrics_from_ranks(even.real(ranks), [1, 5, 10, 20])
 
 
 def _rerank_depth_arg(text: str) -> int:
@@ -571,6 +768,7 @@ def fusion_parser() -> argparse.ArgumentParser:
     return parser
 
 
+@_in_process_group
 def main_fusion(argv=None):
     import json
     parser = fusion_parser()
@@ -593,6 +791,8 @@ def main_fusion(argv=None):
     if args.synthetic > 0:
         clip_api.allow_random_weights(True)
         tokenizer.allow_hash_tokenizer(True)
+    if KD.active_shard() is not None:
+        args.device = _device_of(args)
     clip_model, preprocess = load_clip_model(model_name=args.model_name, checkpoint_path=args.clip_checkpoint, device=args.device)
     _bind_tokenizer(clip_model, args)
     embed_dim = clip_model.arch.embed_dim                 # 768 (ViT-L/14), 512 (ViT-B), 1024 (ViT-H-14); a directory states its own
@@ -613,7 +813,10 @@ def main_fusion(argv=None):
                "fusion_checkpoint": args.fusion_checkpoint, "fusion_type": args.fusion_type, "split": args.split,
                "num_samples": len(dataset), "metrics": result,
                "weights_source": getattr(clip_model, "weights_source", "unknown"), "tokenizer": model_tokenizer_name(clip_model),
-               "precision": _lib.env_precision(), "data": "synthetic" if args.synthetic > 0 else args.dataset}
+               "precision": _lib.env_precision(), "data": "synthetic" if args.synthetic > 0 else args.dataset,
+               **_sharding_record(len(dataset))}
+    if not KD.is_writer():
+        return results
     if args.output_file:
         Path(args.output_file).parent.mkdir(parents=True, exist_ok=True)
         with open(args.output_file, "w") as f:
@@ -641,6 +844,23 @@ def evaluate_text_model(model, dataset, batch_size: int = 32, device: str = "cud
     must be the model's.  `num_workers`: the texts are strings in memory, 0 (the default here; the reference forks 4) loses nothing."""
     model = model.to(device)
     model.eval()
+    shard = KD.active_shard()
+    if shard is not None:                      # this rank's contiguous part of the pairs; ranked against the sharded targets
+        n = len(dataset)
+        lo, hi = KD.shard_bounds(n, shard[1], shard[0])
+        queries, targets = [], []
+        logger.info(f"rank {shard[0]} of {shard[1]}: encoding texts for {hi - lo} of {n} samples...")
+        if hi > lo:
+            for q, t in _text_loader(torch.utils.data.Subset(dataset, range(lo, hi)), batch_size, seed, collate_fn_eval_texts,
+                                     num_workers=num_workers):
+                queries.append(model.encode(q, convert_to_tensor=True, device=device, show_progress_bar=False, normalize_embeddings=True))
+                targets.append(model.encode(t, convert_to_tensor=True, device=device, show_progress_bar=False, normalize_embeddings=True))
+            query, target = torch.cat(queries), torch.cat(targets)
+        else:
+            query = torch.zeros((0, model_embed_dim(model)), dtype=torch.float32, device=device)
+            target = query.clone()
+        return _ShardedEmbeddings(n, None, query, target).metrics(["query"], ["target"], "T2T", compute_recall=compute_recall,
+                                                                  compute_mrr=compute_mrr)
     queries, targets = [], []
     logger.info(f"Encoding texts for {len(dataset)} samples...")
     for q, t in _text_loader(dataset, batch_size, seed, collate_fn_eval_texts, num_workers=num_workers):
@@ -709,23 +929,21 @@ def _save_text_results(log, args, dataset, metrics, extra) -> dict:
         log.info(f"{name}: {value:.2f}" + ("" if "Mean_Rank" in name else "%"))
     results = {"model_name": args.model_name, "split": args.split, "num_samples": len(dataset), "seed": args.seed, "metrics": metrics,
                "precision": _lib.env_precision(), **extra}
-    save_metrics_to_json(results, args.output_file)
+    _save_results(results, args.output_file)
     log.info(f"Results saved to {args.output_file}")
     return results
 
 
+@_in_process_group
 def main_text_lm(argv=None):
     args = text_lm_parser().parse_args(argv)
     _seed_all(args.seed)
-    out_dir = Path(args.output_file).parent
-    out_dir.mkdir(parents=True, exist_ok=True)
     name = "src.clip.eval.evaluator_lm"
-    setup_logger(name, str(out_dir / "evaluation.log"))
-    log = logging.getLogger(name)
+    log = _open_outputs(args.output_file, name)
     log.info(f"Text-Only Model Evaluation (T2T only, MI355X HIP engine)  Model: {args.model_name}  Split: {args.split}  MRR only: {args.mrr_only}  Seed: {args.seed}")
     if not torch.cuda.is_available():
         raise RuntimeError("no GPU visible: the encoder and the ranking run only in the HIP kernels (no CPU fallback)")
-    device = args.device if args.device.startswith("cuda") else "cuda"
+    device = _device_of(args)
     model = _load_sentence_encoder(args.model_name, device)
     if args.synthetic > 0:
         dataset = TextOnlyDatasetHF(_SyntheticTextSplit(args.synthetic, args.seed))
@@ -734,7 +952,8 @@ def main_text_lm(argv=None):
         dataset = TextOnlyDatasetHF(load_dataset(args.dataset)[{"val": "validation"}.get(args.split, args.split)])
     fn = evaluate_text_model_for_training if args.mrr_only else evaluate_text_model
     metrics = fn(model, dataset, batch_size=args.batch_size, device=device, seed=args.seed)
-    return _save_text_results(log, args, dataset, metrics, {"data": "synthetic" if args.synthetic > 0 else args.dataset})
+    return _save_text_results(log, args, dataset, metrics, {"data": "synthetic" if args.synthetic > 0 else args.dataset,
+                                                            **_sharding_record(len(dataset))})
 
 
 # ---- the legacy five-variant script (reference: baselines/evaluate_text_models.py)
