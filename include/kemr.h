@@ -142,7 +142,7 @@ typedef enum kemr_tower { KEMR_TOWER_VISION = 0, KEMR_TOWER_TEXT = 1 } kemr_towe
 #define KEMR_MAX_VISION_TOKENS 1025
 #define KEMR_MAX_TEXT_CTX 288
 /* families 2 and 3 (BERT and MPNet sentence encoders): the longest text, absolute positions 0 .. 511 (non-causal attention over packed
- * items of different lengths, csrc/attention_varlen.hip; family 3's relative position bias spans the distances -511 .. 511) */
+ * items of different lengths, csrc/attention_stream.hip; family 3's relative position bias spans the distances -511 .. 511) */
 #define KEMR_MAX_BERT_CTX 512
 
 /* Architecture numbers of an OpenAI-CLIP style model (MLP is 4*width; heads are width/64, except a vision tower under option
@@ -218,7 +218,7 @@ int kemr_model_create(const kemr_cfg* cfg, kemr_model** out);
  *   relative_position_bucket at 32 buckets and max distance 128, by integer thresholds: with n = query - key, 16 is added when n < 0;
  *   |n| < 8 is bucket |n|; buckets 8 .. 15 begin at |n| = 8, 12, 16, 23, 32, 46, 64, 91.  Finalize expands the 32 buckets once into a
  *   device table by distance, fp32 [heads, 1023], that the attention kernel stages per head into LDS and reads as the start value of its
- *   score accumulators (fp32, unscaled, no rounding of the bias; csrc/attention_varlen.hip).
+ *   score accumulators (fp32, unscaled, no rounding of the bias; csrc/attention_stream.hip).
  *   LayerNorm eps: option "layer_norm_eps" below, 1e-5 by default.
  *   A text's token j sits at position j: what MPNetModel computes whenever no <pad> id occurs inside a text's length. */
 int kemr_model_create_family(const kemr_cfg* cfg, int family, kemr_model** out);
@@ -318,7 +318,7 @@ int kemr_encode_text(kemr_model* m, const int32_t* ids_dev, int batch, float* ou
  * A length shorter than argmax_i + 1 pools text i's last computed row (memory-safe, not the reference's embedding).
  * Served for family 0 at every ctx <= KEMR_MAX_TEXT_CTX (Long-CLIP's 248 positions included) in the bf16-operand and the fp8 precisions
  * (whose text tower is bf16): texts of up to 128 positions run the tile attention kernels, longer contexts the causal streaming
- * kernel (csrc/attention_varlen.hip), both one launch over all packed texts.  A KEMR_PREC_FP32X3 model is served packed up to ctx =
+ * kernel (csrc/attention_stream.hip), both one launch over all packed texts.  A KEMR_PREC_FP32X3 model is served packed up to ctx =
  * 128 only: above, this call and kemr_encode_text_packed_pooled return KEMR_ERR_INVALID and kemr_encode_text is the call to make. */
 size_t kemr_text_packed_workspace_bytes(const kemr_model* m, int rows, int batch);
 int kemr_encode_text_packed(kemr_model* m, const int32_t* ids_dev, const int32_t* lens_dev, int rows, int batch, float* out_dev,

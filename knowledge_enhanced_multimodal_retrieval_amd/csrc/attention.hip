@@ -1,6 +1,6 @@
 // Multi-head self-attention for the CLIP towers (head dim 64; T = 257 / 197 / 50 non-causal, T = 77 causal).
 //
-// Sequences of more than 288 tokens (non-causal) go to the streaming kernel of attention_long.hip.
+// Sequences of more than 288 tokens (non-causal) go to the streaming kernel of attention_stream.hip.
 //
 // One workgroup of NW waves per (image or text, head): NW = 4, or 5 for the 77-token text tower (5 query tiles: one per wave
 // instead of 2 / 1 / 1 / 1; with the key tiles behind the causal diagonal skipped: 27.7 -> 22.7 us per launch at B = 255).
@@ -23,28 +23,9 @@
 
 namespace kemr {
 
-__device__ __forceinline__ bf16x4 lds_read_tr16(const char* p) {
-    typedef __attribute__((ext_vector_type(4))) short s4;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)p);
-}
-
 // TC > 0: the sequence length is a compile-time constant (257 / 77: the shapes that matter), so every pad-key mask and
 // tile-skip test folds away; TC == 0 keeps T a run-time value (other models, tests).  With a run-time T the uniform
 // conditions of the 18 unrolled tiles overflowed the SGPR file (150+ v_readlane/v_writelane spills per query tile).
-// Which (head, image) a workgroup computes.  xbatch == 0: blockIdx.x = head, blockIdx.y = image.  xbatch = the batch size: the
-// grid is (heads, batch rounded up to 8) and the workgroups -- dealt to the eight XCDs round-robin by their linear id -- are
-// renumbered so that XCD x computes the images = x (mod 8), all heads of an image next to each other in time: the 128-byte
-// slices the sixteen heads take out of one token's 6 KB q|k|v row then come through ONE L2 at about the same time instead of
-// through eight (round 3: 155 -> 150 us at B = 255 x 16 heads, bit-identical results; the default, debug switch attn_xcd).
-__device__ __forceinline__ bool attn_item(int xbatch, int& h, int& b) {
-    h = blockIdx.x; b = blockIdx.y;
-    if (xbatch == 0) return true;
-    const int id = blockIdx.y * gridDim.x + blockIdx.x, j = id >> 3;
-    b = (j / (int)gridDim.x) * 8 + (id & 7);
-    h = j % (int)gridDim.x;
-    return b < xbatch;
-}
-
 // NTLOAD (round 4, the default): the q | k | v rows are read ONCE per launch (K / V by the one workgroup of their head, a Q row by one wave),
 // so they are loaded non-temporally and do not displace the attention output -- which the out-proj GEMM reads next -- from L2 / Infinity
 // Cache: vision launch 147.2 -> 144.6 us alone, 4.50 -> 4.43 ms per step in the chain, bit-identical (tools/bench_attention_ab.py 0:0,0:7).
@@ -304,7 +285,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_kernel(const bf16_t* __r
 // by `build.py --ab-variants`; the product library holds ONE attention kernel per shape and kemr_debug_set refuses the others.
 int g_attn_v = 0;          // A/B builds only (attention_ab.hip), T = 257: 0 = the product kernel, 1..5 = the experiments
 
-int g_attn_xcd = 1;        // 1 = the images dealt to the XCDs (attn_item above; default), 0 = grid order (tools)
+int g_attn_xcd = 1;        // 1 = the images dealt to the XCDs (attn_item, common.h; default), 0 = grid order (tools)
 int g_attn_waves = 0;      // tools: 0 = the default choice below, else waves per workgroup for the 257-token shape (4 or 6)
 
 #ifdef KEMR_AB_VARIANTS
@@ -363,7 +344,7 @@ int launch_attention(const bf16_t* qkv, bf16_t* out, int batch, int t, int width
         case 8: return launch_nt<8>(qkv, out, batch, t, width, causal, stream);
         case 9: return launch_nt<9>(qkv, out, batch, t, width, causal, stream);
     }
-    // longer sequences: non-causal only (the vision towers of larger images), K / V streamed (attention_long.hip)
+    // longer sequences: non-causal only (the vision towers of larger images), K / V streamed (attention_stream.hip)
     if (!causal && t <= KEMR_MAX_VISION_TOKENS) return launch_attention_long(qkv, out, batch, t, width, stream);
     if (!causal) KEMR_FAIL(KEMR_ERR_INVALID, "attention: sequence length %d > %d not supported", t, KEMR_MAX_VISION_TOKENS);
     KEMR_FAIL(KEMR_ERR_INVALID, "attention: sequence length %d > 288 not supported (causal)", t);
@@ -377,11 +358,6 @@ int launch_attention(const bf16_t* qkv, bf16_t* out, int batch, int t, int width
 // the 1/sqrt(64) lives in the packed q weights); k, v: the qkv buffer of the whole call (ld 3 * width); out: [items, width] compact.
 // Item b's keys are the rows key0[b] .. key0[b] + nkeys[b] - 1, taken from pool_idx / row_start:
 //   vision (causal = 0): all `tokens` rows from b * tokens;  text: the rows from the text's first up to the pooled one.
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // MAXK: keys per item the LDS row holds -- 320 (every tower of at most 320 tokens: this instantiation is the one of the 224 px models,
 // unchanged) or KEMR_MAX_VISION_TOKENS rounded up to 64 (the long vision towers; the extra passes add exp2(-inf) = +0 to the sum and
@@ -493,7 +469,7 @@ int launch_attention_pooled(const bf16_t* q, const bf16_t* qkv, bf16_t* out, con
 
 // Causal attention over items of different lengths packed one behind the other: item b = rows row_start[b] .. row_start[b + 1] - 1
 // (device array of batch + 1 ints), every length in 1 .. max_t.  max_t <= 128: the tile kernels above, one workgroup per item and
-// head; 129 .. KEMR_MAX_TEXT_CTX: the causal instantiation of the streaming kernel (attention_varlen.hip).
+// head; 129 .. KEMR_MAX_TEXT_CTX: the causal instantiation of the streaming kernel (attention_stream.hip).
 int launch_attention_packed(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream) {
     if (batch <= 0) return KEMR_OK;
     if (!row_start) KEMR_FAIL(KEMR_ERR_INVALID, "attention: packed rows need row_start");

@@ -47,19 +47,6 @@ constexpr int HD = 80;             // head dim
 constexpr int ROWB = HD * 2;       // bytes per K / V row in LDS
 constexpr int RCH = HD / 8;        // 16-byte chunks per row
 
-__device__ __forceinline__ bf16x4 lds80_read_tr16(const char* p) {
-    typedef __attribute__((ext_vector_type(4))) short s4;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)p);
-}
-
-// attention.hip attn_item: XCD x computes the images = x (mod 8), all heads of an image next to each other in time
-__device__ __forceinline__ bool attn80_item(int xbatch, int& h, int& b) {
-    const int id = blockIdx.y * gridDim.x + blockIdx.x, j = id >> 3;
-    b = (j / (int)gridDim.x) * 8 + (id & 7);
-    h = j % (int)gridDim.x;
-    return b < xbatch;
-}
-
 typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
 
 template <int NT32, int TC, int NW>        // keys padded to NT32 * 32; TC > 0: compile-time sequence length; NW waves per workgroup
@@ -76,7 +63,8 @@ __global__ __launch_bounds__(NW * 64) void attention80_kernel(const bf16_t* __re
     char* sZ = smem + 2 * TP * ROWB;                    // 16 bytes of zeros: the K operand of the k slots 16..31 of the third step
 
     int h, b;
-    if (!attn80_item(xbatch, h, b)) return;             // (the whole workgroup)
+    __builtin_assume(xbatch != 0);                      // xbatch = batch >= 1: this kernel always deals the images to the XCDs
+    if (!attn_item(xbatch, h, b)) return;               // (the whole workgroup)
     const int T = TC > 0 ? TC : T_rt;
     const size_t row0 = (size_t)b * T;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -204,8 +192,8 @@ __global__ __launch_bounds__(NW * 64) void attention80_kernel(const bf16_t* __re
 #pragma unroll
             for (int dt = 0; dt < 5; ++dt) {
                 const int cb = dt * 32 + (lrow & 3) * 8;        // columns 16 dt + 4 (lrow & 3) .. + 3 of the row
-                const bf16x4 va = lds80_read_tr16(sV + ra * ROWB + cb);
-                const bf16x4 vb = lds80_read_tr16(sV + rb * ROWB + cb);
+                const bf16x4 va = lds_read_tr16(sV + ra * ROWB + cb);
+                const bf16x4 vb = lds_read_tr16(sV + rb * ROWB + cb);
                 dst[dt][0] = va[0]; dst[dt][1] = va[1]; dst[dt][2] = va[2]; dst[dt][3] = va[3];
                 dst[dt][4] = vb[0]; dst[dt][5] = vb[1]; dst[dt][6] = vb[2]; dst[dt][7] = vb[3];
             }
@@ -267,11 +255,6 @@ int launch80_nt(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, hip
 // attention_pooled_kernel's arithmetic: the scores of the one query against the item's keys (a lane's eight bf16 products summed in
 // fp32 by fma, then the lanes of the key by shuffles), softmax in fp32 with P rounded to bf16 and the row sum taken before the
 // rounding, out[d] = sum_j p_j v_j[d] over the keys of a parity in order, the two parities added, one division.
-__device__ __forceinline__ void wave80_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 constexpr int PMAXK = 320;         // keys per item the LDS row holds (towers of head dim 80 have at most 288 tokens)
 
@@ -321,7 +304,7 @@ __global__ __launch_bounds__(256) void attention80_pooled_kernel(const bf16_t* _
         s += __shfl_xor(s, 8);
         if (ck == 0 && j < nk) sp[wv][j] = s;
     }
-    wave80_lds_fence();
+    wave_lds_fence();
     float sc[PMAXK / 64];
     float mx = -INFINITY;
 #pragma unroll
@@ -342,7 +325,7 @@ __global__ __launch_bounds__(256) void attention80_pooled_kernel(const bf16_t* _
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    wave80_lds_fence();                                  // the bf16-rounded P row: stores of all lanes before any lane's loads
+    wave_lds_fence();                                  // the bf16-rounded P row: stores of all lanes before any lane's loads
     // lane = (dq: columns 4 dq .. 4 dq + 3, key parity): lanes 0..19 the even keys, 20..39 the odd ones, 40..63 idle
     const int par = lane / 20, dq = lane - par * 20;
     float a[4] = {0.f, 0.f, 0.f, 0.f};
@@ -375,17 +358,6 @@ constexpr int AK = 32;     // keys per chunk
 constexpr int KLD = 104;   // bf16 per K row in LDS: 80 + 16 zeros + 8 (208 B = 13 slots of 16 B: ds_read_b128 of 16 consecutive rows spread over the banks)
 constexpr int VLD = 40;    // bf16 per V^T row: 32 slots + 8 (80 B)
 
-__device__ __forceinline__ void split8_80(const float4 a, const float4 b, bf16x8& hi, bf16x8& lo) {
-    u32x4_ h, l;
-    uint32_t x, y;
-    split_bf16x2(a.x, a.y, x, y); h.x = x; l.x = y;
-    split_bf16x2(a.z, a.w, x, y); h.y = x; l.y = y;
-    split_bf16x2(b.x, b.y, x, y); h.z = x; l.z = y;
-    split_bf16x2(b.z, b.w, x, y); h.w = x; l.w = y;
-    hi = __builtin_bit_cast(bf16x8, h);
-    lo = __builtin_bit_cast(bf16x8, l);
-}
-
 __global__ __launch_bounds__(256) void attention80_x3_kernel(const float* __restrict__ qkv, bf16_t* __restrict__ out, int T, int width) {
     __shared__ __attribute__((aligned(16))) bf16_t sKh[AK * KLD];
     __shared__ __attribute__((aligned(16))) bf16_t sKl[AK * KLD];
@@ -413,7 +385,7 @@ __global__ __launch_bounds__(256) void attention80_x3_kernel(const float* __rest
             a = *(const float4*)src;
             bb = *(const float4*)(src + 4);
         }
-        split8_80(a, bb, qh[c], ql[c]);
+        split8(a, bb, qh[c], ql[c]);
     }
     // the K image's pad columns 80..95, zeroed once (the staging below never writes them; the loop's first barrier orders this)
     if (tid < AK * 2) {
@@ -500,7 +472,7 @@ __global__ __launch_bounds__(256) void attention80_x3_kernel(const float* __rest
         }
         lsum = lsum * alpha + psum;
         bf16x8 ph, pl;
-        split8_80(make_float4(p[0], p[1], p[2], p[3]), make_float4(p[4], p[5], p[6], p[7]), ph, pl);
+        split8(make_float4(p[0], p[1], p[2], p[3]), make_float4(p[4], p[5], p[6], p[7]), ph, pl);
 #pragma unroll
         for (int dt = 0; dt < 5; ++dt) {
             const int off = (dt * 16 + lq) * VLD + g * 8;

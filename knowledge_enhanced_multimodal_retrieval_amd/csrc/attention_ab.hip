@@ -11,21 +11,6 @@
 
 namespace kemr {
 
-__device__ __forceinline__ bf16x4 lds_read_tr16(const char* p) {
-    typedef __attribute__((ext_vector_type(4))) short s4;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)p);
-}
-
-// (as in attention.hip) which (head, image) a workgroup computes; xbatch != 0: XCD x computes the images = x (mod 8)
-__device__ __forceinline__ bool attn_item(int xbatch, int& h, int& b) {
-    h = blockIdx.x; b = blockIdx.y;
-    if (xbatch == 0) return true;
-    const int id = blockIdx.y * gridDim.x + blockIdx.x, j = id >> 3;
-    b = (j / (int)gridDim.x) * 8 + (id & 7);
-    h = j % (int)gridDim.x;
-    return b < xbatch;
-}
-
 // ---- T = 257 (ViT-L/14 and ViT-B/16 vision towers): 32-query tiles on v_mfma_f32_32x32x16_bf16 (round 3) ---------------------------
 // Round 2's PMC pass of the 16-query kernel above put a wave at one third issuing, one third parked at s_waitcnt and one third
 // issue-stalled, MFMA pipe 20 % busy: per 16 queries it issues 72 MFMAs, 36 + 72 LDS reads and ~1 100 cycles of softmax VALU, with

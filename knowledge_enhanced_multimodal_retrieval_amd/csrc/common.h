@@ -79,6 +79,18 @@ __device__ __forceinline__ void split_bf16x2(float a, float b, uint32_t& hi, uin
     hi = pack_bf16x2(a, b);
     lo = pack_bf16x2(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
 }
+// 8 fp32 -> the hi and lo MFMA fragments of that pair
+__device__ __forceinline__ void split8(const float4 a, const float4 b, bf16x8& hi, bf16x8& lo) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 h, l;
+    uint32_t x, y;
+    split_bf16x2(a.x, a.y, x, y); h.x = x; l.x = y;
+    split_bf16x2(a.z, a.w, x, y); h.y = x; l.y = y;
+    split_bf16x2(b.x, b.y, x, y); h.z = x; l.z = y;
+    split_bf16x2(b.z, b.w, x, y); h.w = x; l.w = y;
+    hi = __builtin_bit_cast(bf16x8, h);
+    lo = __builtin_bit_cast(bf16x8, l);
+}
 // QuickGELU x * sigmoid(1.702 x) with v_exp_f32 / v_rcp_f32 (exp2 with the constant folded; rcp is 1 ulp)
 __device__ __forceinline__ float quick_gelu(float v) {
     return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * v));
@@ -155,6 +167,32 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
+}
+
+// ---- attention helpers (attention.hip, attention80.hip, attention_stream.hip, attention_ab.hip) ----------------------------
+// ds_read_b64_tr_b16: the transposed read that makes a V^T MFMA fragment out of the row-major V image
+__device__ __forceinline__ bf16x4 lds_read_tr16(const char* p) {
+    typedef __attribute__((ext_vector_type(4))) short s4;
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)p);
+}
+// LDS stores of all lanes of a wave before any lane's loads (a wave working on its own: no workgroup barrier)
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// Which (head, image) a workgroup computes.  xbatch == 0: blockIdx.x = head, blockIdx.y = image.  xbatch = the batch size: the
+// grid is (heads, batch rounded up to 8) and the workgroups -- dealt to the eight XCDs round-robin by their linear id -- are
+// renumbered so that XCD x computes the images = x (mod 8), all heads of an image next to each other in time: the 128-byte
+// slices the sixteen heads take out of one token's 6 KB q|k|v row then come through ONE L2 at about the same time instead of
+// through eight (round 3: 155 -> 150 us at B = 255 x 16 heads, bit-identical results; the default, debug switch attn_xcd).
+__device__ __forceinline__ bool attn_item(int xbatch, int& h, int& b) {
+    h = blockIdx.x; b = blockIdx.y;
+    if (xbatch == 0) return true;
+    const int id = blockIdx.y * gridDim.x + blockIdx.x, j = id >> 3;
+    b = (j / (int)gridDim.x) * 8 + (id & 7);
+    h = j % (int)gridDim.x;
+    return b < xbatch;
 }
 
 // ---- optional per-kernel-class event timing (api.hip); used by bench.py for the roofline line --------
@@ -272,15 +310,15 @@ int launch_attention_x3(const float* qkv, bf16_t* out_panel, const int* row_star
 // im2col whose rows are A-side triples [B * P, 3 kpad]
 int launch_im2col_x3(const float* pixels, bf16_t* patches, int batch, int image_size, int patch, int kpad, hipStream_t stream);
 int launch_attention(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, int causal, hipStream_t stream);
-// non-causal, t up to KEMR_MAX_VISION_TOKENS: K / V streamed through LDS with an online softmax (attention_long.hip)
+// non-causal, t up to KEMR_MAX_VISION_TOKENS: K / V streamed through LDS with an online softmax (attention_stream.hip, the fixed-length instantiation)
 int launch_attention_long(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, hipStream_t stream);
-// attention_varlen.hip: NON-causal, items of lengths 1 .. max_t <= KEMR_MAX_BERT_CTX packed one behind the other (row_start as below): the
+// attention_stream.hip, PACKED: NON-causal, items of lengths 1 .. max_t <= KEMR_MAX_BERT_CTX packed one behind the other (row_start as below): the
 // BERT family's attention; per item the arithmetic of launch_attention_long at t = its length
 // bias_by_distance (family 3, MPNet; nullptr = no bias, the kernel as it was): fp32 [width / 64, 1023] on the device, entry [h][d + 511]
 // is added to the score of every (query, key) pair of head h with key - query = d
 int launch_attention_varlen(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream,
                             const float* bias_by_distance = nullptr);
-// attention_varlen.hip's CAUSAL instantiation (no bias): max_t <= KEMR_MAX_TEXT_CTX; launch_attention_packed's route above 128 rows
+// attention_stream.hip's PACKED CAUSAL instantiation (no bias): max_t <= KEMR_MAX_TEXT_CTX; launch_attention_packed's route above 128 rows
 int launch_attention_varlen_causal(const bf16_t* qkv, bf16_t* out, const int* row_start, int batch, int max_t, int width, hipStream_t stream);
 // causal, items of lengths 1 .. max_t <= KEMR_MAX_TEXT_CTX packed one behind the other: item b = rows row_start[b] .. row_start[b + 1] - 1
 // (device ints); max_t <= 128: the tile kernels of attention.hip, above: the streaming kernel

@@ -27,20 +27,6 @@ constexpr int AK = 32;     // keys per chunk
 constexpr int KLD = 72;    // bf16 per K row in LDS: 64 + 8 (144 B: ds_read_b128 of 16 consecutive rows spread over the banks)
 constexpr int VLD = 40;    // bf16 per V^T row: 32 slots + 8 (80 B)
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-
-// 8 fp32 -> the hi and lo MFMA fragments
-__device__ __forceinline__ void split8(const float4 a, const float4 b, bf16x8& hi, bf16x8& lo) {
-    u32x4_t h, l;
-    uint32_t x, y;
-    split_bf16x2(a.x, a.y, x, y); h.x = x; l.x = y;
-    split_bf16x2(a.z, a.w, x, y); h.y = x; l.y = y;
-    split_bf16x2(b.x, b.y, x, y); h.z = x; l.z = y;
-    split_bf16x2(b.z, b.w, x, y); h.w = x; l.w = y;
-    hi = __builtin_bit_cast(bf16x8, h);
-    lo = __builtin_bit_cast(bf16x8, l);
-}
-
 __global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restrict__ qkv, bf16_t* __restrict__ out,
                                                            const int* __restrict__ row_start, int T, int width, int causal) {
     __shared__ __attribute__((aligned(16))) bf16_t sKh[AK * KLD];

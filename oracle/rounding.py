@@ -156,7 +156,7 @@ def _attention_rows(q, k, v, mask):
 
 
 def attention_long_emulation(qkv_bf16, batch, t, width, kc=64):
-    """fp64 statement of what csrc/attention_long.hip computes (non-causal, K / V streamed in chunks of kc keys; KEMR_ATTN_LONG_KC,
+    """fp64 statement of what csrc/attention_stream.hip computes (non-causal, K / V streamed in chunks of kc keys; KEMR_ATTN_STREAM_KC,
     default 64).  The kernel rounds P to bf16 against the RUNNING maximum of the keys seen so far, not the final one, so
     attention_emulation (one pass, final maximum) does not state it.  Per query row, for chunk c (keys c kc .. min(T, (c + 1) kc) - 1;
     the pad keys of the ragged last chunk are -inf, i.e. absent):

@@ -1,6 +1,6 @@
 """Fixtures and references the Long-CLIP tests share (tests/test_longclip_*.py).  Not a test module; no GPU, no library.
 
-* the packed causal attention over items of up to 288 rows (csrc/attention_varlen.hip, CAUSAL instantiation): the length set, the
+* the packed causal attention over items of up to 288 rows (csrc/attention_stream.hip, PACKED CAUSAL instantiation): the length set, the
   operands, and the per-item fp64 statement ``oracle.rounding._attention_chunked`` with the lower-triangular key mask;
 * the tiny ctx-248 architecture (config.ARCHS["tiny-ctx248"]): the oracle's dict of it, seeded weights from the oracle's generator,
   and texts whose end-of-text tokens sit at chosen positions;
@@ -16,7 +16,7 @@ from knowledge_enhanced_multimodal_retrieval_amd.config import ARCHS
 from oracle import clip_ref
 from oracle import rounding as R
 
-KC = 64                      # keys per chunk of the streaming kernel (KEMR_ATTN_VARLEN_KC)
+KC = 64                      # keys per chunk of the streaming kernel (KEMR_ATTN_STREAM_KC)
 MAX_T = 288                  # KEMR_MAX_TEXT_CTX
 # the edges of a 16-query tile, a 64-key chunk and a 128-query block, and the longest item: 2 009 rows in one packed call
 LENGTHS = [1, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 248, 287, 288]

@@ -158,7 +158,7 @@ def wrong_tables(table):
 
 # ------------------------------------------------------------------------------------------------ biased attention: the rounding statement
 def attention_varlen_bias_emulation(qkv_bf16, row_start, width, table, kc=64):
-    """fp64 statement of csrc/attention_varlen.hip's BIAS instantiation, per packed item on its own rows: oracle.rounding
+    """fp64 statement of csrc/attention_stream.hip's BIAS instantiation, per packed item on its own rows: oracle.rounding
     attention_long_emulation (``_attention_chunked``) restated with s = q . k + bias[h][key - query].  The bias enters the kernel as the
     START VALUE of the fp32 accumulator of the score's first MFMA (the second MFMA continues from it), so the kernel's score is the fp32
     sum of bias and 64 bf16 products accumulated in the MFMAs' order; q carries the 1/8 and the bias is not scaled.  Everything after the

@@ -1,4 +1,4 @@
-"""GPU: non-causal attention beyond 288 tokens (csrc/attention_long.hip: K / V streamed through LDS with an online softmax) against
+"""GPU: non-causal attention beyond 288 tokens (csrc/attention_stream.hip, fixed length: K / V streamed through LDS with an online softmax) against
 the fp32 softmax of the same bf16 inputs, with the bars of tests/test_ops_gpu.py::test_attention, and against the fp64 statement of
 its chunked rounding (oracle/rounding.py attention_long_emulation: budget ratio <= 1, |signed bias| <= 0.02 ulp); and the pooled-row
 attention of the last block at 577 tokens."""

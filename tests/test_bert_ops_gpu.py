@@ -1,9 +1,9 @@
 """GPU: the kernels of the BERT sentence encoders (model family 2) alone, each against its fp64 statement and rounding budget
-(oracle/rounding.py check_budget): the non-causal attention over packed items of different lengths (csrc/attention_varlen.hip), the
+(oracle/rounding.py check_budget): the non-causal attention over packed items of different lengths (csrc/attention_stream.hip, PACKED), the
 post-LN LayerNorm mode, the embedding front and the pooling tail.
 
-The attention kernel is csrc/attention_long.hip's tile code with the length read per item: per item its arithmetic and order are
-attention_long's at T = the item's length, so ``rounding.attention_long_emulation`` called per item states it, with the bars of
+The attention kernel is the fixed-length instantiation's code with the length read per item: per item its arithmetic and order are
+that instantiation's at T = the item's length, so ``rounding.attention_long_emulation`` called per item states it, with the bars of
 tests/test_attention_long_gpu.py (budget ratio <= 1, |signed bias| <= 0.02 ulp)."""
 import pytest
 import torch

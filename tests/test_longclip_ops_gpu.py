@@ -1,4 +1,4 @@
-"""GPU: the causal attention over packed items of 129 .. 288 rows alone (csrc/attention_varlen.hip, CAUSAL instantiation; reached
+"""GPU: the causal attention over packed items of 129 .. 288 rows alone (csrc/attention_stream.hip, PACKED CAUSAL instantiation; reached
 through launch_attention_packed / kemr_debug_op_attention_packed), the kernel Long-CLIP's 248-position text towers run on.
 
 The kernel is the streaming kernel of the BERT family with the chunk loop cut at the query block's diagonal, so the reference is the

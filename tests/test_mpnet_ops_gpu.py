@@ -1,4 +1,4 @@
-"""GPU: the bias instantiation of the packed attention kernel (csrc/attention_varlen.hip, model family 3: MPNet's relative position
+"""GPU: the bias instantiation of the packed attention kernel (csrc/attention_stream.hip, model family 3: MPNet's relative position
 bias) alone -- against its fp64 statement and rounding budget (tests/mpnet_ref.py attention_varlen_bias_emulation, the biased
 restatement of oracle.rounding.attention_long_emulation) with the bars of tests/test_bert_ops_gpu.py (budget ratio <= 1, |signed bias|
 <= 0.02 ulp); a zero table against the kernel without bias, bit for bit; isolation and repeatability; the memory and stream

@@ -1,6 +1,6 @@
 """GPU: the kernels a tower reaches only inside itself, held to fp64 statements of what they compute (oracle/rounding.py):
 
-* the streaming attention of T > 288 (csrc/attention_long.hip) against attention_long_emulation -- P rounded to bf16 against the
+* the streaming attention of T > 288 (csrc/attention_stream.hip) against attention_long_emulation -- P rounded to bf16 against the
   running max of 64-key chunks -- at ragged lengths, through the rescale edge cases, per image and inside its output rows;
 * the pooled-row attention of the last block (attention_pooled_kernel<320> / <1088>), vision and text (causal, packed) forms;
 * the causal attention over packed texts (launch_attention_packed) against the per-item causal statement;

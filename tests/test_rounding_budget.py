@@ -173,7 +173,7 @@ def _long_case(t, batch=3, width=256, seed=17):
 
 
 def _long_kernel_cpu(qkv_bf16, batch, t, width, kc=64, defect=None):
-    """csrc/attention_long.hip in fp32 on the CPU: K / V in chunks of kc keys, running max m and sum l, O and l rescaled by
+    """csrc/attention_stream.hip in fp32 on the CPU: K / V in chunks of kc keys, running max m and sum l, O and l rescaled by
     exp(m - m') when the max moves, P rounded to bf16 against the running max, the sum from the unrounded P."""
     heads = width // 64
     x = qkv_bf16.float().view(batch, t, 3, heads, 64).permute(2, 0, 3, 1, 4)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The streaming attention kernel (csrc/attention_long.hip) alone at the ViT-L/14@336px shape: T = 577, width 1024 (16 heads), B =
+"""The streaming attention kernel (csrc/attention_stream.hip, the fixed-length instantiation) alone at the ViT-L/14@336px shape: T = 577, width 1024 (16 heads), B =
 the engine's images per call (engine.image_call_items), checked against a torch fp32 softmax(QK^T)V of the same bf16 inputs.  Every
 rep is timed on its own hipEvent pair after a warm-up; prints the median us, TFLOP/s (4 T^2 64 heads B) with its share of the
 2.5 PF bf16 MFMA peak, and GB/s (q | k | v read once, the output written once).  For comparison the same for the 257-token
