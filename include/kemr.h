@@ -73,7 +73,9 @@ extern "C" {
  *    they refuse for a family-2 model, no existing caller could reach.  kemr_cfg did not grow.
  *    Still 4: model family 3 (MPNet sentence encoders: a family-2 model under option "family" = 3, with a relative position bias in
  *    every attention score) and option "layer_norm_eps" (family 3 only) are additions; kemr_model_create_family keeps refusing 3; families 0 - 2 keep their tensors, arithmetic and
- *    messages, and no entry point changed. */
+ *    messages, and no entry point changed.
+ *    Still 4: kemr_op_attention_backward (the backward of kemr_op_attention, heads of 64, t <= KEMR_MAX_TEXT_CTX) is an addition; the
+ *    forward kernels did not change and save nothing for it. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -702,6 +704,18 @@ int kemr_op_layernorm_rows(void* x_dev, int x_dtype, const void* delta_dev, cons
  * ragged last key block and query tile of an item are masked, so exactly batch * t rows of out are written and nothing before row 0 or
  * behind row batch * t - 1 of qkv can reach them (kemr_op_attention_hd, both head dims, likewise). */
 int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, int t, int width, int causal, void* stream);
+/* The backward of kemr_op_attention (heads of 64).  qkv bf16 [batch*t, 3*width] exactly as that op reads it (q | k | v, q pre-scaled by
+ * 1/8), dout bf16 [batch*t, width] = the gradient of its output -> dqkv bf16 [batch*t, 3*width] = the gradient with respect to the three
+ * planes AS GIVEN: the caller owns the 1/8 of q (d loss / d unscaled q = dq / 8).  1 <= t <= KEMR_MAX_TEXT_CTX (288), causal 0 or 1,
+ * width % 64 == 0, batch >= 0 (batch == 0 launches nothing; batch * width / 64 <= 2^31 - 1, the grid); anything else, or a NULL
+ * pointer, is KEMR_ERR_INVALID with a message naming the argument, refused on the host before any launch with dqkv untouched.
+ * The forward saves nothing: scores, row maximum and sum and the probabilities P are recomputed from qkv in fp32, D_i = sum_j P_ij dP_ij
+ * from the same values (no `out` argument).  bf16 MFMA with fp32 accumulators; P and dS are rounded to bf16 as MFMA operands, the
+ * outputs to bf16 at the store, nothing else is rounded below fp32.  No workspace, no atomics: every element of dqkv has one owner
+ * and one summation order, so the same inputs give the same bits on every launch.  Exactly batch * t rows of dqkv are written; the
+ * ragged last tiles are masked, and nothing outside an item's own rows of qkv and dout can reach its rows of dqkv. */
+int kemr_op_attention_backward(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width, int causal,
+                               void* stream);
 /* the same with the head dim an argument: 64 = kemr_op_attention; 80 (q pre-scaled by 1/sqrt(80), width % 80 == 0): non-causal, t <= 288.
  * A width that is no multiple of the head dim, another head dim, causal or t > 288 at 80: KEMR_ERR_INVALID, nothing is launched. */
 int kemr_op_attention_hd(const void* qkv_dev, void* out_dev, int batch, int t, int width, int head_dim, int causal, void* stream);

@@ -123,6 +123,7 @@ SIGNATURES = {
     "kemr_op_layernorm_rows": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "kemr_op_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "kemr_op_attention_hd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "kemr_op_attention_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "kemr_op_layernorm_x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "kemr_op_gemm_x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "kemr_op_attention_x3": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

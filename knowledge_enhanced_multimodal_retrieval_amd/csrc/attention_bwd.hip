@@ -1,0 +1,293 @@
+// Backward of the multi-head self-attention of attention.hip (head dim 64, t <= 288, causal or not): kemr_op_attention_backward.
+//
+//   qkv  bf16 [batch * t, 3 width]  q | k | v as the forward reads them (q already scaled by 1/8)
+//   dout bf16 [batch * t, width]    gradient of the forward's output
+//   dqkv bf16 [batch * t, 3 width]  gradient with respect to the three planes AS GIVEN (the caller owns the 1/8 of q)
+//
+// The forward saves nothing, so everything is recomputed from qkv in fp32: S = q k^T, the row maximum and sum, P = softmax(S),
+// dP = dO v^T, D_i = sum_j P_ij dP_ij (which equals dO_i . O_i, so no `out` argument is needed and the op is consistent with the P
+// it uses), dS = P o (dP - D), then dq = dS k, dk = dS^T q, dv = P^T dO.
+//
+// One workgroup of four waves per (item, head).  The Q, K, V and dO tiles of the head (t padded to TP = a multiple of 32 rows, pad
+// rows zero) sit in LDS for the whole kernel: 4 x TP x 128 B, 147 456 B at TP = 288, plus three fp32 per row (below).  Two phases,
+// every element of dqkv owned by one wave and summed in one fixed order -- no atomics, the same bits on every launch:
+//   phase 1, a wave owns 16-QUERY tiles: S^T = K . Q^T and dP^T = V . dO^T over all key tiles (A = K / V rows, B = the tile's Q / dO
+//     rows; a lane holds 4 consecutive keys of ONE query, so row max, row sum and D are register sums and two shuffles), then
+//     dQ^T = K^T . dS^T (A = K^T by ds_read_b64_tr_b16, B = the dS registers rounded to bf16 in place: the forward's PV product
+//     with K for V and dS for P).  It leaves max * log2e, 1 / sum and D of its rows in LDS.
+//   phase 2, a wave owns 16-KEY tiles: the same two products with the roles swapped, S = Q . K^T and dP = dO . V^T over all query
+//     tiles (a lane holds 4 consecutive queries of ONE key), P from the saved row statistics by the same expression as in phase 1,
+//     then dV^T = dO^T . P and dK^T = Q^T . dS (A = dO^T / Q^T by transposed reads, B = the P / dS registers).
+// Both phases are one function (bwd_own_tile) with the operands exchanged.  S and dP are computed twice (7 products instead of 5):
+// the price of owning every output without a workspace.  Causal: tiles wholly behind the diagonal are skipped in both phases.
+// Rounding points: P and dS to bf16 as MFMA operands, fp32 accumulators, dq / dk / dv to bf16 at the store.  Everything else fp32.
+// LDS images: rows of 128 B.  Q, K and dO are read by rows AND transposed, so they carry the forward's V swizzle (32-byte chunk ^=
+// (row >> 1) & 3: transposed reads conflict-free, row reads 2-way); V is only read by rows and carries the K swizzle (16-byte chunk
+// ^= (row >> 1) & 7: conflict-free).
+#include "common.h"
+
+namespace kemr {
+
+template <bool TRL>
+__device__ __forceinline__ int bwd_off(int row, int c) {
+    return row * 128 + ((TRL ? (c ^ (((row >> 1) & 3) << 1)) : (c ^ ((row >> 1) & 7))) << 4);
+}
+template <bool TRL>
+__device__ __forceinline__ bf16x8 bwd_row(const char* img, int row, int c) { return *(const bf16x8*)(img + bwd_off<TRL>(row, c)); }
+
+// the A fragments (4 d-tiles) of M^T for the 32 rows of block u of the image M (forward's load_v): k slot 8 lq + j <-> row 32 u + 16 (j >> 2) + 4 lq + (j & 3)
+__device__ __forceinline__ void bwd_tr(const char* img, int u, int lrow, int lq, bf16x8 (&dst)[4]) {
+    const int ra = u * 32 + lq * 4 + (lrow >> 2), rb = ra + 16;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        const int c = dt * 2 + ((lrow & 3) >> 1);
+        const bf16x4 va = lds_read_tr16(img + bwd_off<true>(ra, c) + (lrow & 1) * 8);
+        const bf16x4 vb = lds_read_tr16(img + bwd_off<true>(rb, c) + (lrow & 1) * 8);
+        dst[dt][0] = va[0]; dst[dt][1] = va[1]; dst[dt][2] = va[2]; dst[dt][3] = va[3];
+        dst[dt][4] = vb[0]; dst[dt][5] = vb[1]; dst[dt][6] = vb[2]; dst[dt][7] = vb[3];
+    }
+}
+__device__ __forceinline__ bf16x8 bwd_pack(const f32x4& a, const f32x4& b) {
+    union { bf16x8 v; uint32_t w[4]; } f;
+    f.w[0] = pack_bf16x2(a[0], a[1]); f.w[1] = pack_bf16x2(a[2], a[3]);
+    f.w[2] = pack_bf16x2(b[0], b[1]); f.w[3] = pack_bf16x2(b[2], b[3]);
+    return f.v;
+}
+__device__ __forceinline__ void bwd_store(bf16_t* dst, const f32x4 (&acc)[4]) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        uint2 pk;
+        pk.x = pack_bf16x2(acc[dt][0], acc[dt][1]);
+        pk.y = pack_bf16x2(acc[dt][2], acc[dt][3]);
+        *(uint2*)(dst + dt * 16) = pk;
+    }
+}
+
+// PHASE 1: own = the 16 queries of tile ot, other = keys; PHASE 2: own = the 16 keys of tile ot, other = queries.
+// s[t][r] / dp[t][r] belong to (own row ot * 16 + lrow, other row t * 16 + lq * 4 + r).  EXEC is full throughout (transposed reads).
+template <int NT32, bool CAUSAL, int PHASE>
+__device__ __forceinline__ void bwd_own_tile(const char* sQ, const char* sK, const char* sV, const char* sG, float* sM, float* sI,
+                                             float* sD, int ot, int T, int lane, bf16_t* dst, size_t ld, int width) {
+    constexpr int NT16 = NT32 * 2;
+    constexpr float LOG2E = 1.4426950408889634f;
+    const int lrow = lane & 15, lq = lane >> 4;
+    const char* own1 = PHASE == 1 ? sQ : sK;
+    const char* own2 = PHASE == 1 ? sG : sV;
+    const char* oth1 = PHASE == 1 ? sK : sQ;
+    const char* oth2 = PHASE == 1 ? sV : sG;
+    const int o = ot * 16 + lrow;
+    bf16x8 b1[2], b2[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        b1[kk] = bwd_row<true>(own1, o, kk * 4 + lq);
+        b2[kk] = bwd_row<PHASE == 1>(own2, o, kk * 4 + lq);
+    }
+    f32x4 s[NT16], dp[NT16];
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) {
+        s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // tiles made only of pad rows, or (causal) wholly behind the diagonal, are skipped (uniform); the masks below cover them
+        if (t * 16 < T && (!CAUSAL || (PHASE == 1 ? t <= ot : t >= ot))) {
+            const int row = t * 16 + lrow;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bwd_row<true>(oth1, row, kk * 4 + lq), b1[kk], s[t], 0, 0, 0);
+                dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bwd_row<PHASE == 2>(oth2, row, kk * 4 + lq), b2[kk], dp[t], 0, 0, 0);
+            }
+        }
+    }
+    if constexpr (PHASE == 1) {
+        float mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < NT16; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int x = t * 16 + lq * 4 + r;
+                const bool ok = x < T && (!CAUSAL || x <= o);       // key 0 is always in: the maximum is finite
+                s[t][r] = ok ? s[t][r] : -INFINITY;
+                mx = fmaxf(mx, s[t][r]);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float m2 = mx * LOG2E;
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT16; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                s[t][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][r], LOG2E, -m2));      // masked: exp2(-inf) = 0
+                sum += s[t][r];
+            }
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        const float inv = 1.0f / sum;
+        float dd = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT16; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                s[t][r] *= inv;
+                dd = __builtin_fmaf(s[t][r], dp[t][r], dd);
+            }
+        dd += __shfl_xor(dd, 16);
+        dd += __shfl_xor(dd, 32);
+#pragma unroll
+        for (int t = 0; t < NT16; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dp[t][r] = s[t][r] * (dp[t][r] - dd);
+        if (lq == 0) { sM[o] = m2; sI[o] = inv; sD[o] = dd; }
+    } else {
+#pragma unroll
+        for (int t = 0; t < NT16; ++t) {
+            if (t * 16 < T && (!CAUSAL || t >= ot)) {
+                const float4 m4 = *(const float4*)(sM + t * 16 + lq * 4);
+                const float4 i4 = *(const float4*)(sI + t * 16 + lq * 4);
+                const float4 d4 = *(const float4*)(sD + t * 16 + lq * 4);
+                const float mm[4] = {m4.x, m4.y, m4.z, m4.w}, ii[4] = {i4.x, i4.y, i4.z, i4.w}, dd[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int x = t * 16 + lq * 4 + r;
+                    const bool ok = x < T && (!CAUSAL || o <= x);
+                    const float p = ok ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][r], LOG2E, -mm[r])) * ii[r] : 0.f;
+                    s[t][r] = p;
+                    dp[t][r] = p * (dp[t][r] - dd[r]);
+                }
+            }
+        }
+    }
+    f32x4 acc1[4], acc2[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) { acc1[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll
+    for (int u = 0; u < NT32; ++u) {
+        // a block of 32 other rows that is all pad, or (causal) all behind the diagonal, has P = dS = 0 and is skipped (uniform)
+        if (!(u * 32 < T && (!CAUSAL || (PHASE == 1 ? u * 32 <= ot * 16 + 15 : u * 32 + 31 >= ot * 16)))) continue;
+        bf16x8 a[4];
+        bwd_tr(oth1, u, lrow, lq, a);                                   // K^T (phase 1) / Q^T (phase 2)
+        const bf16x8 dsf = bwd_pack(dp[2 * u], dp[2 * u + 1]);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) acc1[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[dt], dsf, acc1[dt], 0, 0, 0);
+        if constexpr (PHASE == 2) {
+            bwd_tr(oth2, u, lrow, lq, a);                               // dO^T
+            const bf16x8 pf = bwd_pack(s[2 * u], s[2 * u + 1]);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) acc2[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[dt], pf, acc2[dt], 0, 0, 0);
+        }
+    }
+    // acc[dt][r] = d(own row lrow)[d = dt * 16 + lq * 4 + r]
+    if (o < T) {
+        bf16_t* p = dst + (size_t)o * ld + lq * 4;
+        if constexpr (PHASE == 1) bwd_store(p, acc1);                   // dq
+        else { bwd_store(p + width, acc1); bwd_store(p + 2 * width, acc2); }    // dk, dv
+    }
+}
+
+template <int NT32, bool CAUSAL>
+__global__ __launch_bounds__(256) void attention_bwd_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+                                                            bf16_t* __restrict__ dqkv, int T, int width, int heads) {
+    constexpr int TP = NT32 * 32;
+    constexpr int NTH = 256, NW = 4;
+    constexpr int NCH = (TP * 8 + NTH - 1) / NTH;       // 16-byte chunks of one matrix per thread
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* sQ = smem;
+    char* sK = smem + TP * 128;
+    char* sV = smem + 2 * TP * 128;
+    char* sG = smem + 3 * TP * 128;
+    float* sM = (float*)(smem + 4 * TP * 128);
+    float* sI = sM + TP;
+    float* sD = sI + TP;
+
+    const int b = blockIdx.x / heads, h = blockIdx.x - b * heads;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const size_t ld = 3 * (size_t)width, row0 = (size_t)b * T;
+    const bf16_t* qbase = qkv + row0 * ld + h * 64;
+    const bf16_t* gbase = dout + row0 * width + h * 64;
+
+    // stage Q, K, V and dO: pad rows load the last valid row (branch-free) and are zeroed at the LDS write
+#pragma unroll
+    for (int mtx = 0; mtx < 4; ++mtx) {
+        const bf16_t* src = mtx < 3 ? qbase + mtx * width : gbase;
+        const size_t sld = mtx < 3 ? ld : (size_t)width;
+        char* img = smem + mtx * TP * 128;
+        uint4 v[NCH];
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int idx = tid + i * NTH;
+            const int row = idx >> 3, c = idx & 7;
+            const int rc = row < T ? row : T - 1;
+            v[i] = *(const uint4*)(src + (size_t)rc * sld + c * 8);
+        }
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int idx = tid + i * NTH;
+            const int row = idx >> 3, c = idx & 7;
+            if (idx < TP * 8) {
+                const unsigned keep = row < T ? 0xffffffffu : 0u;
+                uint4 a = v[i];
+                a.x &= keep; a.y &= keep; a.z &= keep; a.w &= keep;
+                *(uint4*)(img + (mtx == 2 ? bwd_off<false>(row, c) : bwd_off<true>(row, c))) = a;
+            }
+        }
+    }
+    __syncthreads();
+    const int nt = (T + 15) >> 4;
+    bf16_t* dst = dqkv + row0 * ld + h * 64;
+    for (int ot = wid; ot < nt; ot += NW)               // wave-uniform trip counts
+        bwd_own_tile<NT32, CAUSAL, 1>(sQ, sK, sV, sG, sM, sI, sD, ot, T, lane, dst, ld, width);
+    __syncthreads();                                    // the row statistics of every query tile
+    for (int ot = wid; ot < nt; ot += NW)
+        bwd_own_tile<NT32, CAUSAL, 2>(sQ, sK, sV, sG, sM, sI, sD, ot, T, lane, dst, ld, width);
+}
+
+template <int NT32>
+static int launch_bwd_nt(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, int batch, int t, int width, int causal, hipStream_t stream) {
+    constexpr int smem = NT32 * 32 * (4 * 128 + 3 * 4);
+    static_assert(smem <= 160 * 1024, "the head's four tiles and row statistics must fit the LDS of one CU");
+    void (*kern)(const bf16_t*, const bf16_t*, bf16_t*, int, int, int) =
+        causal ? attention_bwd_kernel<NT32, true> : attention_bwd_kernel<NT32, false>;
+    ProfScope prof(PROF_ATTENTION, stream);
+    KEMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    const int heads = width / 64;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)batch * heads)), dim3(256), smem, stream, qkv, dout, dqkv, t, width, heads);
+    KEMR_CHECK_LAUNCH("attention_bwd_kernel");
+    return KEMR_OK;
+}
+
+// arguments checked by the caller (kemr_op_attention_backward): 1 <= t <= KEMR_MAX_TEXT_CTX, width % 64 == 0, batch >= 1
+int launch_attention_backward(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, int batch, int t, int width, int causal, hipStream_t stream) {
+    switch ((t + 31) / 32) {
+        case 1: return launch_bwd_nt<1>(qkv, dout, dqkv, batch, t, width, causal, stream);
+        case 2: return launch_bwd_nt<2>(qkv, dout, dqkv, batch, t, width, causal, stream);
+        case 3: return launch_bwd_nt<3>(qkv, dout, dqkv, batch, t, width, causal, stream);
+        case 4: return launch_bwd_nt<4>(qkv, dout, dqkv, batch, t, width, causal, stream);
+        case 5: return launch_bwd_nt<5>(qkv, dout, dqkv, batch, t, width, causal, stream);
+        case 6: return launch_bwd_nt<6>(qkv, dout, dqkv, batch, t, width, causal, stream);
+        case 7: return launch_bwd_nt<7>(qkv, dout, dqkv, batch, t, width, causal, stream);
+        case 8: return launch_bwd_nt<8>(qkv, dout, dqkv, batch, t, width, causal, stream);
+        case 9: return launch_bwd_nt<9>(qkv, dout, dqkv, batch, t, width, causal, stream);
+    }
+    KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: t = %d is outside 1..%d", t, KEMR_MAX_TEXT_CTX);
+}
+
+}  // namespace kemr
+
+using namespace kemr;
+
+extern "C" int kemr_op_attention_backward(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width,
+                                          int causal, void* stream) {
+    // everything is refused here, on the host, before any HIP call
+    if (!qkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: qkv is NULL");
+    if (!dout_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: dout is NULL");
+    if (!dqkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: dqkv is NULL");
+    if (t < 1 || t > KEMR_MAX_TEXT_CTX) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: t = %d is outside 1..%d", t, KEMR_MAX_TEXT_CTX);
+    if (width <= 0 || width % 64 != 0) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: width = %d is not a positive multiple of 64 (heads of 64)", width);
+    if (causal != 0 && causal != 1) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: causal = %d is neither 0 nor 1", causal);
+    if (batch < 0) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: batch = %d is negative", batch);
+    if ((long long)batch * (width / 64) > 0x7fffffffLL)
+        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: batch = %d x %d heads exceeds the grid (2^31 - 1 workgroups)", batch, width / 64);
+    if (batch == 0) return KEMR_OK;
+    return launch_attention_backward((const bf16_t*)qkv_dev, (const bf16_t*)dout_dev, (bf16_t*)dqkv_dev, batch, t, width, causal,
+                                     (hipStream_t)stream);
+}

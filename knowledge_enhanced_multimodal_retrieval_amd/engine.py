@@ -1090,6 +1090,25 @@ def op_attention(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool
     return out
 
 
+def attention_backward(qkv: torch.Tensor, dout: torch.Tensor, batch: int, t: int, width: int, causal: bool) -> torch.Tensor:
+    """The backward of op_attention (heads of 64, t <= 288): qkv bf16 [batch * t, 3 width] as the forward read it (q pre-scaled by 1/8),
+    dout bf16 [batch * t, width] -> dqkv bf16 [batch * t, 3 width], the gradient with respect to the planes as given (the caller owns
+    the 1/8 of q).  Recomputes the probabilities from qkv; no workspace, the same bits on every launch (``kemr_op_attention_backward``)."""
+    _require_cuda(qkv, "attention_backward: qkv")
+    _require_cuda(dout, "attention_backward: dout")
+    if qkv.dtype != torch.bfloat16 or dout.dtype != torch.bfloat16 or not qkv.is_contiguous() or not dout.is_contiguous():
+        raise RuntimeError("attention_backward: qkv and dout must be contiguous bf16")
+    if qkv.device != dout.device or tuple(qkv.shape) != (batch * t, 3 * width) or tuple(dout.shape) != (batch * t, width):
+        raise RuntimeError(f"attention_backward: qkv must be [{batch * t}, {3 * width}] and dout [{batch * t}, {width}] on one device, got "
+                           f"{tuple(qkv.shape)} and {tuple(dout.shape)}")
+    dqkv = torch.empty_like(qkv)
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.lib().kemr_op_attention_backward(C.c_void_p(qkv.data_ptr()), C.c_void_p(dout.data_ptr()), C.c_void_p(dqkv.data_ptr()),
+                                                         batch, t, width, 1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))),
+                   "op_attention_backward")
+    return dqkv
+
+
 def op_layernorm_x3(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
     """fp32 [rows, width] -> the A-side triple [hi | lo | hi] of LayerNorm(x): bf16 [ceil256(rows), 3 width], pad rows zero."""
     L = _lib.lib()

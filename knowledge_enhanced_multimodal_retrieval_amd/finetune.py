@@ -17,6 +17,12 @@ accumulation, ``grad_clip``, AdamW + cosine schedule as ``main_worker`` builds t
 ``clip_model.save_checkpoint`` (the full state dict: ``load_clip_model(name, checkpoint)`` and every evaluator take the result).  One
 difference in the bookkeeping: ``train_loss`` is the mean of the batches' losses; the reference multiplies each by
 ``gradient_accumulation_steps`` on the way (trainer.py:208).  Single process, fp32; ``--mixed_precision`` is accepted and ignored.
+
+``--lock_image_tower`` (an alternative to ``--freeze_encoders``; ``tower_train.py``) trains the whole TEXT tower as well: the image tower
+stays locked -- its pooled rows are cached once (``cache_image_pooled``) -- and queries and targets of every batch run through a
+differentiable restatement of the text tower whose attention is ``kemr_op_attention`` forward and ``kemr_op_attention_backward``
+backward.  The loop, the loss, the validation through the served engine and the checkpoints are this module's.  With neither flag the
+command still exits with ``NOT_SERVED``: the vision tower has no backward pass.
 """
 from __future__ import annotations
 
@@ -86,6 +92,18 @@ def cache_pooled(model: nn.Module, dataset, batch_size: int = 64, seed: int = 42
                  tokenize_fn: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """One pass over `dataset` (items image / query / target / uuid, the evaluators' loader): the pooled rows of the frozen towers as
     three fp32 device tensors [N, v_width], [N, t_width], [N, t_width]."""
+    return _cache(model, dataset, batch_size, seed, num_workers, tokenize_fn, text_pooled=True)
+
+
+@torch.no_grad()
+def cache_image_pooled(model: nn.Module, dataset, batch_size: int = 64, seed: int = 42, num_workers: int = 0,
+                       tokenize_fn: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``cache_pooled``'s image half for a locked image tower (``tower_train.py``): the pooled image rows fp32 [N, v_width] and, in place
+    of the text rows, the token ids of queries and targets, int32 [N, ctx] each, all on the model's device."""
+    return _cache(model, dataset, batch_size, seed, num_workers, tokenize_fn, text_pooled=False)
+
+
+def _cache(model, dataset, batch_size, seed, num_workers, tokenize_fn, text_pooled: bool):
     from . import engine
     from .evaluators import eval_loader, model_tokenize
     from .preprocess import PackedRaw, gpu_preprocess_for
@@ -100,6 +118,10 @@ def cache_pooled(model: nn.Module, dataset, batch_size: int = 64, seed: int = 42
             gpu_pre = gpu_pre or gpu_preprocess_for(m, device)
             images = gpu_pre.batch(images)
         img.append(m.encode_image_pooled(images.to(device, non_blocking=True)))
+        if not text_pooled:
+            qry.append(q_ids.to(device=device, dtype=torch.int32, non_blocking=True))
+            tgt.append(t_ids.to(device=device, dtype=torch.int32, non_blocking=True))
+            continue
         n = q_ids.shape[0]
         lens = torch.cat([engine.text_lengths(q_ids.cpu()), engine.text_lengths(t_ids.cpu())])       # host lengths: no device sync
         both = m.encode_text_pooled(torch.cat([q_ids, t_ids]).to(device, non_blocking=True), lens=lens)
@@ -258,8 +280,12 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--use_wandb", action="store_true", help="accepted and ignored")
     parser.add_argument("--wandb_project", type=str, default="clip-art-retrieval")
     parser.add_argument("--seed", type=int, default=42)
-    parser.add_argument("--freeze_encoders", action="store_true",
-                        help="train the projection heads on frozen towers (required: end-to-end fine-tuning is not served)")
+    mode = parser.add_mutually_exclusive_group()
+    mode.add_argument("--freeze_encoders", action="store_true",
+                      help="train the projection heads on frozen towers (this or --lock_image_tower is required: end-to-end fine-tuning is not served)")
+    mode.add_argument("--lock_image_tower", action="store_true",
+                      help="instead of --freeze_encoders: train the projection heads AND the whole text tower on a locked image tower "
+                           "(cached pooled image rows; attention backward in the HIP library); needs a batch size")
     parser.add_argument("--synthetic", type=int, default=0, metavar="N",
                         help="train and validate on N seeded synthetic items each instead of the HuggingFace dataset (offline)")
     parser.add_argument("--dataset", type=str, default="xuemduan/reevaluate-image-text-pairs")
@@ -267,10 +293,14 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    args = build_parser().parse_args(argv)
-    if not args.freeze_encoders:
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if not args.freeze_encoders and not args.lock_image_tower:
         print(f"error: {NOT_SERVED}", file=sys.stderr)
         return 2
+    if args.lock_image_tower and args.batch_size <= 0:
+        from .tower_train import BATCH_0_REFUSED
+        parser.error(BATCH_0_REFUSED)
     from . import clip_api, tokenizer
     from .datasets import CLIPEvalDatasetHF, SyntheticRetrievalDataset
     from .logging_utils import setup_logger
@@ -296,12 +326,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         train_set = CLIPEvalDatasetHF(ds["train"], preprocess, args.max_text_length)
         val_set = CLIPEvalDatasetHF(ds["validation"], preprocess, args.max_text_length)
     workers = 0 if args.synthetic > 0 else args.num_workers
-    logger.info(f"Caching the pooled rows of {len(train_set)} training items (frozen towers)...")
-    pooled = cache_pooled(model, train_set, batch_size=64, seed=args.seed, num_workers=workers)
-    heads = ProjectionHeads(model)
+    if args.lock_image_tower:
+        from .tower_train import LockedImageTuning, TextTowerTrainer
+        logger.info(f"Caching the pooled image rows of {len(train_set)} training items (locked image tower)...")
+        pooled = cache_image_pooled(model, train_set, batch_size=64, seed=args.seed, num_workers=workers)
+        heads, trainer_cls = LockedImageTuning(model), TextTowerTrainer
+    else:
+        logger.info(f"Caching the pooled rows of {len(train_set)} training items (frozen towers)...")
+        pooled = cache_pooled(model, train_set, batch_size=64, seed=args.seed, num_workers=workers)
+        heads, trainer_cls = ProjectionHeads(model), HeadTrainer
     loss_fn = JointContrastiveLoss(temperature=args.temperature, t2i_weight=args.t2i_weight, t2t_weight=args.t2t_weight)
     optimizer, scheduler = build_optimizer(heads, args.lr, args.weight_decay, args.num_epochs)
-    trainer = HeadTrainer(model, heads, pooled, loss_fn, optimizer, scheduler, val_eval_dataset=val_set, output_dir=str(out),
+    trainer = trainer_cls(model, heads, pooled, loss_fn, optimizer, scheduler, val_eval_dataset=val_set, output_dir=str(out),
                           total_epochs=args.num_epochs, batch_size=args.batch_size, early_stopping_patience=args.early_stopping_patience,
                           early_stopping_metric=args.early_stopping_metric, grad_clip=args.grad_clip,
                           gradient_accumulation_steps=args.gradient_accumulation_steps, seed=args.seed)

@@ -1,0 +1,124 @@
+"""GPU: ``kemr_op_attention_backward`` (csrc/attention_bwd.hip) against the fp64 statement and the rounding emulation of
+tests/attention_bwd_ref.py, its exact properties, its memory contract (tests/footprint.py) and its stream contract
+(tests/stream_order.py).
+
+Shapes: width 128 (two heads), batch 3, t in {1, 16, 17, 77, 129, 248, 288}: one key, exact tiles, a one-row ragged tile, the two text
+lengths, the first length past the forward's tile kernels, the maximum; causal and not.  The bar: per plane (dq, dk, dv) the relative L2
+error against the fp64 statement on the same bf16 inputs is at most 2 x the emulation's error at that shape -- the emulation rounds
+where the kernel rounds, so the factor covers the fp32 summation order and the exponential's implementation and nothing else."""
+import ctypes as C
+import functools
+
+import pytest
+import torch
+
+import attention_bwd_ref as R
+import footprint as F
+import stream_order as SO
+from footprint import In, Out
+from knowledge_enhanced_multimodal_retrieval_amd import _lib, engine
+
+pytestmark = pytest.mark.gpu
+
+BF16 = torch.bfloat16
+BATCH, WIDTH, ZERO_ITEM = 3, 128, 1
+TS = [1, 16, 17, 77, 129, 248, 288]
+CONTRACT_CASES = [(17, 0), (77, 1), (129, 1), (288, 0)]
+
+
+@functools.lru_cache(maxsize=None)
+def _case(t, causal):
+    """(qkv, dout, fp64 statement, emulation) of one shape: computed once, shared, never modified."""
+    qkv, dout = R.make_inputs(BATCH, t, WIDTH, 1000 + 2 * t + causal, zero_item=ZERO_ITEM)
+    return qkv, dout, R.backward_fp64(qkv, dout, BATCH, t, WIDTH, causal), R.backward_emulated(qkv, dout, BATCH, t, WIDTH, causal)
+
+
+def _run(device, qkv, dout, t, causal, batch=BATCH):
+    return engine.attention_backward(qkv.to(device), dout.to(device), batch, t, WIDTH, bool(causal)).cpu()
+
+
+@pytest.mark.parametrize("causal", [0, 1])
+@pytest.mark.parametrize("t", TS)
+def test_error_against_fp64_within_twice_the_emulation(device, t, causal):
+    qkv, dout, ref, emu = _case(t, causal)
+    got = _run(device, qkv, dout, t, causal)
+    assert got.dtype == BF16 and got.shape == ref.shape
+    assert not torch.isnan(got.float()).any() and torch.isfinite(got.float()).all()
+    for name in ("dq", "dk", "dv"):
+        r = R.planes(ref, WIDTH)[name]
+        e_kernel, e_emu = R.rel_l2(R.planes(got, WIDTH)[name], r), R.rel_l2(R.planes(emu, WIDTH)[name], r)
+        print(f"attention_backward t={t} causal={causal} {name}: kernel {e_kernel:.4e} emulation {e_emu:.4e}")
+        assert e_kernel <= 2.0 * e_emu, (name, e_kernel, e_emu)
+    # the item whose dout rows are zero: exactly zero gradients
+    assert not got[ZERO_ITEM * t:(ZERO_ITEM + 1) * t].float().any()
+    if t == 1:          # one key: P = 1, dS = 0
+        g = R.planes(got, WIDTH)
+        assert not g["dq"].float().any() and not g["dk"].float().any()
+        assert F.same_bits(g["dv"], dout)
+
+
+@pytest.mark.parametrize("t,causal", CONTRACT_CASES)
+def test_two_launches_give_the_same_bits(device, t, causal):
+    qkv, dout, _, _ = _case(t, causal)
+    q, d = qkv.to(device), dout.to(device)
+    a = engine.attention_backward(q, d, BATCH, t, WIDTH, bool(causal))
+    b = engine.attention_backward(q, d, BATCH, t, WIDTH, bool(causal))
+    assert F.same_bits(a, b)
+
+
+@pytest.mark.parametrize("t,causal", CONTRACT_CASES)
+def test_an_item_depends_on_its_own_rows_only(device, t, causal):
+    """Item 1 of a call whose other items and whose surroundings (0xff margins in front of and behind every buffer) are different."""
+    qkv, _, _, _ = _case(t, causal)
+    dout = R.make_inputs(BATCH, t, WIDTH, 77 + t)[1]                      # no zero item here
+    base = _run(device, qkv, dout, t, causal)
+    qkv2, dout2 = R.make_inputs(BATCH, t, WIDTH, 555 + t)
+    own = slice(t, 2 * t)
+    qkv2[own], dout2[own] = qkv[own], dout[own]
+    wq = F.window(qkv2.shape, BF16, device, F.POISON, body=qkv2, what="qkv")
+    wd = F.window(dout2.shape, BF16, device, F.POISON, body=dout2, what="dout")
+    wo = F.window(qkv2.shape, BF16, device, F.GUARD, what="dqkv")
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().kemr_op_attention_backward(C.c_void_p(wq.ptr), C.c_void_p(wd.ptr), C.c_void_p(wo.ptr), BATCH, t, WIDTH, causal,
+                                                         C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "op_attention_backward")
+    torch.cuda.synchronize(device)
+    assert wq.margins_intact() and wd.margins_intact() and wo.margins_intact()
+    assert F.same_bits(wo.view[own], base[own])
+    assert not torch.equal(wo.view[:t].cpu().float(), base[:t].float())       # (the other items did change)
+
+
+def _specs(t, causal, extra_rows):
+    qkv, dout, _, _ = _case(t, causal)
+    rows = BATCH * t
+    return [In(qkv), In(dout), Out((rows + extra_rows, 3 * WIDTH), BF16, written=lambda v: v[:rows], keep=lambda v: v[rows:]),
+            BATCH, t, WIDTH, causal]
+
+
+@pytest.mark.parametrize("t,causal", CONTRACT_CASES + [(1, 1)])
+def test_memory_contract_exactly_batch_t_rows_written(device, t, causal):
+    fn = _lib.lib().kemr_op_attention_backward
+
+    def run(*args):
+        with torch.cuda.device(device):
+            _lib.check(fn(*args, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "op_attention_backward")
+    F.run_both(run, _specs(t, causal, 7), device, what=f"attention_backward t={t} causal={causal}")
+
+
+@pytest.mark.parametrize("t,causal", [(77, 1), (288, 0)])
+def test_stream_contract(device, t, causal):
+    fn = _lib.lib().kemr_op_attention_backward
+
+    def run(*args):
+        with torch.cuda.device(device):
+            _lib.check(fn(*args, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "op_attention_backward")
+    SO.run_late(run, _specs(t, causal, 0), device, what=f"attention_backward t={t} causal={causal}")
+
+
+def test_empty_batch_launches_nothing(device):
+    out = torch.full((4, 3 * WIDTH), 7.0, dtype=BF16, device=device)
+    keep = out.clone()
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().kemr_op_attention_backward(C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr()), 0, 4,
+                                                         WIDTH, 1, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "op_attention_backward")
+    torch.cuda.synchronize(device)
+    assert F.same_bits(out, keep)
