@@ -75,7 +75,9 @@ extern "C" {
  *    every attention score) and option "layer_norm_eps" (family 3 only) are additions; kemr_model_create_family keeps refusing 3; families 0 - 2 keep their tensors, arithmetic and
  *    messages, and no entry point changed.
  *    Still 4: kemr_op_attention_backward (the backward of kemr_op_attention, heads of 64, t <= KEMR_MAX_TEXT_CTX) is an addition; the
- *    forward kernels did not change and save nothing for it. */
+ *    forward kernels did not change and save nothing for it.
+ *    Still 4: kemr_layernorm_backward_workspace_bytes, kemr_op_layernorm_backward (the backward of kemr_op_layernorm), kemr_op_act_forward
+ *    and kemr_op_act_backward (the MLP activation on bf16) are additions; no existing entry point changed. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -716,6 +718,33 @@ int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, int t, int 
  * ragged last tiles are masked, and nothing outside an item's own rows of qkv and dout can reach its rows of dqkv. */
 int kemr_op_attention_backward(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width, int causal,
                                void* stream);
+/* The backward of kemr_op_layernorm.  x fp32 [rows, width] exactly as the forward read it, gamma fp32 [width], dy [rows, width] = the
+ * gradient of its output in dy_dtype (KEMR_BF16 where the forward wrote bf16, KEMR_F32 where it wrote fp32) -> dx fp32 [rows, width],
+ * dgamma and dbeta fp32 [width].  The forward saves nothing: mean and rstd are recomputed in fp32 exactly as the forward does (two
+ * passes, the same wave sums, eps 1e-5).  With g = dy gamma and x^ = (x - mean) rstd: dx = rstd (g - mean(g) - x^ mean(g x^)),
+ * dgamma_j = sum over rows of dy x^, dbeta_j = sum over rows of dy; fp32 throughout, nothing is rounded below fp32.
+ * width in {256, 512, 768, 1024, 1280}, rows >= 0, dy_dtype as above, workspace_bytes >= kemr_layernorm_backward_workspace_bytes(rows,
+ * width) (a function of its two arguments only, monotone in rows, 0 at rows == 0; the workspace may be NULL then); x, gamma, dy, dx
+ * and the workspace 16-byte aligned; anything else, or a NULL pointer, is KEMR_ERR_INVALID with a message naming the argument, refused
+ * on the host before any launch with the outputs untouched.  rows == 0 zero-fills dgamma and dbeta and does not touch dx.
+ * One wave per row with the row in registers; x and dy are read once.  Each workgroup keeps the dgamma / dbeta partial sums of the rows
+ * it walks in registers, combines its four waves in a fixed order and stores one [2, width] slab into the workspace; a second kernel
+ * sums the slabs per column in a fixed order.  No atomics: the same inputs give the same bits on every launch.  Exactly rows x width
+ * elements of dx and width elements each of dgamma and dbeta are written (a ragged last row tile is masked); nothing behind row
+ * rows - 1 of x or dy is read.  Every launch goes to `stream`. */
+size_t kemr_layernorm_backward_workspace_bytes(int rows, int width);
+int kemr_op_layernorm_backward(const float* x_dev, const float* gamma_dev, const void* dy_dev, int dy_dtype /*KEMR_BF16|KEMR_F32*/,
+                               float* dx_dev, float* dgamma_dev, float* dbeta_dev, int rows, int width,
+                               void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The MLP activation of a training step on contiguous bf16 buffers of n elements; kind 0 = QuickGELU x sigmoid(1.702 x), 1 = the exact
+ * GELU 0.5 x (1 + erf(x / sqrt 2)).  forward: out = bf16(f(float(pre))) with the arithmetic of the fc1 epilogues
+ * (KEMR_EPI_BIAS_QGELU_BF16 / KEMR_EPI_BIAS_GELU_BF16).  backward: dpre = bf16(float(dout) f'(float(pre))), f' = s + 1.702 x s (1 - s)
+ * with s = sigmoid(1.702 x), or Phi(x) + x phi(x); fp32 arithmetic, one rounding, at the store.  n >= 0 and a multiple of 8 (16-byte
+ * loads and stores; n == 0 launches nothing), 16-byte aligned buffers; another kind, a negative n, an n that is no multiple of 8 or a
+ * NULL pointer is KEMR_ERR_INVALID with a message naming the argument, refused on the host before any launch.  Exactly n elements are
+ * written; out may be pre itself (in place).  Every launch goes to `stream`; the same bits on every launch. */
+int kemr_op_act_forward(const void* pre_dev, void* out_dev, long long n, int kind /*0 QuickGELU, 1 exact GELU*/, void* stream);
+int kemr_op_act_backward(const void* pre_dev, const void* dout_dev, void* dpre_dev, long long n, int kind, void* stream);
 /* the same with the head dim an argument: 64 = kemr_op_attention; 80 (q pre-scaled by 1/sqrt(80), width % 80 == 0): non-causal, t <= 288.
  * A width that is no multiple of the head dim, another head dim, causal or t > 288 at 80: KEMR_ERR_INVALID, nothing is launched. */
 int kemr_op_attention_hd(const void* qkv_dev, void* out_dev, int batch, int t, int width, int head_dim, int causal, void* stream);

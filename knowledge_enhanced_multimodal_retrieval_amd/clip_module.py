@@ -12,8 +12,9 @@ from) and packs them into the HIP engine lazily; the forward arithmetic never ru
 frozen towers -- ``encode_image_pooled`` / ``encode_text_pooled`` return the rows the final LayerNorms read, ``finetune.ProjectionHeads``
 trains ``visual.ln_post`` / ``visual.proj`` / ``ln_final`` / ``text_projection`` (this module's own parameters) on them, and the engine
 re-packs itself after an optimizer step (``_fingerprint``).  After a write through ``p.data`` call ``refresh()``.  The TEXT tower can be
-trained as well, by a differentiable restatement of it over these same parameters (``tower_train.TextTower``, attention backward in the
-library); ``encode_*`` themselves stay without autograd.
+trained as well, and so can both towers end to end, by differentiable restatements of them over these same parameters
+(``tower_train.TextTower`` / ``VisionTower``: attention, LayerNorm and activation backward in the library); ``encode_*`` themselves stay
+without autograd.
 """
 from __future__ import annotations
 

@@ -1109,6 +1109,74 @@ def attention_backward(qkv: torch.Tensor, dout: torch.Tensor, batch: int, t: int
     return dqkv
 
 
+def layernorm_backward(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The backward of op_layernorm: x fp32 [rows, width] as the forward read it, gamma fp32 [width], dy bf16 or fp32 [rows, width] ->
+    (dx fp32 [rows, width], dgamma fp32 [width], dbeta fp32 [width]).  Mean and rstd are recomputed; no atomics, the same bits on every
+    launch (``kemr_op_layernorm_backward``).  The workspace is a torch allocation on the current stream."""
+    for t, what in ((x, "x"), (gamma, "gamma"), (dy, "dy")):
+        _require_cuda(t, f"layernorm_backward: {what}")
+    if x.dtype != torch.float32 or gamma.dtype != torch.float32 or dy.dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError("layernorm_backward: x and gamma must be fp32, dy bf16 or fp32")
+    if x.dim() != 2 or tuple(dy.shape) != tuple(x.shape) or tuple(gamma.shape) != (x.shape[1],) or not (x.device == gamma.device == dy.device):
+        raise RuntimeError(f"layernorm_backward: x and dy must be [rows, width] and gamma [width] on one device, got {tuple(x.shape)}, "
+                           f"{tuple(dy.shape)} and {tuple(gamma.shape)}")
+    if not (x.is_contiguous() and gamma.is_contiguous() and dy.is_contiguous()):
+        raise RuntimeError("layernorm_backward: x, gamma and dy must be contiguous")
+    L = _lib.lib()
+    rows, width = x.shape
+    dx = torch.empty_like(x)
+    if rows == 0:                                        # an empty tensor has no address to hand over; the op's own answer for no rows
+        return dx, torch.zeros_like(gamma), torch.zeros_like(gamma)
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+    need =int(L.kemr_layernorm_backward_workspace_bytes(rows, width))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(L.kemr_op_layernorm_backward(C.c_void_p(x.data_ptr()), C.c_void_p(gamma.data_ptr()), C.c_void_p(dy.data_ptr()),
+                                                _lib.KEMR_BF16 if dy.dtype == torch.bfloat16 else _lib.KEMR_F32,
+                                                C.c_void_p(dx.data_ptr()), C.c_void_p(dgamma.data_ptr()), C.c_void_p(dbeta.data_ptr()),
+                                                rows, width, C.c_void_p(ws.data_ptr()), need, C.c_void_p(_stream_ptr(x.device))),
+                   "op_layernorm_backward")
+    return dx, dgamma, dbeta
+
+
+ACT_KINDS = {"quick_gelu": 0, "gelu": 1}
+
+
+def _act_args(what: str, kind, *tensors: torch.Tensor) -> int:
+    k = ACT_KINDS.get(kind, kind)
+    if k not in (0, 1):
+        raise RuntimeError(f"{what}: kind must be 'quick_gelu' (0) or 'gelu' (1), got {kind!r}")
+    for t in tensors:
+        _require_cuda(t, what)
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise RuntimeError(f"{what}: the buffers must be contiguous bf16")
+        if tuple(t.shape) != tuple(tensors[0].shape) or t.device != tensors[0].device:
+            raise RuntimeError(f"{what}: the buffers must have one shape on one device, got {[tuple(u.shape) for u in tensors]}")
+    if tensors[0].numel() % 8:
+        raise RuntimeError(f"{what}: {tensors[0].numel()} elements are not a multiple of 8")
+    return k
+
+
+def act_forward(pre: torch.Tensor, kind) -> torch.Tensor:
+    """bf16 pre-activation -> bf16(f(float(pre))), f = QuickGELU ('quick_gelu', 0) or the exact GELU ('gelu', 1): ``kemr_op_act_forward``."""
+    k = _act_args("act_forward", kind, pre)
+    out = torch.empty_like(pre)
+    with torch.cuda.device(pre.device):
+        _lib.check(_lib.lib().kemr_op_act_forward(C.c_void_p(pre.data_ptr()), C.c_void_p(out.data_ptr()), pre.numel(), k,
+                                                  C.c_void_p(_stream_ptr(pre.device))), "op_act_forward")
+    return out
+
+
+def act_backward(pre: torch.Tensor, dout: torch.Tensor, kind) -> torch.Tensor:
+    """The backward of act_forward: bf16(float(dout) f'(float(pre))) (``kemr_op_act_backward``)."""
+    k = _act_args("act_backward", kind, pre, dout)
+    dpre = torch.empty_like(pre)
+    with torch.cuda.device(pre.device):
+        _lib.check(_lib.lib().kemr_op_act_backward(C.c_void_p(pre.data_ptr()), C.c_void_p(dout.data_ptr()), C.c_void_p(dpre.data_ptr()),
+                                                   pre.numel(), k, C.c_void_p(_stream_ptr(pre.device))), "op_act_backward")
+    return dpre
+
+
 def op_layernorm_x3(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
     """fp32 [rows, width] -> the A-side triple [hi | lo | hi] of LayerNorm(x): bf16 [ceil256(rows), 3 width], pad rows zero."""
     L = _lib.lib()

@@ -21,8 +21,13 @@ difference in the bookkeeping: ``train_loss`` is the mean of the batches' losses
 ``--lock_image_tower`` (an alternative to ``--freeze_encoders``; ``tower_train.py``) trains the whole TEXT tower as well: the image tower
 stays locked -- its pooled rows are cached once (``cache_image_pooled``) -- and queries and targets of every batch run through a
 differentiable restatement of the text tower whose attention is ``kemr_op_attention`` forward and ``kemr_op_attention_backward``
-backward.  The loop, the loss, the validation through the served engine and the checkpoints are this module's.  With neither flag the
-command still exits with ``NOT_SERVED``: the vision tower has no backward pass.
+backward.  The loop, the loss, the validation through the served engine and the checkpoints are this module's.
+
+``--end_to_end`` (the third mode; ``tower_train.py``) trains both towers, the reference's own recipe: the preprocessed pixels of the
+training split are collected once in pinned host memory (``cache_pixels``), every batch runs through differentiable restatements of
+both towers (attention, LayerNorm and the MLP activation in the HIP library in both directions, vendor GEMMs under bf16 autocast over
+fp32 master weights), and ``logit_scale`` stays out of the graph.  With none of the three flags the command still exits with
+``NOT_SERVED``, word for word as before.
 """
 from __future__ import annotations
 
@@ -101,6 +106,30 @@ def cache_image_pooled(model: nn.Module, dataset, batch_size: int = 64, seed: in
     """``cache_pooled``'s image half for a locked image tower (``tower_train.py``): the pooled image rows fp32 [N, v_width] and, in place
     of the text rows, the token ids of queries and targets, int32 [N, ctx] each, all on the model's device."""
     return _cache(model, dataset, batch_size, seed, num_workers, tokenize_fn, text_pooled=False)
+
+
+@torch.no_grad()
+def cache_pixels(model: nn.Module, dataset, batch_size: int = 64, seed: int = 42, num_workers: int = 0,
+                 tokenize_fn: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One pass of the evaluators' loader for ``--end_to_end`` (``tower_train.EndToEndTrainer``): the preprocessed pixels fp32
+    [N, 3, S, S] and the token ids of queries and targets, int32 [N, ctx] each, all on the HOST -- the pixels in pinned memory where the
+    model sits on a GPU (602 KB per 224 px image).  Where the loader yields ``PackedRaw`` the transform runs on the GPU, like ``_cache``."""
+    from .evaluators import eval_loader, model_tokenize
+    from .preprocess import PackedRaw, gpu_preprocess_for
+    m = _unwrap(model)
+    device = next(m.parameters()).device
+    loader = eval_loader(dataset, batch_size, seed, num_workers, tokenize_fn or model_tokenize(m), pin=device.type == "cuda")
+    img, qry, tgt = [], [], []
+    gpu_pre = None
+    for images, q_ids, t_ids, _ in loader:
+        if isinstance(images, PackedRaw):
+            gpu_pre = gpu_pre or gpu_preprocess_for(m, device)
+            images = gpu_pre.batch(images)
+        img.append(images.float().cpu())
+        qry.append(q_ids.to(device="cpu", dtype=torch.int32))
+        tgt.append(t_ids.to(device="cpu", dtype=torch.int32))
+    pixels = torch.cat(img)
+    return (pixels.pin_memory() if device.type == "cuda" else pixels), torch.cat(qry), torch.cat(tgt)
 
 
 def _cache(model, dataset, batch_size, seed, num_workers, tokenize_fn, text_pooled: bool):
@@ -255,8 +284,9 @@ class HeadTrainer:
 
 # ------------------------------------------------------------------------------------------------ CLI (src/clip/train/trainer.py)
 def build_parser() -> argparse.ArgumentParser:
-    """The reference's arguments (trainer.py:532-580) plus --freeze_encoders, --synthetic and --dataset."""
-    parser = argparse.ArgumentParser(description="Fine-tune CLIP's projection heads with the joint T2I + T2T loss (frozen towers)")
+    """The reference's arguments (trainer.py:532-580) plus the three modes, --synthetic and --dataset."""
+    parser = argparse.ArgumentParser(description="Fine-tune CLIP with the joint T2I + T2T loss: the projection heads on frozen towers, the "
+                                                 "text tower on a locked image tower, or both towers end to end")
     parser.add_argument("--model_name", type=str, default="ViT-L/14")
     parser.add_argument("--checkpoint", type=str, default=None, help="Path to checkpoint to start from")
     parser.add_argument("--images_dir", type=str, default=None, help="accepted for the shipped scripts; the data come from --dataset")
@@ -282,10 +312,13 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--seed", type=int, default=42)
     mode = parser.add_mutually_exclusive_group()
     mode.add_argument("--freeze_encoders", action="store_true",
-                      help="train the projection heads on frozen towers (this or --lock_image_tower is required: end-to-end fine-tuning is not served)")
+                      help="train the projection heads on frozen towers (one of this, --lock_image_tower and --end_to_end is required)")
     mode.add_argument("--lock_image_tower", action="store_true",
                       help="instead of --freeze_encoders: train the projection heads AND the whole text tower on a locked image tower "
                            "(cached pooled image rows; attention backward in the HIP library); needs a batch size")
+    mode.add_argument("--end_to_end", action="store_true",
+                      help="instead of --freeze_encoders: train both towers and the projection heads, the reference's recipe (pixels cached "
+                           "in pinned host memory; attention, LayerNorm and activation backward in the HIP library); needs a batch size")
     parser.add_argument("--synthetic", type=int, default=0, metavar="N",
                         help="train and validate on N seeded synthetic items each instead of the HuggingFace dataset (offline)")
     parser.add_argument("--dataset", type=str, default="xuemduan/reevaluate-image-text-pairs")
@@ -295,9 +328,12 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv: Optional[Sequence[str]] = None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
-    if not args.freeze_encoders and not args.lock_image_tower:
+    if not args.freeze_encoders and not args.lock_image_tower and not args.end_to_end:
         print(f"error: {NOT_SERVED}", file=sys.stderr)
         return 2
+    if args.end_to_end and args.batch_size <= 0:
+        from .tower_train import BATCH_0_REFUSED_END_TO_END
+        parser.error(BATCH_0_REFUSED_END_TO_END)
     if args.lock_image_tower and args.batch_size <= 0:
         from .tower_train import BATCH_0_REFUSED
         parser.error(BATCH_0_REFUSED)
@@ -326,7 +362,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         train_set = CLIPEvalDatasetHF(ds["train"], preprocess, args.max_text_length)
         val_set = CLIPEvalDatasetHF(ds["validation"], preprocess, args.max_text_length)
     workers = 0 if args.synthetic > 0 else args.num_workers
-    if args.lock_image_tower:
+    if args.end_to_end:
+        from .tower_train import EndToEndTrainer, EndToEndTuning
+        logger.info(f"Collecting the preprocessed pixels of {len(train_set)} training items (end to end)...")
+        pooled = cache_pixels(model, train_set, batch_size=64, seed=args.seed, num_workers=workers)
+        heads, trainer_cls = EndToEndTuning(model), EndToEndTrainer
+    elif args.lock_image_tower:
         from .tower_train import LockedImageTuning, TextTowerTrainer
         logger.info(f"Caching the pooled image rows of {len(train_set)} training items (locked image tower)...")
         pooled = cache_image_pooled(model, train_set, batch_size=64, seed=args.seed, num_workers=workers)

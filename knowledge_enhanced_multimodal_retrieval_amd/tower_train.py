@@ -1,4 +1,4 @@
-"""A differentiable CLIP text tower and the locked-image trainer (``python -m src.clip.train.trainer --lock_image_tower``).
+"""Differentiable CLIP towers and their trainers (``python -m src.clip.train.trainer --lock_image_tower`` | ``--end_to_end``).
 
 ``TextTower`` restates the text tower of a CLIP-family model in torch over the MODEL'S OWN parameters (``token_embedding``,
 ``positional_embedding``, ``transformer.resblocks.*``, ``ln_final``, ``text_projection``): token + positional embedding, pre-LN residual
@@ -18,6 +18,25 @@ Running length: ``forward(ids, t)`` may run the first ``t`` positions only, ``t`
 ``longest``).  Under the causal mask no row up to a text's end-of-text token sees a later position, so this is exact for every row that
 reaches the loss.  Family ``clip`` only (Long-CLIP's 248 positions included); SigLIP and BERT models are refused like
 ``finetune.ProjectionHeads`` refuses them.
+
+Elementwise passes: ``elementwise="torch"`` (the default of ``TextTower``) runs the blocks' LayerNorms and the MLP activation as torch
+autograd does -- fp32 passes over ``[rows, 4 width]`` with an fp32 copy of each kept for the backward.  ``elementwise="op"`` routes
+``ln_1`` / ``ln_2`` and the activation through the library in both directions (csrc/train_ops.hip): ``_OpLayerNorm`` is
+``kemr_op_layernorm`` forward (it saves the fp32 rows it read, nothing else) and ``kemr_op_layernorm_backward`` backward; ``_OpAct`` is
+``kemr_op_act_forward`` / ``kemr_op_act_backward`` on the bf16 output of ``mlp.c_fc`` (it saves that bf16 pre-activation).  GPU and
+bf16 autocast only.
+
+``VisionTower`` restates the vision tower over the model's own ``visual.*`` parameters: the ``conv1`` patch embedding (a bias-free
+convolution whose stride is its kernel size: unfold + linear), class token, positional embedding, ``ln_pre``, the same pre-LN blocks
+with NON-causal attention (``kemr_op_attention`` / ``kemr_op_attention_backward`` at ``causal = 0``), then the class-token row -- what
+``kemr_encode_image_pooled`` returns -- and ``visual.ln_post``, ``visual.proj`` and the L2 normalisation through ``finetune.project``.
+Heads of 64 and at most 288 tokens (the attention backward's range): ViT-H-14's heads of 80 and the 577 tokens of ViT-L/14@336px are
+refused, like the SigLIP and BERT families.
+
+``EndToEndTuning`` = ``ProjectionHeads`` + ``VisionTower`` + ``TextTower``: what ``--end_to_end`` trains, every parameter of the model
+but ``logit_scale`` (the loss uses ``--temperature``, as the reference's does).  ``EndToEndTrainer`` is ``HeadTrainer``'s loop over
+(preprocessed pixels in pinned host memory, query ids, target ids): a batch is indexed on the host and moved to the device by
+``EndToEndTuning.forward``.
 
 ``TextTowerTrainer`` is ``finetune.HeadTrainer``'s loop -- batch schedule, accumulation, ``grad_clip``, validation through the served
 engine after each epoch, early stopping, ``metrics_epoch.jsonl``, checkpoints through ``clip_model.save_checkpoint`` -- with another
@@ -43,30 +62,69 @@ class _OpAttention(torch.autograd.Function):
     """qkv [batch * t, 3 width] (q not yet scaled) -> bf16 [batch * t, width] through the library's two attention kernels."""
 
     @staticmethod
-    def forward(ctx, qkv: torch.Tensor, batch: int, t: int, width: int) -> torch.Tensor:
+    def forward(ctx, qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool) -> torch.Tensor:
         from . import engine
         scaled = qkv.detach().to(torch.bfloat16).clone()
         scaled[:, :width] *= 0.125                       # exact: a power of two
         ctx.save_for_backward(scaled)
-        ctx.shape, ctx.in_dtype = (batch, t, width), qkv.dtype
-        return engine.op_attention(scaled, batch, t, width, True)
+        ctx.shape, ctx.in_dtype, ctx.causal = (batch, t, width), qkv.dtype, bool(causal)
+        return engine.op_attention(scaled, batch, t, width, ctx.causal)
 
     @staticmethod
     def backward(ctx, dout: torch.Tensor):
         from . import engine
         (scaled,) = ctx.saved_tensors
         batch, t, width = ctx.shape
-        dqkv = engine.attention_backward(scaled, dout.to(torch.bfloat16).contiguous(), batch, t, width, True)
+        dqkv = engine.attention_backward(scaled, dout.to(torch.bfloat16).contiguous(), batch, t, width, ctx.causal)
         dqkv[:, :width] *= 0.125                         # the caller's 1/8 of q (exact)
-        return dqkv.to(ctx.in_dtype), None, None, None
+        return dqkv.to(ctx.in_dtype), None, None, None, None
 
 
-def torch_attention(qkv: torch.Tensor, batch: int, t: int, width: int) -> torch.Tensor:
-    """The plain formulation: softmax(q k^T / 8 + causal mask) v per head of 64, in qkv's dtype."""
+class _OpLayerNorm(torch.autograd.Function):
+    """x fp32 [rows, width] -> LayerNorm(x) as bf16 (a GEMM operand) or fp32 (``ln_pre``, whose output is the stream) through
+    ``kemr_op_layernorm``; the backward is ``kemr_op_layernorm_backward``, which recomputes mean and rstd from the saved x."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_bf16: bool) -> torch.Tensor:
+        from . import engine
+        x, gamma = x.detach().contiguous(), gamma.detach()
+        ctx.save_for_backward(x, gamma)
+        ctx.out_bf16 = bool(out_bf16)
+        return engine.op_layernorm(x, gamma, beta.detach(), out_bf16=ctx.out_bf16)
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        from . import engine
+        x, gamma = ctx.saved_tensors
+        dx, dgamma, dbeta = engine.layernorm_backward(x, gamma, dy.to(torch.bfloat16 if ctx.out_bf16 else torch.float32).contiguous())
+        return dx, dgamma, dbeta, None
+
+
+class _OpAct(torch.autograd.Function):
+    """bf16 pre-activation -> bf16 activation (``kemr_op_act_forward``); saves the pre-activation, the backward is ``kemr_op_act_backward``."""
+
+    @staticmethod
+    def forward(ctx, pre: torch.Tensor, kind: str) -> torch.Tensor:
+        from . import engine
+        pre = pre.detach().contiguous()
+        ctx.save_for_backward(pre)
+        ctx.kind = kind
+        return engine.act_forward(pre, kind)
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        from . import engine
+        (pre,) = ctx.saved_tensors
+        return engine.act_backward(pre, dout.to(torch.bfloat16).contiguous(), ctx.kind), None
+
+
+def torch_attention(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool = True) -> torch.Tensor:
+    """The plain formulation: softmax(q k^T / 8 [+ causal mask]) v per head of 64, in qkv's dtype."""
     heads = width // 64
     q, k, v = (x.reshape(batch, t, heads, 64).transpose(1, 2) for x in qkv.split(width, dim=-1))
     s = (q * 0.125) @ k.transpose(-1, -2)
-    s = s + torch.full((t, t), float("-inf"), dtype=s.dtype, device=s.device).triu_(1)
+    if causal:
+        s = s + torch.full((t, t), float("-inf"), dtype=s.dtype, device=s.device).triu_(1)
     return (torch.softmax(s, dim=-1).to(v.dtype) @ v).transpose(1, 2).reshape(batch * t, width)
 
 
@@ -75,23 +133,81 @@ def longest(ids: torch.Tensor) -> int:
     return int(ids.argmax(dim=-1).max()) + 1
 
 
-class TextTower(nn.Module):
+OP_LN_WIDTHS = (256, 512, 768, 1024, 1280)          # kemr_op_layernorm and its backward
+
+
+class _Tower(nn.Module):
+    """What the two towers share: the settings and one pre-LN residual block on rows [batch * t, width]."""
+
+    causal = True
+
+    def _configure(self, who: str, attention: str, elementwise: str, autocast: Optional[bool], width: int, eps: Sequence[float]) -> None:
+        if attention not in ("op", "torch"):
+            raise ValueError(f"{who}: attention must be 'op' (the HIP kernels) or 'torch' (the plain formulation), got {attention!r}")
+        if elementwise not in ("op", "torch"):
+            raise ValueError(f"{who}: elementwise must be 'op' (the HIP kernels) or 'torch' (torch autograd), got {elementwise!r}")
+        self.attention, self.elementwise = attention, elementwise
+        self.autocast = (attention == "op" or elementwise == "op") if autocast is None else bool(autocast)
+        if elementwise == "op":
+            if not self.autocast:
+                raise ValueError(f"{who}: elementwise='op' runs on the bf16 outputs of autocast linears; autocast=False is not served with it")
+            if width not in OP_LN_WIDTHS:
+                raise ValueError(f"{who}: elementwise='op' serves widths {OP_LN_WIDTHS}, not {width}")
+            if any(e != 1e-5 for e in eps):
+                raise ValueError(f"{who}: elementwise='op' serves LayerNorms with eps 1e-5 (kemr_op_layernorm's)")
+
+    def _needs_gpu(self, who: str, dev: torch.device) -> None:
+        if (self.attention == "op" or self.elementwise == "op") and dev.type != "cuda":
+            raise RuntimeError(f"{who}: attention='op' / elementwise='op' must live on the GPU (got device {dev}); this path has no CPU "
+                               "fallback (attention='torch' with elementwise='torch' is the reference formulation)")
+
+    def _linear(self, x: torch.Tensor, lin_w: torch.Tensor, lin_b: Optional[torch.Tensor]) -> torch.Tensor:
+        if self.autocast:
+            with torch.autocast(x.device.type, dtype=torch.bfloat16):
+                return F.linear(x, lin_w, lin_b)
+        return F.linear(x, lin_w, lin_b)
+
+    def _ln(self, x: torch.Tensor, ln: nn.LayerNorm, out_bf16: bool = True) -> torch.Tensor:
+        if self.elementwise == "op":
+            return _OpLayerNorm.apply(x, ln.weight, ln.bias, out_bf16)
+        return F.layer_norm(x, (x.shape[-1],), ln.weight, ln.bias, ln.eps)
+
+    def _act(self, h: torch.Tensor) -> torch.Tensor:
+        if self.elementwise == "op":
+            return _OpAct.apply(h, self.activation)
+        h = h.float() if h.dtype == torch.bfloat16 else h
+        return F.gelu(h) if self.activation == "gelu" else h * torch.sigmoid(1.702 * h)
+
+    def _attend(self, qkv: torch.Tensor, batch: int, t: int) -> torch.Tensor:
+        """qkv [batch * t, 3 width] (q not yet scaled) -> [batch * t, width].  (tools/bench_text_tower_train.py overrides this.)"""
+        if self.attention == "op":
+            return _OpAttention.apply(qkv, batch, t, self.width, self.causal)
+        return torch_attention(qkv, batch, t, self.width, self.causal)
+
+    def _block(self, x: torch.Tensor, blk: nn.Module, batch: int, t: int) -> torch.Tensor:
+        qkv = self._linear(self._ln(x, blk.ln_1), blk.attn.in_proj_weight, blk.attn.in_proj_bias)
+        a = self._attend(qkv, batch, t)
+        x = x + self._linear(a, blk.attn.out_proj.weight, blk.attn.out_proj.bias)
+        h = self._act(self._linear(self._ln(x, blk.ln_2), blk.mlp.c_fc.weight, blk.mlp.c_fc.bias))
+        return x + self._linear(h, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias)
+
+
+class TextTower(_Tower):
     """See the module docstring.  ``trainable=True`` sets ``requires_grad`` on the text tower's parameters (and leaves every other
     parameter of the model as it finds it)."""
 
-    def __init__(self, model: nn.Module, attention: str = "op", autocast: Optional[bool] = None, trainable: bool = True):
+    def __init__(self, model: nn.Module, attention: str = "op", autocast: Optional[bool] = None, trainable: bool = True,
+                 elementwise: str = "torch"):
         super().__init__()
         m = _unwrap(model)
         family = getattr(getattr(m, "arch", None), "family", "clip")
         if family != "clip" or not hasattr(m, "text_projection") or not hasattr(m, "visual") or not hasattr(m.visual, "proj"):
             raise ValueError(f"TextTower: only the CLIP family's text tower is restated (this model's family: {family!r}; SigLIP pools the "
                              "last position of a bidirectional tower, BERT models are post-LN sentence encoders)")
-        if attention not in ("op", "torch"):
-            raise ValueError(f"TextTower: attention must be 'op' (the HIP kernels) or 'torch' (the plain formulation), got {attention!r}")
         if m.arch.t_width % 64 or m.arch.t_heads * 64 != m.arch.t_width:
             raise ValueError(f"TextTower: heads of 64 only (width {m.arch.t_width}, {m.arch.t_heads} heads)")
-        self.attention = attention
-        self.autocast = (attention == "op") if autocast is None else bool(autocast)
+        self._configure("TextTower", attention, elementwise, autocast, m.arch.t_width,
+                        [e for b in m.transformer.resblocks for e in (b.ln_1.eps, b.ln_2.eps)])
         self.activation, self.width, self.ctx = m.activation, m.arch.t_width, m.arch.ctx
         self.token_embedding, self.transformer = m.token_embedding, m.transformer              # the model's own modules and parameters
         self.positional_embedding = m.positional_embedding
@@ -107,40 +223,12 @@ class TextTower(nn.Module):
         out.update({"ln_final.weight": self.ln_final.weight, "ln_final.bias": self.ln_final.bias, "text_projection": self.text_projection})
         return out
 
-    def _linear(self, x: torch.Tensor, lin_w: torch.Tensor, lin_b: torch.Tensor) -> torch.Tensor:
-        if self.autocast:
-            with torch.autocast(x.device.type, dtype=torch.bfloat16):
-                return F.linear(x, lin_w, lin_b)
-        return F.linear(x, lin_w, lin_b)
-
-    def _act(self, h: torch.Tensor) -> torch.Tensor:
-        h = h.float() if h.dtype == torch.bfloat16 else h
-        return F.gelu(h) if self.activation == "gelu" else h * torch.sigmoid(1.702 * h)
-
-    def _attend(self, qkv: torch.Tensor, batch: int, t: int) -> torch.Tensor:
-        """qkv [batch * t, 3 width] (q not yet scaled) -> [batch * t, width], causal.  (tools/bench_text_tower_train.py overrides this.)"""
-        if self.attention == "op":
-            return _OpAttention.apply(qkv, batch, t, self.width)
-        return torch_attention(qkv, batch, t, self.width)
-
-    def _block(self, x: torch.Tensor, blk: nn.Module, batch: int, t: int) -> torch.Tensor:
-        w = self.width
-        h = F.layer_norm(x, (w,), blk.ln_1.weight, blk.ln_1.bias, blk.ln_1.eps)
-        qkv = self._linear(h, blk.attn.in_proj_weight, blk.attn.in_proj_bias)
-        a = self._attend(qkv, batch, t)
-        x = x + self._linear(a, blk.attn.out_proj.weight, blk.attn.out_proj.bias)
-        h = F.layer_norm(x, (w,), blk.ln_2.weight, blk.ln_2.bias, blk.ln_2.eps)
-        h = self._act(self._linear(h, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias))
-        return x + self._linear(h, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias)
-
     def pooled(self, ids: torch.Tensor, t: Optional[int] = None) -> torch.Tensor:
         """ids int [B, ctx] -> [B, width]: the residual-stream row at each text's end-of-text token, before ``ln_final``."""
         if ids.dim() != 2 or ids.shape[1] > self.ctx:
             raise ValueError(f"TextTower: ids must be [B, <= {self.ctx}], got {tuple(ids.shape)}")
         dev = self.positional_embedding.device
-        if self.attention == "op" and dev.type != "cuda":
-            raise RuntimeError(f"TextTower: attention='op' must live on the GPU (got device {dev}); this path has no CPU fallback "
-                               "(attention='torch' is the reference formulation)")
+        self._needs_gpu("TextTower", dev)
         ids = ids.to(dev).long()
         batch = ids.shape[0]
         eot = ids.argmax(dim=-1)
@@ -159,6 +247,68 @@ class TextTower(nn.Module):
         return project(self.pooled(ids, t), self.ln_final.weight, self.ln_final.bias, self.text_projection, self.ln_final.eps)
 
 
+class VisionTower(_Tower):
+    """See the module docstring.  ``trainable=True`` sets ``requires_grad`` on the vision tower's parameters (and leaves every other
+    parameter of the model as it finds it)."""
+
+    causal = False
+
+    def __init__(self, model: nn.Module, attention: str = "op", elementwise: str = "op", autocast: Optional[bool] = None,
+                 trainable: bool = True):
+        super().__init__()
+        m = _unwrap(model)
+        arch = getattr(m, "arch", None)
+        family = getattr(arch, "family", "clip")
+        if family != "clip" or not hasattr(m, "visual") or not hasattr(m.visual, "proj") or not hasattr(m.visual, "class_embedding"):
+            raise ValueError(f"VisionTower: only the CLIP family's vision tower is restated (this model's family: {family!r}; SigLIP has no "
+                             "class token and pools by attention, BERT models have no vision tower)")
+        if arch.v_head_dim != 64:
+            raise ValueError(f"VisionTower: heads of 64 only (this tower: width {arch.v_width} in heads of {arch.v_head_dim}; the attention "
+                             "backward serves no other head dim)")
+        if arch.v_tokens > MAX_T:
+            raise ValueError(f"VisionTower: {arch.v_tokens} tokens per image; the attention backward serves at most {MAX_T}")
+        v = m.visual
+        self._configure("VisionTower", attention, elementwise, autocast, arch.v_width,
+                        [v.ln_pre.eps] + [e for b in v.transformer.resblocks for e in (b.ln_1.eps, b.ln_2.eps)])
+        self.activation, self.width, self.tokens, self.patch, self.image_size = m.activation, arch.v_width, arch.v_tokens, arch.patch, arch.image_size
+        self.conv1, self.class_embedding, self.positional_embedding = v.conv1, v.class_embedding, v.positional_embedding
+        self.ln_pre, self.transformer, self.ln_post, self.proj = v.ln_pre, v.transformer, v.ln_post, v.proj
+        if trainable:
+            for p in self.parameters():
+                p.requires_grad = True
+
+    def named_vision_parameters(self) -> Dict[str, nn.Parameter]:
+        """Every parameter of the vision side under its name in the model's state dict."""
+        out = {"visual.conv1.weight": self.conv1.weight, "visual.class_embedding": self.class_embedding,
+               "visual.positional_embedding": self.positional_embedding, "visual.ln_pre.weight": self.ln_pre.weight,
+               "visual.ln_pre.bias": self.ln_pre.bias}
+        out.update({f"visual.transformer.{k}": p for k, p in self.transformer.named_parameters()})
+        out.update({"visual.ln_post.weight": self.ln_post.weight, "visual.ln_post.bias": self.ln_post.bias, "visual.proj": self.proj})
+        return out
+
+    def pooled(self, pixels: torch.Tensor) -> torch.Tensor:
+        """pixels [B, 3, S, S] (preprocessed) -> [B, width]: the class-token row of the residual stream, before ``ln_post``."""
+        s, p, w, t = self.image_size, self.patch, self.width, self.tokens
+        if pixels.dim() != 4 or tuple(pixels.shape[1:]) != (3, s, s):
+            raise ValueError(f"VisionTower: pixels must be [B, 3, {s}, {s}], got {tuple(pixels.shape)}")
+        dev = self.positional_embedding.device
+        self._needs_gpu("VisionTower", dev)
+        pixels = pixels.to(device=dev, dtype=self.positional_embedding.dtype)
+        batch, g = pixels.shape[0], s // p
+        # conv1 has no bias and its stride is its kernel size: every patch is one row of a linear layer
+        patches = pixels.reshape(batch, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(batch * g * g, 3 * p * p)
+        emb = self._linear(patches, self.conv1.weight.reshape(w, 3 * p * p), None).to(pixels.dtype).reshape(batch, g * g, w)
+        x = torch.cat([self.class_embedding.expand(batch, 1, w), emb], dim=1) + self.positional_embedding
+        x = self._ln(x.reshape(batch * t, w), self.ln_pre, out_bf16=False)
+        for blk in self.transformer.resblocks:
+            x = self._block(x, blk, batch, t)
+        return x.reshape(batch, t, w)[:, 0]
+
+    def forward(self, pixels: torch.Tensor) -> torch.Tensor:
+        """[B, embed_dim]: the L2-normalised image embeddings."""
+        return project(self.pooled(pixels), self.ln_post.weight, self.ln_post.bias, self.proj, self.ln_post.eps)
+
+
 class LockedImageTuning(nn.Module):
     """What ``--lock_image_tower`` trains: ``ProjectionHeads`` (six tensors) plus the whole text tower, over the model's own parameters."""
 
@@ -175,6 +325,27 @@ class LockedImageTuning(nn.Module):
         return self.heads.image(pooled_image), text[:n], text[n:]
 
 
+class EndToEndTuning(nn.Module):
+    """What ``--end_to_end`` trains: ``ProjectionHeads`` plus both towers, over the model's own parameters -- every parameter but
+    ``logit_scale``, which takes no part in the graph (the loss has its own temperature) and keeps its bits."""
+
+    def __init__(self, model: nn.Module, attention: str = "op", elementwise: str = "op", autocast: Optional[bool] = None):
+        super().__init__()
+        self.heads = ProjectionHeads(model)              # freezes everything, then its six tensors
+        self.vision = VisionTower(model, attention=attention, elementwise=elementwise, autocast=autocast, trainable=True)
+        self.tower = TextTower(model, attention=attention, autocast=autocast, trainable=True, elementwise=elementwise)
+
+    def forward(self, pixels: torch.Tensor, query_ids: torch.Tensor, target_ids: torch.Tensor
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """A host (or device) batch -> (image, query, target) embeddings on the model's device."""
+        dev = self.tower.positional_embedding.device
+        n = query_ids.shape[0]
+        ids = torch.cat([query_ids, target_ids])
+        t = longest(ids)                                 # read where the ids are: no device sync for host ids
+        text = self.tower(ids.to(dev, non_blocking=True), t)
+        return self.heads.image(self.vision.pooled(pixels.to(dev, non_blocking=True))), text[:n], text[n:]
+
+
 class TextTowerTrainer(HeadTrainer):
     """``HeadTrainer``'s loop with ``rows`` = (cached pooled image rows fp32 [N, v_width], query ids, target ids int [N, ctx], all on the
     model's device) and ``heads`` a ``LockedImageTuning``.  A batch's activations live on the device for its backward pass, so a batch
@@ -187,5 +358,20 @@ class TextTowerTrainer(HeadTrainer):
         super().__init__(model, heads, rows, loss_fn, optimizer, scheduler, batch_size=batch_size, **kw)
 
 
+class EndToEndTrainer(HeadTrainer):
+    """``HeadTrainer``'s loop with ``rows`` = (preprocessed pixels fp32 [N, 3, S, S] in pinned host memory, query ids, target ids int
+    [N, ctx] on the host; ``finetune.cache_pixels``) and ``heads`` an ``EndToEndTuning``: the loop indexes a batch where the rows are
+    and ``EndToEndTuning.forward`` moves it to the device.  A batch must be given: ``batch_size=0`` is refused."""
+
+    def __init__(self, model: nn.Module, heads: EndToEndTuning, rows: Sequence[torch.Tensor], loss_fn, optimizer, scheduler=None,
+                 batch_size: int = 64, **kw):
+        if batch_size <= 0:
+            raise ValueError(BATCH_0_REFUSED_END_TO_END)
+        super().__init__(model, heads, rows, loss_fn, optimizer, scheduler, batch_size=batch_size, **kw)
+
+
+BATCH_0_REFUSED_END_TO_END = ("--batch_size 0 (the whole split as one batch) is not served with --end_to_end: the towers' backward passes "
+                              "keep the activations of a whole batch on the device, and the activations of a whole split do not fit; give a "
+                              "batch size")
 BATCH_0_REFUSED = ("--batch_size 0 (the whole split as one batch) is not served with --lock_image_tower: the text tower's backward pass "
                    "keeps the activations of a whole batch on the device, and the activations of a whole split do not fit; give a batch size")

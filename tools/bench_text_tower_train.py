@@ -73,7 +73,7 @@ def bench_size(n, reps, dev):
 
     def attn(which):
         qkv.grad = None
-        o = tower_train._OpAttention.apply(qkv, 2 * n, CTX, WIDTH) if which == "op" else sdpa_attention(qkv, 2 * n, CTX, WIDTH)
+        o = tower_train._OpAttention.apply(qkv, 2 * n, CTX, WIDTH, True) if which == "op" else sdpa_attention(qkv, 2 * n, CTX, WIDTH)
         o.backward(dout)
         return qkv.grad
 
