@@ -77,7 +77,10 @@ extern "C" {
  *    Still 4: kemr_op_attention_backward (the backward of kemr_op_attention, heads of 64, t <= KEMR_MAX_TEXT_CTX) is an addition; the
  *    forward kernels did not change and save nothing for it.
  *    Still 4: kemr_layernorm_backward_workspace_bytes, kemr_op_layernorm_backward (the backward of kemr_op_layernorm), kemr_op_act_forward
- *    and kemr_op_act_backward (the MLP activation on bf16) are additions; no existing entry point changed. */
+ *    and kemr_op_act_backward (the MLP activation on bf16) are additions; no existing entry point changed.
+ *    Still 4: kemr_attention_backward_long_workspace_bytes and kemr_op_attention_backward_long (the non-causal backward of
+ *    kemr_op_attention for t <= KEMR_MAX_VISION_TOKENS, streaming, with a small workspace) are additions; kemr_op_attention_backward
+ *    keeps its signature, refusals, messages and bits. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -718,7 +721,26 @@ int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, int t, int 
  * ragged last tiles are masked, and nothing outside an item's own rows of qkv and dout can reach its rows of dqkv. */
 int kemr_op_attention_backward(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width, int causal,
                                void* stream);
-/* The backward of kemr_op_layernorm.  x fp32 [rows, width] exactly as the forward read it, gamma fp32 [width], dy [rows, width] = the
+/* The same backward, non-causal, for sequences of any length the forward takes: 1 <= t <= KEMR_MAX_VISION_TOKENS (1025; the long
+ * vision towers, ViT-L/14@336px's 577 tokens).  qkv, dout and dqkv as above; width % 64 == 0, batch >= 0 (batch == 0 launches nothing;
+ * batch * width / 64 * ceil(t / 64) <= 2^31 - 1, the grid); workspace_bytes >= kemr_attention_backward_long_workspace_bytes(batch, t,
+ * width) = batch * (width / 64) * t * 3 * sizeof(float) (a function of its three arguments only; 0 at batch == 0 and for arguments
+ * the op refuses; the workspace may be NULL when it is 0), the workspace 4-byte aligned.  Anything else, or a NULL pointer, is
+ * KEMR_ERR_INVALID with a message that starts with "op_attention_backward_long:" and names the argument, refused on the host before
+ * any launch with dqkv untouched.
+ * The forward saves nothing and nothing longer than 64 rows is held in LDS: a query-owned kernel streams K and V twice (an online
+ * row maximum, sum and sum of e^(s - m) dP in fp32, rescaled by exp(m - m') as the forward's; then P from the final maximum and sum,
+ * dS and dq) and leaves max * log2 e, 1 / sum and D of every query row of every head in the workspace, fp32 [batch * heads * t, 3];
+ * a key-owned kernel streams Q, dO and those statistics once and writes dk and dv.  Rounding as above: P and dS to bf16 as MFMA
+ * operands, the outputs to bf16 at the store, D from the unrounded fp32 P, nothing else below fp32.  No atomics: every element of dqkv
+ * has one owner and one summation order, so the same inputs give the same bits on every launch (not the bits of
+ * kemr_op_attention_backward at t <= 288: the order of the sums differs).  Exactly batch * t rows of dqkv are written and the workspace
+ * only inside its stated size; the ragged last tiles are masked, and nothing outside an item's own rows of qkv and dout can reach its
+ * rows of dqkv.  Every launch goes to `stream`. */
+size_t kemr_attention_backward_long_workspace_bytes(int batch, int t, int width);
+int kemr_op_attention_backward_long(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width,
+                                    void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The backward of kemr_op_layernorm. x fp32 [rows, width] exactly as the forward read it, gamma fp32 [width], dy [rows, width] = the
  * gradient of its output in dy_dtype (KEMR_BF16 where the forward wrote bf16, KEMR_F32 where it wrote fp32) -> dx fp32 [rows, width],
  * dgamma and dbeta fp32 [width].  The forward saves nothing: mean and rstd are recomputed in fp32 exactly as the forward does (two
  * passes, the same wave sums, eps 1e-5).  With g = dy gamma and x^ = (x - mean) rstd: dx = rstd (g - mean(g) - x^ mean(g x^)),

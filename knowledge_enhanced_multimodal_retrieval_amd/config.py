@@ -182,6 +182,8 @@ ARCHS: Dict[str, ClipArch] = {
     # small shapes for tests (same structure, head dim 64)
     "tiny": ClipArch(128, 32, 8, 256, 2, 256, 2, vocab=512, ctx=16),
     "tiny-ctx248": ClipArch(128, 32, 8, 256, 2, 256, 2, vocab=512, ctx=248),      # "tiny" with Long-CLIP's 248 text positions
+    # "tiny" with a 17 x 17 grid: 290 vision tokens, the smallest tower past the 288 rows of the LDS attention backward (training tests)
+    "tiny-290": ClipArch(128, 136, 8, 256, 2, 256, 2, vocab=512, ctx=16),
     "tiny-long": ClipArch(256, 112, 8, 256, 3, 512, 3, vocab=1024, ctx=77),
     # the structure of ViT-H-14 (vision heads of 80 at width 1280, the only width that is a multiple of 256 and of 80): 5 and 257 tokens
     "tiny-h": ClipArch(128, 28, 14, 1280, 2, 256, 2, vocab=512, ctx=16, v_head_dim=80),

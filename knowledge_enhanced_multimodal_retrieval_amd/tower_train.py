@@ -30,8 +30,11 @@ bf16 autocast only.
 convolution whose stride is its kernel size: unfold + linear), class token, positional embedding, ``ln_pre``, the same pre-LN blocks
 with NON-causal attention (``kemr_op_attention`` / ``kemr_op_attention_backward`` at ``causal = 0``), then the class-token row -- what
 ``kemr_encode_image_pooled`` returns -- and ``visual.ln_post``, ``visual.proj`` and the L2 normalisation through ``finetune.project``.
-Heads of 64 and at most 288 tokens (the attention backward's range): ViT-H-14's heads of 80 and the 577 tokens of ViT-L/14@336px are
-refused, like the SigLIP and BERT families.
+Heads of 64: ViT-H-14's heads of 80 are refused, like the SigLIP and BERT families.  ``max_tokens`` bounds the sequence: the default,
+``MAX_T`` = 288, is the range of ``kemr_op_attention_backward`` and refuses the 577 tokens of ViT-L/14@336px; ``max_tokens=MAX_T_LONG``
+(1025, the forward's range) opts in to the long towers, whose attention backward is the streaming ``kemr_op_attention_backward_long``
+(csrc/attention_bwd_stream.hip; ``engine.attention_backward`` routes by length, so towers of up to 288 tokens keep their kernel and bits).
+``EndToEndTuning`` passes ``MAX_T_LONG``.
 
 ``EndToEndTuning`` = ``ProjectionHeads`` + ``VisionTower`` + ``TextTower``: what ``--end_to_end`` trains, every parameter of the model
 but ``logit_scale`` (the loss uses ``--temperature``, as the reference's does).  ``EndToEndTrainer`` is ``HeadTrainer``'s loop over
@@ -56,6 +59,7 @@ from .clip_model import _unwrap
 from .finetune import HeadTrainer, ProjectionHeads, project
 
 MAX_T = 288          # KEMR_MAX_TEXT_CTX: the range of kemr_op_attention (causal) and of its backward
+MAX_T_LONG = 1025    # KEMR_MAX_VISION_TOKENS: the range of kemr_op_attention (non-causal) and of kemr_op_attention_backward_long
 
 
 class _OpAttention(torch.autograd.Function):
@@ -254,8 +258,12 @@ class VisionTower(_Tower):
     causal = False
 
     def __init__(self, model: nn.Module, attention: str = "op", elementwise: str = "op", autocast: Optional[bool] = None,
-                 trainable: bool = True):
+                 trainable: bool = True, max_tokens: int = MAX_T):
         super().__init__()
+        if not 1 <= int(max_tokens) <= MAX_T_LONG:
+            raise ValueError(f"VisionTower: max_tokens = {max_tokens} is outside 1..{MAX_T_LONG} (MAX_T = {MAX_T}: the default; "
+                             f"MAX_T_LONG = {MAX_T_LONG}: the long towers)")
+        max_tokens = int(max_tokens)
         m = _unwrap(model)
         arch = getattr(m, "arch", None)
         family = getattr(arch, "family", "clip")
@@ -265,8 +273,8 @@ class VisionTower(_Tower):
         if arch.v_head_dim != 64:
             raise ValueError(f"VisionTower: heads of 64 only (this tower: width {arch.v_width} in heads of {arch.v_head_dim}; the attention "
                              "backward serves no other head dim)")
-        if arch.v_tokens > MAX_T:
-            raise ValueError(f"VisionTower: {arch.v_tokens} tokens per image; the attention backward serves at most {MAX_T}")
+        if arch.v_tokens > max_tokens:
+            raise ValueError(f"VisionTower: {arch.v_tokens} tokens per image; the attention backward serves at most {max_tokens}")
         v = m.visual
         self._configure("VisionTower", attention, elementwise, autocast, arch.v_width,
                         [v.ln_pre.eps] + [e for b in v.transformer.resblocks for e in (b.ln_1.eps, b.ln_2.eps)])
@@ -332,7 +340,8 @@ class EndToEndTuning(nn.Module):
     def __init__(self, model: nn.Module, attention: str = "op", elementwise: str = "op", autocast: Optional[bool] = None):
         super().__init__()
         self.heads = ProjectionHeads(model)              # freezes everything, then its six tensors
-        self.vision = VisionTower(model, attention=attention, elementwise=elementwise, autocast=autocast, trainable=True)
+        self.vision = VisionTower(model, attention=attention, elementwise=elementwise, autocast=autocast, trainable=True,
+                                  max_tokens=MAX_T_LONG)
         self.tower = TextTower(model, attention=attention, autocast=autocast, trainable=True, elementwise=elementwise)
 
     def forward(self, pixels: torch.Tensor, query_ids: torch.Tensor, target_ids: torch.Tensor
