@@ -80,7 +80,10 @@ extern "C" {
  *    and kemr_op_act_backward (the MLP activation on bf16) are additions; no existing entry point changed.
  *    Still 4: kemr_attention_backward_long_workspace_bytes and kemr_op_attention_backward_long (the non-causal backward of
  *    kemr_op_attention for t <= KEMR_MAX_VISION_TOKENS, streaming, with a small workspace) are additions; kemr_op_attention_backward
- *    keeps its signature, refusals, messages and bits. */
+ *    keeps its signature, refusals, messages and bits.
+ *    Still 4: kemr_op_attention_packed (the causal forward over items of different lengths packed one behind the other, what the text
+ *    encoders run inside themselves) and kemr_op_attention_backward_packed (its backward, and the non-causal one, for items of up to
+ *    KEMR_MAX_TEXT_CTX rows) are additions; the dense ops keep their signatures, refusals, messages and bits. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -721,6 +724,34 @@ int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, int t, int 
  * ragged last tiles are masked, and nothing outside an item's own rows of qkv and dout can reach its rows of dqkv. */
 int kemr_op_attention_backward(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width, int causal,
                                void* stream);
+/* Causal attention (heads of 64) over items of different lengths packed one behind the other, the forward the text encoders run on
+ * packed texts.  qkv bf16 [rows, 3*width] (q | k | v, q pre-scaled by 1/8) -> out bf16 [rows, width]; item b = rows row_start[b] ..
+ * row_start[b + 1] - 1 of both (row_start: device int32 [batch + 1], non-decreasing; batch + 1 ints are read), every length in
+ * 1 .. max_t.  1 <= max_t <= KEMR_MAX_TEXT_CTX (288), width % 64 == 0, 0 <= batch <= 65 528 (batch == 0 launches nothing); anything
+ * else, or a NULL pointer, is KEMR_ERR_INVALID with a message that starts with "op_attention_packed:" and names the argument, refused
+ * on the host before any launch.  max_t <= 128 runs the tile kernels, one workgroup per (item, head); above, the causal streaming
+ * kernel, in which an item longer than max_t is computed as an item of its first max_t rows (its later rows of out are not written)
+ * and an empty item writes nothing -- the tile kernels take lengths 1 .. max_t only.  Exactly the rows row_start[0] ..
+ * row_start[batch] - 1 of out are written, nothing outside an item's own rows of qkv can reach its rows of out, and an item has the
+ * same bits whatever is packed around it.  Every launch goes to `stream`. */
+int kemr_op_attention_packed(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width, void* stream);
+/* The backward of kemr_op_attention_packed (causal = 1), and of its non-causal counterpart (causal = 0), over the same packed layout:
+ * qkv bf16 [rows, 3*width] as the forward reads it (q pre-scaled by 1/8), dout bf16 [rows, width] -> dqkv bf16 [rows, 3*width], the
+ * gradient with respect to the three planes AS GIVEN: the caller owns the 1/8 of q, as with kemr_op_attention_backward.  Item b =
+ * rows row_start[b] .. row_start[b + 1] - 1 of all three (row_start: device int32 [batch + 1]; batch + 1 ints are read).
+ * 1 <= max_t <= KEMR_MAX_TEXT_CTX (288), width % 64 == 0, causal 0 or 1, batch >= 0 (batch == 0 launches nothing; batch * width / 64
+ * <= 2^31 - 1, the grid); anything else, or a NULL qkv, dout, dqkv or row_start, is KEMR_ERR_INVALID with a message that starts with
+ * "op_attention_backward_packed:" and names the argument, refused on the host before any HIP call with dqkv untouched.
+ * Lengths: an empty item (length <= 0) reads and writes nothing; an item longer than max_t is computed as an item of its first max_t
+ * rows and its later rows of dqkv are not written (the forward's convention).  Exactly the rows row_start[0] .. row_start[batch] - 1
+ * of dqkv are written, less those rows; nothing outside an item's own rows of qkv and dout can reach its rows of dqkv.
+ * The kernel is kemr_op_attention_backward's with the item's first row and length read from row_start: one workgroup per (item, head),
+ * the head's Q, K, V and dO in LDS in the allocation of max_t, no workspace, no atomics, every element of dqkv owned by one wave and
+ * summed in one order -- the same bits on every launch, and, per item, the bits of kemr_op_attention_backward(batch = 1, t = the
+ * item's length) on the same rows at any max_t >= that length (the tiles of the larger allocation are skipped, they add nothing to
+ * any sum).  Every launch goes to `stream`. */
+int kemr_op_attention_backward_packed(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, const int* row_start_dev, int batch,
+                                      int max_t, int width, int causal, void* stream);
 /* The same backward, non-causal, for sequences of any length the forward takes: 1 <= t <= KEMR_MAX_VISION_TOKENS (1025; the long
  * vision towers, ViT-L/14@336px's 577 tokens).  qkv, dout and dqkv as above; width % 64 == 0, batch >= 0 (batch == 0 launches nothing;
  * batch * width / 64 * ceil(t / 64) <= 2^31 - 1, the grid); workspace_bytes >= kemr_attention_backward_long_workspace_bytes(batch, t,

@@ -124,6 +124,8 @@ SIGNATURES = {
     "kemr_op_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "kemr_op_attention_hd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "kemr_op_attention_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "kemr_op_attention_packed": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "kemr_op_attention_backward_packed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "kemr_attention_backward_long_workspace_bytes": (_sz, [_i, _i, _i]),
     "kemr_op_attention_backward_long": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "kemr_layernorm_backward_workspace_bytes": (_sz, [_i, _i]),

@@ -265,6 +265,21 @@ extern "C" int kemr_op_attention(const void* qkv_dev, void* out_dev, int batch, 
     return launch_attention((const bf16_t*)qkv_dev, (bf16_t*)out_dev, batch, t, width, causal, (hipStream_t)stream);
 }
 
+// the causal packed forward as a product entry point: launch_attention_packed behind named host-side refusals
+extern "C" int kemr_op_attention_packed(const void* qkv_dev, void* out_dev, const int* row_start_dev, int batch, int max_t, int width,
+                                        void* stream) {
+    if (!qkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_packed: qkv is NULL");
+    if (!out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_packed: out is NULL");
+    if (!row_start_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_packed: row_start is NULL");
+    if (max_t < 1 || max_t > KEMR_MAX_TEXT_CTX)
+        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_packed: max_t = %d is outside 1..%d", max_t, KEMR_MAX_TEXT_CTX);
+    if (width <= 0 || width % 64 != 0)
+        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_packed: width = %d is not a positive multiple of 64 (heads of 64)", width);
+    if (batch < 0) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_packed: batch = %d is negative", batch);
+    if (batch > 65528) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_packed: batch = %d exceeds 65528 (the grid)", batch);
+    return launch_attention_packed((const bf16_t*)qkv_dev, (bf16_t*)out_dev, row_start_dev, batch, max_t, width, (hipStream_t)stream);
+}
+
 extern "C" int kemr_op_attention_hd(const void* qkv_dev, void* out_dev, int batch, int t, int width, int head_dim, int causal, void* stream) {
     if (!qkv_dev || !out_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_hd: null argument");
     KEMR_TRY(check_head_dim("op_attention_hd", head_dim, width));

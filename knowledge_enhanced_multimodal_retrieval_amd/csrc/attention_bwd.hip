@@ -1,4 +1,5 @@
-// Backward of the multi-head self-attention of attention.hip (head dim 64, t <= 288, causal or not): kemr_op_attention_backward.
+// Backward of the multi-head self-attention of attention.hip (head dim 64, t <= 288, causal or not): kemr_op_attention_backward, and
+// kemr_op_attention_backward_packed, the same kernel over items of different lengths packed one behind the other (PACKED, below).
 //
 //   qkv  bf16 [batch * t, 3 width]  q | k | v as the forward reads them (q already scaled by 1/8)
 //   dout bf16 [batch * t, width]    gradient of the forward's output
@@ -25,6 +26,8 @@
 // (row >> 1) & 3: transposed reads conflict-free, row reads 2-way); V is only read by rows and carries the K swizzle (16-byte chunk
 // ^= (row >> 1) & 7: conflict-free).
 #include "common.h"
+
+#include <type_traits>
 
 namespace kemr {
 
@@ -183,9 +186,15 @@ __device__ __forceinline__ void bwd_own_tile(const char* sQ, const char* sK, con
     }
 }
 
-template <int NT32, bool CAUSAL>
+// PACKED: item b = rows row_start[b] .. row_start[b + 1] - 1 of the three buffers, cut at its first T (= max_t) rows; an empty item's
+// workgroup leaves before any load.  NT32 comes from max_t, so an item shorter than NT32 * 32 rows runs in a larger instantiation than
+// the dense op would give it: the tiles beyond its own padded length are skipped by the same wave-uniform tests that skip the pad tiles
+// of the dense op (they add -inf to the maximum, exp2(-inf) = 0 to the sums, and no MFMA), and the order of the sums over the live
+// tiles does not depend on NT32 -- an item has the bits of the dense op at batch = 1, t = its length.
+template <int NT32, bool CAUSAL, bool PACKED>
 __global__ __launch_bounds__(256) void attention_bwd_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
-                                                            bf16_t* __restrict__ dqkv, int T, int width, int heads) {
+                                                            bf16_t* __restrict__ dqkv, const int* __restrict__ row_start, int T, int width,
+                                                            int heads) {
     constexpr int TP = NT32 * 32;
     constexpr int NTH = 256, NW = 4;
     constexpr int NCH = (TP * 8 + NTH - 1) / NTH;       // 16-byte chunks of one matrix per thread
@@ -201,7 +210,14 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const bf16_t* __rest
     const int b = blockIdx.x / heads, h = blockIdx.x - b * heads;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const size_t ld = 3 * (size_t)width, row0 = (size_t)b * T;
+    size_t row0 = (size_t)b * T;
+    if constexpr (PACKED) {
+        const int first = row_start[b], len = row_start[b + 1] - first;
+        T = len < T ? len : T;
+        if (T <= 0) return;                             // an empty item: no load (the pad rows below clamp to row T - 1), no store
+        row0 = (size_t)first;
+    }
+    const size_t ld = 3 * (size_t)width;
     const bf16_t* qbase = qkv + row0 * ld + h * 64;
     const bf16_t* gbase = dout + row0 * width + h * 64;
 
@@ -211,6 +227,40 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const bf16_t* __rest
         const bf16_t* src = mtx < 3 ? qbase + mtx * width : gbase;
         const size_t sld = mtx < 3 ? ld : (size_t)width;
         char* img = smem + mtx * TP * 128;
+        if constexpr (PACKED) {
+            // the item's own padded length (a multiple of 32 rows, at most TP): no row beyond it is ever read.  32 rows are one chunk
+            // per thread, so a thread stages ceil(T / 32) chunks: groups of four in flight, then the one to three that are left
+            // (uniform counts, every load of a group issued before its first LDS write, no load that is not stored)
+            const int nblk = (T + 31) >> 5;
+            auto stage = [&](auto depth, int blk) {
+                constexpr int M = decltype(depth)::value;
+                uint4 v[M];
+#pragma unroll
+                for (int i = 0; i < M; ++i) {
+                    const int idx = (blk + i) * NTH + tid;
+                    const int row = idx >> 3, c = idx & 7;
+                    const int rc = row < T ? row : T - 1;
+                    v[i] = *(const uint4*)(src + (size_t)rc * sld + c * 8);
+                }
+#pragma unroll
+                for (int i = 0; i < M; ++i) {
+                    const int idx = (blk + i) * NTH + tid;
+                    const int row = idx >> 3, c = idx & 7;
+                    const unsigned keep = row < T ? 0xffffffffu : 0u;
+                    uint4 a = v[i];
+                    a.x &= keep; a.y &= keep; a.z &= keep; a.w &= keep;
+                    *(uint4*)(img + (mtx == 2 ? bwd_off<false>(row, c) : bwd_off<true>(row, c))) = a;
+                }
+            };
+            int blk = 0;
+            for (; blk + 4 <= nblk; blk += 4) stage(std::integral_constant<int, 4>{}, blk);
+            switch (nblk - blk) {
+                case 3: stage(std::integral_constant<int, 3>{}, blk); break;
+                case 2: stage(std::integral_constant<int, 2>{}, blk); break;
+                case 1: stage(std::integral_constant<int, 1>{}, blk); break;
+            }
+            continue;
+        }
         uint4 v[NCH];
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
@@ -241,34 +291,43 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const bf16_t* __rest
         bwd_own_tile<NT32, CAUSAL, 2>(sQ, sK, sV, sG, sM, sI, sD, ot, T, lane, dst, ld, width);
 }
 
+// row_start == nullptr: the dense op (items of t rows one behind the other); otherwise the packed op, t = max_t
 template <int NT32>
-static int launch_bwd_nt(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, int batch, int t, int width, int causal, hipStream_t stream) {
+static int launch_bwd_nt(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, const int* row_start, int batch, int t, int width,
+                         int causal, hipStream_t stream) {
     constexpr int smem = NT32 * 32 * (4 * 128 + 3 * 4);
     static_assert(smem <= 160 * 1024, "the head's four tiles and row statistics must fit the LDS of one CU");
-    void (*kern)(const bf16_t*, const bf16_t*, bf16_t*, int, int, int) =
-        causal ? attention_bwd_kernel<NT32, true> : attention_bwd_kernel<NT32, false>;
+    void (*kern)(const bf16_t*, const bf16_t*, bf16_t*, const int*, int, int, int) =
+        row_start ? (causal ? attention_bwd_kernel<NT32, true, true> : attention_bwd_kernel<NT32, false, true>)
+                  : (causal ? attention_bwd_kernel<NT32, true, false> : attention_bwd_kernel<NT32, false, false>);
     ProfScope prof(PROF_ATTENTION, stream);
     KEMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     const int heads = width / 64;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)batch * heads)), dim3(256), smem, stream, qkv, dout, dqkv, t, width, heads);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)batch * heads)), dim3(256), smem, stream, qkv, dout, dqkv, row_start, t, width,
+                       heads);
     KEMR_CHECK_LAUNCH("attention_bwd_kernel");
     return KEMR_OK;
 }
 
+static int launch_bwd(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, const int* row_start, int batch, int t, int width, int causal,
+                      hipStream_t stream, const char* who) {
+    switch ((t + 31) / 32) {
+        case 1: return launch_bwd_nt<1>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
+        case 2: return launch_bwd_nt<2>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
+        case 3: return launch_bwd_nt<3>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
+        case 4: return launch_bwd_nt<4>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
+        case 5: return launch_bwd_nt<5>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
+        case 6: return launch_bwd_nt<6>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
+        case 7: return launch_bwd_nt<7>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
+        case 8: return launch_bwd_nt<8>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
+        case 9: return launch_bwd_nt<9>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
+    }
+    KEMR_FAIL(KEMR_ERR_INVALID, "%s: %s = %d is outside 1..%d", who, row_start ? "max_t" : "t", t, KEMR_MAX_TEXT_CTX);
+}
+
 // arguments checked by the caller (kemr_op_attention_backward): 1 <= t <= KEMR_MAX_TEXT_CTX, width % 64 == 0, batch >= 1
 int launch_attention_backward(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, int batch, int t, int width, int causal, hipStream_t stream) {
-    switch ((t + 31) / 32) {
-        case 1: return launch_bwd_nt<1>(qkv, dout, dqkv, batch, t, width, causal, stream);
-        case 2: return launch_bwd_nt<2>(qkv, dout, dqkv, batch, t, width, causal, stream);
-        case 3: return launch_bwd_nt<3>(qkv, dout, dqkv, batch, t, width, causal, stream);
-        case 4: return launch_bwd_nt<4>(qkv, dout, dqkv, batch, t, width, causal, stream);
-        case 5: return launch_bwd_nt<5>(qkv, dout, dqkv, batch, t, width, causal, stream);
-        case 6: return launch_bwd_nt<6>(qkv, dout, dqkv, batch, t, width, causal, stream);
-        case 7: return launch_bwd_nt<7>(qkv, dout, dqkv, batch, t, width, causal, stream);
-        case 8: return launch_bwd_nt<8>(qkv, dout, dqkv, batch, t, width, causal, stream);
-        case 9: return launch_bwd_nt<9>(qkv, dout, dqkv, batch, t, width, causal, stream);
-    }
-    KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: t = %d is outside 1..%d", t, KEMR_MAX_TEXT_CTX);
+    return launch_bwd(qkv, dout, dqkv, nullptr, batch, t, width, causal, stream, "op_attention_backward");
 }
 
 }  // namespace kemr
@@ -290,4 +349,27 @@ extern "C" int kemr_op_attention_backward(const void* qkv_dev, const void* dout_
     if (batch == 0) return KEMR_OK;
     return launch_attention_backward((const bf16_t*)qkv_dev, (const bf16_t*)dout_dev, (bf16_t*)dqkv_dev, batch, t, width, causal,
                                      (hipStream_t)stream);
+}
+
+// The packed form: item b = rows row_start[b] .. row_start[b + 1] - 1 (device array of batch + 1 ints), one workgroup per (item, head)
+// in the instantiation of max_t.  See kemr.h.
+extern "C" int kemr_op_attention_backward_packed(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, const int* row_start_dev,
+                                                 int batch, int max_t, int width, int causal, void* stream) {
+    // everything is refused here, on the host, before any HIP call
+    if (!qkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: qkv is NULL");
+    if (!dout_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: dout is NULL");
+    if (!dqkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: dqkv is NULL");
+    if (!row_start_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: row_start is NULL");
+    if (max_t < 1 || max_t > KEMR_MAX_TEXT_CTX)
+        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: max_t = %d is outside 1..%d", max_t, KEMR_MAX_TEXT_CTX);
+    if (width <= 0 || width % 64 != 0)
+        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: width = %d is not a positive multiple of 64 (heads of 64)", width);
+    if (causal != 0 && causal != 1) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: causal = %d is neither 0 nor 1", causal);
+    if (batch < 0) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: batch = %d is negative", batch);
+    if ((long long)batch * (width / 64) > 0x7fffffffLL)
+        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: batch = %d x %d heads exceeds the grid (2^31 - 1 workgroups)", batch,
+                  width / 64);
+    if (batch == 0) return KEMR_OK;
+    return launch_bwd((const bf16_t*)qkv_dev, (const bf16_t*)dout_dev, (bf16_t*)dqkv_dev, row_start_dev, batch, max_t, width, causal,
+                      (hipStream_t)stream, "op_attention_backward_packed");
 }

@@ -1123,6 +1123,59 @@ def attention_backward(qkv: torch.Tensor, dout: torch.Tensor, batch: int, t: int
     return dqkv
 
 
+def _check_packed(who: str, qkv: torch.Tensor, row_start: torch.Tensor, width: int, dout: Optional[torch.Tensor] = None) -> None:
+    """What the two packed attention wrappers check before they hand pointers to the library."""
+    tensors = [(qkv, "qkv"), (row_start, "row_start")] + ([(dout, "dout")] if dout is not None else [])
+    for t, what in tensors:
+        _require_cuda(t, f"{who}: {what}")
+    if qkv.dtype != torch.bfloat16 or not qkv.is_contiguous() or (dout is not None and (dout.dtype != torch.bfloat16 or not dout.is_contiguous())):
+        raise RuntimeError(f"{who}: qkv{'' if dout is None else ' and dout'} must be contiguous bf16")
+    if row_start.dtype != torch.int32 or row_start.dim() != 1 or row_start.numel() < 1 or not row_start.is_contiguous():
+        raise RuntimeError(f"{who}: row_start must be contiguous int32 [batch + 1], got {row_start.dtype} {tuple(row_start.shape)}")
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * width or any(t.device != qkv.device for t, _ in tensors) or \
+            (dout is not None and tuple(dout.shape) != (qkv.shape[0], width)):
+        raise RuntimeError(f"{who}: qkv must be [rows, {3 * width}]{'' if dout is None else f', dout [rows, {width}]'} and row_start on the "
+                           f"same device, got {[tuple(t.shape) for t, _ in tensors]} on {[str(t.device) for t, _ in tensors]}")
+
+
+def _check_packed_out(who: str, out: torch.Tensor, qkv: torch.Tensor, shape: Tuple[int, ...]) -> None:
+    if out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != qkv.device or tuple(out.shape) != tuple(shape):
+        raise RuntimeError(f"{who}: out must be contiguous bf16 {tuple(shape)} on qkv's device, got {out.dtype} {tuple(out.shape)} on {out.device}")
+
+
+def op_attention_packed(qkv: torch.Tensor, row_start: torch.Tensor, max_t: int, width: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal attention over packed items (``kemr_op_attention_packed``): qkv bf16 [rows, 3 width] (q pre-scaled by 1/8), row_start
+    int32 [batch + 1] on the same device, item b = rows row_start[b] .. row_start[b + 1] - 1, every length in 1 .. max_t <= 288 ->
+    bf16 [rows, width].  The caller's row_start must stay inside ``rows``: the library reads it on the device.  Rows no item owns are
+    left as they are: as allocated, or as ``out`` (bf16 [rows, width], contiguous, for calls over sub-ranges of the items) has them."""
+    _check_packed("op_attention_packed", qkv, row_start, width)
+    if out is None:
+        out = torch.empty((qkv.shape[0], width), dtype=torch.bfloat16, device=qkv.device)
+    _check_packed_out("op_attention_packed", out, qkv, (qkv.shape[0], width))
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.lib().kemr_op_attention_packed(C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(row_start.data_ptr()),
+                                                       row_start.numel() - 1, int(max_t), int(width), C.c_void_p(_stream_ptr(qkv.device))),
+                   "op_attention_packed")
+    return out
+
+
+def attention_backward_packed(qkv: torch.Tensor, dout: torch.Tensor, row_start: torch.Tensor, max_t: int, width: int,
+                              causal: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of op_attention_packed (``kemr_op_attention_backward_packed``; causal or not): qkv bf16 [rows, 3 width] as the
+    forward read it, dout bf16 [rows, width], row_start int32 [batch + 1] -> dqkv bf16 [rows, 3 width], the gradient with respect to the
+    planes as given (the caller owns the 1/8 of q).  Per item the bits of ``attention_backward(item rows, 1, length, ...)``; the same
+    bits on every launch.  Rows no item owns are left as they are: as allocated, or as ``out`` (like qkv) has them."""
+    _check_packed("attention_backward_packed", qkv, row_start, width, dout)
+    dqkv = torch.empty_like(qkv) if out is None else out
+    _check_packed_out("attention_backward_packed", dqkv, qkv, tuple(qkv.shape))
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.lib().kemr_op_attention_backward_packed(C.c_void_p(qkv.data_ptr()), C.c_void_p(dout.data_ptr()),
+                                                                C.c_void_p(dqkv.data_ptr()), C.c_void_p(row_start.data_ptr()),
+                                                                row_start.numel() - 1, int(max_t), int(width), 1 if causal else 0,
+                                                                C.c_void_p(_stream_ptr(qkv.device))), "op_attention_backward_packed")
+    return dqkv
+
+
 def layernorm_backward(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The backward of op_layernorm: x fp32 [rows, width] as the forward read it, gamma fp32 [width], dy bf16 or fp32 [rows, width] ->
     (dx fp32 [rows, width], dgamma fp32 [width], dbeta fp32 [width]).  Mean and rstd are recomputed; no atomics, the same bits on every

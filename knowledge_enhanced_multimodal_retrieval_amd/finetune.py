@@ -26,7 +26,9 @@ backward.  The loop, the loss, the validation through the served engine and the 
 ``--end_to_end`` (the third mode; ``tower_train.py``) trains both towers, the reference's own recipe: the preprocessed pixels of the
 training split are collected once in pinned host memory (``cache_pixels``), every batch runs through differentiable restatements of
 both towers (attention, LayerNorm and the MLP activation in the HIP library in both directions, vendor GEMMs under bf16 autocast over
-fp32 master weights), and ``logit_scale`` stays out of the graph.  With none of the three flags the command still exits with
+fp32 master weights), and ``logit_scale`` stays out of the graph.  ``--packed_texts`` (with either of these two modes) runs the text
+tower on packed texts, every text up to its own end-of-text token (``TextTower(packed=True)``); it is refused with
+``--freeze_encoders``, where no text tower trains.  With none of the three flags the command still exits with
 ``NOT_SERVED``, word for word as before.
 """
 from __future__ import annotations
@@ -319,10 +321,19 @@ def build_parser() -> argparse.ArgumentParser:
     mode.add_argument("--end_to_end", action="store_true",
                       help="instead of --freeze_encoders: train both towers and the projection heads, the reference's recipe (pixels cached "
                            "in pinned host memory; attention, LayerNorm and activation backward in the HIP library); needs a batch size")
+    parser.add_argument("--packed_texts", action="store_true",
+                        help="with --lock_image_tower or --end_to_end: run the text tower on packed texts, every text up to its own "
+                             "end-of-text token instead of the batch's longest text (packed attention forward and backward in the HIP "
+                             "library); the default is off")
     parser.add_argument("--synthetic", type=int, default=0, metavar="N",
                         help="train and validate on N seeded synthetic items each instead of the HuggingFace dataset (offline)")
     parser.add_argument("--dataset", type=str, default="xuemduan/reevaluate-image-text-pairs")
     return parser
+
+
+PACKED_TEXTS_REFUSED = ("--packed_texts is not served with --freeze_encoders: the frozen towers run once, through the served engine, "
+                        "when the pooled rows are cached, and no text tower takes part in training; give it with --lock_image_tower or "
+                        "--end_to_end")
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -331,6 +342,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if not args.freeze_encoders and not args.lock_image_tower and not args.end_to_end:
         print(f"error: {NOT_SERVED}", file=sys.stderr)
         return 2
+    if args.packed_texts and args.freeze_encoders:
+        parser.error(PACKED_TEXTS_REFUSED)
     if args.end_to_end and args.batch_size <= 0:
         from .tower_train import BATCH_0_REFUSED_END_TO_END
         parser.error(BATCH_0_REFUSED_END_TO_END)
@@ -366,12 +379,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         from .tower_train import EndToEndTrainer, EndToEndTuning
         logger.info(f"Collecting the preprocessed pixels of {len(train_set)} training items (end to end)...")
         pooled = cache_pixels(model, train_set, batch_size=64, seed=args.seed, num_workers=workers)
-        heads, trainer_cls = EndToEndTuning(model), EndToEndTrainer
+        heads, trainer_cls = EndToEndTuning(model, packed=args.packed_texts), EndToEndTrainer
     elif args.lock_image_tower:
         from .tower_train import LockedImageTuning, TextTowerTrainer
         logger.info(f"Caching the pooled image rows of {len(train_set)} training items (locked image tower)...")
         pooled = cache_image_pooled(model, train_set, batch_size=64, seed=args.seed, num_workers=workers)
-        heads, trainer_cls = LockedImageTuning(model), TextTowerTrainer
+        heads, trainer_cls = LockedImageTuning(model, packed=args.packed_texts), TextTowerTrainer
     else:
         logger.info(f"Caching the pooled rows of {len(train_set)} training items (frozen towers)...")
         pooled = cache_pooled(model, train_set, batch_size=64, seed=args.seed, num_workers=workers)

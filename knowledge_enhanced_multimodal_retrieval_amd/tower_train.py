@@ -19,6 +19,13 @@ Running length: ``forward(ids, t)`` may run the first ``t`` positions only, ``t`
 reaches the loss.  Family ``clip`` only (Long-CLIP's 248 positions included); SigLIP and BERT models are refused like
 ``finetune.ProjectionHeads`` refuses them.
 
+Packed texts: ``TextTower(..., packed=True)`` (``--packed_texts``) computes every text up to its own end-of-text token and nothing behind
+it: the live positions of the batch are gathered into ``[rows, width]``, text i owning the rows ``row_start[i] .. row_start[i + 1] - 1``,
+and every linear, LayerNorm and activation of the blocks runs on those rows.  The attention is ``_OpAttentionPacked``
+(``kemr_op_attention_packed`` forward, ``kemr_op_attention_backward_packed`` backward, csrc/attention_bwd.hip) or, with
+attention="torch", ``torch_attention_packed``.  A 16-token query no longer runs at the length of the batch's longest target; there is
+no running length, so ``t`` is refused.  The result is the dense tower's up to rounding (the same rows, another layout).
+
 Elementwise passes: ``elementwise="torch"`` (the default of ``TextTower``) runs the blocks' LayerNorms and the MLP activation as torch
 autograd does -- fp32 passes over ``[rows, 4 width]`` with an fp32 copy of each kept for the backward.  ``elementwise="op"`` routes
 ``ln_1`` / ``ln_2`` and the activation through the library in both directions (csrc/train_ops.hip): ``_OpLayerNorm`` is
@@ -49,7 +56,7 @@ plus the whole text tower.  No other vision parameter can receive a gradient: no
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Callable, Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -82,6 +89,37 @@ class _OpAttention(torch.autograd.Function):
         dqkv = engine.attention_backward(scaled, dout.to(torch.bfloat16).contiguous(), batch, t, width, ctx.causal)
         dqkv[:, :width] *= 0.125                         # the caller's 1/8 of q (exact)
         return dqkv.to(ctx.in_dtype), None, None, None, None
+
+
+class _OpAttentionPacked(torch.autograd.Function):
+    """qkv [rows, 3 width] (q not yet scaled) over packed items -> bf16 [rows, width]: ``kemr_op_attention_packed`` forward,
+    ``kemr_op_attention_backward_packed`` (causal) backward.  ``row_start`` int32 [batch + 1] on qkv's device covers rows 0 .. rows - 1;
+    ``segments`` = ((first item, last item + 1, max_t), ...) splits the items into consecutive runs, one call each at the run's own
+    longest item (``packed_segments``).  The ops read row_start[first .. last + 1] only and write the rows of those items only; an item's
+    gradient has the same bits in any call whose max_t admits it."""
+
+    @staticmethod
+    def forward(ctx, qkv: torch.Tensor, row_start: torch.Tensor, segments: Tuple[Tuple[int, int, int], ...], width: int) -> torch.Tensor:
+        from . import engine
+        scaled = qkv.detach().to(torch.bfloat16).clone()
+        scaled[:, :width] *= 0.125                       # exact: a power of two
+        ctx.save_for_backward(scaled, row_start)
+        ctx.segments, ctx.width, ctx.in_dtype = segments, width, qkv.dtype
+        out = torch.empty((qkv.shape[0], width), dtype=torch.bfloat16, device=qkv.device)
+        for lo, hi, max_t in segments:
+            engine.op_attention_packed(scaled, row_start[lo:hi + 1], max_t, width, out=out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        from . import engine
+        scaled, row_start = ctx.saved_tensors
+        dout = dout.to(torch.bfloat16).contiguous()
+        dqkv = torch.empty_like(scaled)
+        for lo, hi, max_t in ctx.segments:
+            engine.attention_backward_packed(scaled, dout, row_start[lo:hi + 1], max_t, ctx.width, True, out=dqkv)
+        dqkv[:, :ctx.width] *= 0.125                     # the caller's 1/8 of q (exact)
+        return dqkv.to(ctx.in_dtype), None, None, None
 
 
 class _OpLayerNorm(torch.autograd.Function):
@@ -132,9 +170,46 @@ def torch_attention(qkv: torch.Tensor, batch: int, t: int, width: int, causal: b
     return (torch.softmax(s, dim=-1).to(v.dtype) @ v).transpose(1, 2).reshape(batch * t, width)
 
 
+def torch_attention_packed(qkv: torch.Tensor, lens: Sequence[int], width: int, causal: bool = True) -> torch.Tensor:
+    """The plain formulation over packed rows: item i = the next ``lens[i]`` rows of qkv [sum(lens), 3 width], each item attending to
+    itself only (``torch_attention`` per item).  Any device and dtype, differentiable: the reference of the packed op and the way the
+    packed tower runs without a GPU."""
+    lens = [int(n) for n in lens]
+    if qkv.dim() != 2 or qkv.shape[0] != sum(lens) or any(n < 0 for n in lens):
+        raise ValueError(f"torch_attention_packed: qkv has {tuple(qkv.shape)} rows, the lengths sum to {sum(lens)}")
+    outs = [torch_attention(x, 1, n, width, causal) for x, n in zip(qkv.split(lens), lens) if n]
+    return torch.cat(outs) if outs else qkv.new_zeros((0, width))
+
+
+def packed_segments(lens: Sequence[int]) -> Tuple[Tuple[int, int, int], ...]:
+    """How ``_OpAttentionPacked`` issues its calls over items of these lengths (each >= 1): one call at the longest item, or two calls over
+    items [0, k) and [k, n) at each run's own longest item.  The cost of a run is taken as items x LDS allocation of its call (the
+    longest item rounded up to 32 rows): a short item in a long item's launch occupies a long item's share of a compute unit.  Two
+    calls are issued where some k brings that cost to 3/4 of one call's or below (the second launch has to pay for itself) -- a batch of
+    short queries followed by long targets splits between them, a batch of texts of one length does not split."""
+    n = len(lens)
+    up = [(int(x) + 31) // 32 * 32 for x in lens]
+    whole = (0, n, max(int(x) for x in lens))
+    pre, suf = [0] * (n + 1), [0] * (n + 1)
+    for i in range(n):
+        pre[i + 1] = max(pre[i], up[i])
+        suf[n - 1 - i] = max(suf[n - i], up[n - 1 - i])
+    cost, k = min((k * pre[k] + (n - k) * suf[k], k) for k in range(1, n)) if n > 1 else (0, 0)
+    if n < 2 or 4 * cost > 3 * n * pre[n]:
+        return (whole,)
+    return ((0, k, max(int(x) for x in lens[:k])), (k, n, max(int(x) for x in lens[k:])))
+
+
 def longest(ids: torch.Tensor) -> int:
     """The batch's longest text: the highest end-of-text position (first arg-max of the ids) + 1.  One host read for device ids."""
     return int(ids.argmax(dim=-1).max()) + 1
+
+
+class _Packed(NamedTuple):
+    """The layout of a batch of packed texts: host lengths, device row_start int32 [batch + 1], the calls of the attention op."""
+    lens: Tuple[int, ...]
+    row_start: torch.Tensor
+    segments: Tuple[Tuple[int, int, int], ...]
 
 
 OP_LN_WIDTHS = (256, 512, 768, 1024, 1280)          # kemr_op_layernorm and its backward
@@ -188,9 +263,16 @@ class _Tower(nn.Module):
             return _OpAttention.apply(qkv, batch, t, self.width, self.causal)
         return torch_attention(qkv, batch, t, self.width, self.causal)
 
-    def _block(self, x: torch.Tensor, blk: nn.Module, batch: int, t: int) -> torch.Tensor:
+    def _attend_packed(self, qkv: torch.Tensor, packed: "_Packed") -> torch.Tensor:
+        """qkv [rows, 3 width] (q not yet scaled) over packed items -> [rows, width].  (tools/bench_text_tower_packed.py overrides this.)"""
+        if self.attention == "op":
+            return _OpAttentionPacked.apply(qkv, packed.row_start, packed.segments, self.width)
+        return torch_attention_packed(qkv, packed.lens, self.width, self.causal)
+
+    def _block(self, x: torch.Tensor, blk: nn.Module, attend: Callable[[torch.Tensor], torch.Tensor]) -> torch.Tensor:
+        """One pre-LN residual block on rows [rows, width]; ``attend``: qkv [rows, 3 width] -> [rows, width], the layout's attention."""
         qkv = self._linear(self._ln(x, blk.ln_1), blk.attn.in_proj_weight, blk.attn.in_proj_bias)
-        a = self._attend(qkv, batch, t)
+        a = attend(qkv)
         x = x + self._linear(a, blk.attn.out_proj.weight, blk.attn.out_proj.bias)
         h = self._act(self._linear(self._ln(x, blk.ln_2), blk.mlp.c_fc.weight, blk.mlp.c_fc.bias))
         return x + self._linear(h, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias)
@@ -201,8 +283,9 @@ class TextTower(_Tower):
     parameter of the model as it finds it)."""
 
     def __init__(self, model: nn.Module, attention: str = "op", autocast: Optional[bool] = None, trainable: bool = True,
-                 elementwise: str = "torch"):
+                 elementwise: str = "torch", packed: bool = False):
         super().__init__()
+        self.packed = bool(packed)
         m = _unwrap(model)
         family = getattr(getattr(m, "arch", None), "family", "clip")
         if family != "clip" or not hasattr(m, "text_projection") or not hasattr(m, "visual") or not hasattr(m.visual, "proj"):
@@ -233,6 +316,11 @@ class TextTower(_Tower):
             raise ValueError(f"TextTower: ids must be [B, <= {self.ctx}], got {tuple(ids.shape)}")
         dev = self.positional_embedding.device
         self._needs_gpu("TextTower", dev)
+        if self.packed:
+            if t is not None:
+                raise ValueError(f"TextTower: packed=True computes every text up to its own end-of-text token and has no running "
+                                 f"length; t = {t} is not served with it")
+            return self._pooled_packed(ids, dev)
         ids = ids.to(dev).long()
         batch = ids.shape[0]
         eot = ids.argmax(dim=-1)
@@ -243,8 +331,30 @@ class TextTower(_Tower):
             raise ValueError(f"TextTower: running length t = {t} cuts a text whose end-of-text token sits at position {int(eot.max())}")
         x = (self.token_embedding.weight[ids[:, :t]] + self.positional_embedding[:t]).reshape(batch * t, self.width)
         for blk in self.transformer.resblocks:
-            x = self._block(x, blk, batch, t)
+            x = self._block(x, blk, lambda qkv: self._attend(qkv, batch, t))
         return x.reshape(batch, t, self.width)[torch.arange(batch, device=dev), eot]
+
+    def _pooled_packed(self, ids: torch.Tensor, dev: torch.device) -> torch.Tensor:
+        """``pooled`` over packed rows: text i owns the rows row_start[i] .. row_start[i + 1] - 1 = its positions 0 .. end-of-text, and
+        nothing is computed behind an end-of-text token.  The lengths are read where the ids are (one host read for device ids)."""
+        lens = tuple((ids.argmax(dim=-1) + 1).tolist())
+        batch, rows = len(lens), sum(lens)
+        if batch == 0 or max(lens, default=0) > MAX_T:
+            raise ValueError(f"TextTower: packed texts must be [B >= 1, <= {MAX_T} positions up to the end-of-text token], got "
+                             f"{tuple(ids.shape)} with a longest text of {max(lens, default=0)}")
+        ids = ids.to(dev, non_blocking=True).long()
+        lens_dev = torch.tensor(lens, dtype=torch.long, device=dev)
+        ends = lens_dev.cumsum(0)
+        row_start = torch.cat([ends.new_zeros(1), ends]).to(torch.int32)
+        item = torch.repeat_interleave(torch.arange(batch, device=dev), lens_dev, output_size=rows)
+        pos = torch.arange(rows, device=dev) - (ends - lens_dev)[item]
+        # F.embedding, not indexing: every position occurs once per text that reaches it, and the backward of an index sums a row's
+        # duplicates one after the other, where embedding's splits them into partial sums
+        x = F.embedding(ids[item, pos], self.token_embedding.weight) + F.embedding(pos, self.positional_embedding)
+        packed = _Packed(lens, row_start, packed_segments(lens) if self.attention == "op" else ())
+        for blk in self.transformer.resblocks:
+            x = self._block(x, blk, lambda qkv: self._attend_packed(qkv, packed))
+        return x[ends - 1]
 
     def forward(self, ids: torch.Tensor, t: Optional[int] = None) -> torch.Tensor:
         """[B, embed_dim]: the L2-normalised text embeddings."""
@@ -309,7 +419,7 @@ class VisionTower(_Tower):
         x = torch.cat([self.class_embedding.expand(batch, 1, w), emb], dim=1) + self.positional_embedding
         x = self._ln(x.reshape(batch * t, w), self.ln_pre, out_bf16=False)
         for blk in self.transformer.resblocks:
-            x = self._block(x, blk, batch, t)
+            x = self._block(x, blk, lambda qkv: self._attend(qkv, batch, t))
         return x.reshape(batch, t, w)[:, 0]
 
     def forward(self, pixels: torch.Tensor) -> torch.Tensor:
@@ -320,16 +430,16 @@ class VisionTower(_Tower):
 class LockedImageTuning(nn.Module):
     """What ``--lock_image_tower`` trains: ``ProjectionHeads`` (six tensors) plus the whole text tower, over the model's own parameters."""
 
-    def __init__(self, model: nn.Module, attention: str = "op", autocast: Optional[bool] = None):
+    def __init__(self, model: nn.Module, attention: str = "op", autocast: Optional[bool] = None, packed: bool = False):
         super().__init__()
         self.heads = ProjectionHeads(model)              # freezes everything, then its six tensors
-        self.tower = TextTower(model, attention=attention, autocast=autocast, trainable=True)
+        self.tower = TextTower(model, attention=attention, autocast=autocast, trainable=True, packed=packed)
 
     def forward(self, pooled_image: torch.Tensor, query_ids: torch.Tensor, target_ids: torch.Tensor
                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         n = query_ids.shape[0]
         ids = torch.cat([query_ids, target_ids])
-        text = self.tower(ids, longest(ids))
+        text = self.tower(ids) if self.tower.packed else self.tower(ids, longest(ids))
         return self.heads.image(pooled_image), text[:n], text[n:]
 
 
@@ -337,12 +447,13 @@ class EndToEndTuning(nn.Module):
     """What ``--end_to_end`` trains: ``ProjectionHeads`` plus both towers, over the model's own parameters -- every parameter but
     ``logit_scale``, which takes no part in the graph (the loss has its own temperature) and keeps its bits."""
 
-    def __init__(self, model: nn.Module, attention: str = "op", elementwise: str = "op", autocast: Optional[bool] = None):
+    def __init__(self, model: nn.Module, attention: str = "op", elementwise: str = "op", autocast: Optional[bool] = None,
+                 packed: bool = False):
         super().__init__()
         self.heads = ProjectionHeads(model)              # freezes everything, then its six tensors
         self.vision = VisionTower(model, attention=attention, elementwise=elementwise, autocast=autocast, trainable=True,
                                   max_tokens=MAX_T_LONG)
-        self.tower = TextTower(model, attention=attention, autocast=autocast, trainable=True, elementwise=elementwise)
+        self.tower = TextTower(model, attention=attention, autocast=autocast, trainable=True, elementwise=elementwise, packed=packed)
 
     def forward(self, pixels: torch.Tensor, query_ids: torch.Tensor, target_ids: torch.Tensor
                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -350,8 +461,11 @@ class EndToEndTuning(nn.Module):
         dev = self.tower.positional_embedding.device
         n = query_ids.shape[0]
         ids = torch.cat([query_ids, target_ids])
-        t = longest(ids)                                 # read where the ids are: no device sync for host ids
-        text = self.tower(ids.to(dev, non_blocking=True), t)
+        if self.tower.packed:
+            text = self.tower(ids)                       # the lengths are read where the ids are: no device sync for host ids
+        else:
+            t = longest(ids)                             # read where the ids are: no device sync for host ids
+            text = self.tower(ids.to(dev, non_blocking=True), t)
         return self.heads.image(self.vision.pooled(pixels.to(dev, non_blocking=True))), text[:n], text[n:]
 
 

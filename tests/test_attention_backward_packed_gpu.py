@@ -1,0 +1,220 @@
+"""GPU: ``kemr_op_attention_backward_packed`` (csrc/attention_bwd.hip), the attention backward over items of different lengths packed
+one behind the other, and ``kemr_op_attention_packed``, the causal packed forward as a product entry point.
+
+Width 128 (two heads).  One launch at max_t = 288 over items of lengths [17, 1, 288, 16, 33, 2, 129, 77, 32, 248, 15, 64, 128, 97] in
+this order, one at max_t = 77 over [77, 1, 16, 17, 45, 77]: the edges of a 16-row tile and of a 32-row block, the forward's 128-row
+switch, the two text lengths and the maximum; causal and not.  Yardsticks: per item the BITS of the dense op
+(``engine.attention_backward(item rows, 1, L, ...)``: the packed route is a change of layout), and per plane (dq, dk, dv) over all rows
+the bar of tests/test_attention_backward_gpu.py -- the relative L2 error against the fp64 statement, applied per item, is at most
+2 x the error of the rounding emulation.  Then the memory contract (tests/footprint.py) and the stream contract (tests/stream_order.py)."""
+import ctypes as C
+import functools
+
+import pytest
+import torch
+
+import attention_bwd_ref as R
+import footprint as F
+import stream_order as SO
+from footprint import In, IntIn, Out
+from knowledge_enhanced_multimodal_retrieval_amd import _lib, debug, engine
+
+pytestmark = pytest.mark.gpu
+
+BF16 = torch.bfloat16
+WIDTH = 128
+LENS = {288: [17, 1, 288, 16, 33, 2, 129, 77, 32, 248, 15, 64, 128, 97], 77: [77, 1, 16, 17, 45, 77]}
+ZERO_ITEM = 4                           # the item whose dout rows are zero (33 rows / 45 rows)
+LAUNCHES = [(288, 0), (288, 1), (77, 0), (77, 1)]
+
+
+def _row_start(lens, first=0):
+    rs = torch.zeros(len(lens) + 1, dtype=torch.int32)
+    rs[1:] = torch.tensor(lens, dtype=torch.int32).cumsum(0)
+    return rs + first
+
+
+def _per_item(fn, qkv, dout, lens, causal):
+    parts, r = [], 0
+    for n in lens:
+        parts.append(fn(qkv[r:r + n], dout[r:r + n], 1, n, WIDTH, causal))
+        r += n
+    return torch.cat(parts)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(max_t, causal):
+    """(qkv, dout, row_start, fp64 statement per item, emulation per item) of one launch: computed once, shared, never modified."""
+    lens = LENS[max_t]
+    rs = _row_start(lens)
+    qkv, dout = R.make_inputs(1, int(rs[-1]), WIDTH, 4000 + 2 * max_t + causal)
+    dout[int(rs[ZERO_ITEM]):int(rs[ZERO_ITEM + 1])] = 0
+    return qkv, dout, rs, _per_item(R.backward_fp64, qkv, dout, lens, causal), _per_item(R.backward_emulated, qkv, dout, lens, causal)
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _call(device, *args):
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().kemr_op_attention_backward_packed(*args, _stream(device)), "op_attention_backward_packed")
+
+
+def _packed(device, qkv, dout, rs, max_t, causal):
+    return engine.attention_backward_packed(qkv.to(device), dout.to(device), rs.to(device), max_t, WIDTH, bool(causal))
+
+
+@pytest.mark.parametrize("max_t,causal", LAUNCHES)
+def test_every_item_has_the_bits_of_the_dense_op(device, max_t, causal):
+    qkv, dout, rs, _, _ = _case(max_t, causal)
+    got = _packed(device, qkv, dout, rs, max_t, causal)
+    q, d = qkv.to(device), dout.to(device)
+    for i, n in enumerate(LENS[max_t]):
+        own = slice(int(rs[i]), int(rs[i + 1]))
+        want = engine.attention_backward(q[own].contiguous(), d[own].contiguous(), 1, n, WIDTH, bool(causal))
+        try:
+            F.same_bits(got[own], want)
+        except AssertionError as e:
+            raise AssertionError(f"item {i} ({n} rows) at max_t = {max_t}, causal = {causal}: {e}") from None
+
+
+@pytest.mark.parametrize("max_t,causal", LAUNCHES)
+def test_error_against_fp64_within_twice_the_emulation(device, max_t, causal):
+    qkv, dout, rs, ref, emu = _case(max_t, causal)
+    got = _packed(device, qkv, dout, rs, max_t, causal).cpu()
+    assert got.dtype == BF16 and got.shape == ref.shape and torch.isfinite(got.float()).all()
+    for name in ("dq", "dk", "dv"):
+        r = R.planes(ref, WIDTH)[name]
+        e_kernel, e_emu = R.rel_l2(R.planes(got, WIDTH)[name], r), R.rel_l2(R.planes(emu, WIDTH)[name], r)
+        print(f"attention_backward_packed max_t={max_t} causal={causal} {name}: kernel {e_kernel:.4e} emulation {e_emu:.4e}")
+        assert e_kernel <= 2.0 * e_emu, (name, e_kernel, e_emu)
+    # the item whose dout rows are zero: exactly zero gradients
+    assert not got[int(rs[ZERO_ITEM]):int(rs[ZERO_ITEM + 1])].float().any()
+    # an item of one row: one key, P = 1, dS = 0 -- dq = dk = 0 and dv = dout bit for bit
+    i = LENS[max_t].index(1)
+    g = R.planes(got[int(rs[i]):int(rs[i]) + 1], WIDTH)
+    assert not g["dq"].float().any() and not g["dk"].float().any()
+    assert F.same_bits(g["dv"], dout[int(rs[i]):int(rs[i]) + 1])
+
+
+@pytest.mark.parametrize("max_t,causal", [(288, 1), (77, 0)])
+def test_two_launches_give_the_same_bits(device, max_t, causal):
+    qkv, dout, rs, _, _ = _case(max_t, causal)
+    assert F.same_bits(_packed(device, qkv, dout, rs, max_t, causal), _packed(device, qkv, dout, rs, max_t, causal))
+
+
+@pytest.mark.parametrize("causal", [0, 1])
+def test_empty_items_write_nothing_and_change_nothing(device, causal):
+    """Empty items in front, in the middle and at the end (their workgroups leave before any load: the staging clamps pad rows to the
+    item's last row, and an empty item has none).  Inputs in 0xff margins, the output in guard margins."""
+    max_t = 77
+    qkv, dout, rs, _, _ = _case(max_t, causal)
+    base = _packed(device, qkv, dout, rs, max_t, causal)
+    lens = LENS[max_t]
+    holes = _row_start([0] + lens[:3] + [0, 0] + lens[3:] + [0])
+    assert int(holes[-1]) == int(rs[-1]) and len(holes) == len(rs) + 4
+    wq = F.window(qkv.shape, BF16, device, F.POISON, body=qkv, what="qkv")
+    wd = F.window(dout.shape, BF16, device, F.POISON, body=dout, what="dout")
+    wo = F.window(qkv.shape, BF16, device, F.GUARD, what="dqkv")
+    wr = F.window(holes.shape, torch.int32, device, F.INT_POISON, body=holes, what="row_start")
+    _call(device, C.c_void_p(wq.ptr), C.c_void_p(wd.ptr), C.c_void_p(wo.ptr), C.c_void_p(wr.ptr), len(holes) - 1, max_t, WIDTH, causal)
+    torch.cuda.synchronize(device)
+    assert wq.margins_intact() and wd.margins_intact() and wo.margins_intact() and wr.margins_intact()
+    assert F.same_bits(wo.view, base)
+
+
+@pytest.mark.parametrize("causal", [0, 1])
+def test_rows_outside_row_start_keep_the_guard(device, causal):
+    """row_start begins at row 5 of a larger buffer: rows 0 .. 4 and the rows from row_start[batch] on are not written."""
+    max_t, first, behind = 77, 5, 7
+    qkv, dout, rs, _, _ = _case(max_t, causal)
+    base = _packed(device, qkv, dout, rs, max_t, causal)
+    rows = int(rs[-1])
+    big_q = torch.full((first + rows + behind, 3 * WIDTH), float("nan"), dtype=BF16)
+    big_d = torch.full((first + rows + behind, WIDTH), float("nan"), dtype=BF16)
+    big_q[first:first + rows], big_d[first:first + rows] = qkv, dout
+    q, d, r = big_q.to(device), big_d.to(device), (rs + first).to(device)
+    out = torch.empty_like(q)
+    out.view(torch.uint8).fill_(F.GUARD)
+    _call(device, C.c_void_p(q.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(r.data_ptr()), len(rs) - 1,
+          max_t, WIDTH, causal)
+    torch.cuda.synchronize(device)
+    assert F.all_bytes(out[:first], F.GUARD) and F.all_bytes(out[first + rows:], F.GUARD)
+    assert F.same_bits(out[first:first + rows], base)
+
+
+@pytest.mark.parametrize("causal", [0, 1])
+def test_an_item_longer_than_max_t_is_its_first_max_t_rows(device, causal):
+    """The forward's convention (tests/test_longclip_ops_gpu.py): one 288-row item at max_t = 200 is a 200-row item on rows 0 .. 199,
+    and rows 200 .. 287 of dqkv are not written."""
+    qkv, dout = R.make_inputs(1, 288, WIDTH, 31 + causal)
+    q, d = qkv.to(device), dout.to(device)
+    out = torch.empty_like(q)
+    out.view(torch.uint8).fill_(F.GUARD)
+    engine.attention_backward_packed(q, d, torch.tensor([0, 288], dtype=torch.int32, device=device), 200, WIDTH, bool(causal), out=out)
+    want = engine.attention_backward(q[:200].contiguous(), d[:200].contiguous(), 1, 200, WIDTH, bool(causal))
+    assert F.same_bits(out[:200], want) and F.all_bytes(out[200:], F.GUARD)
+
+
+@pytest.mark.parametrize("max_t,causal", [(288, 0), (77, 1)])
+def test_an_item_depends_on_its_own_rows_only(device, max_t, causal):
+    """Every second item of a call whose other items and whose surroundings (0xff margins in front of and behind every buffer) are
+    different, as test_an_item_depends_on_its_own_rows_only of the dense op."""
+    qkv, _, rs, _, _ = _case(max_t, causal)
+    rows = int(rs[-1])
+    dout = R.make_inputs(1, rows, WIDTH, 77 + max_t)[1]                   # no zero item here
+    base = _packed(device, qkv, dout, rs, max_t, causal)
+    qkv2, dout2 = R.make_inputs(1, rows, WIDTH, 555 + max_t)
+    kept = [slice(int(rs[i]), int(rs[i + 1])) for i in range(0, len(rs) - 1, 2)]
+    for own in kept:
+        qkv2[own], dout2[own] = qkv[own], dout[own]
+    wq = F.window(qkv2.shape, BF16, device, F.POISON, body=qkv2, what="qkv")
+    wd = F.window(dout2.shape, BF16, device, F.POISON, body=dout2, what="dout")
+    wo = F.window(qkv2.shape, BF16, device, F.GUARD, what="dqkv")
+    r = rs.to(device)
+    _call(device, C.c_void_p(wq.ptr), C.c_void_p(wd.ptr), C.c_void_p(wo.ptr), C.c_void_p(r.data_ptr()), len(rs) - 1, max_t, WIDTH, causal)
+    torch.cuda.synchronize(device)
+    assert wq.margins_intact() and wd.margins_intact() and wo.margins_intact()
+    for own in kept:
+        assert F.same_bits(wo.view[own], base[own])
+    other = slice(int(rs[1]), int(rs[2]))
+    assert not torch.equal(wo.view[other].cpu().float(), base[other].cpu().float())      # (the other items did change)
+
+
+def _specs(max_t, causal, extra_rows):
+    qkv, dout, rs, _, _ = _case(max_t, causal)
+    rows = int(rs[-1])
+    return [In(qkv), In(dout), Out((rows + extra_rows, 3 * WIDTH), BF16, written=lambda v: v[:rows], keep=lambda v: v[rows:]), IntIn(rs),
+            len(rs) - 1, max_t, WIDTH, causal]
+
+
+@pytest.mark.parametrize("max_t,causal", LAUNCHES)
+def test_memory_contract_exactly_the_items_rows_written(device, max_t, causal):
+    F.run_both(functools.partial(_call, device), _specs(max_t, causal, 7), device, what=f"attention_backward_packed max_t={max_t} causal={causal}")
+
+
+@pytest.mark.parametrize("max_t,causal", [(77, 1), (288, 0)])
+def test_stream_contract(device, max_t, causal):
+    SO.run_late(functools.partial(_call, device), _specs(max_t, causal, 0), device, what=f"attention_backward_packed max_t={max_t} causal={causal}")
+
+
+def test_empty_batch_launches_nothing(device):
+    out = torch.full((4, 3 * WIDTH), 7.0, dtype=BF16, device=device)
+    keep = out.clone()
+    p = C.c_void_p(out.data_ptr())
+    _call(device, p, p, p, p, 0, 4, WIDTH, 1)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().kemr_op_attention_packed(p, p, p, 0, 4, WIDTH, _stream(device)), "op_attention_packed")
+    torch.cuda.synchronize(device)
+    assert F.same_bits(out, keep)
+
+
+def test_the_forward_entry_point_has_the_bits_of_the_debug_one(device):
+    qkv, _, rs, _, _ = _case(288, 1)
+    q, r = qkv.to(device), rs.to(device)
+    got = engine.op_attention_packed(q, r, 288, WIDTH)
+    assert got.dtype == BF16 and tuple(got.shape) == (int(rs[-1]), WIDTH)
+    assert F.same_bits(got, debug.op_attention_packed(q, r, 288, WIDTH))
+    short, rs77 = _case(77, 1)[0].to(device), _case(77, 1)[2].to(device)                 # the tile kernels' route
+    assert F.same_bits(engine.op_attention_packed(short, rs77, 77, WIDTH), debug.op_attention_packed(short, rs77, 77, WIDTH))
