@@ -21,58 +21,20 @@
 //     then dV^T = dO^T . P and dK^T = Q^T . dS (A = dO^T / Q^T by transposed reads, B = the P / dS registers).
 // Both phases are one function (bwd_own_tile) with the operands exchanged.  S and dP are computed twice (7 products instead of 5):
 // the price of owning every output without a workspace.  Causal: tiles wholly behind the diagonal are skipped in both phases.
-// Rounding points: P and dS to bf16 as MFMA operands, fp32 accumulators, dq / dk / dv to bf16 at the store.  Everything else fp32.
-// LDS images: rows of 128 B.  Q, K and dO are read by rows AND transposed, so they carry the forward's V swizzle (32-byte chunk ^=
-// (row >> 1) & 3: transposed reads conflict-free, row reads 2-way); V is only read by rows and carries the K swizzle (16-byte chunk
-// ^= (row >> 1) & 7: conflict-free).
-#include "common.h"
+// The LDS images, the MFMA operand forms and the rounding points are attention_bwd_tile.h's, shared with attention_bwd_stream.hip: Q, K
+// and dO are read by rows AND transposed (TRL images), V is only read by rows.
+#include "attention_bwd_tile.h"
 
 #include <type_traits>
 
 namespace kemr {
 
-template <bool TRL>
-__device__ __forceinline__ int bwd_off(int row, int c) {
-    return row * 128 + ((TRL ? (c ^ (((row >> 1) & 3) << 1)) : (c ^ ((row >> 1) & 7))) << 4);
-}
-template <bool TRL>
-__device__ __forceinline__ bf16x8 bwd_row(const char* img, int row, int c) { return *(const bf16x8*)(img + bwd_off<TRL>(row, c)); }
-
-// the A fragments (4 d-tiles) of M^T for the 32 rows of block u of the image M (forward's load_v): k slot 8 lq + j <-> row 32 u + 16 (j >> 2) + 4 lq + (j & 3)
-__device__ __forceinline__ void bwd_tr(const char* img, int u, int lrow, int lq, bf16x8 (&dst)[4]) {
-    const int ra = u * 32 + lq * 4 + (lrow >> 2), rb = ra + 16;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-        const int c = dt * 2 + ((lrow & 3) >> 1);
-        const bf16x4 va = lds_read_tr16(img + bwd_off<true>(ra, c) + (lrow & 1) * 8);
-        const bf16x4 vb = lds_read_tr16(img + bwd_off<true>(rb, c) + (lrow & 1) * 8);
-        dst[dt][0] = va[0]; dst[dt][1] = va[1]; dst[dt][2] = va[2]; dst[dt][3] = va[3];
-        dst[dt][4] = vb[0]; dst[dt][5] = vb[1]; dst[dt][6] = vb[2]; dst[dt][7] = vb[3];
-    }
-}
-__device__ __forceinline__ bf16x8 bwd_pack(const f32x4& a, const f32x4& b) {
-    union { bf16x8 v; uint32_t w[4]; } f;
-    f.w[0] = pack_bf16x2(a[0], a[1]); f.w[1] = pack_bf16x2(a[2], a[3]);
-    f.w[2] = pack_bf16x2(b[0], b[1]); f.w[3] = pack_bf16x2(b[2], b[3]);
-    return f.v;
-}
-__device__ __forceinline__ void bwd_store(bf16_t* dst, const f32x4 (&acc)[4]) {
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-        uint2 pk;
-        pk.x = pack_bf16x2(acc[dt][0], acc[dt][1]);
-        pk.y = pack_bf16x2(acc[dt][2], acc[dt][3]);
-        *(uint2*)(dst + dt * 16) = pk;
-    }
-}
-
 // PHASE 1: own = the 16 queries of tile ot, other = keys; PHASE 2: own = the 16 keys of tile ot, other = queries.
-// s[t][r] / dp[t][r] belong to (own row ot * 16 + lrow, other row t * 16 + lq * 4 + r).  EXEC is full throughout (transposed reads).
+// Lane ownership of s[t][r] / dp[t][r] as attention_bwd_tile.h states it; every skip below is wave-uniform, so EXEC stays full.
 template <int NT32, bool CAUSAL, int PHASE>
 __device__ __forceinline__ void bwd_own_tile(const char* sQ, const char* sK, const char* sV, const char* sG, float* sM, float* sI,
                                              float* sD, int ot, int T, int lane, bf16_t* dst, size_t ld, int width) {
     constexpr int NT16 = NT32 * 2;
-    constexpr float LOG2E = 1.4426950408889634f;
     const int lrow = lane & 15, lq = lane >> 4;
     const char* own1 = PHASE == 1 ? sQ : sK;
     const char* own2 = PHASE == 1 ? sG : sV;
@@ -91,14 +53,8 @@ __device__ __forceinline__ void bwd_own_tile(const char* sQ, const char* sK, con
         s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         // tiles made only of pad rows, or (causal) wholly behind the diagonal, are skipped (uniform); the masks below cover them
-        if (t * 16 < T && (!CAUSAL || (PHASE == 1 ? t <= ot : t >= ot))) {
-            const int row = t * 16 + lrow;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bwd_row<true>(oth1, row, kk * 4 + lq), b1[kk], s[t], 0, 0, 0);
-                dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bwd_row<PHASE == 2>(oth2, row, kk * 4 + lq), b2[kk], dp[t], 0, 0, 0);
-            }
-        }
+        if (t * 16 < T && (!CAUSAL || (PHASE == 1 ? t <= ot : t >= ot)))
+            bwd_scores<PHASE == 2>(oth1, oth2, t * 16 + lrow, lq, b1, b2, s[t], dp[t]);
     }
     if constexpr (PHASE == 1) {
         float mx = -INFINITY;
@@ -152,6 +108,9 @@ __device__ __forceinline__ void bwd_own_tile(const char* sQ, const char* sK, con
                 for (int r = 0; r < 4; ++r) {
                     const int x = t * 16 + lq * 4 + r;
                     const bool ok = x < T && (!CAUSAL || o <= x);
+                    // bwd_p's expression, spelled out.  Through the call this kernel compiles differently (148 VGPRs at 64 rows for 140,
+                    // 312 at 288 for 264) and measured 0.5 % slower than the previous commit's at 512 x 77 x 768 causal, outside the
+                    // 0.02 % between two copies of that one; spelled out it is within it (profiles/attention_backward_refactor_ab.json)
                     const float p = ok ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][r], LOG2E, -mm[r])) * ii[r] : 0.f;
                     s[t][r] = p;
                     dp[t][r] = p * (dp[t][r] - dd[r]);
@@ -167,16 +126,8 @@ __device__ __forceinline__ void bwd_own_tile(const char* sQ, const char* sK, con
         // a block of 32 other rows that is all pad, or (causal) all behind the diagonal, has P = dS = 0 and is skipped (uniform)
         if (!(u * 32 < T && (!CAUSAL || (PHASE == 1 ? u * 32 <= ot * 16 + 15 : u * 32 + 31 >= ot * 16)))) continue;
         bf16x8 a[4];
-        bwd_tr(oth1, u, lrow, lq, a);                                   // K^T (phase 1) / Q^T (phase 2)
-        const bf16x8 dsf = bwd_pack(dp[2 * u], dp[2 * u + 1]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) acc1[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[dt], dsf, acc1[dt], 0, 0, 0);
-        if constexpr (PHASE == 2) {
-            bwd_tr(oth2, u, lrow, lq, a);                               // dO^T
-            const bf16x8 pf = bwd_pack(s[2 * u], s[2 * u + 1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) acc2[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[dt], pf, acc2[dt], 0, 0, 0);
-        }
+        bwd_accum(oth1, u, lrow, lq, dp[2 * u], dp[2 * u + 1], a, acc1);                            // K^T . dS^T (phase 1) / Q^T . dS (phase 2)
+        if constexpr (PHASE == 2) bwd_accum(oth2, u, lrow, lq, s[2 * u], s[2 * u + 1], a, acc2);    // dO^T . P
     }
     // acc[dt][r] = d(own row lrow)[d = dt * 16 + lq * 4 + r]
     if (o < T) {
@@ -227,6 +178,11 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const bf16_t* __rest
         const bf16_t* src = mtx < 3 ? qbase + mtx * width : gbase;
         const size_t sld = mtx < 3 ? ld : (size_t)width;
         char* img = smem + mtx * TP * 128;
+        auto put = [&](int idx, uint4 a) {              // piece idx of the matrix: chunk idx & 7 of row idx >> 3
+            const int row = idx >> 3, c = idx & 7;
+            if (mtx == 2) bwd_put<false>(img, row, c, a, row < T);
+            else bwd_put<true>(img, row, c, a, row < T);
+        };
         if constexpr (PACKED) {
             // the item's own padded length (a multiple of 32 rows, at most TP): no row beyond it is ever read.  32 rows are one chunk
             // per thread, so a thread stages ceil(T / 32) chunks: groups of four in flight, then the one to three that are left
@@ -243,14 +199,7 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const bf16_t* __rest
                     v[i] = *(const uint4*)(src + (size_t)rc * sld + c * 8);
                 }
 #pragma unroll
-                for (int i = 0; i < M; ++i) {
-                    const int idx = (blk + i) * NTH + tid;
-                    const int row = idx >> 3, c = idx & 7;
-                    const unsigned keep = row < T ? 0xffffffffu : 0u;
-                    uint4 a = v[i];
-                    a.x &= keep; a.y &= keep; a.z &= keep; a.w &= keep;
-                    *(uint4*)(img + (mtx == 2 ? bwd_off<false>(row, c) : bwd_off<true>(row, c))) = a;
-                }
+                for (int i = 0; i < M; ++i) put((blk + i) * NTH + tid, v[i]);
             };
             int blk = 0;
             for (; blk + 4 <= nblk; blk += 4) stage(std::integral_constant<int, 4>{}, blk);
@@ -270,16 +219,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const bf16_t* __rest
             v[i] = *(const uint4*)(src + (size_t)rc * sld + c * 8);
         }
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int idx = tid + i * NTH;
-            const int row = idx >> 3, c = idx & 7;
-            if (idx < TP * 8) {
-                const unsigned keep = row < T ? 0xffffffffu : 0u;
-                uint4 a = v[i];
-                a.x &= keep; a.y &= keep; a.z &= keep; a.w &= keep;
-                *(uint4*)(img + (mtx == 2 ? bwd_off<false>(row, c) : bwd_off<true>(row, c))) = a;
-            }
-        }
+        for (int i = 0; i < NCH; ++i)
+            if (tid + i * NTH < TP * 8) put(tid + i * NTH, v[i]);
     }
     __syncthreads();
     const int nt = (T + 15) >> 4;
@@ -311,6 +252,8 @@ static int launch_bwd_nt(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, co
 
 static int launch_bwd(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, const int* row_start, int batch, int t, int width, int causal,
                       hipStream_t stream, const char* who) {
+    if ((long long)batch * (width / 64) > 0x7fffffffLL)         // on the host, before any HIP call, as every refusal
+        KEMR_FAIL(KEMR_ERR_INVALID, "%s: batch = %d x %d heads exceeds the grid (2^31 - 1 workgroups)", who, batch, width / 64);
     switch ((t + 31) / 32) {
         case 1: return launch_bwd_nt<1>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
         case 2: return launch_bwd_nt<2>(qkv, dout, dqkv, row_start, batch, t, width, causal, stream);
@@ -336,17 +279,8 @@ using namespace kemr;
 
 extern "C" int kemr_op_attention_backward(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width,
                                           int causal, void* stream) {
-    // everything is refused here, on the host, before any HIP call
-    if (!qkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: qkv is NULL");
-    if (!dout_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: dout is NULL");
-    if (!dqkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: dqkv is NULL");
-    if (t < 1 || t > KEMR_MAX_TEXT_CTX) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: t = %d is outside 1..%d", t, KEMR_MAX_TEXT_CTX);
-    if (width <= 0 || width % 64 != 0) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: width = %d is not a positive multiple of 64 (heads of 64)", width);
-    if (causal != 0 && causal != 1) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: causal = %d is neither 0 nor 1", causal);
-    if (batch < 0) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: batch = %d is negative", batch);
-    if ((long long)batch * (width / 64) > 0x7fffffffLL)
-        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward: batch = %d x %d heads exceeds the grid (2^31 - 1 workgroups)", batch, width / 64);
-    if (batch == 0) return KEMR_OK;
+    KEMR_TRY(bwd_refuse("op_attention_backward", qkv_dev, dout_dev, dqkv_dev, nullptr, "t", t, KEMR_MAX_TEXT_CTX, width, causal, batch));
+    if (batch == 0) return KEMR_OK;                     // (the grid of an empty batch cannot be too large)
     return launch_attention_backward((const bf16_t*)qkv_dev, (const bf16_t*)dout_dev, (bf16_t*)dqkv_dev, batch, t, width, causal,
                                      (hipStream_t)stream);
 }
@@ -355,20 +289,8 @@ extern "C" int kemr_op_attention_backward(const void* qkv_dev, const void* dout_
 // in the instantiation of max_t.  See kemr.h.
 extern "C" int kemr_op_attention_backward_packed(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, const int* row_start_dev,
                                                  int batch, int max_t, int width, int causal, void* stream) {
-    // everything is refused here, on the host, before any HIP call
-    if (!qkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: qkv is NULL");
-    if (!dout_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: dout is NULL");
-    if (!dqkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: dqkv is NULL");
-    if (!row_start_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: row_start is NULL");
-    if (max_t < 1 || max_t > KEMR_MAX_TEXT_CTX)
-        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: max_t = %d is outside 1..%d", max_t, KEMR_MAX_TEXT_CTX);
-    if (width <= 0 || width % 64 != 0)
-        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: width = %d is not a positive multiple of 64 (heads of 64)", width);
-    if (causal != 0 && causal != 1) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: causal = %d is neither 0 nor 1", causal);
-    if (batch < 0) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: batch = %d is negative", batch);
-    if ((long long)batch * (width / 64) > 0x7fffffffLL)
-        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_packed: batch = %d x %d heads exceeds the grid (2^31 - 1 workgroups)", batch,
-                  width / 64);
+    KEMR_TRY(bwd_refuse("op_attention_backward_packed", qkv_dev, dout_dev, dqkv_dev, &row_start_dev, "max_t", max_t, KEMR_MAX_TEXT_CTX, width,
+                        causal, batch));
     if (batch == 0) return KEMR_OK;
     return launch_bwd((const bf16_t*)qkv_dev, (const bf16_t*)dout_dev, (bf16_t*)dqkv_dev, row_start_dev, batch, max_t, width, causal,
                       (hipStream_t)stream, "op_attention_backward_packed");

@@ -23,23 +23,20 @@
 // 9 score-sized products (S and dP three times each, then dQ, dK, dV) against the 7 of the LDS kernel and the minimum of 5: the
 // price of saving nothing in the forward and owning every output.  No atomics: every element of dqkv and of the workspace has one
 // owner and one fixed summation order (chunks in ascending order, the MFMA's own order inside), so two launches give the same bits.
-// Rounding points, those of attention_bwd.hip: P and dS to bf16 only as MFMA operands, dq / dk / dv to bf16 at the store, D from the
-// unrounded fp32 P, everything else fp32; P is exp2(fma(s, log2e, -m log2e)) * (1 / l) in both kernels.
-// tests/attention_bwd_ref.backward_emulated states the arithmetic.
+// The tile steps, the LDS layout, the MFMA operand forms and the rounding points are attention_bwd_tile.h's, shared with
+// attention_bwd.hip; D comes from the unrounded fp32 P.
 // Memory: staging loads and fragment loads clamp their row to the item's last one, pad rows are zeroed at the LDS write and masked (pad
 // keys to -inf in sweep 1, P = 0 elsewhere), tiles made only of pad rows are skipped (wave-uniform, never a barrier: EXEC is full at
 // every transposed read), rows >= t are not stored: exactly batch * t rows of dqkv and batch * heads * t rows of the workspace are
 // written, and nothing outside an item's rows of qkv and dout can reach its rows of dqkv.  The key-owned kernel reads only workspace
 // rows the query-owned kernel of the same call wrote.
-// LDS images (rows of 128 B) and MFMA operand forms are attention_bwd.hip's, restated here because that file's helpers are local to it:
-// K (query-owned), Q and dO (key-owned) are read by rows AND transposed and carry the 32-byte-chunk swizzle ^= (row >> 1) & 3; V is
-// only read by rows and carries the 16-byte-chunk swizzle ^= (row >> 1) & 7.  A chunk starts at a multiple of 64 rows, so the swizzle
-// of a chunk-local row is that of the row.  32 KB (query-owned) / 33.5 KB (key-owned) of LDS per workgroup.
+// LDS images: K (query-owned), Q and dO (key-owned) are read by rows AND transposed (TRL images), V is only read by rows; a chunk is
+// addressed by its local rows.  32 KB (query-owned) / 33.5 KB (key-owned) of LDS per workgroup.
 // Measured on an MI355X (the op alone, width 1024, medians of alternating windows; DESIGN.md "Streaming attention backward"): one tile
 // per wave at 3 waves per SIMD, as here, 0.437 ms at batch 32 x 577 tokens and 1.177 ms at 32 x 1025; at 2 waves per SIMD 0.441 / 1.237;
 // two tiles per wave (128-row blocks, half the chunk traffic, 198 VGPRs) 0.534 / 1.622, so blocks of 64 rows it is.  The three
 // variants gave the same bits.
-#include "common.h"
+#include "attention_bwd_tile.h"
 
 namespace kemr {
 
@@ -53,49 +50,6 @@ constexpr int IMG = RC * 128;               // bytes of one chunk image
 constexpr int NCH = RC * 8 / (NW * 64);     // 16-byte pieces of one image per thread and chunk
 constexpr int STAGE_Q = 2 * IMG;            // query-owned: K | V
 constexpr int STAGE_KV = 2 * IMG + RC * 3 * 4;      // key-owned: Q | dO | the chunk's statistics [3][64]
-constexpr float LOG2E = 1.4426950408889634f;
-
-template <bool TRL>
-__device__ __forceinline__ int bws_off(int row, int c) {
-    return row * 128 + ((TRL ? (c ^ (((row >> 1) & 3) << 1)) : (c ^ ((row >> 1) & 7))) << 4);
-}
-template <bool TRL>
-__device__ __forceinline__ bf16x8 bws_row(const char* img, int row, int c) { return *(const bf16x8*)(img + bws_off<TRL>(row, c)); }
-
-// the A fragments (4 d-tiles) of M^T for the 32 rows of block u of the image M: k slot 8 lq + j <-> row 32 u + 16 (j >> 2) + 4 lq + (j & 3)
-__device__ __forceinline__ void bws_tr(const char* img, int u, int lrow, int lq, bf16x8 (&dst)[4]) {
-    const int ra = u * 32 + lq * 4 + (lrow >> 2), rb = ra + 16;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-        const int c = dt * 2 + ((lrow & 3) >> 1);
-        const bf16x4 va = lds_read_tr16(img + bws_off<true>(ra, c) + (lrow & 1) * 8);
-        const bf16x4 vb = lds_read_tr16(img + bws_off<true>(rb, c) + (lrow & 1) * 8);
-        dst[dt][0] = va[0]; dst[dt][1] = va[1]; dst[dt][2] = va[2]; dst[dt][3] = va[3];
-        dst[dt][4] = vb[0]; dst[dt][5] = vb[1]; dst[dt][6] = vb[2]; dst[dt][7] = vb[3];
-    }
-}
-__device__ __forceinline__ bf16x8 bws_pack(const f32x4& a, const f32x4& b) {
-    union { bf16x8 v; uint32_t w[4]; } f;
-    f.w[0] = pack_bf16x2(a[0], a[1]); f.w[1] = pack_bf16x2(a[2], a[3]);
-    f.w[2] = pack_bf16x2(b[0], b[1]); f.w[3] = pack_bf16x2(b[2], b[3]);
-    return f.v;
-}
-__device__ __forceinline__ void bws_store(bf16_t* dst, const f32x4 (&acc)[4]) {
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-        uint2 pk;
-        pk.x = pack_bf16x2(acc[dt][0], acc[dt][1]);
-        pk.y = pack_bf16x2(acc[dt][2], acc[dt][3]);
-        *(uint2*)(dst + dt * 16) = pk;
-    }
-}
-// one 16-byte piece of a chunk row into its image, zeroed when the row is a pad row
-template <bool TRL>
-__device__ __forceinline__ void bws_put(char* img, int row, int c, uint4 a, bool valid) {
-    const unsigned keep = valid ? 0xffffffffu : 0u;
-    a.x &= keep; a.y &= keep; a.z &= keep; a.w &= keep;
-    *(uint4*)(img + bws_off<TRL>(row, c)) = a;
-}
 
 }  // namespace
 
@@ -142,8 +96,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_q_kernel(const bf1
             const int idx = tid + i * (NW * 64);
             const int row = idx >> 3, ch = idx & 7;
             const bool valid = c * RC + row < T;
-            bws_put<true>(stage, row, ch, kv[i], valid);
-            bws_put<false>(stage + IMG, row, ch, vv[i], valid);
+            bwd_put<true>(stage, row, ch, kv[i], valid);
+            bwd_put<false>(stage + IMG, row, ch, vv[i], valid);
         }
     };
 
@@ -186,14 +140,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_q_kernel(const bf1
         for (int t = 0; t < 4; ++t) {
             s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
             dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (k0 + t * 16 < T) {
-                const int row = t * 16 + lrow;
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bws_row<true>(sK, row, kk * 4 + lq), qf[kk], s[t], 0, 0, 0);
-                    dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bws_row<false>(sV, row, kk * 4 + lq), gf[kk], dp[t], 0, 0, 0);
-                }
-            }
+            if (k0 + t * 16 < T) bwd_scores<false>(sK, sV, t * 16 + lrow, lq, qf, gf, s[t], dp[t]);
         }
 
         if (cc < nch) {
@@ -228,18 +175,14 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_q_kernel(const bf1
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const bool ok = k0 + t * 16 + lq * 4 + r < T;
-                    const float p = ok ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][r], LOG2E, -ml)) * inv : 0.f;
+                    const float p = bwd_p(s[t][r], ml, inv, k0 + t * 16 + lq * 4 + r < T);
                     dp[t][r] = p * (dp[t][r] - dd);
                 }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 if (k0 + u * 32 >= T) continue;         // a block of pad keys only has dS = 0 (uniform)
                 bf16x8 af[4];
-                bws_tr(sK, u, lrow, lq, af);
-                const bf16x8 dsf = bws_pack(dp[2 * u], dp[2 * u + 1]);
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], dsf, dq[dt], 0, 0, 0);
+                bwd_accum(sK, u, lrow, lq, dp[2 * u], dp[2 * u + 1], af, dq);
             }
         }
 
@@ -248,7 +191,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_q_kernel(const bf1
     }
 
     // dq[dt][r] = dQ[query lrow of the tile][d = 16 dt + 4 lq + r]
-    if (q < T) bws_store(dqkv + (row0 + q) * ld + h * 64 + lq * 4, dq);
+    if (q < T) bwd_store(dqkv + (row0 + q) * ld + h * 64 + lq * 4, dq);
 }
 
 __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_kv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
@@ -303,8 +246,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_kv_kernel(const bf
             const int idx = tid + i * (NW * 64);
             const int row = idx >> 3, ch = idx & 7;
             const bool valid = c * RC + row < T;
-            bws_put<true>(stage, row, ch, qv[i], valid);
-            bws_put<true>(stage + IMG, row, ch, gv[i], valid);
+            bwd_put<true>(stage, row, ch, qv[i], valid);
+            bwd_put<true>(stage + IMG, row, ch, gv[i], valid);
         }
         if (tid < RC * 3) ((float*)(stage + 2 * IMG))[scomp * RC + srow] = sv;
     };
@@ -332,20 +275,14 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_kv_kernel(const bf
             s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
             dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (q0 + t * 16 < T) {
-                const int row = t * 16 + lrow;
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bws_row<true>(sQ, row, kk * 4 + lq), kf[kk], s[t], 0, 0, 0);
-                    dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bws_row<true>(sG, row, kk * 4 + lq), vf[kk], dp[t], 0, 0, 0);
-                }
+                bwd_scores<true>(sQ, sG, t * 16 + lrow, lq, kf, vf, s[t], dp[t]);
                 const float4 m4 = *(const float4*)(sS + t * 16 + lq * 4);
                 const float4 i4 = *(const float4*)(sS + RC + t * 16 + lq * 4);
                 const float4 d4 = *(const float4*)(sS + 2 * RC + t * 16 + lq * 4);
                 const float mm[4] = {m4.x, m4.y, m4.z, m4.w}, ii[4] = {i4.x, i4.y, i4.z, i4.w}, d[4] = {d4.x, d4.y, d4.z, d4.w};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const bool ok = q0 + t * 16 + lq * 4 + r < T;
-                    const float p = ok ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][r], LOG2E, -mm[r])) * ii[r] : 0.f;
+                    const float p = bwd_p(s[t][r], mm[r], ii[r], q0 + t * 16 + lq * 4 + r < T);
                     s[t][r] = p;
                     dp[t][r] = p * (dp[t][r] - d[r]);
                 }
@@ -355,14 +292,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_kv_kernel(const bf
         for (int u = 0; u < 2; ++u) {
             if (q0 + u * 32 >= T) continue;             // a block of pad queries only has P = dS = 0 (uniform)
             bf16x8 af[4];
-            bws_tr(sQ, u, lrow, lq, af);                                    // Q^T
-            const bf16x8 dsf = bws_pack(dp[2 * u], dp[2 * u + 1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], dsf, dk[dt], 0, 0, 0);
-            bws_tr(sG, u, lrow, lq, af);                                    // dO^T
-            const bf16x8 pf = bws_pack(s[2 * u], s[2 * u + 1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], pf, dv[dt], 0, 0, 0);
+            bwd_accum(sQ, u, lrow, lq, dp[2 * u], dp[2 * u + 1], af, dk);   // Q^T . dS
+            bwd_accum(sG, u, lrow, lq, s[2 * u], s[2 * u + 1], af, dv);     // dO^T . P
         }
 
         if (more) store_chunk(c + 1, smem + ((c + 1) & 1) * STAGE_KV);      // that buffer was last read before the previous barrier
@@ -372,8 +303,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_kv_kernel(const bf
     // dk[dt][r] / dv[dt][r] = d(key lrow of the tile)[d = 16 dt + 4 lq + r]
     if (k < T) {
         bf16_t* p = dqkv + (row0 + k) * ld + h * 64 + lq * 4;
-        bws_store(p + width, dk);
-        bws_store(p + 2 * width, dv);
+        bwd_store(p + width, dk);
+        bwd_store(p + 2 * width, dv);
     }
 }
 
@@ -388,15 +319,8 @@ extern "C" size_t kemr_attention_backward_long_workspace_bytes(int batch, int t,
 
 extern "C" int kemr_op_attention_backward_long(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width,
                                                void* workspace_dev, size_t workspace_bytes, void* stream) {
-    // everything is refused here, on the host, before any HIP call
-    if (!qkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_long: qkv is NULL");
-    if (!dout_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_long: dout is NULL");
-    if (!dqkv_dev) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_long: dqkv is NULL");
-    if (t < 1 || t > KEMR_MAX_VISION_TOKENS)
-        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_long: t = %d is outside 1..%d", t, KEMR_MAX_VISION_TOKENS);
-    if (width <= 0 || width % 64 != 0)
-        KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_long: width = %d is not a positive multiple of 64 (heads of 64)", width);
-    if (batch < 0) KEMR_FAIL(KEMR_ERR_INVALID, "op_attention_backward_long: batch = %d is negative", batch);
+    // everything is refused here, on the host, before any HIP call (non-causal: causal = 0)
+    KEMR_TRY(bwd_refuse("op_attention_backward_long", qkv_dev, dout_dev, dqkv_dev, nullptr, "t", t, KEMR_MAX_VISION_TOKENS, width, 0, batch));
     const int heads = width / 64, nrb = (t + RB - 1) / RB;
     const long long blocks = (long long)batch * heads * nrb;
     if (blocks > 0x7fffffffLL)

@@ -8,9 +8,11 @@ dqkv [batch * t, 3 width] = the gradient with respect to the three planes as giv
   backward_emulated  the same with the kernel's rounding points: every product sum in fp32, P and dS rounded to bf16 where they are
                      MFMA operands (D from the unrounded fp32 P), the three outputs rounded to bf16.  What is left between it and the
                      kernel is the summation order of the fp32 sums and the exponential's implementation.
-  rel_l2             the error measure of the tests.
+  rel_l2             the error measure of the tests; check_against_fp64 is the bar the three GPU test files hold their op to.
   plain_attention    softmax(q k^T) v in the dtype given, for torch autograd (the plain formulation the statement is checked against).
 """
+import ctypes
+
 import torch
 
 HEAD = 64
@@ -72,6 +74,23 @@ def rel_l2(x, ref):
 
 def planes(dqkv, width):
     return {"dq": dqkv[:, :width], "dk": dqkv[:, width:2 * width], "dv": dqkv[:, 2 * width:]}
+
+
+def check_against_fp64(got, ref, emu, width, what):
+    """The bar of the GPU tests: bf16, finite, and per plane (dq, dk, dv) the relative L2 error against the fp64 statement is at most
+    2 x the emulation's.  `what` names the op and the shape in the printed figures."""
+    assert got.dtype == torch.bfloat16 and got.shape == ref.shape
+    assert bool(torch.isfinite(got.float()).all())
+    for name in ("dq", "dk", "dv"):
+        r = planes(ref, width)[name]
+        e_kernel, e_emu = rel_l2(planes(got, width)[name], r), rel_l2(planes(emu, width)[name], r)
+        print(f"{what} {name}: kernel {e_kernel:.4e} emulation {e_emu:.4e}")
+        assert e_kernel <= 2.0 * e_emu, (name, e_kernel, e_emu)
+
+
+def stream(device):
+    """The current stream of `device` as the C ABI takes it."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def make_inputs(batch, t, width, seed, zero_item=None):

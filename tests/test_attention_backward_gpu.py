@@ -42,13 +42,7 @@ def _run(device, qkv, dout, t, causal, batch=BATCH):
 def test_error_against_fp64_within_twice_the_emulation(device, t, causal):
     qkv, dout, ref, emu = _case(t, causal)
     got = _run(device, qkv, dout, t, causal)
-    assert got.dtype == BF16 and got.shape == ref.shape
-    assert not torch.isnan(got.float()).any() and torch.isfinite(got.float()).all()
-    for name in ("dq", "dk", "dv"):
-        r = R.planes(ref, WIDTH)[name]
-        e_kernel, e_emu = R.rel_l2(R.planes(got, WIDTH)[name], r), R.rel_l2(R.planes(emu, WIDTH)[name], r)
-        print(f"attention_backward t={t} causal={causal} {name}: kernel {e_kernel:.4e} emulation {e_emu:.4e}")
-        assert e_kernel <= 2.0 * e_emu, (name, e_kernel, e_emu)
+    R.check_against_fp64(got, ref, emu, WIDTH, f"attention_backward t={t} causal={causal}")
     # the item whose dout rows are zero: exactly zero gradients
     assert not got[ZERO_ITEM * t:(ZERO_ITEM + 1) * t].float().any()
     if t == 1:          # one key: P = 1, dS = 0
@@ -80,7 +74,7 @@ def test_an_item_depends_on_its_own_rows_only(device, t, causal):
     wo = F.window(qkv2.shape, BF16, device, F.GUARD, what="dqkv")
     with torch.cuda.device(device):
         _lib.check(_lib.lib().kemr_op_attention_backward(C.c_void_p(wq.ptr), C.c_void_p(wd.ptr), C.c_void_p(wo.ptr), BATCH, t, WIDTH, causal,
-                                                         C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "op_attention_backward")
+                                                         R.stream(device)), "op_attention_backward")
     torch.cuda.synchronize(device)
     assert wq.margins_intact() and wd.margins_intact() and wo.margins_intact()
     assert F.same_bits(wo.view[own], base[own])
@@ -100,7 +94,7 @@ def test_memory_contract_exactly_batch_t_rows_written(device, t, causal):
 
     def run(*args):
         with torch.cuda.device(device):
-            _lib.check(fn(*args, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "op_attention_backward")
+            _lib.check(fn(*args, R.stream(device)), "op_attention_backward")
     F.run_both(run, _specs(t, causal, 7), device, what=f"attention_backward t={t} causal={causal}")
 
 
@@ -110,7 +104,7 @@ def test_stream_contract(device, t, causal):
 
     def run(*args):
         with torch.cuda.device(device):
-            _lib.check(fn(*args, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "op_attention_backward")
+            _lib.check(fn(*args, R.stream(device)), "op_attention_backward")
     SO.run_late(run, _specs(t, causal, 0), device, what=f"attention_backward t={t} causal={causal}")
 
 
@@ -119,6 +113,6 @@ def test_empty_batch_launches_nothing(device):
     keep = out.clone()
     with torch.cuda.device(device):
         _lib.check(_lib.lib().kemr_op_attention_backward(C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr()), 0, 4,
-                                                         WIDTH, 1, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "op_attention_backward")
+                                                         WIDTH, 1, R.stream(device)), "op_attention_backward")
     torch.cuda.synchronize(device)
     assert F.same_bits(out, keep)

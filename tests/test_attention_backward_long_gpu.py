@@ -36,10 +36,6 @@ def _case(t, width=WIDTH, batch=BATCH):
     return qkv, dout, R.backward_fp64(qkv, dout, batch, t, width, 0), R.backward_emulated(qkv, dout, batch, t, width, 0)
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _need(batch, t, width):
     return int(_lib.lib().kemr_attention_backward_long_workspace_bytes(batch, t, width))
 
@@ -52,26 +48,16 @@ def _direct(device, qkv, dout, t, width=WIDTH, batch=BATCH):
     ws = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
         _lib.check(_lib.lib().kemr_op_attention_backward_long(C.c_void_p(q.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                              batch, t, width, C.c_void_p(ws.data_ptr()), need, _stream(device)),
+                                                              batch, t, width, C.c_void_p(ws.data_ptr()), need, R.stream(device)),
                    "op_attention_backward_long")
     return out
-
-
-def _check_against_fp64(got, ref, emu, width, what):
-    assert got.dtype == BF16 and got.shape == ref.shape
-    assert bool(torch.isfinite(got.float()).all())
-    for name in ("dq", "dk", "dv"):
-        r = R.planes(ref, width)[name]
-        e_kernel, e_emu = R.rel_l2(R.planes(got, width)[name], r), R.rel_l2(R.planes(emu, width)[name], r)
-        print(f"attention_backward_long {what} {name}: kernel {e_kernel:.4e} emulation {e_emu:.4e}")
-        assert e_kernel <= 2.0 * e_emu, (name, e_kernel, e_emu)
 
 
 @pytest.mark.parametrize("t", TS)
 def test_error_against_fp64_within_twice_the_emulation(device, t):
     qkv, dout, ref, emu = _case(t)
     got = _direct(device, qkv, dout, t).cpu()
-    _check_against_fp64(got, ref, emu, WIDTH, f"t={t}")
+    R.check_against_fp64(got, ref, emu, WIDTH, f"attention_backward_long t={t}")
     # the item whose dout rows are zero: exactly zero gradients
     assert not got[ZERO_ITEM * t:(ZERO_ITEM + 1) * t].float().any()
     if t == 1:          # one key: P = 1, dS = 0
@@ -85,7 +71,7 @@ def test_head_indexing_at_width_1024(device):
     t, width, batch = 577, 1024, 2
     qkv, dout, ref, emu = _case(t, width, batch)
     got = _direct(device, qkv, dout, t, width, batch).cpu()
-    _check_against_fp64(got, ref, emu, width, f"t={t} width={width}")
+    R.check_against_fp64(got, ref, emu, width, f"attention_backward_long t={t} width={width}")
     assert not got[t:].float().any()
 
 
@@ -111,7 +97,7 @@ def test_an_item_depends_on_its_own_rows_only(device, t):
     ww = F.window((need,), torch.uint8, device, F.GUARD, body=F.POISON, what="workspace")
     with torch.cuda.device(device):
         _lib.check(_lib.lib().kemr_op_attention_backward_long(C.c_void_p(wq.ptr), C.c_void_p(wd.ptr), C.c_void_p(wo.ptr), BATCH, t, WIDTH,
-                                                              C.c_void_p(ww.ptr), need, _stream(device)), "op_attention_backward_long")
+                                                              C.c_void_p(ww.ptr), need, R.stream(device)), "op_attention_backward_long")
     torch.cuda.synchronize(device)
     assert wq.margins_intact() and wd.margins_intact() and wo.margins_intact() and ww.margins_intact()
     assert F.same_bits(wo.view[own], base[own])
@@ -130,7 +116,7 @@ def _run(device):
 
     def run(*args):
         with torch.cuda.device(device):
-            _lib.check(fn(*args, _stream(device)), "op_attention_backward_long")
+            _lib.check(fn(*args, R.stream(device)), "op_attention_backward_long")
     return run
 
 
@@ -151,7 +137,7 @@ def test_empty_batch_launches_nothing(device):
     assert _need(0, 4, WIDTH) == 0
     with torch.cuda.device(device):
         _lib.check(_lib.lib().kemr_op_attention_backward_long(C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                              0, 4, WIDTH, None, 0, _stream(device)), "op_attention_backward_long")
+                                                              0, 4, WIDTH, None, 0, R.stream(device)), "op_attention_backward_long")
     torch.cuda.synchronize(device)
     assert F.same_bits(out, keep)
 
@@ -164,7 +150,7 @@ def test_route_at_288_is_the_lds_kernel(device):
     want = torch.empty_like(q)
     with torch.cuda.device(device):
         _lib.check(_lib.lib().kemr_op_attention_backward(C.c_void_p(q.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(want.data_ptr()), BATCH, t,
-                                                         WIDTH, 0, _stream(device)), "op_attention_backward")
+                                                         WIDTH, 0, R.stream(device)), "op_attention_backward")
     assert F.same_bits(engine.attention_backward(q, d, BATCH, t, WIDTH, False), want)
 
 
