@@ -10,16 +10,12 @@
 // what the launch waits for.  The whole K and V of that head (T <= 288 keys,
 // 2 x 36 KB) sit in LDS; every wave owns 16-query tiles and, because T is short, keeps the full score
 // row in registers -- plain softmax, no online rescaling.  MFMA v_mfma_f32_16x16x32_bf16 throughout:
-//   S^T tile = K_tile . Q^T      (A = K rows from LDS, B = Q rows straight from HBM)  -> a lane holds
-//              4 consecutive keys of ONE query column, so row max / sum are 2 shuffles (xor 16, 32);
-//   O^T      = V^T . P^T         (A = V^T fragment by ds_read_b64_tr_b16 from the row-major V image,
-//                                 B = P^T fragment = the score registers, converted to bf16 in place).
-// The k-slot order of the second product is permuted (slot 8*lq+j <-> key 32u + 16*(j>>2) + 4*lq + (j&3))
-// identically for both operands, which is what lets P feed the MFMA without any lane movement.
-// LDS images: K rows of 128 B with chunk ^= (row>>1)&7 (conflict-free ds_read_b128), V rows of 128 B
-// with 32-byte-chunk ^= (row>>1)&3 (conflict-free transposed reads).  Pad keys are zero-filled and masked.
+//   S^T tile = K_tile . Q^T      (A = K rows from LDS, B = Q rows straight from HBM);
+//   O^T      = V^T . P^T         (A = V^T fragment by transposed reads of the row-major V image, B = the score registers).
+// The lane ownership, the permuted k-slot order of the second product, the two LDS images (K: Img64<false>, V: Img64<true>) and the
+// rounding points are attention_tile.h's.  Pad keys are zero-filled and masked.
 // The 1/sqrt(64) scale is folded into W_q / b_q when the weights are packed (exact: a power of two).
-#include "common.h"
+#include "attention_tile.h"
 
 namespace kemr {
 
@@ -46,6 +42,10 @@ __device__ __forceinline__ bf16x8 load_q8(const bf16_t* p) {
     else return *(const bf16x8*)p;
 }
 
+// Where attention_kernel spells attention_tile.h's arithmetic out: with every step a call into the header the bits were equal, but
+// attention_kernel<3, true, 77, 5> measured +0.10 % and +0.15 % at 512 x 77 x 768 where two copies of the previous library differed by
+// 0.04 % and 0.03 % (profiles/attention_tile_refactor_ab.json).  The spots were not timed one by one: each marked spot below is a step
+// whose call changes the device code; as it stands, all 22 kernels of this file compile to the previous commit's instructions.
 template <int NT32, bool CAUSAL, int TC, int NW = 4, bool STAMP = false, int NTLOAD = 1, bool SKIPTAIL = false>   // keys padded to NT32 * 32; NW waves per workgroup; NTLOAD: 0 plain loads, 1 = K / V non-temporal, 2 = Q too
 __global__ __launch_bounds__(NW * 64, 2) void attention_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                            int T_rt, int width, int xbatch, const int* __restrict__ row_start) {
@@ -53,7 +53,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_kernel(const bf16_t* __r
     constexpr int NT16 = NT32 * 2;
     constexpr int NTH = NW * 64;
     constexpr int NCH = (TP * 8 + NTH - 1) / NTH;      // 16-byte chunks of K (and of V) per thread
-    constexpr float LOG2E = 1.4426950408889634f;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sK = smem;
     char* sV = smem + TP * 128;
@@ -124,6 +123,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_kernel(const bf16_t* __r
             const int idx = tid + i * NTH;
             const int row = idx >> 3, c = idx & 7;
             if (idx < TP * 8) {
+                // two tile_put, spelled out (through the calls, or on the header's swizzle alone, every instantiation changes)
                 const unsigned keep = row < T ? 0xffffffffu : 0u;       // component-wise: a struct select went to scratch
                 uint4 a = kv[i], b2 = vv[i];
                 a.x &= keep; a.y &= keep; a.z &= keep; a.w &= keep;
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_kernel(const bf16_t* __r
             for (int j = 0; j < G; ++j)
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
-                    dst[j][kk] = *(const bf16x8*)(sK + ((g * G + j) * 16 + lrow) * 128 + (((kk * 4 + lq) ^ (lrow >> 1)) << 4));
+                    dst[j][kk] = *(const bf16x8*)(sK + ((g * G + j) * 16 + lrow) * 128 + Img64<false>::swz((g * G + j) * 16 + lrow, kk * 4 + lq));   // tile_row, pointer first
         };
         load_group(0, kfr[0]);
         attn_prio(1);
@@ -194,15 +194,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_kernel(const bf16_t* __r
                 mx = fmaxf(mx, s[t][r]);
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mxl = mx * LOG2E;
+        const float mxl = row_max(mx) * LOG2E;
         stamp(2);                                       // mask + row max + exchange
-        // exp(s - max) = exp2(s * log2e - max * log2e); masked keys -> 0.  The multiply-add and the row sum run two elements per
-        // instruction (v_pk_fma_f32 / v_pk_add_f32): the softmax is issue-bound, the MFMAs hide behind it
         f32x2_t sum2 = {0.f, 0.f};
         const f32x2_t l2 = {LOG2E, LOG2E}, nm = {-mxl, -mxl};
-        auto exp_tile = [&](int t) {
+        auto exp_tile = [&](int t) {                    // tile_exp, spelled out (through the call the instantiations of up to 128 keys change)
             f32x2_t a = f32x2_t{s[t][0], s[t][1]} * l2 + nm, c = f32x2_t{s[t][2], s[t][3]} * l2 + nm;
             a.x = __builtin_amdgcn_exp2f(a.x); a.y = __builtin_amdgcn_exp2f(a.y);
             c.x = __builtin_amdgcn_exp2f(c.x); c.y = __builtin_amdgcn_exp2f(c.y);
@@ -219,14 +215,16 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_kernel(const bf16_t* __r
         for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         // O^T += V^T . P^T per 32-key block, V fragments double-buffered the same way
         bf16x8 vfr[2][4];
+        // tile_tr<Img64<true>>, spelled out on the header's swizzle: through the call attention_kernel<3, true, 77, 5> has 81 VGPRs for 78
+        // and 5 waves per SIMD for 6; with the whole offset from the header attention_kernel<5, false, 0> has 2 waves for 3
         auto load_v = [&](int u, bf16x8 (&dst)[4]) {
             const int ra = u * 32 + lq * 4 + (lrow >> 2);       // rows 32u + 4lq .. +3 (first half of the k slots)
             const int rb = ra + 16;                             // rows 32u + 16 + 4lq .. +3
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 const int c = dt * 2 + ((lrow & 3) >> 1);
-                const bf16x4 va = lds_read_tr16(sV + ra * 128 + ((c ^ (((ra >> 1) & 3) << 1)) << 4) + (lrow & 1) * 8);
-                const bf16x4 vb = lds_read_tr16(sV + rb * 128 + ((c ^ (((rb >> 1) & 3) << 1)) << 4) + (lrow & 1) * 8);
+                const bf16x4 va = lds_read_tr16(sV + ra * 128 + Img64<true>::swz(ra, c) + (lrow & 1) * 8);
+                const bf16x4 vb = lds_read_tr16(sV + rb * 128 + Img64<true>::swz(rb, c) + (lrow & 1) * 8);
                 dst[dt][0] = va[0]; dst[dt][1] = va[1]; dst[dt][2] = va[2]; dst[dt][3] = va[3];
                 dst[dt][4] = vb[0]; dst[dt][5] = vb[1]; dst[dt][6] = vb[2]; dst[dt][7] = vb[3];
             }
@@ -240,23 +238,17 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_kernel(const bf16_t* __r
             if (!live(u)) continue;
             if (u + 1 < NT32 && (u + 1) * 32 < T) load_v(u + 1, vfr[(u + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
-            union { bf16x8 v; uint32_t w[4]; } pf;
-            pf.w[0] = pack_bf16x2(s[2 * u][0], s[2 * u][1]);
-            pf.w[1] = pack_bf16x2(s[2 * u][2], s[2 * u][3]);
-            pf.w[2] = pack_bf16x2(s[2 * u + 1][0], s[2 * u + 1][1]);
-            pf.w[3] = pack_bf16x2(s[2 * u + 1][2], s[2 * u + 1][3]);
+            const bf16x8 pf = tile_pack(s[2 * u], s[2 * u + 1]);
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr[u & 1][dt], pf.v, o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr[u & 1][dt], pf, o[dt], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
         attn_prio(0);
         stamp(4);                                       // PV MFMAs + V reads + P packing
-        float sum = sum2.x + sum2.y;
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
+        const float sum = row_sum(sum2.x + sum2.y);
         // o[dt][r] = O[query lrow][d = dt*16 + lq*4 + r]
-        if (q < T) {
+        if (q < T) {                                    // tile_store, spelled out (through the call seventeen instantiations change)
             const float inv = 1.0f / sum;
             bf16_t* dst = out + (row0 + q) * width + h * 64 + lq * 4;
 #pragma unroll
@@ -285,7 +277,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_kernel(const bf16_t* __r
 // by `build.py --ab-variants`; the product library holds ONE attention kernel per shape and kemr_debug_set refuses the others.
 int g_attn_v = 0;          // A/B builds only (attention_ab.hip), T = 257: 0 = the product kernel, 1..5 = the experiments
 
-int g_attn_xcd = 1;        // 1 = the images dealt to the XCDs (attn_item, common.h; default), 0 = grid order (tools)
+int g_attn_xcd = 1;        // 1 = the images dealt to the XCDs (attn_item; default), 0 = grid order (tools)
 int g_attn_waves = 0;      // tools: 0 = the default choice below, else waves per workgroup for the 257-token shape (4 or 6)
 
 #ifdef KEMR_AB_VARIANTS
@@ -367,7 +359,6 @@ __global__ __launch_bounds__(256) void attention_pooled_kernel(const bf16_t* __r
                                                                bf16_t* __restrict__ out, const int* __restrict__ pool_idx,
                                                                const int* __restrict__ row_start, int items, int tokens, int width,
                                                                int causal) {
-    constexpr float LOG2E = 1.4426950408889634f;
     __shared__ float sp[4][MAXK];
     const int heads = width >> 6, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int item = blockIdx.x * 4 + wv;
@@ -408,7 +399,8 @@ __global__ __launch_bounds__(256) void attention_pooled_kernel(const bf16_t* __r
         s += __shfl_xor(s, 4);
         if (ck == 0 && j < nk) sp[wv][j] = s;
     }
-    // softmax over the wave's LDS row, written and read by this wave only: the hardware keeps a wave's LDS accesses in order, the
+    // softmax over the wave's LDS row, written and read by this wave only (the same lines as in attention80_pooled_kernel: as one
+    // function in attention_tile.h the op measured +0.06 % at 255 x 257 x 1024 where two copies of the previous library differed by 0.02 %): the hardware keeps a wave's LDS accesses in order, the
     // fence + wave barrier keep the COMPILER from moving a lane's loads above another lane's stores it cannot prove to alias
     wave_lds_fence();
     float sc[MAXK / 64];

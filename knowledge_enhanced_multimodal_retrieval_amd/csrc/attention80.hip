@@ -3,25 +3,16 @@
 // kernels are not touched.  Non-causal only: no text tower has heads of 80.
 //
 // attention80_kernel -- the design of attention_kernel: one workgroup per (image, head), the whole K and V of that head in LDS
-// (T <= 288 keys), a wave owns 16-query tiles and keeps the full score row in registers, plain softmax with the row sum taken
-// before P is rounded to bf16, v_mfma_f32_16x16x32_bf16 throughout.
+// (T <= 288 keys), a wave owns 16-query tiles and keeps the full score row in registers, plain softmax, v_mfma_f32_16x16x32_bf16
+// throughout; lane ownership, k-slot order, the LDS image (Img80: rows of 160 B, no swizzle) and the rounding points are
+// attention_tile.h's.
 //   S^T tile = K_tile . Q^T: the contraction over 80 is two K = 32 steps (columns 0..63) and a THIRD K = 32 step whose k slots
 //              0..15 are columns 64..79 and whose slots 16..31 are zero in BOTH operands.  Slot 8 * lq + j belongs to lane group
 //              lq = lane >> 4, so the zero slots are the lanes lq >= 2: their Q registers are cleared in the kernel and their K
-//              read goes to a 16-byte chunk of zeros the kernel writes behind the V image.  Nothing beyond column 79 of a head is
+//              read goes to the chunk of zeros the kernel writes behind the V image.  Nothing beyond column 79 of a head is
 //              ever loaded -- columns 80..95 would be the next head, the next plane of the row, or (V of the last row) memory past
 //              the allocation.
-//   O^T      = V^T . P^T: 5 d-tiles of 16 instead of 4; same permuted k-slot order as attention_kernel, so P feeds the MFMA from
-//              the score registers.
-// LDS images: K and V rows of exactly 160 B (80 bf16, no pad columns), plain row-major, NO XOR swizzle -- the 10 chunks of a row
-// are no power of two, and the pitch itself spreads the banks: 160 B = 10 slots of 16 B = 40 banks, and 5 r mod 8 is a bijection
-// of r mod 8, so
-//   * ds_read_b128 (K fragments; a lane group of 16 = rows {0-3, 12-15} at chunk c and rows 4-11 at chunk c + 1, or the mirror):
-//     slot (10 r + c) mod 16 = 2 (5 r mod 8) + c takes the 8 even values over 8 rows that differ mod 8, chunk c + 1 the odd ones:
-//     16 lanes on 16 different slots, conflict-free; the third step has the lanes lq >= 2 on ONE address (broadcast);
-//   * ds_read_b64_tr_b16 (V^T fragments; a 32-lane half = 8 consecutive rows 8 n .. 8 n + 7, 32 B = 8 banks of each at the same
-//     column offset): bank (40 r + 8 dt) mod 64 = 8 (5 r + dt mod 8) is a different multiple of 8 for each of the 8 rows: 8 x 8
-//     banks = all 64, conflict-free.
+//   O^T      = V^T . P^T: 5 d-tiles of 16 instead of 4.
 // LDS per workgroup: 288 keys x 160 B x 2 + 16 = 92 176 B, so ONE workgroup per CU (two would need 184 KB of the CU's 160 KiB; a
 // 257-key image cannot go below 272 rows = 87 KB either), not the two of the head-dim-64 kernel.  The occupancy is restored inside
 // the workgroup: EIGHT waves (two per SIMD, 17 query tiles = 3 / 2 / 2 / 2 / 2 / 2 / 2 / 2) share one K / V image, <= 256 VGPRs
@@ -34,8 +25,10 @@
 // chunk), four keys per pass; out[d] with lane = (4 columns of d, key parity), the two parities added by one shuffle.
 //
 // attention80_x3_kernel -- attention_x3_kernel (streaming, hi / lo operand pairs, three products) with d padded to 96 in the K
-// image (zeros written once by the kernel), the Q pad slots cleared in registers, 80 V^T rows and 5 output d-tiles.
-#include "common.h"
+// image (zeros written once by the kernel), the Q pad slots cleared in registers, 80 V^T rows and 5 output d-tiles.  A kernel of its
+// own: as the HD = 80 instantiation of one attention_x3_kernel<HD> template it had the same bits but measured 0.9 % and 1.2 % slower
+// at 64 x 257 x 1280, where two copies of the previous library differed by 0.02 % and 0.07 % (profiles/attention_tile_refactor_ab.json).
+#include "attention_tile.h"
 
 namespace kemr {
 
@@ -44,7 +37,7 @@ int g_attn80_waves = 0;    // tools: 0 = the default (8 waves per workgroup), 4 
 namespace {
 
 constexpr int HD = 80;             // head dim
-constexpr int ROWB = HD * 2;       // bytes per K / V row in LDS
+constexpr int ROWB = Img80::ROWB;  // bytes per K / V row in LDS
 constexpr int RCH = HD / 8;        // 16-byte chunks per row
 
 typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
@@ -56,7 +49,6 @@ __global__ __launch_bounds__(NW * 64) void attention80_kernel(const bf16_t* __re
     constexpr int NT16 = NT32 * 2;
     constexpr int NTH = NW * 64;
     constexpr int NCH = (TP * RCH + NTH - 1) / NTH;     // 16-byte chunks of K (and of V) per thread
-    constexpr float LOG2E = 1.4426950408889634f;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sK = smem;
     char* sV = smem + TP * ROWB;
@@ -106,12 +98,8 @@ __global__ __launch_bounds__(NW * 64) void attention80_kernel(const bf16_t* __re
             const int idx = tid + i * NTH;
             const int row = idx / RCH, c = idx - row * RCH;
             if (idx < TP * RCH) {
-                const unsigned keep = row < T ? 0xffffffffu : 0u;
-                uint4 a = kv[i], b2 = vv[i];
-                a.x &= keep; a.y &= keep; a.z &= keep; a.w &= keep;
-                b2.x &= keep; b2.y &= keep; b2.z &= keep; b2.w &= keep;
-                *(uint4*)(sK + row * ROWB + c * 16) = a;
-                *(uint4*)(sV + row * ROWB + c * 16) = b2;
+                tile_put<Img80>(sK, row, c, kv[i], row < T);
+                tile_put<Img80>(sV, row, c, vv[i], row < T);
             }
         }
     }
@@ -129,10 +117,10 @@ __global__ __launch_bounds__(NW * 64) void attention80_kernel(const bf16_t* __re
         auto load_group = [&](int g, bf16x8 (&dst)[G][3]) {
 #pragma unroll
             for (int j = 0; j < G; ++j) {
-                const char* rowp = sK + ((g * G + j) * 16 + lrow) * ROWB;
-                dst[j][0] = *(const bf16x8*)(rowp + lq * 16);
-                dst[j][1] = *(const bf16x8*)(rowp + (4 + lq) * 16);
-                dst[j][2] = *(const bf16x8*)(lq < 2 ? rowp + (8 + lq) * 16 : sZ);
+                const int row = (g * G + j) * 16 + lrow;
+                dst[j][0] = tile_row<Img80>(sK, row, lq);
+                dst[j][1] = tile_row<Img80>(sK, row, 4 + lq);
+                dst[j][2] = *(const bf16x8*)(lq < 2 ? sK + Img80::off(row, 8 + lq) : sZ);
             }
         };
         load_group(0, kfr[0]);
@@ -166,75 +154,38 @@ __global__ __launch_bounds__(NW * 64) void attention80_kernel(const bf16_t* __re
                 mx = fmaxf(mx, s[t][r]);
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mxl = mx * LOG2E;
+        const float mxl = row_max(mx) * LOG2E;
         f32x2_t sum2 = {0.f, 0.f};
         const f32x2_t l2 = {LOG2E, LOG2E}, nm = {-mxl, -mxl};
 #pragma unroll
-        for (int t = 0; t < NT16; ++t) {
-            f32x2_t a = f32x2_t{s[t][0], s[t][1]} * l2 + nm, c = f32x2_t{s[t][2], s[t][3]} * l2 + nm;
-            a.x = __builtin_amdgcn_exp2f(a.x); a.y = __builtin_amdgcn_exp2f(a.y);
-            c.x = __builtin_amdgcn_exp2f(c.x); c.y = __builtin_amdgcn_exp2f(c.y);
-            s[t][0] = a.x; s[t][1] = a.y; s[t][2] = c.x; s[t][3] = c.y;
-            sum2 += a;
-            sum2 += c;
-        }
+        for (int t = 0; t < NT16; ++t) tile_exp(s[t], l2, nm, sum2);
 
         f32x4 o[5];
 #pragma unroll
         for (int dt = 0; dt < 5; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         // O^T += V^T . P^T per 32-key block, V fragments double-buffered
         bf16x8 vfr[2][5];
-        auto load_v = [&](int u, bf16x8 (&dst)[5]) {
-            const int ra = u * 32 + lq * 4 + (lrow >> 2);       // rows 32u + 4lq .. +3 (first half of the k slots)
-            const int rb = ra + 16;                             // rows 32u + 16 + 4lq .. +3
-#pragma unroll
-            for (int dt = 0; dt < 5; ++dt) {
-                const int cb = dt * 32 + (lrow & 3) * 8;        // columns 16 dt + 4 (lrow & 3) .. + 3 of the row
-                const bf16x4 va = lds_read_tr16(sV + ra * ROWB + cb);
-                const bf16x4 vb = lds_read_tr16(sV + rb * ROWB + cb);
-                dst[dt][0] = va[0]; dst[dt][1] = va[1]; dst[dt][2] = va[2]; dst[dt][3] = va[3];
-                dst[dt][4] = vb[0]; dst[dt][5] = vb[1]; dst[dt][6] = vb[2]; dst[dt][7] = vb[3];
-            }
-        };
-        load_v(0, vfr[0]);
+        tile_tr<Img80>(sV, 0, lrow, lq, vfr[0]);
 #pragma unroll
         for (int u = 0; u < NT32; ++u) {
             if (u * 32 >= T) continue;                  // a block that is all pad keys has P = 0 (uniform); the live blocks are a prefix
-            if (u + 1 < NT32 && (u + 1) * 32 < T) load_v(u + 1, vfr[(u + 1) & 1]);
+            if (u + 1 < NT32 && (u + 1) * 32 < T) tile_tr<Img80>(sV, u + 1, lrow, lq, vfr[(u + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
-            union { bf16x8 v; uint32_t w[4]; } pf;
-            pf.w[0] = pack_bf16x2(s[2 * u][0], s[2 * u][1]);
-            pf.w[1] = pack_bf16x2(s[2 * u][2], s[2 * u][3]);
-            pf.w[2] = pack_bf16x2(s[2 * u + 1][0], s[2 * u + 1][1]);
-            pf.w[3] = pack_bf16x2(s[2 * u + 1][2], s[2 * u + 1][3]);
+            const bf16x8 pf = tile_pack(s[2 * u], s[2 * u + 1]);
 #pragma unroll
             for (int dt = 0; dt < 5; ++dt)
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr[u & 1][dt], pf.v, o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr[u & 1][dt], pf, o[dt], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-        float sum = sum2.x + sum2.y;
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
+        const float sum = row_sum(sum2.x + sum2.y);
         // o[dt][r] = O[query lrow][d = dt*16 + lq*4 + r]
-        if (q < T) {
-            const float inv = 1.0f / sum;
-            bf16_t* dst = out + (row0 + q) * width + h * HD + lq * 4;
-#pragma unroll
-            for (int dt = 0; dt < 5; ++dt) {
-                uint2 pk;
-                pk.x = pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv);
-                pk.y = pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv);
-                *(uint2*)(dst + dt * 16) = pk;
-            }
-        }
+        if (q < T) tile_store(out + (row0 + q) * width + h * HD + lq * 4, o, 1.0f / sum);
     }
 }
 
 template <int NT32>
 int launch80_nt(const bf16_t* qkv, bf16_t* out, int batch, int t, int width, hipStream_t stream) {
-    constexpr int smem = NT32 * 32 * ROWB * 2 + 16;
+    constexpr int smem = NT32 * 32 * ROWB * 2 + Img80::ZERO;
     const dim3 grid(width / HD, (batch + 7) / 8 * 8);
     ProfScope prof(PROF_ATTENTION, stream);
     // run-time T (tests, other image sizes): four waves, whose 512-VGPR budget holds the uniform conditions of the unrolled tiles that
@@ -260,7 +211,6 @@ constexpr int PMAXK = 320;         // keys per item the LDS row holds (towers of
 
 __global__ __launch_bounds__(256) void attention80_pooled_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ qkv,
                                                                  bf16_t* __restrict__ out, int items, int tokens, int width) {
-    constexpr float LOG2E = 1.4426950408889634f;
     __shared__ float sp[4][PMAXK];
     const int heads = width / HD, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int item = blockIdx.x * 4 + wv;
@@ -304,6 +254,9 @@ __global__ __launch_bounds__(256) void attention80_pooled_kernel(const bf16_t* _
         s += __shfl_xor(s, 8);
         if (ck == 0 && j < nk) sp[wv][j] = s;
     }
+    // the softmax of attention_pooled_kernel, line for line (the wave's LDS row is written and read by this wave only).  As a shared
+    // pooled_softmax<MAXK> in attention_tile.h it gave the same bits, but the 64-column op measured +0.06 % at 255 x 257 x 1024 and this one
+    // +0.01 % over the slower of two copies of the previous library at 64 x 257 x 1280 in one of four runs, so both kernels keep theirs
     wave_lds_fence();
     float sc[PMAXK / 64];
     float mx = -INFINITY;
@@ -395,7 +348,6 @@ __global__ __launch_bounds__(256) void attention80_x3_kernel(const float* __rest
     }
 
     const float NEG_INF = -__builtin_inff();
-    const float LOG2E = 1.4426950408889634f;
     float m = NEG_INF, lsum = 0.f;
     f32x4 acc[5];
 #pragma unroll
@@ -457,6 +409,7 @@ __global__ __launch_bounds__(256) void attention80_x3_kernel(const float* __rest
             s[j] = kk < len ? st[j >> 2][j & 3] : NEG_INF;
             cmax = fmaxf(cmax, s[j]);
         }
+        // attention_tile.h's row_max (and row_sum at the end), spelled out: the kernel is kept at the previous commit's code
         cmax = fmaxf(cmax, __shfl_xor(cmax, 16));
         cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
         const float m_new = fmaxf(m, cmax);

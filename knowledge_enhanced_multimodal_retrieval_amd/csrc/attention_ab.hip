@@ -7,7 +7,7 @@
 //   attn_v = 3  persistent workgroup per CU, next head by LDS-DMA     (attention_pd_kernel)
 //   attn_v = 4  two query tiles per pass sharing K / V fragments      (attention_s2_kernel)
 //   attn_v = 5  persistent workgroups, two per CU, next item's K / V prefetched into registers (round 4; attention_persist_kernel)
-#include "common.h"
+#include "attention_tile.h"
 
 namespace kemr {
 

@@ -21,8 +21,8 @@
 //     then dV^T = dO^T . P and dK^T = Q^T . dS (A = dO^T / Q^T by transposed reads, B = the P / dS registers).
 // Both phases are one function (bwd_own_tile) with the operands exchanged.  S and dP are computed twice (7 products instead of 5):
 // the price of owning every output without a workspace.  Causal: tiles wholly behind the diagonal are skipped in both phases.
-// The LDS images, the MFMA operand forms and the rounding points are attention_bwd_tile.h's, shared with attention_bwd_stream.hip: Q, K
-// and dO are read by rows AND transposed (TRL images), V is only read by rows.
+// The LDS images and the MFMA operand forms are attention_tile.h's, the backward's tile steps and rounding points attention_bwd_tile.h's,
+// shared with attention_bwd_stream.hip: Q, K and dO are read by rows AND transposed (Img64<true>), V is only read by rows.
 #include "attention_bwd_tile.h"
 
 #include <type_traits>
@@ -30,7 +30,7 @@
 namespace kemr {
 
 // PHASE 1: own = the 16 queries of tile ot, other = keys; PHASE 2: own = the 16 keys of tile ot, other = queries.
-// Lane ownership of s[t][r] / dp[t][r] as attention_bwd_tile.h states it; every skip below is wave-uniform, so EXEC stays full.
+// Lane ownership of s[t][r] / dp[t][r] as attention_tile.h states it; every skip below is wave-uniform, so EXEC stays full.
 template <int NT32, bool CAUSAL, int PHASE>
 __device__ __forceinline__ void bwd_own_tile(const char* sQ, const char* sK, const char* sV, const char* sG, float* sM, float* sI,
                                              float* sD, int ot, int T, int lane, bf16_t* dst, size_t ld, int width) {
@@ -44,8 +44,8 @@ __device__ __forceinline__ void bwd_own_tile(const char* sQ, const char* sK, con
     bf16x8 b1[2], b2[2];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-        b1[kk] = bwd_row<true>(own1, o, kk * 4 + lq);
-        b2[kk] = bwd_row<PHASE == 1>(own2, o, kk * 4 + lq);
+        b1[kk] = tile_row<Img64<true>>(own1, o, kk * 4 + lq);
+        b2[kk] = tile_row<Img64<PHASE == 1>>(own2, o, kk * 4 + lq);
     }
     f32x4 s[NT16], dp[NT16];
 #pragma unroll
@@ -132,8 +132,8 @@ __device__ __forceinline__ void bwd_own_tile(const char* sQ, const char* sK, con
     // acc[dt][r] = d(own row lrow)[d = dt * 16 + lq * 4 + r]
     if (o < T) {
         bf16_t* p = dst + (size_t)o * ld + lq * 4;
-        if constexpr (PHASE == 1) bwd_store(p, acc1);                   // dq
-        else { bwd_store(p + width, acc1); bwd_store(p + 2 * width, acc2); }    // dk, dv
+        if constexpr (PHASE == 1) tile_store(p, acc1);                   // dq
+        else { tile_store(p + width, acc1); tile_store(p + 2 * width, acc2); }    // dk, dv
     }
 }
 
@@ -180,8 +180,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const bf16_t* __rest
         char* img = smem + mtx * TP * 128;
         auto put = [&](int idx, uint4 a) {              // piece idx of the matrix: chunk idx & 7 of row idx >> 3
             const int row = idx >> 3, c = idx & 7;
-            if (mtx == 2) bwd_put<false>(img, row, c, a, row < T);
-            else bwd_put<true>(img, row, c, a, row < T);
+            if (mtx == 2) tile_put<Img64<false>>(img, row, c, a, row < T);
+            else tile_put<Img64<true>>(img, row, c, a, row < T);
         };
         if constexpr (PACKED) {
             // the item's own padded length (a multiple of 32 rows, at most TP): no row beyond it is ever read.  32 rows are one chunk

@@ -23,14 +23,14 @@
 // 9 score-sized products (S and dP three times each, then dQ, dK, dV) against the 7 of the LDS kernel and the minimum of 5: the
 // price of saving nothing in the forward and owning every output.  No atomics: every element of dqkv and of the workspace has one
 // owner and one fixed summation order (chunks in ascending order, the MFMA's own order inside), so two launches give the same bits.
-// The tile steps, the LDS layout, the MFMA operand forms and the rounding points are attention_bwd_tile.h's, shared with
-// attention_bwd.hip; D comes from the unrounded fp32 P.
+// The LDS layout and the MFMA operand forms are attention_tile.h's, the backward's tile steps and rounding points attention_bwd_tile.h's,
+// shared with attention_bwd.hip; D comes from the unrounded fp32 P.
 // Memory: staging loads and fragment loads clamp their row to the item's last one, pad rows are zeroed at the LDS write and masked (pad
 // keys to -inf in sweep 1, P = 0 elsewhere), tiles made only of pad rows are skipped (wave-uniform, never a barrier: EXEC is full at
 // every transposed read), rows >= t are not stored: exactly batch * t rows of dqkv and batch * heads * t rows of the workspace are
 // written, and nothing outside an item's rows of qkv and dout can reach its rows of dqkv.  The key-owned kernel reads only workspace
 // rows the query-owned kernel of the same call wrote.
-// LDS images: K (query-owned), Q and dO (key-owned) are read by rows AND transposed (TRL images), V is only read by rows; a chunk is
+// LDS images: K (query-owned), Q and dO (key-owned) are read by rows AND transposed (Img64<true>), V is only read by rows; a chunk is
 // addressed by its local rows.  32 KB (query-owned) / 33.5 KB (key-owned) of LDS per workgroup.
 // Measured on an MI355X (the op alone, width 1024, medians of alternating windows; DESIGN.md "Streaming attention backward"): one tile
 // per wave at 3 waves per SIMD, as here, 0.437 ms at batch 32 x 577 tokens and 1.177 ms at 32 x 1025; at 2 waves per SIMD 0.441 / 1.237;
@@ -96,8 +96,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_q_kernel(const bf1
             const int idx = tid + i * (NW * 64);
             const int row = idx >> 3, ch = idx & 7;
             const bool valid = c * RC + row < T;
-            bwd_put<true>(stage, row, ch, kv[i], valid);
-            bwd_put<false>(stage + IMG, row, ch, vv[i], valid);
+            tile_put<Img64<true>>(stage, row, ch, kv[i], valid);
+            tile_put<Img64<false>>(stage + IMG, row, ch, vv[i], valid);
         }
     };
 
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_q_kernel(const bf1
     }
 
     // dq[dt][r] = dQ[query lrow of the tile][d = 16 dt + 4 lq + r]
-    if (q < T) bwd_store(dqkv + (row0 + q) * ld + h * 64 + lq * 4, dq);
+    if (q < T) tile_store(dqkv + (row0 + q) * ld + h * 64 + lq * 4, dq);
 }
 
 __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_kv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
@@ -246,8 +246,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_kv_kernel(const bf
             const int idx = tid + i * (NW * 64);
             const int row = idx >> 3, ch = idx & 7;
             const bool valid = c * RC + row < T;
-            bwd_put<true>(stage, row, ch, qv[i], valid);
-            bwd_put<true>(stage + IMG, row, ch, gv[i], valid);
+            tile_put<Img64<true>>(stage, row, ch, qv[i], valid);
+            tile_put<Img64<true>>(stage + IMG, row, ch, gv[i], valid);
         }
         if (tid < RC * 3) ((float*)(stage + 2 * IMG))[scomp * RC + srow] = sv;
     };
@@ -303,8 +303,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attention_bwd_kv_kernel(const bf
     // dk[dt][r] / dv[dt][r] = d(key lrow of the tile)[d = 16 dt + 4 lq + r]
     if (k < T) {
         bf16_t* p = dqkv + (row0 + k) * ld + h * 64 + lq * 4;
-        bwd_store(p + width, dk);
-        bwd_store(p + 2 * width, dv);
+        tile_store(p + width, dk);
+        tile_store(p + 2 * width, dv);
     }
 }
 

@@ -15,13 +15,10 @@
 //     registers while chunk c is computed, then written to the other LDS buffer -- one barrier per chunk;
 //   * per query a running max m and row sum l in fp32: for every chunk m' = max(m, chunk max), O and l are scaled by
 //     exp(m - m') (exactly 1 when the max did not move), P = exp(S - m');
-//   * the MFMA forms and LDS images are attention.hip's: S^T = K . Q^T puts four keys of one query in a lane (row max and
-//     sum: two shuffles), V^T comes through ds_read_b64_tr_b16 from the row-major V image, and the permuted k-slot order lets
-//     the bf16 P registers feed the PV MFMA with no lane movement.  K rows 128 B with chunk ^= (row >> 1) & 7, V rows with
-//     32-byte chunk ^= (row >> 1) & 3: conflict-free (a chunk starts at a multiple of 64 rows, so the swizzle is unchanged).
-// Rounding as in the tile kernels: P is rounded to bf16 for the PV product, the row sum is accumulated in fp32 from the unrounded P,
-// and the output is divided by it once at the end (oracle/rounding.py attention_long_emulation states it, for every instantiation
-// per item at T = the item's length).  No atomics, a fixed order of every sum: bit-identical run to run.
+//   * the MFMA forms, the lane ownership and the LDS images (K: Img64<false>, V: Img64<true>) are attention_tile.h's, as in
+//     attention.hip; a chunk starts at a multiple of 64 rows, so it has the swizzle of its local rows.
+// Rounding at attention_tile.h's three points, as in the tile kernels (oracle/rounding.py attention_long_emulation states it, for every
+// instantiation per item at T = the item's length).  No atomics, a fixed order of every sum: bit-identical run to run.
 // Pad keys (the ragged last chunk: 577 = 9 * 64 + 1) are zero-filled in LDS and masked to -inf; key tiles made only of pad keys
 // are skipped (wave-uniform).  Pad queries read the last valid row and are not stored.
 // Every difference between the instantiations is under `if constexpr`: each is the kernel it would be if written alone.
@@ -66,7 +63,7 @@
 // B = 85, width 1024 (tools/bench_attention_long.py): QT 2 / KC 64 / 2 waves (180 VGPRs) 314-326 us; QT 1 / KC 64 / 4 waves (126
 // VGPRs) 325 us; QT 1 / KC 128, 3 or 4 waves, 415 us.  Occupancy is not what holds it back: the counters put it at 2.35 x the VALU
 // instructions per MFMA of the 257-token kernel (softmax and per-chunk bookkeeping; DESIGN.md, "Long sequences").
-#include "common.h"
+#include "attention_tile.h"
 
 namespace kemr {
 
@@ -99,11 +96,16 @@ static_assert(NDP <= NW * 64 * 4, "the bias row is staged in one pass of four fl
 // deals linear ids round-robin over the eight XCDs) take a contiguous range: the query blocks of one (item, head) read the same
 // K / V rows through the same L2.  Only a locality heuristic; every work item is computed exactly once whatever the placement.
 // !PACKED: T = max_t for every item, row_start is not read.  !BIAS: bias_by_distance is not read.
+// Where the kernel spells attention_tile.h's arithmetic out: with every step a call the bits were equal and the non-causal instantiations
+// 0.6 - 0.7 % faster, but <true, false, true> measured +0.02 % and +0.09 % at the 248-position packed mix in two of three runs where two
+// copies of the previous library differed by 0.03 % and 0.02 % (profiles/attention_tile_refactor_ab.json).  The spots were not timed one by
+// one: row_max, tile_exp and tile_pack stay calls and the V gather takes the header's swizzle, which leave the device code as it was; the
+// staging write, the K read, row_sum and the store change it and are spelled out.  All four instantiations compile to the previous
+// commit's instructions.
 template <bool PACKED, bool BIAS, bool CAUSAL>
 __global__ __launch_bounds__(NW * 64, KEMR_ATTN_STREAM_OCC) void attention_stream_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                                        const int* __restrict__ row_start, int max_t, int width, int nqb, int items,
                                                                        const float* __restrict__ bias_by_distance) {
-    constexpr float LOG2E = 1.4426950408889634f;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE + (BIAS ? NDP * 4 : 0)];
 
     const int heads = width >> 6;
@@ -171,7 +173,7 @@ __global__ __launch_bounds__(NW * 64, KEMR_ATTN_STREAM_OCC) void attention_strea
         for (int i = 0; i < NCH; ++i) {
             const int idx = tid + i * (NW * 64);
             const int row = idx >> 3, ch = idx & 7;
-            const unsigned keep = c * KC + row < T ? 0xffffffffu : 0u;
+            const unsigned keep = c * KC + row < T ? 0xffffffffu : 0u;      // two tile_put, spelled out (see the note at the kernel)
             uint4 a = kv[i], v = vv[i];
             a.x &= keep; a.y &= keep; a.z &= keep; a.w &= keep;
             v.x &= keep; v.y &= keep; v.z &= keep; v.w &= keep;
@@ -222,7 +224,7 @@ __global__ __launch_bounds__(NW * 64, KEMR_ATTN_STREAM_OCC) void attention_strea
         for (int t = 0; t < NT16; ++t)
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
-                kf[t][kk] = *(const bf16x8*)(sK + (t * 16 + lrow) * 128 + (((kk * 4 + lq) ^ (lrow >> 1)) << 4));
+                kf[t][kk] = *(const bf16x8*)(sK + (t * 16 + lrow) * 128 + (((kk * 4 + lq) ^ (lrow >> 1)) << 4));   // tile_row<Img64<false>>, spelled out
 #pragma unroll
         for (int t = 0; t < NT16; ++t)
 #pragma unroll
@@ -241,14 +243,14 @@ __global__ __launch_bounds__(NW * 64, KEMR_ATTN_STREAM_OCC) void attention_strea
         // V^T fragments of the chunk's two 32-key blocks, issued before the softmax so that their latency hides behind it
         bf16x8 vf[NU][4];
 #pragma unroll
-        for (int u = 0; u < NU; ++u) {
+        for (int u = 0; u < NU; ++u) {                 // tile_tr<Img64<true>>, spelled out on the header's swizzle
             const int ra = u * 32 + lq * 4 + (lrow >> 2);
             const int rb = ra + 16;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 const int cc = dt * 2 + ((lrow & 3) >> 1);
-                const bf16x4 va = lds_read_tr16(sV + ra * 128 + ((cc ^ (((ra >> 1) & 3) << 1)) << 4) + (lrow & 1) * 8);
-                const bf16x4 vb = lds_read_tr16(sV + rb * 128 + ((cc ^ (((rb >> 1) & 3) << 1)) << 4) + (lrow & 1) * 8);
+                const bf16x4 va = lds_read_tr16(sV + ra * 128 + Img64<true>::swz(ra, cc) + (lrow & 1) * 8);
+                const bf16x4 vb = lds_read_tr16(sV + rb * 128 + Img64<true>::swz(rb, cc) + (lrow & 1) * 8);
                 vf[u][dt][0] = va[0]; vf[u][dt][1] = va[1]; vf[u][dt][2] = va[2]; vf[u][dt][3] = va[3];
                 vf[u][dt][4] = vb[0]; vf[u][dt][5] = vb[1]; vf[u][dt][6] = vb[2]; vf[u][dt][7] = vb[3];
             }
@@ -280,22 +282,13 @@ __global__ __launch_bounds__(NW * 64, KEMR_ATTN_STREAM_OCC) void attention_strea
             for (int t = 0; t < NT16; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[i][t][r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 16));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float mnew = fmaxf(ml[i], mx * LOG2E);
+            const float mnew = fmaxf(ml[i], row_max(mx) * LOG2E);
             const float alpha = __builtin_amdgcn_exp2f(ml[i] - mnew);     // 0 on the first chunk (-inf), 1 when the max stays
             ml[i] = mnew;
             f32x2_t sum2 = {0.f, 0.f};
             const f32x2_t l2 = {LOG2E, LOG2E}, nm = {-mnew, -mnew};
 #pragma unroll
-            for (int t = 0; t < NT16; ++t) {
-                f32x2_t a = f32x2_t{s[i][t][0], s[i][t][1]} * l2 + nm, e = f32x2_t{s[i][t][2], s[i][t][3]} * l2 + nm;
-                a.x = __builtin_amdgcn_exp2f(a.x); a.y = __builtin_amdgcn_exp2f(a.y);
-                e.x = __builtin_amdgcn_exp2f(e.x); e.y = __builtin_amdgcn_exp2f(e.y);
-                s[i][t][0] = a.x; s[i][t][1] = a.y; s[i][t][2] = e.x; s[i][t][3] = e.y;
-                sum2 += a;
-                sum2 += e;
-            }
+            for (int t = 0; t < NT16; ++t) tile_exp(s[i][t], l2, nm, sum2);
             l[i] = l[i] * alpha + (sum2.x + sum2.y);
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) o[i][dt] *= alpha;
@@ -308,14 +301,10 @@ __global__ __launch_bounds__(NW * 64, KEMR_ATTN_STREAM_OCC) void attention_strea
 #pragma unroll
             for (int i = 0; i < QT; ++i) {
                 if (!act(i) || !reach(i, k0 + u * 32)) continue;   // (out of reach: every key of the block is behind the tile, P = 0)
-                union { bf16x8 v; uint32_t w[4]; } pf;
-                pf.w[0] = pack_bf16x2(s[i][2 * u][0], s[i][2 * u][1]);
-                pf.w[1] = pack_bf16x2(s[i][2 * u][2], s[i][2 * u][3]);
-                pf.w[2] = pack_bf16x2(s[i][2 * u + 1][0], s[i][2 * u + 1][1]);
-                pf.w[3] = pack_bf16x2(s[i][2 * u + 1][2], s[i][2 * u + 1][3]);
+                const bf16x8 pf = tile_pack(s[i][2 * u], s[i][2 * u + 1]);
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt)
-                    o[i][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[u][dt], pf.v, o[i][dt], 0, 0, 0);
+                    o[i][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[u][dt], pf, o[i][dt], 0, 0, 0);
             }
         }
 
@@ -326,7 +315,7 @@ __global__ __launch_bounds__(NW * 64, KEMR_ATTN_STREAM_OCC) void attention_strea
     // o[i][dt][r] = O[query lrow of tile i][d = 16 dt + 4 lq + r]
 #pragma unroll
     for (int i = 0; i < QT; ++i) {
-        float sum = l[i];
+        float sum = l[i];                              // row_sum and tile_store, spelled out
         sum += __shfl_xor(sum, 16);
         sum += __shfl_xor(sum, 32);
         const int q = qb * QB + i * (NW * 16) + wid * 16 + lrow;

@@ -169,31 +169,7 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// ---- attention helpers (attention.hip, attention80.hip, attention_stream.hip, attention_ab.hip) ----------------------------
-// ds_read_b64_tr_b16: the transposed read that makes a V^T MFMA fragment out of the row-major V image
-__device__ __forceinline__ bf16x4 lds_read_tr16(const char* p) {
-    typedef __attribute__((ext_vector_type(4))) short s4;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)p);
-}
-// LDS stores of all lanes of a wave before any lane's loads (a wave working on its own: no workgroup barrier)
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// Which (head, image) a workgroup computes.  xbatch == 0: blockIdx.x = head, blockIdx.y = image.  xbatch = the batch size: the
-// grid is (heads, batch rounded up to 8) and the workgroups -- dealt to the eight XCDs round-robin by their linear id -- are
-// renumbered so that XCD x computes the images = x (mod 8), all heads of an image next to each other in time: the 128-byte
-// slices the sixteen heads take out of one token's 6 KB q|k|v row then come through ONE L2 at about the same time instead of
-// through eight (round 3: 155 -> 150 us at B = 255 x 16 heads, bit-identical results; the default, debug switch attn_xcd).
-__device__ __forceinline__ bool attn_item(int xbatch, int& h, int& b) {
-    h = blockIdx.x; b = blockIdx.y;
-    if (xbatch == 0) return true;
-    const int id = blockIdx.y * gridDim.x + blockIdx.x, j = id >> 3;
-    b = (j / (int)gridDim.x) * 8 + (id & 7);
-    h = j % (int)gridDim.x;
-    return b < xbatch;
-}
+// (the attention helpers -- LDS images, transposed reads, MFMA operand forms, softmax steps -- are attention_tile.h's)
 
 // ---- optional per-kernel-class event timing (api.hip); used by bench.py for the roofline line --------
 enum ProfClass : int { PROF_GEMM = 0, PROF_LAYERNORM = 1, PROF_ATTENTION = 2, PROF_OTHER = 3, PROF_SIM = 4, PROF_NCLASS = 5 };

@@ -16,7 +16,7 @@
 // that slot order.  Softmax in fp32 (v_exp_f32 on (s - m) log2 e; the argument's rounding, |s - m| 2^-23, is far inside the
 // 3 x 2^-16 |s| that the operand split leaves in a logit), P split like every other operand, O / l at the end, stored as the
 // A-side triple [hi | lo | hi] of the out-proj GEMM.  Same bits on every launch (no atomics, fixed order).
-#include "common.h"
+#include "attention_tile.h"
 
 namespace kemr {
 
@@ -63,7 +63,6 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restri
     }
 
     const float NEG_INF = -__builtin_inff();
-    const float LOG2E = 1.4426950408889634f;
     float m = NEG_INF, lsum = 0.f;
     f32x4 acc[4];
 #pragma unroll
@@ -125,6 +124,7 @@ __global__ __launch_bounds__(256) void attention_x3_kernel(const float* __restri
             s[j] = ok ? st[j >> 2][j & 3] : NEG_INF;
             cmax = fmaxf(cmax, s[j]);
         }
+        // attention_tile.h's row_max (and row_sum at the end), spelled out: the kernel is kept at the previous commit's code
         cmax = fmaxf(cmax, __shfl_xor(cmax, 16));
         cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
         const float m_new = fmaxf(m, cmax);
