@@ -419,7 +419,8 @@ int kemr_scores_dense(const void* q_panel_dev, int nq, const void* g_panel_dev, 
  * ahead of a finite ground truth).  The deep routes (kemr_select_topk, kemr_sim_topk_deep*) differ: they list every candidate with
  * an id >= 0, -inf ones behind the finite ones and NaN behind -inf.  kemr_topk_merge itself tells padding by the id (< 0), not by
  * the score: an entry (-inf, id >= 0) handed to it IS listed, behind the finite entries in id order; kemr_sim_topk never produces
- * one.  A NaN entry is not supported by kemr_topk_merge (where it lands depends on its position in the input). */
+ * one.  A NaN entry is not supported by kemr_topk_merge (where it lands depends on its position in the input).
+ * The rule itself, its two forms and where they differ: csrc/rank_order.h. */
 int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t ld, const int32_t* gt_idx_dev,
                     int32_t* ahead_dev, int k, float* top_scores_dev, int32_t* top_idx_dev, void* stream);
 

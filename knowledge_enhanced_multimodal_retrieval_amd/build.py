@@ -24,7 +24,7 @@ SOURCES = ["api.hip", "model.hip", "encode.hip", "gemm.hip", "gemm256.hip", "gem
 # GEMM, the long-interval K loop, the stamped instantiations: built only with `python -m ...build --ab-variants` (or
 # KEMR_BUILD_AB=1), never into the product library, whose kemr_debug_set refuses the values that would select them.
 AB_SOURCES = ["gemm256p.hip", "gemm256q.hip", "gemm256w.hip", "gemm256r.hip", "attention_ab.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "model.h"), os.path.join(CSRC, "nce_tile.h"), os.path.join(CSRC, "attention_tile.h"), os.path.join(CSRC, "attention_bwd_tile.h"), os.path.join(ROOT, "include", "kemr.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "model.h"), os.path.join(CSRC, "nce_tile.h"), os.path.join(CSRC, "attention_tile.h"), os.path.join(CSRC, "attention_bwd_tile.h"), os.path.join(CSRC, "rank_order.h"), os.path.join(ROOT, "include", "kemr.h")]
 ARCH = "gfx950"
 
 

@@ -4,15 +4,15 @@
 // Per slot (q, j), j < depth, with id c = list_idx[q, j]:
 //   c < 0 (the deep lists' padding): out = -inf;
 //   otherwise f = score_scale * s as ONE fp32 multiply (skipped at score_scale == 1: the input's own bits), then every entry of bonus
-//   row q whose column is c added one after the other in list order, each as ONE fp32 add (no contraction into an FMA): the rule of
-//   kemr_sim_topk_deep_fused (sim.hip, deep_bonus_kernel), so the dense route and this one give a pair the same bits.
+//   row q whose column is c added one after the other in list order, each as ONE fp32 add (bonus_run_add, rank_order.h: what
+//   kemr_sim_topk_deep_fused's deep_bonus_kernel calls too), so the dense route and this one give a pair the same bits.
 // The bonus row is a run of the CSR with ascending columns: a lower-bound binary search finds the first entry of column c, the
 // entries of that column follow it.  Rows of at most LF_STAGE entries are copied to LDS first (every slot of the list searches the
 // same row); longer rows -- a query with thousands of hits -- are searched where they lie.  The arithmetic is the same either way.
 //
 // Ground truth (optional): found = the row lists gt_idx[q]; gt_score = that slot's fused score (-inf where absent); ahead = the
-// slots with id >= 0 and id != gt whose (fused score, id) ranks before (gt_score, gt) by select.hip's key (score descending, -0.0
-// == +0.0, NaN behind -inf, then lower id) -- where the ground truth is absent every slot with id >= 0.  So where found, ahead + 1
+// slots with id >= 0 and id != gt whose (fused score, id) ranks before (gt_score, gt) by order_key (rank_order.h: score descending,
+// -0.0 == +0.0, NaN behind -inf, then lower id) -- where the ground truth is absent every slot with id >= 0.  So where found, ahead + 1
 // is the ground truth's position in kemr_select_topk(out, idx, k = depth).
 //
 // Layout: one 256-thread workgroup per query row, slot j belongs to thread j % 256 (at most 4 slots per thread at depth 1024, kept
@@ -20,6 +20,7 @@
 // kind that names the ground truth's slot.  Every output element has one owner, nothing is accumulated in memory, no atomics: the
 // result is a pure function of the input.  out may alias list_scores (a slot is read and written by the same thread).
 #include "common.h"
+#include "rank_order.h"
 
 namespace kemr {
 
@@ -28,30 +29,14 @@ constexpr int LF_SLOTS = KEMR_MAX_DEEP_K / LF_THREADS;      // slots per thread 
 constexpr int LF_STAGE = 2048;                              // bonus entries staged in LDS: 16 KiB
 static_assert(LF_SLOTS * LF_THREADS == KEMR_MAX_DEEP_K, "a thread owns depth / 256 slots, rounded up");
 
-typedef unsigned long long lf_u64;
-
-// select.hip's key: larger key = earlier in the list
-__device__ __forceinline__ lf_u64 list_fuse_key(float s, int id) {
-    uint32_t u = __float_as_uint(s);
-    uint32_t o;
-    if ((u & 0x7fffffffu) > 0x7f800000u) {
-        o = 0u;                                                   // NaN: behind -inf
-    } else {
-        if (u == 0x80000000u) u = 0u;                             // -0.0 ties with +0.0
-        o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    return ((lf_u64)o << 32) | (uint32_t)(0x7fffffff - id);
-}
-
-// f + the entries of column c in cols[0 .. len), ascending columns, one fp32 add each in list order
+// f + the entries of column c in cols[0 .. len), ascending columns (bonus_run_add's arithmetic)
 __device__ __forceinline__ float list_fuse_add(float f, int c, const int32_t* cols, const float* vals, int len) {
     int lo = 0, hi = len;
     while (lo < hi) {                                             // first entry with column >= c
         const int mid = (lo + hi) >> 1;
         if (cols[mid] < c) lo = mid + 1; else hi = mid;
     }
-    for (; lo < len && cols[lo] == c; ++lo) f = __fadd_rn(f, vals[lo]);
-    return f;
+    return bonus_run_add(f, c, cols, vals, lo, len);
 }
 
 __device__ __forceinline__ int lf_block_reduce(int v, bool take_min, int* s_red, int tid) {
@@ -144,11 +129,11 @@ __global__ __launch_bounds__(LF_THREADS) void list_fuse_kernel(const float* list
     }
     __syncthreads();
     const float g = here ? s_gt : -INFINITY;
-    const lf_u64 gkey = list_fuse_key(g, gt);
+    const u64 gkey = order_key(g, gt);
     int cnt = 0;
 #pragma unroll
     for (int s = 0; s < LF_SLOTS; ++s)
-        if (id[s] >= 0 && id[s] != gt) cnt += (!here || list_fuse_key(f[s], id[s]) > gkey) ? 1 : 0;
+        if (id[s] >= 0 && id[s] != gt) cnt += (!here || order_key(f[s], id[s]) > gkey) ? 1 : 0;
     const int total = lf_block_reduce(cnt, false, s_red, tid);
     if (tid == 0) {
         ahead[q] = total;

@@ -4,85 +4,34 @@
 // (metrics.py:165-185), evaluate_retrieval (eval/fusion.py:6-20) and the learned-fusion evaluator
 // (eval/evaluator_fusion.py:126).  One 256-thread workgroup per query row: 16-byte loads where the row is
 // aligned, per-thread `ahead` count + sorted top-KMAX list in registers, then a k-round selection over the
-// 256 lists through LDS.  Algorithmic bytes: 4 * N per row.  rank_dense_shard_kernel is the same pass over ONE SHARD's columns
-// (global ids, the ground truth's score handed in): what dist.sharded_ranks_dense runs on every rank of a sharded evaluation.
+// 256 lists through LDS (the order rule, the lists, the selection and the row reader: rank_order.h).  Algorithmic bytes: 4 * N per
+// row.  One kernel serves the whole matrix and ONE SHARD's columns (global ids, the ground truth's score handed in): what
+// dist.sharded_ranks_dense runs on every rank of a sharded evaluation.
 #include "common.h"
+#include "rank_order.h"
 
 namespace kemr {
 
-__device__ __forceinline__ bool rank_before(float sa, int ia, float sb, int ib) {
-    return sa > sb || (sa == sb && ia < ib);
-}
-
-template <int KMAX>
-__device__ __forceinline__ void list_insert(float (&s)[KMAX], int (&id)[KMAX], float v, int idx) {
-#pragma unroll
-    for (int i = KMAX - 1; i > 0; --i) {
-        const bool shift = v > s[i - 1];
-        const bool here = !shift && v > s[i];
-        s[i] = shift ? s[i - 1] : (here ? v : s[i]);
-        id[i] = shift ? id[i - 1] : (here ? idx : id[i]);
-    }
-    if (v > s[0]) { s[0] = v; id[0] = idx; }
-}
-
-// The k best of the 256 per-thread lists in LDS (ids < 0 = padding), by the first wave: k rounds of "best entry after the previous
-// pick", so the output is a pure function of the SET of listed entries -- how the columns were dealt to the threads does not matter.
-template <int KMAX>
-__device__ __forceinline__ void select_from_lists(const float* xs, const int* xi, int lane, int q, int k, float* __restrict__ top_s,
-                                                  int32_t* __restrict__ top_i) {
-    float ps = INFINITY;
-    int pi = -1;
-    bool done = false;
-    for (int o = 0; o < k; ++o) {
-        float bs = -INFINITY;
-        int bi = -1;
-        if (!done) {
-            for (int e = lane; e < 256 * KMAX; e += 64) {
-                const int ei = xi[e];
-                if (ei < 0) continue;
-                const float es = xs[e];
-                const bool after_prev = (o == 0) || rank_before(ps, pi, es, ei);
-                if (after_prev && (bi < 0 || rank_before(es, ei, bs, bi))) { bs = es; bi = ei; }
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const float os = __shfl_xor(bs, off);
-                const int oi = __shfl_xor(bi, off);
-                if (oi >= 0 && (bi < 0 || rank_before(os, oi, bs, bi))) { bs = os; bi = oi; }
-            }
-            if (bi < 0) done = true;
-        }
-        if (lane == 0) { top_s[(size_t)q * k + o] = bi >= 0 ? bs : -INFINITY; top_i[(size_t)q * k + o] = bi; }
-        ps = bs;
-        pi = bi;
-    }
-}
-
-template <int KMAX>
-__global__ __launch_bounds__(256) void rank_dense_kernel(const float* __restrict__ S, long long ld, int nq, int ng,
-                                                         const int32_t* __restrict__ gt_idx, int32_t* __restrict__ ahead,
-                                                         int k, float* __restrict__ top_s, int32_t* __restrict__ top_i) {
+// One row's pass over the candidates (v, id) that for_each_col hands to take() -- a thread's ids only increase: the `ahead` count
+// against the ground truth (sgt, gt), each thread's sorted top-KMAX list in registers, then the first wave's selection over the 256
+// lists in LDS (rank_order.h).
+template <int KMAX, class Cols>
+__device__ __forceinline__ void rank_row(int q, bool has_gt, int gt, float sgt, int32_t* __restrict__ ahead, int k,
+                                         float* __restrict__ top_s, int32_t* __restrict__ top_i, Cols&& for_each_col) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* xs = (float*)smem;                 // [256][KMAX]
     int* xi = (int*)(xs + 256 * KMAX);        // [256][KMAX]
     int* red = xi + 256 * KMAX;               // [4]
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const float* row = S + (size_t)q * ld;
-    const int gt = gt_idx ? gt_idx[q] : -1;
-    const bool has_gt = gt >= 0 && gt < ng;
-    const float sgt = has_gt ? row[gt] : 0.f;
+    const int tid = threadIdx.x, lane = tid & 63;
     float ls[KMAX];
     int li[KMAX];
 #pragma unroll
     for (int i = 0; i < KMAX; ++i) { ls[i] = -INFINITY; li[i] = -1; }
     int cnt = 0;
-    // a thread's candidate ids increase monotonically, so strict '>' keeps "lower id first" inside its list
-    for (int j = tid; j < ng; j += 256) {
-        const float v = row[j];
-        if (has_gt && j != gt) cnt += rank_before(v, j, sgt, gt) ? 1 : 0;
-        if (top_s && v > ls[KMAX - 1]) list_insert<KMAX>(ls, li, v, j);
-    }
+    for_each_col([&](float v, int id) {
+        if (has_gt && id != gt) cnt += ranks_before(v, id, sgt, gt) ? 1 : 0;
+        if (top_s && v > ls[KMAX - 1]) topk_insert<KMAX>(ls, li, v, id);
+    });
     if (ahead && has_gt) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
@@ -94,66 +43,28 @@ __global__ __launch_bounds__(256) void rank_dense_kernel(const float* __restrict
     }
     __syncthreads();
     if (ahead && tid == 0) ahead[q] = has_gt ? (red[0] + red[1]) + (red[2] + red[3]) : 0;
-    if (top_s && tid < 64) select_from_lists<KMAX>(xs, xi, lane, q, k, top_s, top_i);
+    if (top_s && tid < 64)
+        wave_select(lane, 256 * KMAX, q, k, top_s, top_i, [&](int e, float& es, int& ei) { ei = xi[e]; es = xs[e]; return ei >= 0; });
 }
 
-// rank_dense_kernel for ONE SHARD's columns of a matrix whose ground truth may live on another shard (dist.sharded_ranks_dense): the
-// candidate id of column j is id0 + j, the ground truth comes as (gt_score, GLOBAL gt id) instead of being read from the row, and every
+// The whole matrix (kemr_rank_dense: gt_score == nullptr, the ground truth is column gt_idx[q] of the row itself, one outside
+// 0 .. ng - 1 is none) and ONE SHARD's columns of a matrix whose ground truth may live on another shard (kemr_rank_dense_shard,
+// dist.sharded_ranks_dense: the candidate id of column j is id0 + j, the ground truth comes as (gt_score, GLOBAL gt id), and every
 // column whose id is not the ground truth's is counted when it ranks before that pair -- so the per-shard counts add up to the count
-// over the whole matrix.  Same single pass, lists and selection; the row is read with 16-byte loads from its first aligned element
-// (rows need no alignment: up to 3 leading and 3 trailing columns go one by one).  A thread's ids still only increase: head columns
-// (< first float4), then its float4s in order, then tail columns.
+// over the whole matrix).
 template <int KMAX>
-__global__ __launch_bounds__(256) void rank_dense_shard_kernel(const float* __restrict__ S, long long ld, int nq, int ng, int id0,
-                                                               const int32_t* __restrict__ gt_idx, const float* __restrict__ gt_score,
-                                                               int32_t* __restrict__ ahead, int k, float* __restrict__ top_s,
-                                                               int32_t* __restrict__ top_i) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* xs = (float*)smem;                 // [256][KMAX]
-    int* xi = (int*)(xs + 256 * KMAX);        // [256][KMAX]
-    int* red = xi + 256 * KMAX;               // [4]
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+__global__ __launch_bounds__(256) void rank_dense_kernel(const float* __restrict__ S, long long ld, int nq, int ng, int id0,
+                                                         const int32_t* __restrict__ gt_idx, const float* __restrict__ gt_score,
+                                                         int32_t* __restrict__ ahead, int k, float* __restrict__ top_s,
+                                                         int32_t* __restrict__ top_i) {
+    const int q = blockIdx.x;
     const float* row = S + (size_t)q * ld;
     const int gt = gt_idx ? gt_idx[q] : -1;
-    const bool has_gt = gt >= 0;
-    const float sgt = has_gt ? gt_score[q] : 0.f;
-    float ls[KMAX];
-    int li[KMAX];
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) { ls[i] = -INFINITY; li[i] = -1; }
-    int cnt = 0;
-    auto take = [&](float v, int j) {
-        const int id = id0 + j;               // id0 + ng <= INT32_MAX (checked on the host)
-        if (has_gt && id != gt) cnt += rank_before(v, id, sgt, gt) ? 1 : 0;
-        if (top_s && v > ls[KMAX - 1]) list_insert<KMAX>(ls, li, v, id);
-    };
-    const int mis = (int)(((uintptr_t)row >> 2) & 3);            // fp32 elements past a 16-byte boundary
-    const int head = min(ng, (4 - mis) & 3);
-    const int nvec = (ng - head) >> 2;
-    if (tid < head) take(row[tid], tid);
-    const float4* row4 = (const float4*)(row + head);
-    for (int v4 = tid; v4 < nvec; v4 += 256) {
-        const float4 v = row4[v4];
-        const int j = head + 4 * v4;
-        take(v.x, j);
-        take(v.y, j + 1);
-        take(v.z, j + 2);
-        take(v.w, j + 3);
-    }
-    const int tail = head + 4 * nvec;
-    if (tail + tid < ng) take(row[tail + tid], tail + tid);      // at most 3 columns
-    if (ahead && has_gt) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-        if (lane == 0) red[tid >> 6] = cnt;
-    }
-    if (top_s) {
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) { xs[tid * KMAX + i] = ls[i]; xi[tid * KMAX + i] = li[i]; }
-    }
-    __syncthreads();
-    if (ahead && tid == 0) ahead[q] = has_gt ? (red[0] + red[1]) + (red[2] + red[3]) : 0;
-    if (top_s && tid < 64) select_from_lists<KMAX>(xs, xi, lane, q, k, top_s, top_i);
+    const bool has_gt = gt >= 0 && (gt_score || gt < ng);
+    const float sgt = !has_gt ? 0.f : (gt_score ? gt_score[q] : row[gt]);
+    rank_row<KMAX>(q, has_gt, gt, sgt, ahead, k, top_s, top_i, [&](auto&& take) {
+        row_for_each(row, ng, threadIdx.x, 256, [&](float v, int j) { take(v, id0 + j); });      // id0 + ng <= INT32_MAX (checked on the host)
+    });
 }
 
 // Learned "linear" fusion head (reference fusion_model.py:25-48, eval mode): out = w1 . relu(W0 . [t2i, t2t] + b0) + b1
@@ -302,6 +213,20 @@ extern "C" int kemr_linear_head(const float* t2i_dev, const float* t2t_dev, int6
     return KEMR_OK;
 }
 
+// k <= 10 (and rank-only calls) keep 10-entry lists, k <= 32 the 32-entry ones, whose 64 KiB + 16 of LDS have to be asked for
+template <int KM>
+static int launch_rank_dense(const char* what, const float* S, int nq, int ng, int64_t ld, int id0, const int32_t* gt_idx,
+                             const float* gt_score, int32_t* ahead, int k, float* top_s, int32_t* top_i, void* stream) {
+    constexpr size_t smem = 256 * KM * 8 + 16;
+    auto kern = rank_dense_kernel<KM>;
+    if constexpr (smem > 64 * 1024)
+        KEMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(kern, dim3(nq), dim3(256), smem, (hipStream_t)stream, S, (long long)ld, nq, ng, id0, gt_idx, gt_score, ahead, k,
+                       top_s, top_i);
+    KEMR_CHECK_LAUNCH(what);
+    return KEMR_OK;
+}
+
 extern "C" int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t ld, const int32_t* gt_idx_dev,
                                int32_t* ahead_dev, int k, float* top_scores_dev, int32_t* top_idx_dev, void* stream) {
     if (nq == 0) return KEMR_OK;
@@ -309,22 +234,8 @@ extern "C" int kemr_rank_dense(const float* scores_dev, int nq, int ng, int64_t 
     if ((top_scores_dev != nullptr) != (top_idx_dev != nullptr)) KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense: top_scores/top_idx together");
     if (top_scores_dev && (k < 1 || k > 32)) KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense: k=%d not in 1..32", k);
     if ((gt_idx_dev != nullptr) != (ahead_dev != nullptr)) KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense: gt_idx and ahead together");
-    hipStream_t s = (hipStream_t)stream;
-    if (!top_scores_dev || k <= 10) {
-        constexpr int KM = 10;
-        const size_t smem = 256 * KM * 8 + 16;
-        hipLaunchKernelGGL(rank_dense_kernel<KM>, dim3(nq), dim3(256), smem, s, scores_dev, (long long)ld, nq, ng, gt_idx_dev,
-                           ahead_dev, k, top_scores_dev, top_idx_dev);
-    } else {
-        constexpr int KM = 32;
-        const size_t smem = 256 * KM * 8 + 16;
-        auto kern = rank_dense_kernel<KM>;
-        KEMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL(kern, dim3(nq), dim3(256), smem, s, scores_dev, (long long)ld, nq, ng, gt_idx_dev, ahead_dev, k,
-                           top_scores_dev, top_idx_dev);
-    }
-    KEMR_CHECK_LAUNCH("rank_dense_kernel");
-    return KEMR_OK;
+    return (!top_scores_dev || k <= 10 ? launch_rank_dense<10> : launch_rank_dense<32>)(
+        "rank_dense_kernel", scores_dev, nq, ng, ld, 0, gt_idx_dev, nullptr, ahead_dev, k, top_scores_dev, top_idx_dev, stream);
 }
 
 extern "C" int kemr_rank_dense_shard(const float* scores_dev, int nq, int ng, int64_t ld, int64_t id_offset,
@@ -340,20 +251,7 @@ extern "C" int kemr_rank_dense_shard(const float* scores_dev, int nq, int ng, in
     if (top_scores_dev && (k < 1 || k > 32)) KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense_shard: k=%d not in 1..32", k);
     if ((gt_idx_dev != nullptr) != (ahead_dev != nullptr) || (gt_idx_dev != nullptr) != (gt_score_dev != nullptr))
         KEMR_FAIL(KEMR_ERR_INVALID, "rank_dense_shard: gt_idx, gt_score and ahead together");
-    hipStream_t s = (hipStream_t)stream;
-    if (!top_scores_dev || k <= 10) {
-        constexpr int KM = 10;
-        const size_t smem = 256 * KM * 8 + 16;
-        hipLaunchKernelGGL(rank_dense_shard_kernel<KM>, dim3(nq), dim3(256), smem, s, scores_dev, (long long)ld, nq, ng, (int)id_offset,
-                           gt_idx_dev, gt_score_dev, ahead_dev, k, top_scores_dev, top_idx_dev);
-    } else {
-        constexpr int KM = 32;
-        const size_t smem = 256 * KM * 8 + 16;
-        auto kern = rank_dense_shard_kernel<KM>;
-        KEMR_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL(kern, dim3(nq), dim3(256), smem, s, scores_dev, (long long)ld, nq, ng, (int)id_offset, gt_idx_dev,
-                           gt_score_dev, ahead_dev, k, top_scores_dev, top_idx_dev);
-    }
-    KEMR_CHECK_LAUNCH("rank_dense_shard_kernel");
-    return KEMR_OK;
+    return (!top_scores_dev || k <= 10 ? launch_rank_dense<10> : launch_rank_dense<32>)(
+        "rank_dense_shard_kernel", scores_dev, nq, ng, ld, (int)id_offset, gt_idx_dev, gt_score_dev, ahead_dev, k, top_scores_dev,
+        top_idx_dev, stream);
 }

@@ -2,10 +2,9 @@
 // project's order rule (score descending, then lower id).  Serves kemr_select_topk and the second stage of kemr_sim_topk_deep
 // (sim.hip), where the register-resident lists of sim.hip / rank.hip (O(k) per insert, k registers per lane) end at k = 32.
 //
-// One 1024-thread workgroup per row.  Every entry becomes a 64-bit key
-//     ordered_u32(score) << 32 | (0x7fffffff - id)
-// (sign-flip mapping of the fp32 bits, -0.0 as +0.0, NaN below -inf), so with distinct ids all keys are distinct and "the k
-// largest keys" IS the order rule: ties at the k-th score need no special case.
+// One 1024-thread workgroup per row.  Every entry becomes its 64-bit order_key (rank_order.h: sign-flip mapping of the fp32 bits,
+// -0.0 as +0.0, NaN below -inf, then 0x7fffffff - id), so with distinct ids all keys are distinct and "the k largest keys" IS the
+// order rule: ties at the k-th score need no special case.
 //   1. radix select, 12 key bits per pass from the top: an integer LDS histogram of the entries that share the prefix found so
 //      far, a suffix scan over its 4 096 bins, the bin that holds the k-th largest key extends the prefix.  Integer sums do not
 //      depend on the order the atomics arrive in.  The passes stop as soon as the entries above the boundary bin plus the bin
@@ -19,6 +18,7 @@
 // Ids must be distinct within a row (they are candidate ids).  Repeated (score, id) pairs stay memory-safe -- the gather stops
 // at SEL_CAP entries -- but which of the copies is returned is then unspecified.
 #include "common.h"
+#include "rank_order.h"
 
 namespace kemr {
 
@@ -29,27 +29,17 @@ constexpr int SEL_CAP = 4096;                  // gathered entries: < KEMR_MAX_D
 static_assert(SEL_BINS == 4 * SEL_THREADS, "the suffix scan gives every thread four bins");
 static_assert(SEL_CAP >= 2 * KEMR_MAX_DEEP_K && (SEL_CAP & (SEL_CAP - 1)) == 0, "SEL_CAP: a power of two with room for k winners");
 
-typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 select_key(float s, int id) {
-    uint32_t u = __float_as_uint(s);
-    uint32_t o;
-    if ((u & 0x7fffffffu) > 0x7f800000u) {
-        o = 0u;                                                   // NaN: behind -inf (0x007fffff)
-    } else {
-        if (u == 0x80000000u) u = 0u;                             // -0.0 ties with +0.0
-        o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    return ((u64)o << 32) | (uint32_t)(0x7fffffff - id);
-}
-
-// f(key, column) for every valid entry of the row (id >= 0), each column < n exactly once, spread over the workgroup
+// f(key, column) for every valid entry of the row (id >= 0), each column < n exactly once, spread over the workgroup: the head /
+// 16-byte vectors / tail walk of row_for_each (rank_order.h) SPELLED OUT, with the ids read 16 bytes at a time next to the scores.
+// Built on row_for_each the kernels ran new instructions (same registers, LDS and occupancy) and kemr_sim_topk_deep_fused at
+// 1 024 x 43 000, k = 100 took +0.9 % where two copies of the previous library differed by 0.05 %
+// (profiles/rank_order_refactor_ab.json); this form compiles to the previous instructions.
 template <class F>
 __device__ __forceinline__ void select_for_each(const float* __restrict__ row, const int32_t* __restrict__ ids, int n,
                                                 long long id_offset, int tid, F&& f) {
     auto one = [&](int c, float s) {
         const int id = ids ? ids[c] : (int)(id_offset + c);
-        if (id >= 0) f(select_key(s, id), c);
+        if (id >= 0) f(order_key(s, id), c);
     };
     int head = (int)((4u - (uint32_t)(((uintptr_t)row >> 2) & 3u)) & 3u);          // columns in front of the first 16-byte boundary
     head = head < n ? head : n;
@@ -63,10 +53,10 @@ __device__ __forceinline__ void select_for_each(const float* __restrict__ row, c
         const int c = head + v * 4;
         if (ids16) {
             const int4 i4 = *(const int4*)(ids + c);
-            if (i4.x >= 0) f(select_key(s4.x, i4.x), c);
-            if (i4.y >= 0) f(select_key(s4.y, i4.y), c + 1);
-            if (i4.z >= 0) f(select_key(s4.z, i4.z), c + 2);
-            if (i4.w >= 0) f(select_key(s4.w, i4.w), c + 3);
+            if (i4.x >= 0) f(order_key(s4.x, i4.x), c);
+            if (i4.y >= 0) f(order_key(s4.y, i4.y), c + 1);
+            if (i4.z >= 0) f(order_key(s4.z, i4.z), c + 2);
+            if (i4.w >= 0) f(order_key(s4.w, i4.w), c + 3);
         } else {
             one(c, s4.x); one(c + 1, s4.y); one(c + 2, s4.z); one(c + 3, s4.w);
         }
@@ -76,8 +66,8 @@ __device__ __forceinline__ void select_for_each(const float* __restrict__ row, c
 
 // COUNT (kemr_sim_topk_deep_fused with a ground truth; ids are id_offset + column): the first sweep -- the one pass that sees every
 // entry of the row -- also counts the entries that rank before (gt_score[row], gt_idx[row]) and adds the sum to ahead[row].  On the
-// keys that is `key > key(gt_score, gt_idx)`: the key order IS sim.hip's ranks_before (score descending, -0.0 == +0.0, then lower
-// id; a NaN entry ranks before nothing finite), except for a NaN gt_score, before which ranks_before puts nothing: no count then.
+// keys that is `key > key(gt_score, gt_idx)`: the key order IS ranks_before except for a NaN gt_score, before which ranks_before
+// puts nothing (rank_order.h: where the two forms differ): no count then.
 // The entry with the ground truth's own id is left out whatever its score.  Integer sums: wave shuffles, one LDS atomic per wave.
 template <bool COUNT>
 __global__ __launch_bounds__(SEL_THREADS) void select_topk_kernel(const float* __restrict__ S, const int32_t* __restrict__ I, int n,
@@ -107,7 +97,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_topk_kernel(const float* _
     u64 gt_key = ~0ull;       // COUNT: the ground truth's key; all ones (above every key) = count nothing
     if constexpr (COUNT) {
         const float sg = gt_score[blockIdx.x];
-        if (sg == sg) gt_key = select_key(sg, gt_idx[blockIdx.x]);
+        if (sg == sg) gt_key = order_key(sg, gt_idx[blockIdx.x]);
         if (tid == 0) s_ahead = 0;
     }
     for (;;) {

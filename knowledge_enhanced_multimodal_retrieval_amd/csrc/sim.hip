@@ -12,8 +12,10 @@
 //      count candidates ranked ahead of the ground truth, and keep a sorted top-KMAX list in registers
 //      (threshold test first, the insertion runs only on a hit).
 // Per (query, gallery chunk) partial lists go to the workspace and are merged by topk_merge_kernel, the same
-// kernel that merges per-GPU shards.  Order rule everywhere: higher score first, then lower candidate id.
+// kernel that merges per-GPU shards.  Order rule everywhere: higher score first, then lower candidate id (rank_order.h: the rule,
+// the register lists, the selection rounds and the bonus add that this file shares with rank.hip, select.hip and listfuse.hip).
 #include "common.h"
+#include "rank_order.h"
 #include "../../include/kemr_debug.h"
 #include <cmath>
 #include <vector>
@@ -88,22 +90,6 @@ struct SimParams {
     int nchunks, tiles_per_chunk, g_tiles;
     const int32_t* run_if;   // non-null: the launch is the exact fallback of the candidate-list path and exits unless *run_if != 0
 };
-
-template <int KMAX>
-__device__ __forceinline__ void topk_insert(float (&s)[KMAX], int (&id)[KMAX], float v, int idx) {
-#pragma unroll
-    for (int i = KMAX - 1; i > 0; --i) {
-        const bool shift = v > s[i - 1];
-        const bool here = !shift && v > s[i];
-        s[i] = shift ? s[i - 1] : (here ? v : s[i]);
-        id[i] = shift ? id[i - 1] : (here ? idx : id[i]);
-    }
-    if (v > s[0]) { s[0] = v; id[0] = idx; }
-}
-
-__device__ __forceinline__ bool ranks_before(float sa, int ia, float sb, int ib) {
-    return sa > sb || (sa == sb && ia < ib);
-}
 
 template <int KMAX, bool DENSE>
 __global__ __launch_bounds__(256) void sim_kernel(const SimParams p) {
@@ -233,6 +219,9 @@ __global__ __launch_bounds__(256) void sim_kernel(const SimParams p) {
                     float sc = ve[e];
                     if (gid >= next_col) {                    // rare: this candidate may carry a SPARQL bonus
                         while (bcur < bend && p.bcol[bcur] < gid) ++bcur;
+                        // bonus_run_add (rank_order.h) SPELLED OUT: called here, the scanner ran new instructions (same registers and
+                        // occupancy) and kemr_sim_topk at 43 000 x 43 000 took +0.5 % where two copies of the previous library differed
+                        // by 0.02 % (profiles/rank_order_refactor_ab.json).  One fp32 add per entry, in list order: the same bits.
                         while (bcur < bend && p.bcol[bcur] == gid) { sc += p.bval[bcur]; ++bcur; }
                         next_col = bcur < bend ? p.bcol[bcur] : INT_MAX;
                     }
@@ -278,7 +267,7 @@ __global__ __launch_bounds__(256) void sim_kernel(const SimParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------ list merge
-// one wave per query; k rounds of "best element strictly after the previous pick" over nlists*k entries
+// one wave per query over nlists*k entries (wave_select, rank_order.h)
 __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict__ in_s, const int32_t* __restrict__ in_i,
                                                          int nq, int total, int k, float* __restrict__ out_s,
                                                          int32_t* __restrict__ out_i, const int32_t* __restrict__ run_if) {
@@ -288,32 +277,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     if (q >= nq) return;
     const float* s = in_s + (size_t)q * total;
     const int32_t* ix = in_i + (size_t)q * total;
-    float ps = INFINITY;
-    int pi = -1;
-    for (int o = 0; o < k; ++o) {
-        float bs = -INFINITY;
-        int bi = -1;
-        for (int e = lane; e < total; e += 64) {
-            const float es = s[e];
-            const int ei = ix[e];
-            if (ei < 0) continue;
-            const bool after_prev = (o == 0) || ranks_before(ps, pi, es, ei);
-            if (after_prev && (bi < 0 || ranks_before(es, ei, bs, bi))) { bs = es; bi = ei; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float os = __shfl_xor(bs, off);
-            const int oi = __shfl_xor(bi, off);
-            if (oi >= 0 && (bi < 0 || ranks_before(os, oi, bs, bi))) { bs = os; bi = oi; }
-        }
-        if (lane == 0) { out_s[(size_t)q * k + o] = bi >= 0 ? bs : -INFINITY; out_i[(size_t)q * k + o] = bi; }
-        if (bi < 0) {                                     // exhausted: pad the rest
-            for (int r = o + 1 + lane; r < k; r += 64) { out_s[(size_t)q * k + r] = -INFINITY; out_i[(size_t)q * k + r] = -1; }
-            break;
-        }
-        ps = bs;
-        pi = bi;
-    }
+    wave_select(lane, total, q, k, out_s, out_i, [&](int e, float& es, int& ei) { es = s[e]; ei = ix[e]; return ei >= 0; });
 }
 
 // Few queries, many lists (the online path: 1 query x 336 gallery chunks x k): one 256-thread workgroup per query keeps
@@ -336,6 +300,9 @@ __global__ __launch_bounds__(256) void topk_merge_block_kernel(const float* __re
         es[j] = e < total ? s[e] : 0.f;
         ei[j] = e < total ? ix[e] : -1;
     }
+    // The rounds of wave_select (rank_order.h) SPELLED OUT, with the four waves' picks meeting in LDS: built from the header's pieces
+    // this kernel ran new instructions (same registers, LDS and occupancy) and kemr_topk_merge at 1 x 336 x 10 took +0.2 % where two
+    // copies of the previous library differed by 0.02 % (profiles/rank_order_refactor_ab.json); this form compiles to the previous ones.
     float ps = INFINITY;
     int pi = -1;
     for (int o = 0; o < k; ++o) {
@@ -542,6 +509,9 @@ __global__ __launch_bounds__(256) void simk_select_kernel(const float* __restric
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    // wave_select (rank_order.h) SPELLED OUT over the wave's LDS entries: called here, the kernel ran new instructions (same registers,
+    // LDS and occupancy) and kemr_sim_topk at 43 000 x 43 000 took +0.09 % where two copies of the previous library differed by 0.08 %
+    // (profiles/rank_order_refactor_ab.json; a first run: +0.08 % against 0.01 %); this form compiles to the previous instructions.
     float ps = INFINITY;
     int pi = -1;
     for (int o = 0; o < k; ++o) {
@@ -611,11 +581,11 @@ __global__ __launch_bounds__(64) void bonus_rank_fixup_kernel(const bf16_t* __re
                 const long long lc = (long long)c - goff;
                 if (lc < 0 || lc >= ng || c == gt) continue;
                 if (ee > e0 && bcol[ee - 1] == c) continue;              // not the first entry of this candidate's run
-                float fused = acc[r];
-                for (int t = ee; t < e1 && bcol[t] == c; ++t) fused += bval[t];
                 const float raw = acc[r];
-                const int before = (raw > g || (raw == g && c < gt)) ? 1 : 0;
-                const int after = (fused > g || (fused == g && c < gt)) ? 1 : 0;
+                int t = ee;
+                const float fused = bonus_run_add(raw, c, bcol, bval, t, e1);
+                const int before = ranks_before(raw, c, g, gt) ? 1 : 0;
+                const int after = ranks_before(fused, c, g, gt) ? 1 : 0;
                 delta += after - before;
             }
         }
@@ -853,9 +823,8 @@ __global__ __launch_bounds__(256) void deep_bonus_kernel(float* __restrict__ blo
         if (e > e0 && bcol[e - 1] == c) continue;                // inside a run: its first entry's lane adds it
         const long long loc = (long long)c - goff;
         if (loc < 0 || loc >= ng) continue;
-        float sc = row[loc];
-        for (int t = e; t < e1 && bcol[t] == c; ++t) sc += bval[t];
-        row[loc] = sc;
+        int t = e;
+        row[loc] = bonus_run_add(row[loc], c, bcol, bval, t, e1);
     }
 }
 

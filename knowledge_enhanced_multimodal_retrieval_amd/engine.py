@@ -617,6 +617,26 @@ def sim_topk(qp: Panel, gp: Panel, k: int, gallery_offset: int = 0,
     return top_s, top_i
 
 
+def _f32_rows(scores: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """A [nq, n] score matrix as the kernels read it: fp32, unit column stride, and the row stride ``ld`` of the ABI (row-strided views
+    are read in place)."""
+    scores = scores.to(torch.float32)
+    if scores.stride(-1) != 1 or (scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]):
+        scores = scores.contiguous()
+    nq, n = scores.shape
+    return scores, (scores.stride(0) if nq > 1 else max(n, 1))
+
+
+def _rank_outputs(nq: int, ng: int, k: int, with_ahead: bool, dev) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(ahead, top scores, top ids) of the dense rankers: zeros, and lists that are padding already where there is no column."""
+    ahead = torch.zeros(nq, dtype=torch.int32, device=dev) if with_ahead else None
+    if k <= 0:
+        return ahead, None, None
+    if ng == 0:
+        return ahead, torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev), torch.full((nq, k), -1, dtype=torch.int32, device=dev)
+    return ahead, torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int32, device=dev)
+
+
 def topk_merge(scores: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """[nq, nlists, k] candidate lists -> [nq, k] (score desc, id asc)."""
     L = _lib.lib()
@@ -645,12 +665,9 @@ def select_topk(scores: torch.Tensor, k: int, idx: Optional[torch.Tensor] = None
     _require_cuda(scores, "score matrix")
     if scores.dim() != 2:
         raise RuntimeError("select_topk: expected a [nq, n] score matrix")
-    scores = scores.to(torch.float32)
-    if scores.stride(-1) != 1 or (scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]):
-        scores = scores.contiguous()
+    scores, ld = _f32_rows(scores)
     nq, n = scores.shape
     dev = scores.device
-    ld = scores.stride(0) if nq > 1 else max(n, 1)
     if idx is not None:
         if tuple(idx.shape) != (nq, n):
             raise RuntimeError("select_topk: idx must have the shape of scores")
@@ -853,21 +870,11 @@ def rank_dense(scores: torch.Tensor, gt_idx: Optional[torch.Tensor] = None, k: i
     (an empty gallery: padding only, ahead = 0); a candidate whose score is -inf or NaN is never listed (include/kemr.h)."""
     L = _lib.lib()
     _require_cuda(scores, "score matrix")
-    scores = scores.to(torch.float32)
-    if scores.stride(-1) != 1 or (scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]):
-        scores = scores.contiguous()
+    scores, ld = _f32_rows(scores)
     nq, ng = scores.shape
     dev = scores.device
-    ld = scores.stride(0) if nq > 1 else max(ng, 1)
-    ahead = gt = top_s = top_i = None
-    if gt_idx is not None:
-        gt = gt_idx.to(device=dev, dtype=torch.int32).contiguous()
-        ahead = torch.zeros(nq, dtype=torch.int32, device=dev)
-    if k > 0:
-        top_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev) if ng == 0 else \
-            torch.empty((nq, k), dtype=torch.float32, device=dev)
-        top_i = torch.full((nq, k), -1, dtype=torch.int32, device=dev) if ng == 0 else \
-            torch.empty((nq, k), dtype=torch.int32, device=dev)
+    gt = None if gt_idx is None else gt_idx.to(device=dev, dtype=torch.int32).contiguous()
+    ahead, top_s, top_i = _rank_outputs(nq, ng, k, gt is not None, dev)
     if nq and ng:
         with torch.cuda.device(dev):
             _lib.check(L.kemr_rank_dense(C.c_void_p(scores.data_ptr()), nq, ng, ld, _opt_ptr(gt), _opt_ptr(ahead),
@@ -885,26 +892,18 @@ def rank_dense_shard(scores: torch.Tensor, id_offset: int = 0, gt_idx: Optional[
     (no columns) gives ahead = 0 and padding."""
     L = _lib.lib()
     _require_cuda(scores, "score matrix")
-    scores = scores.to(torch.float32)
-    if scores.stride(-1) != 1 or (scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]):
-        scores = scores.contiguous()
+    scores, ld = _f32_rows(scores)
     nq, ng = scores.shape
     dev = scores.device
-    ld = scores.stride(0) if nq > 1 else max(ng, 1)
     if (gt_idx is None) != (gt_score is None):
         raise RuntimeError("rank_dense_shard: gt_idx and gt_score together")
-    ahead = gt = sgt = top_s = top_i = None
+    gt = sgt = None
     if gt_idx is not None:
         gt = gt_idx.to(device=dev, dtype=torch.int32).contiguous()
         sgt = gt_score.to(device=dev, dtype=torch.float32).contiguous()
         if gt.numel() != nq or sgt.numel() != nq:
             raise RuntimeError("rank_dense_shard: gt_idx and gt_score must have one entry per query")
-        ahead = torch.zeros(nq, dtype=torch.int32, device=dev)
-    if k > 0:
-        top_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev) if ng == 0 else \
-            torch.empty((nq, k), dtype=torch.float32, device=dev)
-        top_i = torch.full((nq, k), -1, dtype=torch.int32, device=dev) if ng == 0 else \
-            torch.empty((nq, k), dtype=torch.int32, device=dev)
+    ahead, top_s, top_i = _rank_outputs(nq, ng, k, gt is not None, dev)
     if nq and ng:
         with torch.cuda.device(dev):
             _lib.check(L.kemr_rank_dense_shard(C.c_void_p(scores.data_ptr()), nq, ng, ld, int(id_offset), _opt_ptr(gt), _opt_ptr(sgt),
