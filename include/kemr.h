@@ -83,7 +83,10 @@ extern "C" {
  *    keeps its signature, refusals, messages and bits.
  *    Still 4: kemr_op_attention_packed (the causal forward over items of different lengths packed one behind the other, what the text
  *    encoders run inside themselves) and kemr_op_attention_backward_packed (its backward, and the non-causal one, for items of up to
- *    KEMR_MAX_TEXT_CTX rows) are additions; the dense ops keep their signatures, refusals, messages and bits. */
+ *    KEMR_MAX_TEXT_CTX rows) are additions; the dense ops keep their signatures, refusals, messages and bits.
+ *    Still 4: kemr_attention_backward_hd_workspace_bytes and kemr_op_attention_backward_hd (the attention backward with the head dim as
+ *    an argument: heads of 80, non-causal, streaming; at 64 the existing ops) are additions; kemr_op_attention_backward,
+ *    kemr_op_attention_backward_long and kemr_op_attention_hd keep their signatures, refusals, messages and bits. */
 #define KEMR_ABI_VERSION 4
 
 typedef enum kemr_status {
@@ -772,6 +775,31 @@ int kemr_op_attention_backward_packed(const void* qkv_dev, const void* dout_dev,
 size_t kemr_attention_backward_long_workspace_bytes(int batch, int t, int width);
 int kemr_op_attention_backward_long(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width,
                                     void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The attention backward with the head dim as an argument: the backward of kemr_op_attention_hd.
+ * head_dim == 80 (the vision tower of ViT-H-14): qkv bf16 [batch*t, 3*width] exactly as kemr_op_attention_hd reads it (q | k | v, q
+ * pre-scaled by 1/sqrt(80)), dout bf16 [batch*t, width] -> dqkv bf16 [batch*t, 3*width], the gradient with respect to the three planes
+ * AS GIVEN: the caller owns the 1/sqrt(80) of q.  width % 80 == 0, causal == 0 (no tower has causal heads of 80), 1 <= t <=
+ * KEMR_MAX_VISION_TOKENS (1025; longer than the 288 the head-dim-80 forward takes), batch >= 0 (batch == 0 launches nothing;
+ * batch * width / 80 * ceil(t / 64) <= 2^31 - 1, the grid); workspace_bytes >= kemr_attention_backward_hd_workspace_bytes(batch, t,
+ * width, 80) = batch * (width / 80) * t * 3 * sizeof(float), the workspace 4-byte aligned (it may be NULL when the size is 0).  Anything
+ * else -- a NULL pointer, a head_dim other than 64 or 80, causal = 1 at 80, a causal that is neither 0 nor 1 -- is KEMR_ERR_INVALID
+ * with a message that starts with "op_attention_backward_hd:" and names the argument, refused on the host before any HIP call with dqkv
+ * untouched.  The kernels are the head-dim-80 forms of kemr_op_attention_backward_long's (csrc/attention_bwd80.hip): streaming at every
+ * t -- a head's four images do not fit a CU's LDS at 257 tokens --, a query-owned kernel (K and V stream twice; dq and the statistics
+ * max * log2 e, 1 / sum and D of every query row of every head, fp32 [batch * heads * t, 3], into the workspace) and a key-owned kernel
+ * (Q, dO and the statistics stream once; dk and dv).  The forward saves nothing.  P and dS are rounded to bf16 as MFMA operands, the
+ * outputs to bf16 at the store, D comes from the unrounded fp32 P, nothing else is below fp32.  No atomics: every element of dqkv and of
+ * the workspace has one owner and one summation order, so the same inputs give the same bits on every launch.  Exactly batch * t rows
+ * of dqkv are written and the workspace only inside its stated size; nothing beyond column 79 of a head, and nothing outside an item's
+ * own rows of qkv and dout, is read for its rows of dqkv.  Every launch goes to `stream`.
+ * head_dim == 64: the call IS kemr_op_attention_backward (causal, or t <= KEMR_MAX_TEXT_CTX: no workspace, workspace_dev and
+ * workspace_bytes are ignored) or kemr_op_attention_backward_long (non-causal, longer: its workspace), with that op's bits, refusals
+ * and messages; kemr_attention_backward_hd_workspace_bytes(.., 64) is 0 up to KEMR_MAX_TEXT_CTX rows and
+ * kemr_attention_backward_long_workspace_bytes above.  The size function is a function of its four arguments only and returns 0 at
+ * batch == 0 and for arguments the op refuses. */
+size_t kemr_attention_backward_hd_workspace_bytes(int batch, int t, int width, int head_dim);
+int kemr_op_attention_backward_hd(const void* qkv_dev, const void* dout_dev, void* dqkv_dev, int batch, int t, int width,
+                                  int head_dim, int causal, void* workspace_dev, size_t workspace_bytes, void* stream);
 /* The backward of kemr_op_layernorm. x fp32 [rows, width] exactly as the forward read it, gamma fp32 [width], dy [rows, width] = the
  * gradient of its output in dy_dtype (KEMR_BF16 where the forward wrote bf16, KEMR_F32 where it wrote fp32) -> dx fp32 [rows, width],
  * dgamma and dbeta fp32 [width].  The forward saves nothing: mean and rstd are recomputed in fp32 exactly as the forward does (two

@@ -128,6 +128,8 @@ SIGNATURES = {
     "kemr_op_attention_backward_packed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "kemr_attention_backward_long_workspace_bytes": (_sz, [_i, _i, _i]),
     "kemr_op_attention_backward_long": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "kemr_attention_backward_hd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "kemr_op_attention_backward_hd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "kemr_layernorm_backward_workspace_bytes": (_sz, [_i, _i]),
     "kemr_op_layernorm_backward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "kemr_op_act_forward": (_i, [_vp, _vp, C.c_longlong, _i, _vp]),

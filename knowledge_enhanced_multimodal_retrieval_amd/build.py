@@ -18,7 +18,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 ROOT = os.path.dirname(PKG_DIR)
 LIB_PATH = os.path.join(PKG_DIR, "libkemr.so")
-SOURCES = ["api.hip", "model.hip", "encode.hip", "gemm.hip", "gemm256.hip", "gemm256u.hip", "gemm_skinny.hip", "layernorm.hip", "attention.hip", "attention_bwd.hip", "attention_bwd_stream.hip", "attention_stream.hip", "attention80.hip", "fp32x3.hip", "embed.hip", "sim.hip", "select.hip", "rank.hip", "rerank.hip", "listfuse.hip", "infonce.hip", "pairhead.hip", "preprocess.hip", "train_ops.hip"]
+SOURCES = ["api.hip", "model.hip", "encode.hip", "gemm.hip", "gemm256.hip", "gemm256u.hip", "gemm_skinny.hip", "layernorm.hip", "attention.hip", "attention_bwd.hip", "attention_bwd_stream.hip", "attention_bwd80.hip", "attention_stream.hip", "attention80.hip", "fp32x3.hip", "embed.hip", "sim.hip", "select.hip", "rank.hip", "rerank.hip", "listfuse.hip", "infonce.hip", "pairhead.hip", "preprocess.hip", "train_ops.hip"]
 # Experiment kernels kept for A/B timing from tools/ only -- earlier persistent-GEMM generations (gemm_variant 4, 5, 6, 9), the
 # attention variants of round 3 (attn_v 1..4), and, inside the product sources behind -DKEMR_AB_VARIANTS, the staggered 256x256
 # GEMM, the long-interval K loop, the stamped instantiations: built only with `python -m ...build --ab-variants` (or

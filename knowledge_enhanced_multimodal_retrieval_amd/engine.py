@@ -1092,13 +1092,15 @@ def op_attention(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool
 ATTENTION_BACKWARD_LDS_T = 288     # KEMR_MAX_TEXT_CTX: up to here kemr_op_attention_backward (a head in LDS), beyond it the streaming op
 
 
-def attention_backward(qkv: torch.Tensor, dout: torch.Tensor, batch: int, t: int, width: int, causal: bool) -> torch.Tensor:
+def attention_backward(qkv: torch.Tensor, dout: torch.Tensor, batch: int, t: int, width: int, causal: bool, head_dim: int = 64) -> torch.Tensor:
     """The backward of op_attention (heads of 64): qkv bf16 [batch * t, 3 width] as the forward read it (q pre-scaled by 1/8),
     dout bf16 [batch * t, width] -> dqkv bf16 [batch * t, 3 width], the gradient with respect to the planes as given (the caller owns
     the 1/8 of q).  Recomputes the probabilities from qkv; the same bits on every launch.  Routed by shape: t <= 288, causal or not, is
     ``kemr_op_attention_backward`` (no workspace); non-causal 289 <= t <= 1025 is ``kemr_op_attention_backward_long`` (streaming, with
     a workspace of three fp32 per query row and head, a torch allocation on qkv's device and the current stream); causal t > 288 is
-    refused by the first op, as the forward refuses it."""
+    refused by the first op, as the forward refuses it.  ``head_dim=80`` (q pre-scaled by 1/sqrt(80), non-causal, t <= 1025) is
+    ``kemr_op_attention_backward_hd``, streaming at every length with the same kind of workspace; any other head dim, and
+    ``causal=True`` at 80, are refused with that op's message."""
     _require_cuda(qkv, "attention_backward: qkv")
     _require_cuda(dout, "attention_backward: dout")
     if qkv.dtype != torch.bfloat16 or dout.dtype != torch.bfloat16 or not qkv.is_contiguous() or not dout.is_contiguous():
@@ -1109,7 +1111,13 @@ def attention_backward(qkv: torch.Tensor, dout: torch.Tensor, batch: int, t: int
     dqkv = torch.empty_like(qkv)
     L = _lib.lib()
     with torch.cuda.device(qkv.device):
-        if causal or t <= ATTENTION_BACKWARD_LDS_T:
+        if head_dim != 64:
+            need = int(L.kemr_attention_backward_hd_workspace_bytes(batch, t, width, int(head_dim)))
+            ws = torch.empty(max(need, 4), dtype=torch.uint8, device=qkv.device)
+            _lib.check(L.kemr_op_attention_backward_hd(C.c_void_p(qkv.data_ptr()), C.c_void_p(dout.data_ptr()), C.c_void_p(dqkv.data_ptr()),
+                                                       batch, t, width, int(head_dim), 1 if causal else 0, C.c_void_p(ws.data_ptr()), need,
+                                                       C.c_void_p(_stream_ptr(qkv.device))), "op_attention_backward_hd")
+        elif causal or t <= ATTENTION_BACKWARD_LDS_T:
             _lib.check(L.kemr_op_attention_backward(C.c_void_p(qkv.data_ptr()), C.c_void_p(dout.data_ptr()), C.c_void_p(dqkv.data_ptr()),
                                                     batch, t, width, 1 if causal else 0, C.c_void_p(_stream_ptr(qkv.device))),
                        "op_attention_backward")

@@ -37,11 +37,15 @@ bf16 autocast only.
 convolution whose stride is its kernel size: unfold + linear), class token, positional embedding, ``ln_pre``, the same pre-LN blocks
 with NON-causal attention (``kemr_op_attention`` / ``kemr_op_attention_backward`` at ``causal = 0``), then the class-token row -- what
 ``kemr_encode_image_pooled`` returns -- and ``visual.ln_post``, ``visual.proj`` and the L2 normalisation through ``finetune.project``.
-Heads of 64: ViT-H-14's heads of 80 are refused, like the SigLIP and BERT families.  ``max_tokens`` bounds the sequence: the default,
+``head_dims`` names the head dims the tower may have: the default, ``(64,)``, refuses ViT-H-14's heads of 80 (like the SigLIP and BERT
+families); ``head_dims=HEAD_DIMS`` (64 and 80) opts in.  At 80 ``_OpAttention`` scales q by 80 ** -0.5 in fp32 and rounds it to bf16
+once (the 1/8 of heads of 64 is exact), the forward is ``kemr_op_attention_hd``, the backward the streaming
+``kemr_op_attention_backward_hd`` (csrc/attention_bwd80.hip) and the returned dq is the op's times 80 ** -0.5 in fp32; such a tower has
+at most 288 tokens, where the head-dim-80 forward ends, whatever ``max_tokens`` says.  ``max_tokens`` bounds the sequence: the default,
 ``MAX_T`` = 288, is the range of ``kemr_op_attention_backward`` and refuses the 577 tokens of ViT-L/14@336px; ``max_tokens=MAX_T_LONG``
 (1025, the forward's range) opts in to the long towers, whose attention backward is the streaming ``kemr_op_attention_backward_long``
 (csrc/attention_bwd_stream.hip; ``engine.attention_backward`` routes by length, so towers of up to 288 tokens keep their kernel and bits).
-``EndToEndTuning`` passes ``MAX_T_LONG``.
+``EndToEndTuning`` passes ``MAX_T_LONG`` and ``HEAD_DIMS``.
 
 ``EndToEndTuning`` = ``ProjectionHeads`` + ``VisionTower`` + ``TextTower``: what ``--end_to_end`` trains, every parameter of the model
 but ``logit_scale`` (the loss uses ``--temperature``, as the reference's does).  ``EndToEndTrainer`` is ``HeadTrainer``'s loop over
@@ -67,28 +71,41 @@ from .finetune import HeadTrainer, ProjectionHeads, project
 
 MAX_T = 288          # KEMR_MAX_TEXT_CTX: the range of kemr_op_attention (causal) and of its backward
 MAX_T_LONG = 1025    # KEMR_MAX_VISION_TOKENS: the range of kemr_op_attention (non-causal) and of kemr_op_attention_backward_long
+HEAD_DIMS = (64, 80)  # the head dims the attention ops serve in both directions; 80: non-causal only (ViT-H-14's vision tower)
+MAX_T_HD80 = 288     # the range of kemr_op_attention_hd at head dim 80 (its backward goes to MAX_T_LONG)
 
 
 class _OpAttention(torch.autograd.Function):
-    """qkv [batch * t, 3 width] (q not yet scaled) -> bf16 [batch * t, width] through the library's two attention kernels."""
+    """qkv [batch * t, 3 width] (q not yet scaled) -> bf16 [batch * t, width] through the library's two attention kernels.  Heads of 64:
+    the 1/8 of q is exact in bf16.  Heads of 80: q is scaled by 80 ** -0.5 in fp32 and rounded to bf16 once; the backward scales the
+    op's dq by the same factor in fp32."""
 
     @staticmethod
-    def forward(ctx, qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool) -> torch.Tensor:
+    def forward(ctx, qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool, head_dim: int = 64) -> torch.Tensor:
         from . import engine
+        ctx.shape, ctx.in_dtype, ctx.causal, ctx.head_dim = (batch, t, width), qkv.dtype, bool(causal), int(head_dim)
         scaled = qkv.detach().to(torch.bfloat16).clone()
-        scaled[:, :width] *= 0.125                       # exact: a power of two
+        if ctx.head_dim == 64:
+            scaled[:, :width] *= 0.125                   # exact: a power of two
+            ctx.save_for_backward(scaled)
+            return engine.op_attention(scaled, batch, t, width, ctx.causal)
+        scaled[:, :width] = (qkv.detach()[:, :width].float() * ctx.head_dim ** -0.5).to(torch.bfloat16)       # one rounding
         ctx.save_for_backward(scaled)
-        ctx.shape, ctx.in_dtype, ctx.causal = (batch, t, width), qkv.dtype, bool(causal)
-        return engine.op_attention(scaled, batch, t, width, ctx.causal)
+        return engine.op_attention(scaled, batch, t, width, ctx.causal, head_dim=ctx.head_dim)
 
     @staticmethod
     def backward(ctx, dout: torch.Tensor):
         from . import engine
         (scaled,) = ctx.saved_tensors
         batch, t, width = ctx.shape
-        dqkv = engine.attention_backward(scaled, dout.to(torch.bfloat16).contiguous(), batch, t, width, ctx.causal)
-        dqkv[:, :width] *= 0.125                         # the caller's 1/8 of q (exact)
-        return dqkv.to(ctx.in_dtype), None, None, None, None
+        if ctx.head_dim == 64:
+            dqkv = engine.attention_backward(scaled, dout.to(torch.bfloat16).contiguous(), batch, t, width, ctx.causal)
+            dqkv[:, :width] *= 0.125                     # the caller's 1/8 of q (exact)
+            return dqkv.to(ctx.in_dtype), None, None, None, None, None
+        dqkv = engine.attention_backward(scaled, dout.to(torch.bfloat16).contiguous(), batch, t, width, ctx.causal, head_dim=ctx.head_dim)
+        out = dqkv.to(ctx.in_dtype)
+        out[:, :width] = (dqkv[:, :width].float() * ctx.head_dim ** -0.5).to(ctx.in_dtype)      # the caller's 1/sqrt(80) of q
+        return out, None, None, None, None, None
 
 
 class _OpAttentionPacked(torch.autograd.Function):
@@ -160,11 +177,11 @@ class _OpAct(torch.autograd.Function):
         return engine.act_backward(pre, dout.to(torch.bfloat16).contiguous(), ctx.kind), None
 
 
-def torch_attention(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool = True) -> torch.Tensor:
-    """The plain formulation: softmax(q k^T / 8 [+ causal mask]) v per head of 64, in qkv's dtype."""
-    heads = width // 64
-    q, k, v = (x.reshape(batch, t, heads, 64).transpose(1, 2) for x in qkv.split(width, dim=-1))
-    s = (q * 0.125) @ k.transpose(-1, -2)
+def torch_attention(qkv: torch.Tensor, batch: int, t: int, width: int, causal: bool = True, head_dim: int = 64) -> torch.Tensor:
+    """The plain formulation: softmax(q k^T / sqrt(head_dim) [+ causal mask]) v per head of ``head_dim`` (64: / 8), in qkv's dtype."""
+    heads = width // head_dim
+    q, k, v = (x.reshape(batch, t, heads, head_dim).transpose(1, 2) for x in qkv.split(width, dim=-1))
+    s = (q * (0.125 if head_dim == 64 else head_dim ** -0.5)) @ k.transpose(-1, -2)
     if causal:
         s = s + torch.full((t, t), float("-inf"), dtype=s.dtype, device=s.device).triu_(1)
     return (torch.softmax(s, dim=-1).to(v.dtype) @ v).transpose(1, 2).reshape(batch * t, width)
@@ -219,6 +236,7 @@ class _Tower(nn.Module):
     """What the two towers share: the settings and one pre-LN residual block on rows [batch * t, width]."""
 
     causal = True
+    head_dim = 64        # the text towers' always; VisionTower sets its architecture's
 
     def _configure(self, who: str, attention: str, elementwise: str, autocast: Optional[bool], width: int, eps: Sequence[float]) -> None:
         if attention not in ("op", "torch"):
@@ -260,8 +278,8 @@ class _Tower(nn.Module):
     def _attend(self, qkv: torch.Tensor, batch: int, t: int) -> torch.Tensor:
         """qkv [batch * t, 3 width] (q not yet scaled) -> [batch * t, width].  (tools/bench_text_tower_train.py overrides this.)"""
         if self.attention == "op":
-            return _OpAttention.apply(qkv, batch, t, self.width, self.causal)
-        return torch_attention(qkv, batch, t, self.width, self.causal)
+            return _OpAttention.apply(qkv, batch, t, self.width, self.causal, self.head_dim)
+        return torch_attention(qkv, batch, t, self.width, self.causal, self.head_dim)
 
     def _attend_packed(self, qkv: torch.Tensor, packed: "_Packed") -> torch.Tensor:
         """qkv [rows, 3 width] (q not yet scaled) over packed items -> [rows, width].  (tools/bench_text_tower_packed.py overrides this.)"""
@@ -368,23 +386,33 @@ class VisionTower(_Tower):
     causal = False
 
     def __init__(self, model: nn.Module, attention: str = "op", elementwise: str = "op", autocast: Optional[bool] = None,
-                 trainable: bool = True, max_tokens: int = MAX_T):
+                 trainable: bool = True, max_tokens: int = MAX_T, head_dims: Sequence[int] = (64,)):
         super().__init__()
         if not 1 <= int(max_tokens) <= MAX_T_LONG:
             raise ValueError(f"VisionTower: max_tokens = {max_tokens} is outside 1..{MAX_T_LONG} (MAX_T = {MAX_T}: the default; "
                              f"MAX_T_LONG = {MAX_T_LONG}: the long towers)")
         max_tokens = int(max_tokens)
+        head_dims = tuple(int(d) for d in head_dims)
+        if not head_dims or any(d not in HEAD_DIMS for d in head_dims):
+            raise ValueError(f"VisionTower: head_dims = {head_dims} must be taken from HEAD_DIMS = {HEAD_DIMS} ((64,): the default; "
+                             f"HEAD_DIMS: ViT-H-14's heads of 80 as well)")
         m = _unwrap(model)
         arch = getattr(m, "arch", None)
         family = getattr(arch, "family", "clip")
         if family != "clip" or not hasattr(m, "visual") or not hasattr(m.visual, "proj") or not hasattr(m.visual, "class_embedding"):
             raise ValueError(f"VisionTower: only the CLIP family's vision tower is restated (this model's family: {family!r}; SigLIP has no "
                              "class token and pools by attention, BERT models have no vision tower)")
-        if arch.v_head_dim != 64:
-            raise ValueError(f"VisionTower: heads of 64 only (this tower: width {arch.v_width} in heads of {arch.v_head_dim}; the attention "
-                             "backward serves no other head dim)")
+        if arch.v_head_dim not in head_dims:
+            if head_dims == (64,):
+                raise ValueError(f"VisionTower: heads of 64 only (this tower: width {arch.v_width} in heads of {arch.v_head_dim}; the "
+                                 "attention backward serves no other head dim)")
+            raise ValueError(f"VisionTower: heads of {head_dims} only (this tower: width {arch.v_width} in heads of {arch.v_head_dim})")
         if arch.v_tokens > max_tokens:
             raise ValueError(f"VisionTower: {arch.v_tokens} tokens per image; the attention backward serves at most {max_tokens}")
+        if arch.v_head_dim == 80 and arch.v_tokens > MAX_T_HD80:
+            raise ValueError(f"VisionTower: {arch.v_tokens} tokens per image in heads of 80; the head-dim-80 attention forward serves at "
+                             f"most {MAX_T_HD80}, whatever max_tokens says")
+        self.head_dim = arch.v_head_dim
         v = m.visual
         self._configure("VisionTower", attention, elementwise, autocast, arch.v_width,
                         [v.ln_pre.eps] + [e for b in v.transformer.resblocks for e in (b.ln_1.eps, b.ln_2.eps)])
@@ -452,7 +480,7 @@ class EndToEndTuning(nn.Module):
         super().__init__()
         self.heads = ProjectionHeads(model)              # freezes everything, then its six tensors
         self.vision = VisionTower(model, attention=attention, elementwise=elementwise, autocast=autocast, trainable=True,
-                                  max_tokens=MAX_T_LONG)
+                                  max_tokens=MAX_T_LONG, head_dims=HEAD_DIMS)
         self.tower = TextTower(model, attention=attention, autocast=autocast, trainable=True, elementwise=elementwise, packed=packed)
 
     def forward(self, pixels: torch.Tensor, query_ids: torch.Tensor, target_ids: torch.Tensor
